@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of VISFD's dense 3-D filtering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the whole hot path (BASELINE.json: "Gauss+DoG+TV pipeline") over one
 synthetic float32 volume that is already resident in HBM:
@@ -21,10 +21,15 @@ MODES.  BASELINE.json's north_star asks for bit-exact indices and for float voxe
 headline step therefore runs the library's TOLERANCE modes where the output is a float field -- tensor voting
 (option tv_fma: fused multiply-adds, sub-patches with two sender streams, hit lists: csrc/tv_box.hip) and the plain Gaussian of stage 1 (gauss_fma) -- and
 the exact kernels wherever an index depends on the bits (every LoG of the blob stage, the non-max scan, the radix
-select).  `--mode exact` times the all-exact pipeline instead; the line always carries both (`modes`), and
+select).  `--mode exact` times the all-exact pipeline instead; with --full the line carries both (`modes`), and
 tests/test_tolerance_modes.py + tests/test_full_size.py hold the tolerance kernels to 1e-5 of the field's scale.
 
-Prints ONE JSON line on rank 0.  `roofline` describes the DOMINANT kernel of the step (tensor voting, ~70 % of it: a
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, `stages_ms`, and `roofline_pipeline` from the stage times of those steps).  `--dump-outputs DIR` writes what
+the last timed step computed to DIR/<name>.npy (write_outputs).  Everything else is measured only with `--full`: the other
+mode, the per-kernel roofline objects, the 2048^3 Gaussian, the CPU baseline and, with N > 1, the slab seam check.
+
+With --full, `roofline` describes the DOMINANT kernel of the step (tensor voting, ~70 % of it: a
 VALU-bound stencil priced against the FP32 vector peak); `roofline_gauss` the separable-Gaussian kernel
 BASELINE.json's HBM target names; both are timed alone with HIP events on the stream they run on.  `copy_gbs` is a
 device-to-device copy measured in the same run: every HBM-bound object also states its fraction of that.  `stages_ms`
@@ -262,6 +267,38 @@ def pipeline_roofline(stage_ms, ms_per_step, nvox):
     return out
 
 
+DUMP_VOXELS = 1 << 20    # voxels --dump-outputs takes from every volume-sized output (all of them in smaller volumes)
+DUMP_BLOBS = 1 << 19     # rows it keeps of a blob list; with the voxels' 32 MiB at most 52 MiB in all
+DUMP_SEED = 20240607
+
+
+def dump_sample(nvox):
+    """Flat indices (into one rank's owned planes) of the voxels --dump-outputs writes: a fixed, seeded sample, so that two
+    runs -- or two builds -- with the same arguments write the same voxels."""
+    if nvox <= DUMP_VOXELS:
+        return np.arange(nvox, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, nvox, DUMP_VOXELS, dtype=np.int64))
+
+
+def blob_rows(rows):
+    """A blob list (rows x,y,z,sigma,score) in a canonical order -- by position, then sigma and score: the list's own order
+    depends on thread scheduling -- and at most DUMP_BLOBS rows of it (a seeded sample of a longer list)."""
+    rows = np.asarray(rows, np.float32).reshape(-1, 5)
+    rows = rows[np.lexsort(rows.T[::-1])]
+    if len(rows) > DUMP_BLOBS:
+        rows = rows[np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), DUMP_BLOBS, replace=False))]
+    return np.ascontiguousarray(rows)
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one float32/float64 .npy per output of the timed path."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-child":
         raise SystemExit(cpu_baseline_child(sys.argv[2:]))
@@ -276,9 +313,14 @@ def main():
                                                                 "work over its three OpenMP teams)")
     ap.add_argument("--mode", choices=("tolerance", "exact"), default="tolerance",
                     help="headline mode: tolerance = FMA tensor voting + FMA plain Gaussian (1e-5 contract), exact = bit-exact kernels only")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-2048", action="store_true", help="skip the extra Gaussian timing on a 2048^3 volume")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-2048", action="store_true", help="with --full: skip the extra Gaussian timing on a 2048^3 volume")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure the other mode, the roofline objects, the 2048^3 "
+                                                        "Gaussian, the CPU baseline and (N > 1) the slab seam check")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` run directly: start the N ranks as a FRESH child (torch.distributed.run, one rank per
@@ -303,7 +345,7 @@ def main():
     # and is WAITED FOR before the first step: a 256-thread OpenMP job beside the timed steps starves the blob stage's
     # host side (measured: 125 -> 600 ms).
     cpu_proc = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         import subprocess
         cpu_proc = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--cpu-child", "orchestrate", str(args.cpu_sample)],
                                     stdout=subprocess.PIPE, text=True)
@@ -374,6 +416,9 @@ def main():
     sal = torch.empty(shape, device=device, dtype=torch.float32)
     dirs = torch.empty((3,) + shape, device=device, dtype=torch.float32)
     ten = torch.empty((6,) + shape, device=device, dtype=torch.float32)
+    dump_idx = None   # --dump-outputs (rank 0): the voxels written of every volume-sized output
+    if args.dump_outputs and rank == 0:
+        dump_idx = torch.from_numpy(dump_sample((layout.z1 - layout.z0) * S * S)).to(device)
     torch.cuda.synchronize()
 
     cpu = None
@@ -394,7 +439,7 @@ def main():
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     counts = {}
 
-    def step(record, stage_ms):
+    def step(record, stage_ms, outputs=None):
         if record:
             ev[0].record()
         if world > 1:
@@ -402,6 +447,8 @@ def main():
         pipeline.gauss(ctx, src, dst, GAUSS_SIGMA)
         if record:
             ev[1].record()
+        if outputs is not None:   # the Gaussian's sample now: `dst` lends the membrane stage its scratch below
+            outputs["gauss"] = layout.owned(dst).reshape(-1)[dump_idx]
         job = None
         if world > 1:
             mins, maxs = slab.blob_detect_slab(ctx, layout, src, sig, src_halo_ready=True)
@@ -425,9 +472,12 @@ def main():
             for i in range(3):
                 stage_ms[i] += ev[i].elapsed_time(ev[i + 1])
         counts.update(minima=len(mins), maxima=len(maxs), threshold=float(thr))
+        if outputs is not None:
+            outputs.update(blob_minima=mins, blob_maxima=maxs, membrane_threshold=thr)
 
-    def run_mode(mode, steps, warmup):
-        """W untimed + exactly K timed steps, barrier + synchronize on both sides, MAX over ranks."""
+    def run_mode(mode, steps, warmup, outputs=None):
+        """W untimed + exactly K timed steps, barrier + synchronize on both sides, MAX over ranks.  `outputs` (a dict): filled
+        with what the last timed step computed that the buffers do not keep (the Gaussian's sample, the blob lists)."""
         stage_ms = np.zeros(3)
         with ctx.options(**MODE_OPTS[mode]):
             for _ in range(warmup):
@@ -442,8 +492,8 @@ def main():
                 if world > 1:
                     dist.barrier()
                 t0 = time.perf_counter()
-                for _ in range(steps):
-                    step(True, stage_ms)
+                for i in range(steps):
+                    step(True, stage_ms, outputs if i == steps - 1 else None)
                 torch.cuda.synchronize()
                 if world > 1:
                     dist.barrier()
@@ -460,10 +510,23 @@ def main():
                               "membrane_tv": round(stage_ms[2] / steps, 3)},
                 "results": dict(counts)}, stage_ms / steps
 
-    headline, stage_avg = run_mode(args.mode, args.steps, args.warmup)
-    other_mode = "exact" if args.mode == "tolerance" else "tolerance"
-    other, _ = run_mode(other_mode, 2, 1)      # the other mode, briefly, for the record
+    outputs = {} if dump_idx is not None else None
+    headline, stage_avg = run_mode(args.mode, args.steps, args.warmup, outputs)
     ms_per_step, value = headline["ms_per_step"], headline["value"]
+    if outputs is not None:
+        # what a caller of the step receives, from the last timed step: the Gaussian, the blob lists and the threshold (kept by
+        # the step) and the post-vote saliency and vote tensor (still in `sal` and `ten`); rank 0's planes when N > 1
+        write_outputs(args.dump_outputs, {
+            "gauss": outputs["gauss"].cpu().numpy(),
+            "blob_minima": blob_rows(outputs["blob_minima"]),
+            "blob_maxima": blob_rows(outputs["blob_maxima"]),
+            "membrane_threshold": np.array([outputs["membrane_threshold"]], np.float64),
+            "membrane_saliency": layout.owned(sal).reshape(-1)[dump_idx].cpu().numpy(),
+            "vote_tensor": torch.stack([layout.owned(ten[c]).reshape(-1)[dump_idx] for c in range(6)]).cpu().numpy()})
+
+    # ---- --full only from here to the result line ---------------------------------------------------------------------
+    other_mode = "exact" if args.mode == "tolerance" else "tolerance"
+    other = run_mode(other_mode, 2, 1)[0] if args.full else None      # the other mode, briefly, for the record
 
     # ---- multi-GPU: a seam check, so that the first run with one GPU per rank validates bits as well as speed ------
     # Every rank > 0 regenerates the top planes of its lower neighbour's slab (the generator is a pure function of the
@@ -471,7 +534,7 @@ def main():
     # single-volume ridge + voting stages on it with the GLOBAL threshold the slab run selected, and compares the planes
     # just above the seam with what the slab run left in `ten` (bit for bit in exact mode, 1e-5 in tolerance mode).
     slab_check = None
-    if world > 1:
+    if args.full and world > 1:
         ok, nchk = 1, 0
         D = 40
         thr = counts["threshold"]
@@ -537,7 +600,7 @@ def main():
         o.update(extra)
         return o
 
-    if rank == 0:
+    if args.full and rank == 0:
         nv = shape[0] * shape[1] * shape[2]
         # what this box's HBM gives a plain device-to-device copy of the same volume (read 4 + write 4 B/voxel)
         c_ms = timed(lambda: dst.copy_(src), 5)
@@ -640,7 +703,7 @@ def main():
 
     # ---- the north-star target case: the separable Gaussian on a 2048^3 volume (2^33 voxels, 32 GiB) -------
     roofline_2048 = None
-    if rank == 0 and world == 1 and not args.no_2048:
+    if args.full and rank == 0 and world == 1 and not args.no_2048:
         del dst, sal, dirs, ten
         torch.cuda.empty_cache()
         free, _ = torch.cuda.mem_get_info()
@@ -692,19 +755,15 @@ def main():
                        "halo_transport": halo_transport},
             "stages_ms": headline["stages_ms"],
             "results": headline["results"],
-            "modes": {args.mode: headline, other_mode: other},
-            "copy_gbs": copy_gbs,
+            "modes": {args.mode: headline, other_mode: other} if args.full else {args.mode: headline},
             # the BASELINE metric's own "% HBM roofline": algorithmic bytes of SURVEY.md 8d per voxel (3-D Gaussian 8, blob
             # detection with 12 scales 8*12 + 12*10 = 216, Gauss + Hessian/eigen + select + TV + score 112) over the
             # measured stage times of the timed steps, per GPU
             "roofline_pipeline": pipeline_roofline(stage_avg, ms_per_step, nvox_rank),
-            "roofline": roofline,
-            "roofline_tv": tv_objs,
-            "roofline_gauss": roofline_gauss,
-            "roofline_pass": roofline_pass,
-            "roofline_ridge": roofline_ridge,
-            "roofline_2048": roofline_2048,
         }
+        if args.full:
+            out.update(copy_gbs=copy_gbs, roofline=roofline, roofline_tv=tv_objs, roofline_gauss=roofline_gauss,
+                       roofline_pass=roofline_pass, roofline_ridge=roofline_ridge, roofline_2048=roofline_2048)
         if slab_check is not None:
             out["slab_check"] = slab_check
         if cpu is not None:

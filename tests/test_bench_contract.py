@@ -1,23 +1,55 @@
-"""bench.py's output contract on a small volume (GPU): one JSON line with the fields the driver reads, the roofline
-objects and the CPU baseline."""
+"""bench.py's output contract on a small volume (GPU): one JSON line with the fields the driver reads; with --full the
+roofline objects and the CPU baseline; --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
 
 
-@pytest.mark.gpu
-def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "128", "--steps", "1", "--warmup", "1",
-                        "--no-2048", "--cpu-sample", "48"], capture_output=True, text=True, cwd=ROOT, timeout=900)
+def run_bench(*args, timeout=900):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + [str(a) for a in args], capture_output=True,
+                       text=True, cwd=ROOT, timeout=timeout)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
-    out = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run: the headline fields only, `--steps` timed steps, and with --dump-outputs the outputs of the last timed
+    step as float .npy files (at most 64 MB), identical from run to run."""
+    dumps = []
+    for tag in ("a", "b"):
+        out = run_bench("--size", 128, "--steps", 3, "--warmup", 1, "--dump-outputs", tmp_path / tag)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "stages_ms", "roofline_pipeline"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["modes"]["tolerance"]["steps"] == 3 and set(out["modes"]) == {"tolerance"}
+        assert out["unit"] == "Mvoxels/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert abs(out["value"] - 128 ** 3 / (out["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * out["value"]
+        for key in ("cpu_baseline", "roofline", "roofline_gauss", "roofline_2048", "copy_gbs"):
+            assert key not in out, key
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == sorted(n + ".npy" for n in ("gauss", "blob_minima", "blob_maxima", "membrane_threshold",
+                                                     "membrane_saliency", "vote_tensor")), files
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+        arrays = {f: np.load(tmp_path / tag / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert len(arrays["blob_minima.npy"]) == out["results"]["minima"] and arrays["vote_tensor.npy"].shape[0] == 6
+        assert arrays["membrane_threshold.npy"][0] == out["results"]["threshold"] and np.abs(arrays["gauss.npy"]).max() > 0
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+@pytest.mark.gpu
+def test_bench_prints_one_json_line_with_the_contract_fields():
+    out = run_bench("--size", 128, "--steps", 1, "--warmup", 1, "--no-2048", "--cpu-sample", 48, "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key

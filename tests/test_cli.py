@@ -33,11 +33,11 @@ def test_cli_rejects_unknown_arguments(cli):
     assert r.returncode == 1 and "Unable to open" in r.stderr
 
 
-def test_cli_fails_loudly_without_gpu(cli):
+def test_cli_fails_loudly_without_gpu(cli, tmp_path):
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present")
-    r = run(cli, "-in", os.path.join(GOLDEN, "test_blob_detect.rec"), "-out", "/tmp/_x.rec", "-gauss", 2, "-w", 1)
+    r = run(cli, "-in", os.path.join(GOLDEN, "test_blob_detect.rec"), "-out", tmp_path / "x.rec", "-gauss", 2, "-w", 1)
     assert r.returncode == 1 and "no HIP device" in r.stderr
 
 

@@ -1,5 +1,5 @@
 import sys, os, torch, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visfd_amd import api
 dev = torch.device("cuda:0")
 stream = torch.cuda.Stream(); torch.cuda.set_stream(stream)

@@ -7,9 +7,9 @@ out=${1:-gpurun_out/round}; n=${2:-1024}
 export TMPDIR=/tmp
 mkdir -p $out
 set -e
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 600 $out/bench.json; echo
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu > $out/bench_under_rocprof.json 2> $out/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu --full > $out/bench_under_rocprof.json 2> $out/prof.err
 cp $out/prof/*/*kernel_stats.csv $out/kernel_stats.csv
 # the Gaussian launches of that run by grid size (1024^3 and 2048^3 launches share one kernel name in the statistics)
 python3 - $out/prof > $out/gauss_launches.txt <<'PY'

@@ -15,7 +15,7 @@ stats = os.path.join(src_dir, "kernel_stats.csv")
 shutil.copy(stats, os.path.join(P, "%s_bench_1024_kernel_stats.csv" % tag))
 rows = list(csv.DictReader(open(stats)))
 with open(os.path.join(P, "%s_bench_1024_summary.txt" % tag), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu"
+    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu --full"
             "   (MI355X, 1024^3, %s)\n" % tag)
     f.write("# 2 timed + 1 warm-up step in the headline (tolerance) mode, 2 + 1 in the other mode, and the extra launches of the\n"
             "#   roofline objects (device copy, Gaussian exact/FMA at 1024^3 and 2048^3, single-axis passes, ridge kernels, tensor voting\n"
