@@ -59,7 +59,7 @@ void* visfd_hip_get_stream(visfd_hip_ctx* ctx);
 /* release the cached workspace (it otherwise persists between calls) */
 int visfd_hip_trim(visfd_hip_ctx* ctx);
 const char* visfd_hip_last_error(void);
-int visfd_hip_abi_version(void);   /* 9: entry points only get added between versions */
+int visfd_hip_abi_version(void);   /* 10: entry points only get added between versions */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -527,6 +527,8 @@ int visfd_hip_slab_create_rccl(visfd_hip_ctx*, const void* unique_id_128_bytes /
                                int world, int64_t nz_global, int ghost, visfd_hip_slab** out);
 int visfd_hip_slab_create_custom(visfd_hip_ctx*, const visfd_hip_transport*, int rank, int world, int64_t nz_global,
                                  int ghost, visfd_hip_slab** out);
+/* Both refuse (VISFD_HIP_EINVAL) when world > 1 and the THINNEST slab, nz_global / world planes, is thinner than `ghost`:
+ * the answer is the same on every rank, so no rank goes on into a collective that the others never join. */
 int visfd_hip_slab_destroy(visfd_hip_slab*);
 /* out = {z0, z1, lo, hi, own0, own1, nz_local}: owned planes [z0, z1) and stored planes [lo, hi) of the volume; the owned
  * planes are [own0, own1) of the local array */
@@ -571,6 +573,11 @@ int visfd_hip_blob_dog_slab_dev(visfd_hip_slab*, float* src, int64_t nx, int64_t
                                 float maxima_threshold, int src_halo_ready,
                                 visfd_hip_blob* minima, int64_t minima_capacity, int64_t* n_minima,
                                 visfd_hip_blob* maxima, int64_t maxima_capacity, int64_t* n_maxima);
+/* The halo depth the slab blob stage exchanges (and the least ghost depth it accepts): the Z half-width of the widest LoG
+ * in the kernels' own float arithmetic (sigma_b = (float)(sigma * (1 + delta/2)), floor(truncate_ratio * sigma_b) as a float
+ * product; lib/visfd/filter3d.hpp:1451-1464) plus the one plane the 26-neighbour scan reads beyond it. */
+int visfd_hip_blob_halo_depth(const float* blob_sigma, int n_sigma, float delta_sigma_over_sigma, float truncate_ratio,
+                              int* depth_out);
 /* Host-memory faces for a host that runs one process per GPU (`filter_mrc -gauss|-blob ... -slab`): the rank's OWNED planes
  * [z1-z0][ny][nx] in, the owned planes of the filtered volume / the blobs of the owned planes (iz GLOBAL) out.  A blob list that
  * does not fit returns VISFD_HIP_ECAPACITY with the needed counts in n_minima / n_maxima; the retry is local. */

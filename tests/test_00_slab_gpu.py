@@ -38,6 +38,30 @@ def test_slab_pipeline_on_gpu_equals_single_volume(world, path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_slab_case_matrix_on_gpu(world):
+    """One launch per world size runs the case list of tools/slab_check.py --matrix through the C entry points, each case on
+    a fresh slab handle with NaN ghosts; rank 0 compares the gathered owned planes (threshold, post-vote saliency, vote
+    tensor) and the merged blob lists with the single-volume GPU run and, in exact mode, with the CPU oracle:
+      uneven      nz % world != 0 (the `rem` planes), a ghost with slack: planes beyond every exchanged halo stay NaN;
+      tight*      ghost exactly the deepest window (blob halo 5 at sigma 1.4954885 with a blob centred on a seam plane; h_tv;
+                  h_gauss + 1), and the same with a wide ghost;
+      thin        slabs exactly `ghost` planes thick: the middle ranks have no interior band (the vote split's else branch);
+      background  the peak-height factor (h_bg = ghost = 5) through the device and the host-memory faces;
+      host-faces  visfd_hip_apply_gauss_slab (normalize 1/0, anisotropic; isotropic takes the fused route) and
+                  visfd_hip_blob_dog_slab;
+      plateau     a constant block across ranks with the fraction's cut inside its run of equal scores;
+      tolerance   bench.py's tolerance options: threshold bit-equal, tensors within 1e-5 of the field scale;
+      refusals    windows deeper than the ghost zone refused on every rank, then the same handle runs a valid stage."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+           os.path.join(ROOT, "tools", "slab_check.py"), "--matrix"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    print(r.stdout[-4000:])
+    assert r.returncode == 0 and "SLAB-OK world=%d cases=" % world in r.stdout, (r.stdout[-4000:], r.stderr[-3000:])
+
+
+@pytest.mark.gpu
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` run directly (as the driver runs the N=1 line) starts its ranks itself as a fresh child
     and relays ONE JSON line and the exit code; on a one-GPU box the ranks share the card (a rehearsal of the code path:

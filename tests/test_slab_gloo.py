@@ -1,7 +1,9 @@
-"""The N>1 (Z-slab) path on CPU: world_size 2 and 3 over gloo, oracle arithmetic plugged in for the
+"""The N>1 (Z-slab) path on CPU: world sizes 2, 3 and 4 over gloo, oracle arithmetic plugged in for the
 kernels (tests/oracle_ops.py).  Slab results must equal the single-volume oracle results bit-for-bit:
 halo exchange, ghost handling at true vs interior faces, the distributed exact radix select and the
-blob-list merge are what is being tested."""
+blob-list merge are what is being tested -- over even and uneven splits, slabs exactly `ghost` thick and
+ghosts with slack.  Also here: the host arithmetic of the blob halo depth, the planes next to a seam of
+every LoG scale with that depth, and the "slab too thin" refusal being the same on every rank."""
 import os
 import tempfile
 
@@ -14,15 +16,14 @@ import torch.multiprocessing as mp
 import volgen
 from conftest import assert_bits_equal
 
-SHAPE = (30, 18, 20)
+XY = (18, 20)
 SIGMA = 1.2
 TV_RATIO = 2.0
 FRACTION = 0.15
-GHOST = 6
 BLOB_SIGMAS = np.array([1.0, 1.25, 1.55, 1.9], np.float32)
 
 
-def _worker(rank, world, store_path, out_dir):
+def _worker(rank, world, store_path, out_dir, nz, ghost):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from oracle_ops import OracleOps
@@ -30,9 +31,9 @@ def _worker(rank, world, store_path, out_dir):
     dist.init_process_group("gloo", init_method="file://" + store_path, rank=rank, world_size=world)
     try:
         ops = OracleOps()
-        full = torch.from_numpy(volgen.membrane_volume(SHAPE, seed=55))
-        L = slab.SlabLayout(SHAPE[0], rank, world, ghost=GHOST)
-        shape = (L.nz_local,) + SHAPE[1:]
+        full = torch.from_numpy(volgen.membrane_volume((nz,) + XY, seed=55))
+        L = slab.SlabLayout(nz, rank, world, ghost=ghost)
+        shape = (L.nz_local,) + XY
         src = torch.full(shape, float("nan"))          # ghosts must come from the exchange, not from here
         L.owned(src).copy_(full[L.z0:L.z1])
         sal = torch.zeros(shape)
@@ -49,15 +50,30 @@ def _worker(rank, world, store_path, out_dir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_slab_pipeline_equals_single_volume(oracle, world):
+# The deepest window of this stage is the blob halo (6 planes for sigma 1.9); the ridge stage needs floor(1.2 * ratio) + 1 = 4
+# and the vote h_tv = 3.  (nz, world, ghost):
+GEOMETRIES = [
+    (30, 2, 6), (30, 3, 6),     # even splits
+    (31, 2, 6), (31, 3, 6),     # uneven: nz % world != 0
+    (31, 4, 6),                 # uneven, 7 or 8 planes per rank
+    (47, 4, 6),                 # uneven, rem 3
+    (24, 4, 6),                 # every slab exactly `ghost` thick: the middle ranks vote without an interior band
+    (47, 3, 9),                 # a ghost with slack: stored planes beyond every exchanged halo stay NaN
+]
+
+
+@pytest.mark.parametrize("nz,world,ghost", GEOMETRIES)
+def test_slab_pipeline_equals_single_volume(oracle, nz, world, ghost):
     from oracle import pyoracle as po
+    from visfd_amd import slab
+    assert [slab.SlabLayout(nz, r, world, ghost).z1 for r in range(world)][-1] == nz
     with tempfile.TemporaryDirectory() as tmp:
         store = os.path.join(tmp, "store")
-        mp.spawn(_worker, args=(world, store, tmp), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, store, tmp, nz, ghost), nprocs=world, join=True)
         parts = [np.load(os.path.join(tmp, "rank%d.npz" % r)) for r in range(world)]
+    assert [int(p["z1"]) - int(p["z0"]) for p in parts] == [nz // world + (r < nz % world) for r in range(world)]
     # single-volume oracle
-    full = volgen.membrane_volume(SHAPE, seed=55)
+    full = volgen.membrane_volume((nz,) + XY, seed=55)
     ratio = oracle.ratio_from_threshold(0.03)
     _, hess = oracle.calc_hessian(full, SIGMA, ratio, None, want_grad=False)
     sal, dirs = oracle.hessian_saliency(hess, po.ORDER_DECREASING)
@@ -91,3 +107,85 @@ def test_layout_covers_volume():
             assert L.lo == max(0, L.z0 - ghost) and L.hi == min(nz, L.z1 + ghost)
             assert L.own1 - L.own0 == L.z1 - L.z0
         assert (seen == 1).all()
+
+
+# sigma_max values (float32) at which floor(ratio * sigma * (1 + delta/2)) in double precision is one less than the LoG
+# kernels' float window (delta 0.02, truncate 0.03): a halo depth restated in double was one plane short for these
+SEAM_SIGMAS = (1.4954885, 0.74774426, 1.8693607, 2.990977, 3.7387214)
+
+
+def _plan_log_hw_f32(sigma, delta, ratio):
+    """plan_log (csrc/api.hip) restated in float32 numpy: sigma_a/b = (float)(sigma * (1 -/+ delta/2)) with the factor in
+    double, the half-width floor(ratio * max(sigma_a, sigma_b)) as a float32 product."""
+    s, d = float(np.float32(sigma)), float(np.float32(delta))
+    sa = np.float32(s * (1.0 - 0.5 * d))
+    sb = np.float32(s * (1.0 + 0.5 * d))
+    return int(np.floor(np.float32(np.float32(ratio) * max(sa, sb))))
+
+
+def test_blob_halo_depth_is_the_kernels_float_window():
+    from visfd_amd import api
+    rng = np.random.default_rng(7)
+    for thr in (0.03, 0.01, 0.1):
+        ratio = api.ratio_from_threshold(thr)
+        for delta in (0.02, 0.05, 0.1):
+            # sigmas whose float window lies just below / on / just above every integer half-width 0..24
+            for h in range(0, 25):
+                s0 = np.float32(h / (np.float32(ratio) * (1.0 + 0.5 * delta)))
+                for k in range(-3, 4):
+                    s = np.float32(s0 + np.float32(k) * np.spacing(s0)) if s0 > 0 else np.float32(1e-3 * (k + 4))
+                    want = _plan_log_hw_f32(s, delta, ratio) + 1
+                    assert api.blob_halo_depth([s], delta, ratio) == want, (thr, delta, float(s))
+            # several scales: the widest window decides
+            for _ in range(20):
+                sig = np.sort(rng.uniform(0.3, 6.0, 5).astype(np.float32))
+                want = max(_plan_log_hw_f32(x, delta, ratio) for x in sig) + 1
+                assert api.blob_halo_depth(sig, delta, ratio) == want
+    ratio = api.ratio_from_threshold(0.03)
+    for s in SEAM_SIGMAS:
+        assert api.blob_halo_depth([s], 0.02, ratio) == _plan_log_hw_f32(s, 0.02, ratio) + 1
+    assert api.blob_halo_depth([1.4954885], 0.02, ratio) == 5
+
+
+@pytest.mark.parametrize("smax", SEAM_SIGMAS)
+def test_blob_halo_depth_covers_the_planes_next_to_a_seam(oracle, smax):
+    """With the ghost planes exchanged as deep as the library says (the rest NaN, as if never received), the LoG of every
+    scale on the local array equals the full-volume LoG bit for bit on planes [own0-1, own1+1): the owned planes and the
+    one plane on each side that the 26-neighbour scan of the first/last owned plane reads."""
+    from visfd_amd import api, slab
+    delta, ratio = 0.02, api.ratio_from_threshold(0.03)
+    sigmas = np.array([smax * 0.62, smax * 0.8, smax], np.float32)
+    sigmas[-1] = np.float32(smax)
+    depth = api.blob_halo_depth(sigmas, delta, ratio)
+    assert depth == _plan_log_hw_f32(smax, delta, ratio) + 1
+    world, ghost = 3, depth + 2
+    nz = world * ghost + 2
+    full = volgen.blob_volume((nz, 12, 14), seed=21)
+    logs = [oracle.log(full, (s, s, s), delta, ratio)[0] for s in sigmas]
+    for r in range(world):
+        L = slab.SlabLayout(nz, r, world, ghost)
+        loc = np.full((L.nz_local, 12, 14), np.nan, np.float32)
+        a, b = max(0, L.own0 - depth), min(L.nz_local, L.own1 + depth)
+        loc[a:b] = full[L.lo + a:L.lo + b]
+        za, zb = max(0, L.own0 - 1), min(L.nz_local, L.own1 + 1)
+        for s, want in zip(sigmas, logs):
+            got = oracle.log(loc, (s, s, s), delta, ratio)[0]
+            assert_bits_equal(got[za:zb], want[L.lo + za:L.lo + zb],
+                              "LoG sigma %r, rank %d, planes %d..%d" % (float(s), r, L.lo + za, L.lo + zb))
+
+
+@pytest.mark.parametrize("nz,world,ghost", [(25, 4, 7), (100, 8, 13), (31, 3, 11), (31, 3, 10), (24, 4, 6), (47, 4, 11),
+                                            (48, 8, 6), (49, 8, 6), (17, 2, 9), (18, 2, 9)])
+def test_too_thin_refusal_is_the_same_on_every_rank(nz, world, ghost):
+    """A rank that accepted a geometry another refused would wait for ever in the first halo exchange."""
+    from visfd_amd import slab
+    verdict = []
+    for r in range(world):
+        try:
+            slab.SlabLayout(nz, r, world, ghost)
+            verdict.append(True)
+        except ValueError as e:
+            assert "thinner than the ghost depth" in str(e)
+            verdict.append(False)
+    assert len(set(verdict)) == 1, verdict
+    assert verdict[0] == (nz // world >= ghost)

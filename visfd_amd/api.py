@@ -155,6 +155,7 @@ _SIGS = {
     "visfd_hip_apply_gauss_slab": (C.c_int, [_vp, _vp, _i64, _i64, _fp, _ip, C.c_int, _vp, _fp]),
     "visfd_hip_blob_dog_slab": (C.c_int, [_vp, _vp, _i64, _i64, _fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                           _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64)]),
+    "visfd_hip_blob_halo_depth": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, _ip]),
     "visfd_hip_slab_selftest": (C.c_int, [_vp, _i64]),
     "visfd_hip_slab_exchange_dev": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _i64, _i64, C.c_int]),
     "visfd_hip_membrane_detect_slab_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int,
@@ -236,6 +237,15 @@ def gauss_taps(sigma, h):
 
 def ratio_from_threshold(thr):
     return float(load_library().visfd_hip_ratio_from_threshold(float(thr)))
+
+
+def blob_halo_depth(sigmas, delta, ratio):
+    """visfd_hip_blob_halo_depth: the halo depth of the slab blob stage (widest LoG Z half-width + 1, float arithmetic)."""
+    sig = np.ascontiguousarray(sigmas, np.float32).reshape(-1)
+    out = C.c_int()
+    L = load_library()
+    _chk_host(L, L.visfd_hip_blob_halo_depth(sig.ctypes.data_as(_fp), len(sig), float(delta), float(ratio), C.byref(out)))
+    return int(out.value)
 
 
 def gauss_halfwidths(sigma, ratio):
@@ -1007,14 +1017,44 @@ class Slab:
                 continue
             self.ctx._chk(rc)
             break
+        return _slab_blob_rows(mn, int(nmin.value)), _slab_blob_rows(mx, int(nmax.value))
 
-        def rows(arr, n):
-            a = np.frombuffer(arr, dtype=np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("scale", "<i4"),
-                                                   ("sigma", "<f4"), ("score", "<f4")]), count=n)
-            out = np.empty((n, 5), np.float32)
-            out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = a["ix"], a["iy"], a["iz"], a["sigma"], a["score"]
-            return out
-        return rows(mn, int(nmin.value)), rows(mx, int(nmax.value))
+    def gauss_host(self, src_owned, sigma, hw, normalize=True):
+        """visfd_hip_apply_gauss_slab: the Gaussian of the rank's owned planes (numpy float32 [z1-z0][ny][nx], the ghost
+        planes come from the neighbours) -> (owned planes of the result, A)."""
+        src_owned = np.ascontiguousarray(src_owned, np.float32)
+        nzo, ny, nx = src_owned.shape
+        assert nzo == self.z1 - self.z0
+        dst = np.empty_like(src_owned)
+        A = C.c_float()
+        self.ctx._chk(self._L.visfd_hip_apply_gauss_slab(self._h, _np(src_owned), nx, ny, _f3(sigma), _i3(hw), int(bool(normalize)),
+                                                         _np(dst), C.byref(A)))
+        return dst, float(A.value)
+
+    def blob_dog_host(self, src_owned, sigmas, delta=0.02, ratio=2.5, minima_threshold=np.inf, maxima_threshold=-np.inf,
+                      cap=1 << 16):
+        """visfd_hip_blob_dog_slab: the blobs of the rank's owned planes (numpy float32 [z1-z0][ny][nx]) -> (minima, maxima)
+        rows as blob_dog returns them.  A list longer than `cap` raises (VISFD_HIP_ECAPACITY): this face exchanges the halo
+        on every call, so a retry is not local to one rank."""
+        src_owned = np.ascontiguousarray(src_owned, np.float32)
+        nzo, ny, nx = src_owned.shape
+        assert nzo == self.z1 - self.z0
+        sig = np.ascontiguousarray(sigmas, np.float32)
+        mn, mx = (Blob * cap)(), (Blob * cap)()
+        nmin, nmax = _i64(), _i64()
+        self.ctx._chk(self._L.visfd_hip_blob_dog_slab(self._h, _np(src_owned), nx, ny, sig.ctypes.data_as(_fp), len(sig), float(delta),
+                                                      float(ratio), float(minima_threshold), float(maxima_threshold),
+                                                      C.addressof(mn), cap, C.byref(nmin), C.addressof(mx), cap, C.byref(nmax)))
+        return _slab_blob_rows(mn, int(nmin.value)), _slab_blob_rows(mx, int(nmax.value))
+
+
+def _slab_blob_rows(arr, n):
+    """visfd_hip_blob records -> float32 rows x, y, z, sigma, score."""
+    a = np.frombuffer(arr, dtype=np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("scale", "<i4"),
+                                           ("sigma", "<f4"), ("score", "<f4")]), count=n)
+    out = np.empty((n, 5), np.float32)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = a["ix"], a["iy"], a["iz"], a["sigma"], a["score"]
+    return out
 
 
 def _device_view(torch, ptr, count, dtype):

@@ -682,9 +682,8 @@ void handle_blob_slab(const Settings& s, Mrc& tomo_in, float ratio, vector<visfd
     if (s.blob_aspect_ratio[d] != 1.0f) throw VisfdErr("Error: -slab runs isotropic blob detection only (no -blob-aspect-ratio).\n");
   vector<float> sig(s.blob_diameters.size());
   hip_detail::check(visfd_hip_blob_diameters_to_sigmas(s.blob_diameters.data(), (int)sig.size(), sig.data()));
-  float smax = 0;
-  for (size_t i = 0; i < sig.size(); i++) smax = std::max(smax, sig[i]);
-  const int ghost = (int)std::floor(ratio * (double)smax * (1.0 + 0.5 * s.delta)) + 1;
+  int ghost = 0;
+  hip_detail::check(visfd_hip_blob_halo_depth(sig.data(), (int)sig.size(), s.delta, ratio, &ghost));
   visfd_hip_slab* slab = open_slab(s, tomo_in.nz, ghost);
   int64_t lay[7];
   hip_detail::check(visfd_hip_slab_layout(slab, lay));

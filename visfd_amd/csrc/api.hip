@@ -374,7 +374,7 @@ void options_from_environment(visfd_hip_options* o) {
 }
 }  // namespace
 
-int visfd_hip_abi_version(void) { return 9; }   // 9: + visfd_hip_blob_dog_begin_dev / _end / _abort (BlobDog in two halves); 8: + the peak-height factor (`-membrane-background`): visfd_hip_peak_background_dev, _ridge_scores_bg_dev, _tensor_saliency_bg_dev, _membrane_detect_bg[_dev], _membrane_detect_slab_bg[_dev]; slab Gaussian / blob entry points of the program; 7: + visfd_hip_membrane_detect_slab (host-memory face of the slab stage); 6: + visfd_hip_get_option, tolerance modes (tv_fma, gauss_fma), slab entry points; 5: + visfd_hip_set_option, CompactMultiChannelImage3D/TVDenseStick normalisation in the shim; 2: + blob post-processing, binning, LabelConnected and its host helpers; 3: + host DiagonalizeFlatSym3 / ConvertFlatSym2Evects3; 4: + LocalFluctuations, two-step ridge (scores / directions)
+int visfd_hip_abi_version(void) { return 10; }   // 10: + visfd_hip_blob_halo_depth (the blob halo in the kernels' float arithmetic); 9: + visfd_hip_blob_dog_begin_dev / _end / _abort (BlobDog in two halves); 8: + the peak-height factor (`-membrane-background`): visfd_hip_peak_background_dev, _ridge_scores_bg_dev, _tensor_saliency_bg_dev, _membrane_detect_bg[_dev], _membrane_detect_slab_bg[_dev]; slab Gaussian / blob entry points of the program; 7: + visfd_hip_membrane_detect_slab (host-memory face of the slab stage); 6: + visfd_hip_get_option, tolerance modes (tv_fma, gauss_fma), slab entry points; 5: + visfd_hip_set_option, CompactMultiChannelImage3D/TVDenseStick normalisation in the shim; 2: + blob post-processing, binning, LabelConnected and its host helpers; 3: + host DiagonalizeFlatSym3 / ConvertFlatSym2Evects3; 4: + LocalFluctuations, two-step ridge (scores / directions)
 const char* visfd_hip_last_error(void) { return g_last_error.c_str(); }
 
 int visfd_hip_create(int device, void* stream, visfd_hip_ctx** out) {
@@ -466,6 +466,19 @@ float visfd_hip_ratio_from_threshold(float thr) { return std::sqrt(-2 * std::log
 int visfd_hip_gauss_halfwidths(const float sigma[3], float ratio, int hw[3]) {
   VH_REQUIRE(sigma && hw, "null argument");
   return halfwidths_from_ratio(sigma, ratio, hw);
+}
+// The Z window of the widest LoG in the float arithmetic of the kernels' own plan (plan_log), plus the plane the 26-neighbour
+// scan reads beyond it: every slab caller of the blob stage takes its halo depth from here, so it cannot be one plane short
+// of what the filters read (a double-precision restatement of floor(ratio * sigma * (1 + delta/2)) can round the other way).
+int visfd_hip_blob_halo_depth(const float* blob_sigma, int n_sigma, float delta, float ratio, int* depth_out) {
+  VH_REQUIRE(blob_sigma && n_sigma >= 1 && depth_out, "bad argument");
+  int hw = 0;
+  for (int i = 0; i < n_sigma; i++) {
+    const float sg[3] = {blob_sigma[i], blob_sigma[i], blob_sigma[i]};
+    hw = std::max(hw, plan_log(sg, delta, ratio).hw[2]);
+  }
+  *depth_out = hw + 1;
+  return VISFD_HIP_OK;
 }
 
 // ---- a4 ------------------------------------------------------------------------------------

@@ -112,7 +112,9 @@ int slab_common(visfd_hip_ctx* ctx, int rank, int world, i64 nz_global, int ghos
   s->nz_local = s->hi - s->lo;
   s->own0 = s->z0 - s->lo;
   s->own1 = s->z1 - s->lo;
-  if (world > 1 && s->z1 - s->z0 < ghost) {
+  // decided from the THINNEST slab (nz_global / world planes), so every rank gives the same answer: a rank that accepted
+  // while another refused would wait for ever in the first collective (ncclCommInitRank, the first halo exchange)
+  if (world > 1 && base < ghost) {
     delete s;
     return fail(VISFD_HIP_EINVAL, "slabs thinner than the ghost depth are not supported");
   }
@@ -577,9 +579,8 @@ int visfd_hip_blob_dog_slab_dev(visfd_hip_slab* s, float* src, int64_t nx, int64
                                 int64_t max_cap, int64_t* n_max) {
   VH_REQUIRE(s && src && blob_sigma && n_sigma >= 1 && minima && maxima && n_min && n_max, "bad argument");
   VH_HIP(hipSetDevice(s->ctx->device));
-  float smax = 0.0f;
-  for (int i = 0; i < n_sigma; i++) smax = std::max(smax, blob_sigma[i]);
-  const int depth = (int)std::floor(ratio * (double)smax * (1.0 + 0.5 * delta)) + 1;
+  int depth = 0;
+  VH_TRY(visfd_hip_blob_halo_depth(blob_sigma, n_sigma, delta, ratio, &depth));
   VH_REQUIRE(s->world == 1 || depth <= s->ghost, "ghost depth too small for the widest LoG");
   if (!src_halo_ready) {
     float* v[1] = {src};

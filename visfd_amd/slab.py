@@ -45,7 +45,9 @@ class SlabLayout:
         self.nz_local = self.hi - self.lo
         self.own0 = self.z0 - self.lo               # owned planes inside the local array
         self.own1 = self.z1 - self.lo
-        if world > 1 and (self.z1 - self.z0) < ghost:
+        # decided from the THINNEST slab (base planes), so every rank gives the same answer (a rank that went on would wait
+        # for ever in the first halo exchange)
+        if world > 1 and base < ghost:
             raise ValueError("slabs thinner than the ghost depth are not supported")
 
     def owned(self, t):
@@ -279,8 +281,7 @@ def blob_detect_slab(ops, layout, src, sigmas, truncate_threshold=0.03, delta=0.
     4-D non-max scan keeps candidates of owned planes only, lists are merged on every rank."""
     L = layout
     ratio = api.ratio_from_threshold(truncate_threshold)
-    smax = float(np.max(sigmas)) * (1.0 + 0.5 * delta)
-    depth = int(math.floor(ratio * smax)) + 1
+    depth = api.blob_halo_depth(sigmas, delta, ratio)   # the LoG kernels' own float arithmetic (visfd_hip_blob_halo_depth)
     assert L.world == 1 or depth <= L.ghost, "ghost depth too small for the widest LoG"
     if isinstance(L, api.Slab) and not use_ratios:   # the C-ABI path (absolute thresholds prune inside the scan)
         check_stream(L.ctx, src)
