@@ -59,7 +59,9 @@ void* visfd_hip_get_stream(visfd_hip_ctx* ctx);
 /* release the cached workspace (it otherwise persists between calls) */
 int visfd_hip_trim(visfd_hip_ctx* ctx);
 const char* visfd_hip_last_error(void);
-int visfd_hip_abi_version(void);   /* 10: entry points only get added between versions */
+int visfd_hip_abi_version(void);   /* 10: entry points only get added between versions (since 10 was set: the
+                                     * morphology entries visfd_hip_sphere_structure, visfd_hip_morph_sphere[_dev],
+                                     * visfd_hip_morph_table[_dev] and visfd_hip_morph_last_path) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -85,6 +87,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *   tv_no_replay     csrc/tv_tiled.hip only: every sender plane is listed again for every receiver plane (no reuse within a run)
  *   tv_max_wg        cap on the number of persistent workgroups (tests: forces many units of work per workgroup)
  *   blob_test_cap    tests: capacity the pipelined blob scan pretends to have (exercises its overflow path)
+ *   morph_general    1: morphology always walks the element entry by entry (csrc/morph.hip), never takes the flat X-run
+ *                    kernel; results are bit-identical either way
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -132,6 +136,38 @@ int visfd_hip_local_fluctuations_dev(visfd_hip_ctx*, const float* src, float* ds
  * sigma = radius / (9 pi / 2)^(1/6); a negative truncate_ratio is replaced by (-log threshold)^(1/exponent). */
 int visfd_hip_fluctuation_sigmas(const float radius[3], float exponent, float truncate_ratio,
                                  float truncate_threshold, float sigma_out[3], float* ratio_out);
+
+/* ---- m1: grayscale morphology (lib/visfd/morphology.hpp:134-597) ------------------------------- */
+#define VISFD_HIP_MORPH_DILATE 0          /* DilateSphere / Dilate                         morphology.hpp:134-172, 241-330 */
+#define VISFD_HIP_MORPH_ERODE 1           /* ErodeSphere / Erode                           :188-229, 336-420 */
+#define VISFD_HIP_MORPH_OPEN 2            /* OpenSphere: erode, then dilate                :431-468 */
+#define VISFD_HIP_MORPH_CLOSE 3           /* CloseSphere: dilate, then erode               :475-510 */
+#define VISFD_HIP_MORPH_TOP_HAT_WHITE 4   /* WhiteTopHatSphere: dst = dst - open(src)      :517-553 */
+#define VISFD_HIP_MORPH_TOP_HAT_BLACK 5   /* BlackTopHatSphere: dst = close(src) - dst     :560-597 */
+/* The structuring element of DilateSphere / ErodeSphere (morphology.hpp:254-316), host arithmetic: entries (dx, dy, dz)
+ * in dxyz (3 ints each) and b, dz outermost, then dy, then dx.  *n = the number of entries; the first min(n, cap) are
+ * written (cap == 0: count only; 0 < cap < n: VISFD_HIP_ECAPACITY).  ceil(max(radius, radius_max)) must be <= 128. */
+int visfd_hip_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, int64_t cap,
+                               int64_t* n);
+/* op = VISFD_HIP_MORPH_*, with the sphere element above.  The reference library's semantics: voxels with mask == 0 are
+ * not written (dst keeps its values there); neighbours with mask == 0 or outside the image are skipped; the top-hats
+ * read dst.  A dst that overlaps src or mask is VISFD_HIP_EINVAL.  The temporaries live in the context's workspace.
+ * Flat elements made of symmetric X-runs of half-length <= 10 (every flat ball of radius < 11) run on the X-run kernel,
+ * everything else on the general element walk; both give the reference's bits. */
+int visfd_hip_morph_sphere(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                           int64_t nx, int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax);
+int visfd_hip_morph_sphere_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                               int64_t nx, int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax);
+/* Dilate / Erode (op VISFD_HIP_MORPH_DILATE or _ERODE) with an arbitrary element of n entries: (dx, dy, dz) in dxyz
+ * (3 ints each) and b, walked in the given order (host arrays on both faces). */
+int visfd_hip_morph_table(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                          int64_t nx, int64_t ny, int64_t nz, int op, const int* dxyz, const float* b, int64_t n);
+int visfd_hip_morph_table_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                              int64_t nx, int64_t ny, int64_t nz, int op, const int* dxyz, const float* b, int64_t n);
+/* the kernel the context's last morphology call ran: VISFD_HIP_MORPH_PATH_* (-1 before the first call) */
+#define VISFD_HIP_MORPH_PATH_GENERAL 0    /* morph_kernel: the element walked entry by entry */
+#define VISFD_HIP_MORPH_PATH_XRUNS 1      /* morph_runs_kernel: window maxima of X-runs, zero-sign fix-up of erosions */
+int visfd_hip_morph_last_path(visfd_hip_ctx*, int* path);
 
 /* ---- a6: ApplyDog, lib/visfd/filter3d.hpp:1338-1402 -------------------------------------------- */
 int visfd_hip_apply_dog(visfd_hip_ctx*, const float* src, float* dst, const float* mask,

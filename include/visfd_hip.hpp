@@ -30,6 +30,7 @@
 #include <limits>
 #include <ostream>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -314,6 +315,83 @@ inline void ApplyLog(const int image_size[3], float const* const* const* src, fl
                      std::ostream* pReportProgress = nullptr) {
   const float s[3] = {sigma, sigma, sigma};
   ApplyLog(image_size, src, dest, mask, s, delta_sigma_over_sigma, truncate_ratio, pA, pB, pReportProgress);
+}
+
+// ---- grayscale morphology: lib/visfd/morphology.hpp:134-597 ------------------------------------------------------
+// Dilate / Erode with an arbitrary structuring element: a list of (ix, iy, iz, b), walked in the given order.
+namespace hip_detail {
+inline void morph_table(int op, const std::vector<std::tuple<int, int, int, float> >& structure_factor,
+                        const int image_size[3], float const* const* const* src, float*** dest,
+                        float const* const* const* mask) {
+  require_contiguous(src, image_size);
+  require_contiguous(dest, image_size);
+  require_contiguous(mask, image_size);
+  std::vector<int> dxyz;
+  std::vector<float> b;
+  dxyz.reserve(3 * structure_factor.size());
+  b.reserve(structure_factor.size());
+  for (size_t k = 0; k < structure_factor.size(); k++) {
+    dxyz.push_back(std::get<0>(structure_factor[k]));
+    dxyz.push_back(std::get<1>(structure_factor[k]));
+    dxyz.push_back(std::get<2>(structure_factor[k]));
+    b.push_back(std::get<3>(structure_factor[k]));
+  }
+  check(visfd_hip_morph_table(context(), flat(src), flat(dest), flat(mask), image_size[0], image_size[1], image_size[2],
+                              op, dxyz.empty() ? nullptr : &dxyz[0], b.empty() ? nullptr : &b[0],
+                              (int64_t)b.size()));
+}
+// the *Sphere functions: dest keeps its values where mask == 0; the top-hats read it (dest -= open(src), dest = close(src) - dest)
+inline void morph_sphere(int op, float radius, const int image_size[3], float const* const* const* src, float*** dest,
+                         float const* const* const* mask, float radius_max, float bmax) {
+  require_contiguous(src, image_size);
+  require_contiguous(dest, image_size);
+  require_contiguous(mask, image_size);
+  check(visfd_hip_morph_sphere(context(), flat(src), flat(dest), flat(mask), image_size[0], image_size[1], image_size[2],
+                               op, radius, radius_max, bmax));
+}
+}  // namespace hip_detail
+
+inline void Dilate(std::vector<std::tuple<int, int, int, float> > structure_factor, const int image_size[3],
+                   float const* const* const* aaafSource, float*** aaafDest,
+                   float const* const* const* aaafMask = nullptr, std::ostream* = nullptr) {
+  hip_detail::morph_table(VISFD_HIP_MORPH_DILATE, structure_factor, image_size, aaafSource, aaafDest, aaafMask);
+}
+inline void Erode(std::vector<std::tuple<int, int, int, float> > structure_factor, const int image_size[3],
+                  float const* const* const* aaafSource, float*** aaafDest,
+                  float const* const* const* aaafMask = nullptr, std::ostream* = nullptr) {
+  hip_detail::morph_table(VISFD_HIP_MORPH_ERODE, structure_factor, image_size, aaafSource, aaafDest, aaafMask);
+}
+inline void DilateSphere(float radius, int const image_size[3], float const* const* const* aaafSource, float*** aaafDest,
+                         float const* const* const* aaafMask = nullptr, float radius_max = 0.0, float bmax = 0.0,
+                         std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_DILATE, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max, bmax);
+}
+inline void ErodeSphere(float radius, int const image_size[3], float const* const* const* aaafSource, float*** aaafDest,
+                        float const* const* const* aaafMask = nullptr, float radius_max = 0.0, float bmax = 0.0,
+                        std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_ERODE, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max, bmax);
+}
+inline void OpenSphere(float radius, const int image_size[3], float const* const* const* aaafSource, float*** aaafDest,
+                       float const* const* const* aaafMask = nullptr, float radius_max = 0.0, float bmax = 0.0,
+                       std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_OPEN, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max, bmax);
+}
+inline void CloseSphere(float radius, const int image_size[3], float const* const* const* aaafSource, float*** aaafDest,
+                        float const* const* const* aaafMask = nullptr, float radius_max = 0.0, float bmax = 0.0,
+                        std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_CLOSE, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max, bmax);
+}
+inline void WhiteTopHatSphere(float radius, const int image_size[3], float const* const* const* aaafSource,
+                              float*** aaafDest, float const* const* const* aaafMask = nullptr, float radius_max = 0.0,
+                              float bmax = 0.0, std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_TOP_HAT_WHITE, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max,
+                           bmax);
+}
+inline void BlackTopHatSphere(float radius, const int image_size[3], float const* const* const* aaafSource,
+                              float*** aaafDest, float const* const* const* aaafMask = nullptr, float radius_max = 0.0,
+                              float bmax = 0.0, std::ostream* = nullptr) {
+  hip_detail::morph_sphere(VISFD_HIP_MORPH_TOP_HAT_BLACK, radius, image_size, aaafSource, aaafDest, aaafMask, radius_max,
+                           bmax);
 }
 
 // ---- LocalFluctuations: lib/visfd/filter3d.hpp:1698-1711 (Gaussian weights: exponent must be 2) -------

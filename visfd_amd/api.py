@@ -21,6 +21,10 @@ LIB_PATH = os.environ.get("VISFD_HIP_LIB") or os.path.join(_HERE, "libvisfd_hip.
 INCREASING_EIVALS = 0
 DECREASING_EIVALS = 1
 
+# grayscale morphology ops (VISFD_HIP_MORPH_*, lib/visfd/morphology.hpp:134-597)
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_TOP_HAT_WHITE, MORPH_TOP_HAT_BLACK = range(6)
+MORPH_PATH_GENERAL, MORPH_PATH_XRUNS = 0, 1   # visfd_hip_morph_last_path
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _i64 = C.c_int64
@@ -54,6 +58,12 @@ _SIGS = {
     "visfd_hip_ratio_from_threshold": (C.c_float, [C.c_float]),
     "visfd_hip_local_fluctuations": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
     "visfd_hip_local_fluctuations_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
+    "visfd_hip_sphere_structure": (C.c_int, [C.c_float, C.c_float, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64)]),
+    "visfd_hip_morph_sphere": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
+    "visfd_hip_morph_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
+    "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
+    "visfd_hip_morph_table_dev": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
+    "visfd_hip_morph_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_fluctuation_sigmas": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _fp, C.POINTER(C.c_float)]),
     "visfd_hip_gauss_halfwidths": (C.c_int, [_fp, C.c_float, _ip]),
     "visfd_hip_separable3d": (C.c_int, [_vp] + _VOL + [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
@@ -262,6 +272,26 @@ def fluctuation_sigmas(radius, exponent=2.0, truncate_ratio=-1.0, truncate_thres
     load_library().visfd_hip_fluctuation_sigmas(_f3(radius), float(exponent), float(truncate_ratio),
                                                 float(truncate_threshold), sg, C.byref(r))
     return tuple(sg), r.value
+
+
+def sphere_structure(radius, radius_max=0.0, bmax=0.0):
+    """The structuring element of DilateSphere / ErodeSphere (morphology.hpp:254-316): (dxyz int32 (n, 3), b float32 (n,)),
+    in the reference's order (dz outermost, then dy, then dx)."""
+    L = load_library()
+    n = C.c_int64()
+    _chk_host(L, L.visfd_hip_sphere_structure(float(radius), float(radius_max), float(bmax), None, None, 0, C.byref(n)))
+    d = np.zeros((max(n.value, 1), 3), np.int32)
+    b = np.zeros(max(n.value, 1), np.float32)
+    _chk_host(L, L.visfd_hip_sphere_structure(float(radius), float(radius_max), float(bmax), d.ctypes.data_as(_ip),
+                                              b.ctypes.data_as(_fp), len(b), C.byref(n)))
+    return d[:n.value].copy(), b[:n.value].copy()
+
+
+def _morph_table(dxyz, b):
+    d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
+    bb = np.ascontiguousarray(b, np.float32).reshape(-1)
+    assert len(d) == len(bb), "one b per (dx, dy, dz)"
+    return d, bb
 
 
 def tv_tables(sigma_tv, cutoff):
@@ -556,6 +586,56 @@ class Context:
                                                        float(exponent), float(ratio), int(normalize)))
         return dst
 
+    def morph_sphere(self, op, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        """DilateSphere / ErodeSphere / OpenSphere / CloseSphere / WhiteTopHatSphere / BlackTopHatSphere (op = MORPH_*,
+        morphology.hpp:241-597).  dst (default: a copy of src, as filter_mrc starts its output) keeps its values where
+        mask == 0 and is what the top-hats subtract from / are subtracted from; a new array is returned."""
+        nz, ny, nx = src.shape
+        dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
+        self._chk(self._L.visfd_hip_morph_sphere(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, int(op),
+                                                 float(radius), float(radius_max), float(bmax)))
+        return dst
+
+    def dilate_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_DILATE, src, radius, radius_max, bmax, mask, dst)
+
+    def erode_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_ERODE, src, radius, radius_max, bmax, mask, dst)
+
+    def open_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_OPEN, src, radius, radius_max, bmax, mask, dst)
+
+    def close_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_CLOSE, src, radius, radius_max, bmax, mask, dst)
+
+    def white_top_hat_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_TOP_HAT_WHITE, src, radius, radius_max, bmax, mask, dst)
+
+    def black_top_hat_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
+        return self.morph_sphere(MORPH_TOP_HAT_BLACK, src, radius, radius_max, bmax, mask, dst)
+
+    def morph_table(self, op, src, dxyz, b, mask=None, dst=None):
+        """Dilate / Erode (op MORPH_DILATE or MORPH_ERODE, morphology.hpp:134-229) with an arbitrary element: dxyz (n, 3)
+        offsets and b (n,), walked in the given order."""
+        nz, ny, nx = src.shape
+        d, bb = _morph_table(dxyz, b)
+        dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
+        self._chk(self._L.visfd_hip_morph_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, int(op),
+                                                d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
+        return dst
+
+    def morph_last_path(self):
+        """The kernel the last morphology call ran: MORPH_PATH_GENERAL or MORPH_PATH_XRUNS (-1 before the first)."""
+        p = C.c_int()
+        self._chk(self._L.visfd_hip_morph_last_path(self._h, C.byref(p)))
+        return p.value
+
+    def dilate(self, src, dxyz, b, mask=None, dst=None):
+        return self.morph_table(MORPH_DILATE, src, dxyz, b, mask, dst)
+
+    def erode(self, src, dxyz, b, mask=None, dst=None):
+        return self.morph_table(MORPH_ERODE, src, dxyz, b, mask, dst)
+
     def dog(self, src, sigma_a, sigma_b, hw, mask=None):
         nz, ny, nx = src.shape
         dst = np.empty_like(src)
@@ -746,6 +826,42 @@ class Context:
         nz, ny, nx = src.shape
         self._chk(self._L.visfd_hip_local_fluctuations_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
                                                            _f3(sigma), float(exponent), float(ratio), int(normalize)))
+
+    def morph_sphere_dev(self, op, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        """morph_sphere on device tensors; dst is read (top-hats, masked voxels) and written in place."""
+        nz, ny, nx = src.shape
+        self._chk(self._L.visfd_hip_morph_sphere_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, int(op),
+                                                     float(radius), float(radius_max), float(bmax)))
+
+    def dilate_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_DILATE, src, dst, radius, radius_max, bmax, mask)
+
+    def erode_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_ERODE, src, dst, radius, radius_max, bmax, mask)
+
+    def open_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_OPEN, src, dst, radius, radius_max, bmax, mask)
+
+    def close_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_CLOSE, src, dst, radius, radius_max, bmax, mask)
+
+    def white_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_TOP_HAT_WHITE, src, dst, radius, radius_max, bmax, mask)
+
+    def black_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_TOP_HAT_BLACK, src, dst, radius, radius_max, bmax, mask)
+
+    def morph_table_dev(self, op, src, dst, dxyz, b, mask=None):
+        nz, ny, nx = src.shape
+        d, bb = _morph_table(dxyz, b)
+        self._chk(self._L.visfd_hip_morph_table_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, int(op),
+                                                    d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
+
+    def dilate_dev(self, src, dst, dxyz, b, mask=None):
+        self.morph_table_dev(MORPH_DILATE, src, dst, dxyz, b, mask)
+
+    def erode_dev(self, src, dst, dxyz, b, mask=None):
+        self.morph_table_dev(MORPH_ERODE, src, dst, dxyz, b, mask)
 
     def gauss_slab_dev(self, src, dst, z_lo, nz_global, sigma, hw, normalize=True):
         nz, ny, nx = src.shape

@@ -16,6 +16,9 @@
 //   -tv RATIO | -tv-angle-exponent N | -tv-truncate R | -tv-best F | -detection-threshold T
 //   -save-progress BASE        writes BASE_tensor_{0..5}.rec           (handlers.cpp:1897-1922)
 //   -truncate R | -truncate-threshold T | -normalize-filters no | -bin 1 | -np N (ignored)
+//   -dilate|-dilation R | -erode|-erosion R | -open|-opening R | -close|-closing R | -top-hat-white R | -top-hat-black R
+//   -dilate-binary-soft|-dilation-binary-soft R RMAX BMAX | -erode-binary-soft|-erosion-binary-soft R RMAX BMAX
+//                                                                      (settings.cpp:722-915, handlers.cpp:41-145)
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is written from the MRC2014 layout description (1024-byte header: nx,ny,nz,mode,
@@ -143,7 +146,10 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY } type = NONE;
+  // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until main() divides
+  int morph_op = VISFD_HIP_MORPH_DILATE;
+  float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
   float width_a[3] = {0, 0, 0}, width_b[3] = {0, 0, 0}, log_width[3] = {0, 0, 0};
   float template_background_radius[3] = {-1, -1, -1};        // settings.cpp:222-225 (-fluct)
   float template_background_exponent = 2.0f;
@@ -202,6 +208,13 @@ float num(const vector<string>& v, size_t i, const string& flag) {
   try { return std::stof(v[i]); } catch (...) { throw VisfdErr("Error: The " + flag + " argument must be followed by a number.\n"); }
 }
 
+// the morphology flags' arguments (settings.cpp:722-915): present, not empty, not starting with '-', a number
+float morph_num(const vector<string>& v, size_t i, const string& flag, const char* what) {
+  const string msg = "Error: The " + flag + " argument must be followed by " + what + "\n";
+  if (i >= v.size() || v[i].empty() || v[i][0] == '-') throw VisfdErr(msg);
+  try { return std::stof(v[i]); } catch (...) { throw VisfdErr(msg); }
+}
+
 Settings parse(int argc, char** argv) {
   Settings s;
   vector<string> v(argv + 1, argv + argc);
@@ -232,6 +245,26 @@ Settings parse(int argc, char** argv) {
       need(3);
       for (int d = 0; d < 3; d++) s.template_background_radius[d] = num(v, i + 1 + d, f);
       s.type = Settings::LOCAL_FLUCTUATIONS; s.masked_voxel_brightness = 0.0f; i += 4;
+    }
+    else if (f == "-dilate" || f == "-dilation" || f == "-erode" || f == "-erosion" || f == "-open" || f == "-opening" ||
+             f == "-close" || f == "-closing" || f == "-top-hat-white" || f == "-top-hat-black") {
+      s.morph_r = morph_num(v, i + 1, f, "a nonnegative number");
+      s.morph_op = (f == "-dilate" || f == "-dilation") ? VISFD_HIP_MORPH_DILATE
+                 : (f == "-erode" || f == "-erosion") ? VISFD_HIP_MORPH_ERODE
+                 : (f == "-open" || f == "-opening") ? VISFD_HIP_MORPH_OPEN
+                 : (f == "-close" || f == "-closing") ? VISFD_HIP_MORPH_CLOSE
+                 : (f == "-top-hat-white") ? VISFD_HIP_MORPH_TOP_HAT_WHITE : VISFD_HIP_MORPH_TOP_HAT_BLACK;
+      s.type = Settings::MORPHOLOGY; i += 2;
+    }
+    else if (f == "-dilate-binary-soft" || f == "-dilation-binary-soft" || f == "-erode-binary-soft" ||
+             f == "-erosion-binary-soft") {
+      // all three numbers are required (the reference's -dilate-binary-soft tests only two of them before reading the third)
+      for (size_t k = 1; k <= 3; k++) morph_num(v, i + k, f, "nonnegative numbers");
+      s.morph_r = morph_num(v, i + 1, f, "nonnegative numbers");
+      s.morph_rmax = morph_num(v, i + 2, f, "nonnegative numbers");
+      s.morph_bmax = morph_num(v, i + 3, f, "nonnegative numbers");
+      s.morph_op = (f == "-dilate-binary-soft" || f == "-dilation-binary-soft") ? VISFD_HIP_MORPH_DILATE : VISFD_HIP_MORPH_ERODE;
+      s.type = Settings::MORPHOLOGY; i += 4;
     }
     else if (f == "-gauss-aniso") { need(3); for (int d = 0; d < 3; d++) s.width_a[d] = num(v, i + 1 + d, f); s.type = Settings::GAUSS; i += 4; }
     else if (f == "-dog") {
@@ -781,6 +814,8 @@ int main(int argc, char** argv) {
     for (int d = 0; d < 3; d++) { s.width_a[d] /= vw[d]; s.width_b[d] /= vw[d]; s.log_width[d] /= vw[d]; s.template_background_radius[d] /= vw[d]; }
     s.tv_sigma /= vw[0];
     for (size_t k = 0; k < s.blob_diameters.size(); k++) s.blob_diameters[k] /= vw[0];
+    s.morph_r /= vw[0];      // filter_mrc.cpp:297-298 (bmax is not a length)
+    s.morph_rmax /= vw[0];
 
     tomo_out.alloc(size[0], size[1], size[2]);
     std::memcpy(tomo_out.data(), tomo_in.data(), tomo_in.nvox() * 4);   // filter_mrc.cpp:398
@@ -865,6 +900,22 @@ int main(int argc, char** argv) {
           out << c[i][0] * vw[0] << " " << c[i][1] * vw[1] << " " << c[i][2] * vw[2] << " " << dia[i] * vw[0] << " "
               << sc[i] << "\n";
         }
+      }
+    } else if (s.type == Settings::MORPHOLOGY) {
+      // HandleDilation ... HandleTopHatBlack, handlers.cpp:41-145: tomo_out starts as a copy of the input (the top-hats read it)
+      switch (s.morph_op) {
+        case VISFD_HIP_MORPH_DILATE:
+          DilateSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+        case VISFD_HIP_MORPH_ERODE:
+          ErodeSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+        case VISFD_HIP_MORPH_OPEN:
+          OpenSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+        case VISFD_HIP_MORPH_CLOSE:
+          CloseSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+        case VISFD_HIP_MORPH_TOP_HAT_WHITE:
+          WhiteTopHatSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+        default:
+          BlackTopHatSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
       }
     } else if (s.type == Settings::BLOB_NONMAX) {
       handle_blob_nonmax(s, vw, M, size);

@@ -1,6 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/visfd_hip.h.
 // Device-pointer entry points orchestrate the stage functions; host-pointer entry points stage the
 // caller's volumes through the context workspace (H2D, run, D2H) and are synchronous.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cctype>
@@ -348,6 +349,7 @@ const OptionDesc kOptions[] = {
     {"tv_no_replay", &visfd_hip_options::tv_no_replay, nullptr}, {"tv_max_wg", &visfd_hip_options::tv_max_wg, nullptr},
     {"tv_poison", &visfd_hip_options::tv_poison, nullptr}, {"tv_no_fold", &visfd_hip_options::tv_no_fold, nullptr}, {"tv_exact_tiled", &visfd_hip_options::tv_exact_tiled, nullptr}, {"tv_reserve_wg", &visfd_hip_options::tv_reserve_wg, nullptr},
     {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
+    {"morph_general", &visfd_hip_options::morph_general, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {
@@ -424,6 +426,7 @@ int visfd_hip_trim(visfd_hip_ctx* ctx) {
   VH_HIP(hipStreamSynchronize(ctx->stream));
   ctx->tv_table_dev = nullptr;   // lives in a workspace slot
   ctx->tv_table_h = -1;
+  ctx->morph_tab.clear();        // so does the structuring element
   for (int s = 0; s < WS_NSLOTS; s++) {
     if (ctx->slot_ptr[s]) VH_HIP(hipFree(ctx->slot_ptr[s]));
     ctx->slot_ptr[s] = nullptr;
@@ -1144,6 +1147,175 @@ int visfd_hip_tensor_saliency(visfd_hip_ctx* ctx, const float* ten, const float*
   VH_TRY(upload(ctx, WS_H2D_3, sal, n, &dsal));
   VH_TRY(dev_tensor_saliency(ctx, pten, dm, nvox, order, dsal));
   return download(ctx, sal, dsal, n);
+}
+
+// ---- m1: grayscale morphology (lib/visfd/morphology.hpp:134-597) ---------------------------------
+namespace {
+
+// puts the element in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b); an element equal to the one already
+// there is not sent again.  Fills `el`: count, bounding box, flatness and, for flat elements made of symmetric X-runs,
+// the run length of every (dy, dz) row (the X-run kernel's input).
+int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el) {
+  VH_REQUIRE(n >= 0 && n < ((i64)1 << 31), "morphology: too many structuring element entries");
+  VH_REQUIRE(n == 0 || (dxyz && b), "null argument");
+  std::vector<int> t((size_t)(4 * n));
+  el->n = n;
+  el->flat = true;
+  int* lo = el->lo;
+  int* hi = el->hi;
+  for (int d = 0; d < 3; d++) lo[d] = hi[d] = 0;
+  for (i64 k = 0; k < n; k++) {
+    for (int d = 0; d < 3; d++) {
+      const int v = dxyz[3 * k + d];
+      VH_REQUIRE(v > -(1 << 30) && v < (1 << 30), "morphology: structuring element offsets must be below 2^30");
+      lo[d] = (k == 0 || v < lo[d]) ? v : lo[d];
+      hi[d] = (k == 0 || v > hi[d]) ? v : hi[d];
+      t[4 * k + d] = v;
+    }
+    int bits;
+    std::memcpy(&bits, &b[k], 4);
+    t[4 * k + 3] = bits;
+    if (bits != 0) el->flat = false;
+  }
+  // X-runs: each (dy, dz) row holds exactly the offsets dx = -L..L (in any order, repeats allowed)
+  el->runs = false;
+  int R = 0;
+  for (int d = 0; d < 3; d++) R = std::max(R, std::max(-lo[d], hi[d]));
+  if (n > 0 && el->flat && R <= MORPH_RUN_MAX_R) {
+    const int S = 2 * R + 1;
+    std::vector<uint32_t> rows((size_t)(S * S), 0u);   // bit dx + R of row (dy, dz)
+    for (i64 k = 0; k < n; k++) rows[(size_t)((t[4 * k + 2] + R) * S + t[4 * k + 1] + R)] |= 1u << (t[4 * k] + R);
+    bool ok = true;
+    for (int r = 0; r < S * S && ok; r++) {
+      el->run_len[r] = -1;
+      if (!rows[r]) continue;
+      int L = 0;
+      while (L < R && (rows[r] >> (R - L - 1) & 1u)) L++;
+      const uint32_t want = ((1u << (2 * L + 1)) - 1u) << (R - L);
+      ok = rows[r] == want;
+      el->run_len[r] = (signed char)L;
+    }
+    el->runs = ok;
+    el->R = R;
+  }
+  if (n == 0 || t == ctx->morph_tab) return VISFD_HIP_OK;
+  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read the element now in the slot
+  int* d = nullptr;
+  VH_TRY(ws(ctx, WS_MORPH_TAB, t.size(), &d));
+  VH_HIP(hipMemcpyAsync(d, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->morph_tab.swap(t);
+  return VISFD_HIP_OK;
+}
+
+// one op with the element in WS_MORPH_TAB.  Open = erode then dilate, close = dilate then erode (morphology.hpp:431-510),
+// both steps with the same mask and element; the top-hats fuse their subtraction into the second step.
+int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
+              MorphElem el) {
+  if (ctx->opt.morph_general) el.runs = false;
+  const i64 nv = nx * ny * nz;
+  const float* s0 = src;
+  if (mask) {
+    float* sn = nullptr;
+    VH_TRY(ws(ctx, WS_MORPH_SRC, (size_t)nv, &sn));
+    VH_TRY(dev_nan_masked(ctx, src, mask, sn, nv));
+    s0 = sn;
+  }
+  int path = 0;
+  if (op == VISFD_HIP_MORPH_DILATE || op == VISFD_HIP_MORPH_ERODE) {
+    VH_TRY(dev_morph_table(ctx, s0, dst, mask, nx, ny, nz, el, op == VISFD_HIP_MORPH_DILATE, 0, false, &path));
+    ctx->morph_last_path = path;
+    return VISFD_HIP_OK;
+  }
+  float* tmp = nullptr;
+  VH_TRY(ws(ctx, WS_MORPH_TMP, (size_t)nv, &tmp));
+  const bool dilate_first = (op == VISFD_HIP_MORPH_CLOSE || op == VISFD_HIP_MORPH_TOP_HAT_BLACK);
+  const int epi = op == VISFD_HIP_MORPH_TOP_HAT_WHITE ? 1 : op == VISFD_HIP_MORPH_TOP_HAT_BLACK ? 2 : 0;
+  VH_TRY(dev_morph_table(ctx, s0, tmp, mask, nx, ny, nz, el, dilate_first, 0, mask != nullptr, &path));
+  VH_TRY(dev_morph_table(ctx, tmp, dst, mask, nx, ny, nz, el, !dilate_first, epi, false, &path));
+  ctx->morph_last_path = path;
+  return VISFD_HIP_OK;
+}
+
+bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
+
+int morph_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
+                int max_op) {
+  VH_REQUIRE(ctx && src && dst, "null argument");
+  VH_REQUIRE(op >= 0 && op <= max_op, "unknown morphology op");
+  VH_TRY(check_dims(nx, ny, nz));
+  VH_REQUIRE(!overlaps(src, dst, nx * ny * nz), "morphology cannot run in place (dst overlaps src)");
+  VH_REQUIRE(!overlaps(mask, dst, nx * ny * nz), "morphology: dst overlaps mask");
+  VH_HIP(hipSetDevice(ctx->device));
+  return VISFD_HIP_OK;
+}
+
+// the host face: dst goes up too (masked voxels keep their values, the top-hats read it)
+extern "C++" template <typename Run>
+int morph_host(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, Run run) {
+  const size_t n = (size_t)(nx * ny * nz);
+  float *ds, *dm, *dd;
+  VH_TRY(upload(ctx, WS_H2D_0, src, n, &ds));
+  VH_TRY(upload(ctx, WS_H2D_1, mask, n, &dm));
+  VH_TRY(upload(ctx, WS_H2D_2, dst, n, &dd));
+  VH_TRY(run(ds, dd, dm));
+  return download(ctx, dst, dd, n);
+}
+
+}  // namespace
+
+int visfd_hip_morph_last_path(visfd_hip_ctx* ctx, int* path) {
+  VH_REQUIRE(ctx && path, "null argument");
+  *path = ctx->morph_last_path;
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, int64_t cap,
+                               int64_t* n) {
+  VH_REQUIRE(n && cap >= 0 && (cap == 0 || (dxyz && b)), "bad argument");
+  VH_REQUIRE(std::isfinite(radius) && std::isfinite(radius_max) && std::isfinite(bmax),
+             "sphere radii and bmax must be finite");
+  VH_REQUIRE(std::ceil(std::max(radius, radius_max)) <= 128.0f, "sphere radius must be at most 128 voxels");
+  *n = host_sphere_structure(radius, radius_max, bmax, dxyz, b, cap);
+  if (cap > 0 && cap < *n) return fail(VISFD_HIP_ECAPACITY, "structuring element has more entries than cap");
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_morph_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
+                               int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax) {
+  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
+  int64_t n = 0;
+  VH_TRY(visfd_hip_sphere_structure(radius, radius_max, bmax, nullptr, nullptr, 0, &n));
+  std::vector<int> dxyz((size_t)(3 * n + 3));
+  std::vector<float> b((size_t)(n + 1));
+  VH_TRY(visfd_hip_sphere_structure(radius, radius_max, bmax, dxyz.data(), b.data(), n + 1, &n));
+  MorphElem el;
+  VH_TRY(morph_put_table(ctx, dxyz.data(), b.data(), n, &el));
+  return morph_run(ctx, src, dst, mask, nx, ny, nz, op, el);
+}
+
+int visfd_hip_morph_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                           int64_t nz, int op, float radius, float radius_max, float bmax) {
+  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
+  return morph_host(ctx, src, dst, mask, nx, ny, nz, [&](const float* ds, float* dd, const float* dm) {
+    return visfd_hip_morph_sphere_dev(ctx, ds, dd, dm, nx, ny, nz, op, radius, radius_max, bmax);
+  });
+}
+
+int visfd_hip_morph_table_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
+                              int64_t ny, int64_t nz, int op, const int* dxyz, const float* b, int64_t n) {
+  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_ERODE));
+  MorphElem el;
+  VH_TRY(morph_put_table(ctx, dxyz, b, n, &el));
+  return morph_run(ctx, src, dst, mask, nx, ny, nz, op, el);
+}
+
+int visfd_hip_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                          int64_t nz, int op, const int* dxyz, const float* b, int64_t n) {
+  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_ERODE));
+  return morph_host(ctx, src, dst, mask, nx, ny, nz, [&](const float* ds, float* dd, const float* dm) {
+    return visfd_hip_morph_table_dev(ctx, ds, dd, dm, nx, ny, nz, op, dxyz, b, n);
+  });
 }
 
 }  // extern "C"

@@ -53,6 +53,9 @@ enum Slot {
   WS_TVSCRATCH,                    // tensor voting: per-workgroup rings of compacted sender planes (exact kernel) / the launch's sender lists
   WS_TVLIST,                       // tolerance-mode tensor voting: row offsets of the sender lists
   WS_H2D_0, WS_H2D_1, WS_H2D_2, WS_H2D_3, WS_H2D_4,  // staging for the host-pointer face
+  WS_MORPH_TAB,                    // morphology: the structuring element on the device (host copy in visfd_hip_ctx::morph_tab)
+  WS_MORPH_SRC,                    // morphology: the source with masked voxels replaced by NaN
+  WS_MORPH_TMP,                    // morphology: the intermediate image of open / close / the top-hats
   WS_NSLOTS
 };
 
@@ -78,6 +81,7 @@ struct visfd_hip_options {
   int tv_reserve_wg = 0;    // workgroup slots the persistent voting grid leaves free (slab runs: the halo transport's kernels)
   int tv_max_wg = 0;        // cap on the persistent grid (0: fill the chip); tests use it to make workgroups claim many units
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
+  int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
   int debug = 0;
 };
 
@@ -93,6 +97,8 @@ struct visfd_hip_ctx {
   size_t slot_bytes[vh::WS_NSLOTS] = {};
   int num_cus = 256;
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
+  std::vector<int> morph_tab;         // the structuring element now in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b)
+  int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
 };
 
 namespace vh {
@@ -143,6 +149,7 @@ void host_conv_ones(i64 n, const float* t, int h, float* out);  // filter applie
 int host_tv_halfwidth(float sigma, float cutoff);
 void host_tv_tables(float sigma, int h, float* w, float* rhat);
 float host_gengauss3d_peak(const float width[3], float m_exp, float ratio);
+i64 host_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, i64 cap);
 
 // ---- device stages (each in its own .hip; all asynchronous on ctx->stream) -------------------
 struct SlabInfo {   // Z-slab placement for multi-GPU runs; whole volume: z_lo=0, nz_global=nz
@@ -207,6 +214,30 @@ int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir_pl
 
 int dev_tv_weight_sum(visfd_hip_ctx* ctx, const float* sal, float* den, const float* mask_src, const float* mask_dst, i64 nx,
                       i64 ny, i64 nz, float sigma_tv, float cutoff);
+
+// A structuring element as the morphology kernels see it (the entries themselves are in slot WS_MORPH_TAB).
+// runs: every b is +0.0f and every (dy, dz) row of the element is one symmetric X-run [-L, L], |dy|, |dz|, L <= R <=
+// MORPH_RUN_MAX_R; run_len[(dz + R) * (2R + 1) + dy + R] = L, or -1 where the row is not in the element.
+constexpr int MORPH_RUN_MAX_R = 10;
+struct MorphElem {
+  i64 n = 0;
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  bool flat = true;
+  bool runs = false;
+  int R = 0;
+  signed char run_len[(2 * MORPH_RUN_MAX_R + 1) * (2 * MORPH_RUN_MAX_R + 1)];
+};
+
+// morph.hip: Dilate / Erode with a structuring element already in WS_MORPH_TAB.  el.runs selects the X-run kernel
+// (window maxima per row, then a zero-sign fix-up of flat erosions in element order), otherwise the element walk.
+// Neighbours come from `src`, whose excluded voxels the caller has made NaN (a NaN candidate never wins, exactly like a
+// skipped one).  Voxels with mask == 0 are left untouched, or set to NaN when nan_masked (an intermediate image).
+// epi: 0 dst = result, 1 dst = dst - result (white top-hat), 2 dst = result - dst (black top-hat).
+// Returns the path it took in *path (VISFD_HIP_MORPH_PATH_*).
+int dev_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+                    const MorphElem& el, bool dilate, int epi, bool nan_masked, int* path);
+// out = (mask == 0) ? NaN : src
+int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, float* out, i64 n);
 
 // resample.hip (sizes are {nx, ny, nz}; offset nullable)
 int dev_bin_array3d(visfd_hip_ctx* ctx, const float* src, const int64_t size_src[3], float* dst,

@@ -2,6 +2,7 @@
 // tensor-voting lookup tables.  These are O(filter width) computations the reference also does
 // on the CPU; their float/long-double evaluation order is part of the
 // parity contract, so this file must be built without FMA contraction or fast-math.
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -113,6 +114,67 @@ float host_gengauss3d_peak(const float width[3], float m_exp, float ratio) {
         total += v;
       }
   return 1.0f / total;   // the centre entry is 1 before the division by the sum
+}
+
+// Structuring element of DilateSphere / ErodeSphere (reference lib/visfd/morphology.hpp:241-420): entries
+// (dx, dy, dz, b) with dz outermost, then dy, then dx, each over [-Ri, Ri], Ri = ceil(max(radius, radius_max)) in float.
+// Three rules, tested in this order, with the reference's types (integer squares, double sqrt stored to float, float b):
+//   bmax == 0                flat ball: r <= radius, b = +0
+//   radius_max > radius      linear rim: b = -(r - radius) / (radius_max - radius) * bmax for radius < r <= radius_max
+//   otherwise                corner rule on the 8 corners (d +- 0.5): in when r_max < radius (b = +0), out when
+//                            r_min > radius, else b = -(r_max - radius) / (r_max - r_min) * bmax (may be -0.0f)
+// Writes the first min(n, cap) entries (dxyz: 3 ints per entry) and returns the count n.
+i64 host_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, i64 cap) {
+  const int Ri = (int)std::ceil(std::max(radius, radius_max));
+  i64 n = 0;
+  for (int iz = -Ri; iz <= Ri; iz++)
+    for (int iy = -Ri; iy <= Ri; iy++)
+      for (int ix = -Ri; ix <= Ri; ix++) {
+        bool add = false;
+        float bb = 0.0f;
+        if (bmax == 0.0f) {
+          const float r = (float)std::sqrt((double)(ix * ix + iy * iy + iz * iz));
+          add = r <= radius;
+        } else if (radius_max > radius) {
+          const float r = (float)std::sqrt((double)(ix * ix + iy * iy + iz * iz));
+          if (r <= radius) {
+            add = true;
+          } else if (r <= radius_max) {
+            add = true;
+            bb = -(r - radius) / (radius_max - radius);
+            bb *= bmax;
+          }
+        } else {
+          float r_max = -std::numeric_limits<float>::infinity();
+          float r_min = std::numeric_limits<float>::infinity();
+          for (int jz = 0; jz <= 1; jz++)
+            for (int jy = 0; jy <= 1; jy++)
+              for (int jx = 0; jx <= 1; jx++) {
+                const double cx = ix + jx - 0.5, cy = iy + jy - 0.5, cz = iz + jz - 0.5;
+                const float r = (float)std::sqrt(cx * cx + cy * cy + cz * cz);
+                if (r < r_min) r_min = r;
+                if (r > r_max) r_max = r;
+              }
+          if (r_max < radius) {
+            add = true;
+          } else if (r_min > radius) {
+            add = false;
+          } else {
+            add = true;
+            bb = -(r_max - radius) / (r_max - r_min);
+            bb *= bmax;
+          }
+        }
+        if (!add) continue;
+        if (n < cap) {
+          dxyz[3 * n + 0] = ix;
+          dxyz[3 * n + 1] = iy;
+          dxyz[3 * n + 2] = iz;
+          b[n] = bb;
+        }
+        n++;
+      }
+  return n;
 }
 
 }  // namespace vh
