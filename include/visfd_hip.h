@@ -52,16 +52,19 @@ typedef struct visfd_hip_ctx visfd_hip_ctx;
 /* ---- lifecycle ------------------------------------------------------------------------------- */
 /* device: HIP ordinal.  stream: a hipStream_t to run on (e.g. the caller's), or NULL to create one. */
 int visfd_hip_create(int device, void* stream, visfd_hip_ctx** out);
+/* also aborts the context's blob jobs that were begun and not ended (their handles are then no longer live) */
 int visfd_hip_destroy(visfd_hip_ctx* ctx);
 int visfd_hip_synchronize(visfd_hip_ctx* ctx);
 /* the hipStream_t every _dev entry point of this context runs on (the one given to visfd_hip_create, or the context's own) */
 void* visfd_hip_get_stream(visfd_hip_ctx* ctx);
-/* release the cached workspace (it otherwise persists between calls) */
+/* release the cached workspace (it otherwise persists between calls).  Allowed at any time, also between the halves of a
+ * blob job: what the job has queued is fetched to the host first. */
 int visfd_hip_trim(visfd_hip_ctx* ctx);
 const char* visfd_hip_last_error(void);
 int visfd_hip_abi_version(void);   /* 10: entry points only get added between versions (since 10 was set: the
                                      * morphology entries visfd_hip_sphere_structure, visfd_hip_morph_sphere[_dev],
-                                     * visfd_hip_morph_table[_dev] and visfd_hip_morph_last_path) */
+                                     * visfd_hip_morph_table[_dev] and visfd_hip_morph_last_path; then
+                                     * visfd_hip_blob_jobs_pending and visfd_hip_debug_poison_workspace) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -94,6 +97,11 @@ int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
 /* bytes of device workspace currently held by the context */
 int64_t visfd_hip_workspace_bytes(visfd_hip_ctx* ctx);
+/* TEST AID: waits for the context's stream, then fills every workspace slot the context holds with 0xFF bytes (NaN as
+ * floats, huge as counters) and forgets what it had cached inside them (vote table, structuring element), without freeing
+ * anything.  No stage may depend on what a slot held before the call that uses it, so every result after this call is the
+ * same as before it.  What live blob jobs have queued is fetched to the host first, as visfd_hip_trim does. */
+int visfd_hip_debug_poison_workspace(visfd_hip_ctx* ctx);
 
 /* ---- a1: filter taps (host arithmetic, long double) ------------------------------------------ */
 /* GenFilterGauss1D<float>, lib/visfd/filter1d.hpp:409-460.  taps_out has 2*halfwidth+1 entries. */
@@ -231,9 +239,14 @@ int visfd_hip_blob_dog_dev(visfd_hip_ctx*, const float* src, const float* mask,
  * BlobDog is one call there).  `begin` queues every filter and scan and fetches the lists of all scales but the last few; `end`
  * fetches those, repeats scales whose buffers overflowed, merges, and hands the lists over exactly as visfd_hip_blob_dog_dev does.
  * Between the two the caller may queue other calls of the SAME context (a membrane stage): the device then goes from the last
- * scan straight into that work instead of idling through the host's list handling.  src and mask must stay unchanged until
- * `end` returns.  VISFD_HIP_ECAPACITY from `end` leaves the job alive and returns the counts: call `end` again with room for
- * them; every other return value of `end` -- and visfd_hip_blob_dog_abort -- frees the job. */
+ * scan straight into that work instead of idling through the host's list handling.  ANY call of the context is allowed
+ * there -- larger volumes, another blob call or a second `begin`, visfd_hip_trim, changed options: a pending scan keeps the
+ * buffers and capacities it was launched with, and whatever would free or overwrite those first fetches the job's
+ * lists to the host (which waits for the job's scans; a membrane stage with a caller-supplied `dir` never does that).  src and
+ * mask must stay unchanged until `end` returns.  VISFD_HIP_ECAPACITY from `end` leaves the job alive and returns the counts:
+ * call `end` again with room for them; every other return value of `end` -- a refused argument included -- and
+ * visfd_hip_blob_dog_abort free the job.  visfd_hip_destroy aborts the context's live jobs.  A handle that is not live
+ * (ended, aborted, destroyed with its context) is never dereferenced: `end` answers VISFD_HIP_EINVAL, `abort` does nothing. */
 typedef struct visfd_hip_blob_job visfd_hip_blob_job;
 int visfd_hip_blob_dog_begin_dev(visfd_hip_ctx*, const float* src, const float* mask,
                                  int64_t nx, int64_t ny, int64_t nz, const float* blob_sigma,
@@ -244,6 +257,8 @@ int visfd_hip_blob_dog_end(visfd_hip_blob_job* job,
                            visfd_hip_blob* minima, int64_t minima_capacity, int64_t* n_minima,
                            visfd_hip_blob* maxima, int64_t maxima_capacity, int64_t* n_maxima);
 void visfd_hip_blob_dog_abort(visfd_hip_blob_job* job);
+/* the context's live blob jobs: begun, and neither ended nor aborted */
+int visfd_hip_blob_jobs_pending(visfd_hip_ctx* ctx);
 /* BlobDogD's conversions, lib/visfd/feature.hpp:475 and :504 */
 int visfd_hip_blob_diameters_to_sigmas(const float* diameters, int n, float* sigmas);
 int visfd_hip_blob_sigmas_to_diameters(const float* sigmas, int n, float* diameters);

@@ -1,7 +1,10 @@
 """Randomised parity sweep: GPU (through the C ABI) against the CPU restatement on random shapes, windows,
 masks and parameters, bit for bit.  A development aid beyond the fixed cases of tests/:
 
-    python tools/fuzz_parity.py [--seconds 120] [--seed 1]
+    python tools/fuzz_parity.py [--seconds 120] [--seed 1] [--poison]
+
+--poison fills the context's workspace with 0xFF bytes before every case (visfd_hip_debug_poison_workspace): the sweep
+reuses one context for thousands of shapes, so it then also shows a stage that depends on what its slots held.
 """
 import argparse
 import os
@@ -32,6 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--poison", action="store_true", help="poison the workspace before every case")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     O = po.load("oracle")
@@ -58,6 +62,8 @@ def main():
             if rng.random() < 0.3:
                 mask *= rng.uniform(0.2, 2.0, shape).astype(np.float32)   # weighted mask
         try:
+            if a.poison:
+                ctx.debug_poison_workspace()
             if kind == "gauss":
                 if rng.random() < 0.5:
                     h = int(rng.integers(0, 14))

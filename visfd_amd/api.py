@@ -85,6 +85,8 @@ _SIGS = {
                                                C.c_float, C.c_float, C.c_int, C.POINTER(_vp)]),
     "visfd_hip_blob_dog_end": (C.c_int, [_vp, C.POINTER(Blob), _i64, C.POINTER(_i64), C.POINTER(Blob), _i64, C.POINTER(_i64)]),
     "visfd_hip_blob_dog_abort": (None, [_vp]),
+    "visfd_hip_blob_jobs_pending": (C.c_int, [_vp]),
+    "visfd_hip_debug_poison_workspace": (C.c_int, [_vp]),
     "visfd_hip_blob_diameters_to_sigmas": (C.c_int, [_fp, C.c_int, _fp]),
     "visfd_hip_blob_sigmas_to_diameters": (C.c_int, [_fp, C.c_int, _fp]),
     "visfd_hip_calc_hessian": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float]),
@@ -509,6 +511,10 @@ class Context:
             if s is not None:
                 s.close()
         self._slabs = []
+        # blob jobs handed out and not finished: visfd_hip_destroy aborts them, so their handles are dead from here on
+        for job in getattr(self, "_jobs", []):
+            job[0] = None
+        self._jobs = []
         if getattr(self, "_h", None):
             self._L.visfd_hip_destroy(self._h)
             self._h = None
@@ -527,6 +533,16 @@ class Context:
 
     def workspace_bytes(self):
         return int(self._L.visfd_hip_workspace_bytes(self._h))
+
+    def debug_poison_workspace(self):
+        """Test aid (visfd_hip_debug_poison_workspace): 0xFF bytes in every workspace slot, in-slot caches forgotten."""
+        self._chk(self._L.visfd_hip_debug_poison_workspace(self._h))
+
+    def blob_jobs_pending(self):
+        return int(self._L.visfd_hip_blob_jobs_pending(self._h))
+
+    def _forget_job(self, job):
+        self._jobs = [j for j in getattr(self, "_jobs", []) if j is not job]
 
     def set_option(self, name, value):
         """Tuning / test switch of this context (include/visfd_hip.h: visfd_hip_set_option)."""
@@ -687,7 +703,9 @@ class Context:
         self._chk(self._L.visfd_hip_blob_dog_begin_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, sig.ctypes.data_as(_fp), len(sig),
                                                        asp, float(delta), float(ratio), float(minima_threshold),
                                                        float(maxima_threshold), int(use_ratios), C.byref(job)))
-        return [job, src, mask, sig]   # (the tensors and the sigma array live as long as the job)
+        job = [job, src, mask, sig]   # (the tensors and the sigma array live as long as the job)
+        self._jobs = getattr(self, "_jobs", []) + [job]   # close() ends what the caller has not
+        return job
 
     def blob_dog_end(self, job, cap=1 << 16):
         """Second half: -> (minima, maxima) rows x,y,z,sigma,score, as blob_dog_dev returns them."""
@@ -706,6 +724,7 @@ class Context:
                 cap = max(nmin.value, nmax.value, 1)
                 continue
             job[0] = None                   # every other outcome has freed the job
+            self._forget_job(job)
             if rc == 4:
                 self._L.visfd_hip_blob_dog_abort(h)
             self._chk(rc)
@@ -716,6 +735,7 @@ class Context:
         if job[0] is not None:
             self._L.visfd_hip_blob_dog_abort(job[0])
             job[0] = None
+            self._forget_job(job)
 
     def blob_dog(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
                  maxima_threshold=-np.inf, use_ratios=False, cap=1 << 16):
@@ -815,6 +835,21 @@ class Context:
         return sal, ten, dirs, thr.value
 
     # ---------------------------------------------------------------- device face (torch)
+    def membrane_detect_dev(self, src, sal, sigma, ratio, order, best_fraction=0.05, threshold_abs=0.0, sigma_tv=0.0,
+                            tv_exponent=4, tv_cutoff=2.0 ** 0.5, mask=None, dirs=None, tensor=None, sigma_background=0.0,
+                            normalize_background=True):
+        """visfd_hip_membrane_detect_bg_dev: HandleTV's compute section on device tensors; sal receives the scores, and
+        -> the threshold.  dirs (3,nz,ny,nx) and tensor (6,nz,ny,nx) are optional outputs: None keeps them in the workspace."""
+        nz, ny, nx = src.shape
+        thr = C.c_float()
+        self._chk(self._L.visfd_hip_membrane_detect_bg_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma),
+                                                           float(ratio), int(order), float(best_fraction),
+                                                           float(threshold_abs), float(sigma_tv), int(tv_exponent),
+                                                           float(tv_cutoff), float(sigma_background),
+                                                           int(bool(normalize_background)), _dev(sal), _dev(tensor), _dev(dirs),
+                                                           C.byref(thr)))
+        return thr.value
+
     def gauss_dev(self, src, dst, sigma, hw, mask=None, normalize=True):
         nz, ny, nx = src.shape
         A = C.c_float()

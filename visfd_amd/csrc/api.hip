@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <limits>
 #include <memory>
+#include <mutex>
+#include <set>
 #include <vector>
 
 #include "common.hpp"
@@ -24,6 +26,8 @@ int fail(int code, const std::string& msg) {
 int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out) {
   if (bytes == 0) bytes = 16;
   if (ctx->slot_bytes[s] < bytes) {
+    // a queued blob scan that nobody has collected yet writes its survivors and counts here: fetch them first
+    if (ctx->slot_ptr[s] && (s == WS_CAND || s == WS_SCANCNT)) VH_TRY(blob_jobs_drain(ctx));
     if (ctx->slot_ptr[s]) {
       // buffers may still be in use by queued kernels
       VH_HIP(hipStreamSynchronize(ctx->stream));
@@ -41,6 +45,88 @@ int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out) {
   }
   *out = ctx->slot_ptr[s];
   return VISFD_HIP_OK;
+}
+
+// BlobDog in two halves (visfd_hip_blob_dog_begin_dev / _end): `begin` queues every filter and scan and collects the lists
+// of all scales but the last few; `end` collects those, repeats overflowed scales, merges and hands the lists over.  A caller
+// that has more device work for the same stream (the membrane stage of a pipeline) queues it between the two: the device
+// then goes from the last scan straight into that work instead of idling through the host's list handling (6-9 ms at
+// 1024^3 -- and an idle MI355X took up to 25 ms more to start the next kernel).
+//
+// Live jobs are registered twice: in their context (visfd_hip_ctx::blob_jobs), so that whatever is about to free, reallocate or
+// overwrite the buffers a queued scan writes to can collect those scans first (blob_jobs_drain, common.hpp), and process-wide
+// (g_jobs), so that `end` and `abort` recognise a handle whose job is gone -- ended, aborted, or destroyed with its context.
+struct BlobJob;
+static std::mutex g_jobs_mutex;
+static std::set<const BlobJob*> g_jobs;
+
+struct BlobJob {
+  visfd_hip_ctx* const ctx;
+  const float* src = nullptr;
+  const float* mask = nullptr;
+  i64 nx = 0, ny = 0, nz = 0;
+  std::vector<float> sigma;
+  float asp[3] = {1.0f, 1.0f, 1.0f};
+  float delta = 0, ratio = 0, min_thr = 0, max_thr = 0, scan_min = 0, scan_max = 0;
+  bool use_ratios = false, can_scan = false, merged = false;
+  static constexpr int NSET = 3;
+  hipEvent_t ev[NSET] = {nullptr, nullptr, nullptr};
+  std::vector<std::vector<visfd_hip_blob>> smin, smax;   // lists per middle scale (output order is scale order, feature.hpp:236-358)
+  std::vector<int> redo;                                  // scales whose buffers overflowed in the pipelined scan
+  int pending_first = 0, pending_n = 0;                   // middle scales whose scans are queued but not collected yet (set: scale % NSET)
+  ScanPending pend[NSET];                                 // ... and where each of them writes, as recorded at its launch
+  std::vector<visfd_hip_blob> mins, maxs;                 // the merged lists (after `merged`)
+  std::chrono::steady_clock::time_point t_start;
+  double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); }
+  explicit BlobJob(visfd_hip_ctx* c) : ctx(c) {   // a job is in both registries for as long as it exists
+    ctx->blob_jobs.push_back(this);
+    std::lock_guard<std::mutex> lock(g_jobs_mutex);
+    g_jobs.insert(this);
+  }
+  BlobJob(const BlobJob&) = delete;
+  BlobJob& operator=(const BlobJob&) = delete;
+  ~BlobJob() {
+    for (int k = 0; k < NSET; k++)
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+    ctx->blob_jobs.erase(std::remove(ctx->blob_jobs.begin(), ctx->blob_jobs.end(), this), ctx->blob_jobs.end());
+    std::lock_guard<std::mutex> lock(g_jobs_mutex);
+    g_jobs.erase(this);
+  }
+  // a handle a caller gives back: only ever dereferenced when it names a job that exists
+  static bool live(const void* handle) {
+    std::lock_guard<std::mutex> lock(g_jobs_mutex);
+    return g_jobs.count(static_cast<const BlobJob*>(handle)) != 0;
+  }
+  int collect(int scale) {
+    bool overflow = false;
+    VH_TRY(blob_scan_collect(ctx, pend[scale % NSET], ev[scale % NSET], ctx->aux_stream, nx, ny, scale, sigma[(size_t)scale],
+                             &smin[(size_t)scale], &smax[(size_t)scale], &overflow));
+    if (overflow) redo.push_back(scale);
+    return VISFD_HIP_OK;
+  }
+  // every queued scan into the host lists (waits for their events); afterwards the job owns no device memory
+  int drain() {
+    while (pending_n > 0) {
+      VH_TRY(collect(pending_first));
+      pending_first++;
+      pending_n--;
+    }
+    return VISFD_HIP_OK;
+  }
+};
+
+int blob_jobs_drain(visfd_hip_ctx* ctx, const BlobJob* except) {
+  for (BlobJob* j : ctx->blob_jobs)
+    if (j != except) VH_TRY(j->drain());
+  return VISFD_HIP_OK;
+}
+
+// visfd_hip_destroy: the context's jobs go with it (their handles then name no live job)
+static void blob_jobs_abort(visfd_hip_ctx* ctx) {
+  if (ctx->blob_jobs.empty()) return;
+  if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
+  (void)hipStreamSynchronize(ctx->stream);   // nothing of a job is in flight when its events go
+  while (!ctx->blob_jobs.empty()) delete ctx->blob_jobs.back();
 }
 
 namespace {
@@ -133,41 +219,6 @@ int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, float* tmp, const 
   return VISFD_HIP_OK;
 }
 
-// BlobDog in two halves (visfd_hip_blob_dog_begin_dev / _end): `begin` queues every filter and scan and collects the lists
-// of all scales but the last few; `end` collects those, repeats overflowed scales, merges and hands the lists over.  A caller
-// that has more device work for the same stream (the membrane stage of a pipeline) queues it between the two: the device
-// then goes from the last scan straight into that work instead of idling through the host's list handling (6-9 ms at
-// 1024^3 -- and an idle MI355X took up to 25 ms more to start the next kernel).
-struct BlobJob {
-  visfd_hip_ctx* ctx = nullptr;
-  const float* src = nullptr;
-  const float* mask = nullptr;
-  i64 nx = 0, ny = 0, nz = 0;
-  std::vector<float> sigma;
-  float asp[3] = {1.0f, 1.0f, 1.0f};
-  float delta = 0, ratio = 0, min_thr = 0, max_thr = 0, scan_min = 0, scan_max = 0;
-  bool use_ratios = false, can_scan = false, merged = false;
-  static constexpr int NSET = 3;
-  hipEvent_t ev[NSET] = {nullptr, nullptr, nullptr};
-  std::vector<std::vector<visfd_hip_blob>> smin, smax;   // lists per middle scale (output order is scale order, feature.hpp:236-358)
-  std::vector<int> redo;                                  // scales whose buffers overflowed in the pipelined scan
-  int pending_first = 0, pending_n = 0;                   // middle scales whose scans are queued but not collected yet (set: scale % NSET)
-  std::vector<visfd_hip_blob> mins, maxs;                 // the merged lists (after `merged`)
-  std::chrono::steady_clock::time_point t_start;
-  double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); }
-  ~BlobJob() {
-    for (int k = 0; k < NSET; k++)
-      if (ev[k]) (void)hipEventDestroy(ev[k]);
-  }
-  int collect(int scale) {
-    bool overflow = false;
-    VH_TRY(blob_scan_collect(ctx, scale % NSET, ev[scale % NSET], ctx->aux_stream, nx, ny, nx * ny * nz, scale, sigma[(size_t)scale],
-                             &smin[(size_t)scale], &smax[(size_t)scale], &overflow));
-    if (overflow) redo.push_back(scale);
-    return VISFD_HIP_OK;
-  }
-};
-
 int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz,
                    const float* blob_sigma, int n_sigma, const float* aspect, float delta, float ratio,
                    float min_thr, float max_thr, bool use_ratios, BlobJob** job_out) {
@@ -183,8 +234,8 @@ int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 
   VH_TRY(ws(ctx, WS_LOG2, (size_t)n, &vol[2]));
   float* tmp = nullptr;
   VH_TRY(ws(ctx, WS_C, (size_t)n, &tmp));
-  std::unique_ptr<BlobJob> J(new BlobJob);
-  J->ctx = ctx; J->src = src; J->mask = mask; J->nx = nx; J->ny = ny; J->nz = nz;
+  std::unique_ptr<BlobJob> J(new BlobJob(ctx));
+  J->src = src; J->mask = mask; J->nx = nx; J->ny = ny; J->nz = nz;
   J->sigma.assign(blob_sigma, blob_sigma + n_sigma);
   if (aspect) for (int d = 0; d < 3; d++) J->asp[d] = aspect[d];
   J->delta = delta; J->ratio = ratio; J->min_thr = min_thr; J->max_thr = max_thr; J->use_ratios = use_ratios;
@@ -206,8 +257,8 @@ int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 
     const float sg[3] = {blob_sigma[ir] * J->asp[0], blob_sigma[ir] * J->asp[1], blob_sigma[ir] * J->asp[2]};
     VH_TRY(log_dev(ctx, src, vol[ir % 3], tmp, mask, nx, ny, nz, sg, delta, ratio, nullptr, nullptr));
     if (ir < 2 || !J->can_scan) continue;
-    VH_TRY(blob_scan_launch(ctx, (ir - 1) % BlobJob::NSET, J->ev[(ir - 1) % BlobJob::NSET], vol[(ir - 2) % 3], vol[(ir - 1) % 3],
-                            vol[ir % 3], mask, nx, ny, nz, J->scan_min, J->scan_max));
+    VH_TRY(blob_scan_launch(ctx, J.get(), (ir - 1) % BlobJob::NSET, J->ev[(ir - 1) % BlobJob::NSET], vol[(ir - 2) % 3], vol[(ir - 1) % 3],
+                            vol[ir % 3], mask, nx, ny, nz, J->scan_min, J->scan_max, &J->pend[(ir - 1) % BlobJob::NSET]));
     if (J->pending_n == 0) J->pending_first = ir - 1;
     J->pending_n++;
     if (J->pending_n == BlobJob::NSET) {   // every buffer set is in use: the oldest list now (its scan was queued two scales ago)
@@ -222,19 +273,16 @@ int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 
 }
 
 // Collects what `begin` left, merges, and copies out.  VISFD_HIP_ECAPACITY leaves the job alive (the counts are returned: call
-// again with room for them); every other outcome frees it.
+// again with room for them); every other outcome frees it -- a refused argument included: the job is owned before anything
+// is checked.
 int blob_dog_end(BlobJob* job, visfd_hip_blob* minima, int64_t min_cap, int64_t* n_min, visfd_hip_blob* maxima, int64_t max_cap,
                  int64_t* n_max) {
-  VH_REQUIRE(job && n_min && n_max, "null argument");
   std::unique_ptr<BlobJob> J(job);
+  VH_REQUIRE(n_min && n_max, "null argument");
   visfd_hip_ctx* ctx = J->ctx;
   const float inf = std::numeric_limits<float>::infinity();
   if (!J->merged) {
-    while (J->pending_n > 0) {
-      VH_TRY(J->collect(J->pending_first));
-      J->pending_first++;
-      J->pending_n--;
-    }
+    VH_TRY(J->drain());
     if (ctx->opt.debug) fprintf(stderr, "[blob_dog] last list collected at %.1f ms\n", J->since());
     // a candidate or survivor buffer overflowed (dense extrema): those scales again, one at a time, with buffers that grow
     // (the three LoG volumes of the scale are filtered again; the other scales keep their lists)
@@ -420,13 +468,19 @@ int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value) {
   return VISFD_HIP_OK;
 }
 
-int visfd_hip_trim(visfd_hip_ctx* ctx) {
-  VH_REQUIRE(ctx, "null context");
-  VH_HIP(hipSetDevice(ctx->device));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
+// what the context remembers about the CONTENTS of its slots (trim frees them, the poison call overwrites them)
+static void forget_slot_caches(visfd_hip_ctx* ctx) {
   ctx->tv_table_dev = nullptr;   // lives in a workspace slot
   ctx->tv_table_h = -1;
   ctx->morph_tab.clear();        // so does the structuring element
+}
+
+int visfd_hip_trim(visfd_hip_ctx* ctx) {
+  VH_REQUIRE(ctx, "null context");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(blob_jobs_drain(ctx));   // live blob jobs keep their lists on the host from here on
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  forget_slot_caches(ctx);
   for (int s = 0; s < WS_NSLOTS; s++) {
     if (ctx->slot_ptr[s]) VH_HIP(hipFree(ctx->slot_ptr[s]));
     ctx->slot_ptr[s] = nullptr;
@@ -435,8 +489,24 @@ int visfd_hip_trim(visfd_hip_ctx* ctx) {
   return VISFD_HIP_OK;
 }
 
+int visfd_hip_debug_poison_workspace(visfd_hip_ctx* ctx) {
+  VH_REQUIRE(ctx, "null context");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(blob_jobs_drain(ctx));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  forget_slot_caches(ctx);
+  for (int s = 0; s < WS_NSLOTS; s++)
+    if (ctx->slot_ptr[s]) VH_HIP(hipMemsetAsync(ctx->slot_ptr[s], 0xFF, ctx->slot_bytes[s], ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_blob_jobs_pending(visfd_hip_ctx* ctx) { return ctx ? (int)ctx->blob_jobs.size() : 0; }
+
 int visfd_hip_destroy(visfd_hip_ctx* ctx) {
   if (!ctx) return VISFD_HIP_OK;
+  (void)hipSetDevice(ctx->device);
+  blob_jobs_abort(ctx);
   int rc = visfd_hip_trim(ctx);
   if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
@@ -677,14 +747,14 @@ int visfd_hip_blob_dog_begin_dev(visfd_hip_ctx* ctx, const float* src, const flo
 }
 int visfd_hip_blob_dog_end(visfd_hip_blob_job* job, visfd_hip_blob* minima, int64_t min_cap, int64_t* n_min,
                            visfd_hip_blob* maxima, int64_t max_cap, int64_t* n_max) {
-  VH_REQUIRE(job, "null job");
+  VH_REQUIRE(job && BlobJob::live(job), "not a live blob job");
   BlobJob* j = reinterpret_cast<BlobJob*>(job);
-  VH_HIP(hipSetDevice(j->ctx->device));
+  (void)hipSetDevice(j->ctx->device);   // (no early return between here and blob_dog_end, which owns the job)
   return blob_dog_end(j, minima, min_cap, n_min, maxima, max_cap, n_max);
 }
 void visfd_hip_blob_dog_abort(visfd_hip_blob_job* job) {
+  if (!job || !BlobJob::live(job)) return;   // ended, aborted or destroyed with its context: nothing to do
   BlobJob* j = reinterpret_cast<BlobJob*>(job);
-  if (!j) return;
   (void)hipSetDevice(j->ctx->device);
   if (j->ctx->aux_stream) (void)hipStreamSynchronize(j->ctx->aux_stream);
   (void)hipStreamSynchronize(j->ctx->stream);   // nothing of the job is in flight when its events go

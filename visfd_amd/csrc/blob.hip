@@ -252,8 +252,10 @@ blob_verify_kernel(const unsigned long long* __restrict__ cand_idx, const unsign
 // this scale's list (BlobDog runs a dozen scales back to back): blob_scan_launch only enqueues the two kernels on
 // the context's stream (buffer set 0 or 1: candidate codes, survivors, counters) and records an event;
 // blob_scan_collect waits for that event on an auxiliary stream, copies the survivors to the host there (the main
-// stream keeps running), sorts them and appends them to the lists.  Returns 1 when a buffer overflowed (the caller
-// then repeats the scale with dev_blob_scan, which grows the buffers).
+// stream keeps running), sorts them and appends them to the lists; *overflow tells that a buffer overflowed (the caller
+// then repeats the scale with dev_blob_scan, which grows the buffers).  Any call of the context may come between the
+// two: the launch records where it writes and how much fits (ScanPending), the collect reads only that record, and
+// whatever would free or overwrite those buffers collects first (blob_jobs_drain, common.hpp).
 struct ScanBufs {
   unsigned long long* idx = nullptr;
   Cand* cand = nullptr;
@@ -355,21 +357,29 @@ static int scan_enqueue(visfd_hip_ctx* ctx, const ScanBufs& B, const float* lo, 
   return VISFD_HIP_OK;
 }
 
-int blob_scan_launch(visfd_hip_ctx* ctx, int set, hipEvent_t done, const float* lo, const float* mid, const float* hi,
-                     const float* mask, i64 nx, i64 ny, i64 nz, float min_thr, float max_thr) {
+int blob_scan_launch(visfd_hip_ctx* ctx, const BlobJob* owner, int set, hipEvent_t done, const float* lo, const float* mid,
+                     const float* hi, const float* mask, i64 nx, i64 ny, i64 nz, float min_thr, float max_thr,
+                     ScanPending* pending) {
+  VH_TRY(blob_jobs_drain(ctx, owner));   // the buffer sets and counters are the context's: another job's pending lists first
   ScanBufs B;
   VH_TRY(scan_bufs(ctx, set, &B, true, nx * ny * nz));
   VH_TRY(scan_enqueue(ctx, B, lo, mid, hi, mask, nx, ny, nz, min_thr, max_thr));
   VH_HIP(hipEventRecord(done, ctx->stream));
+  // the candidate codes (B.idx) are not recorded: only the two kernels just queued read them, and the stream orders
+  // every later user of WS_TVAUX behind those (ws_get waits for the stream before it frees a slot)
+  pending->counters = B.counters;
+  pending->survivors = B.cand;
+  pending->cap_idx = B.cap_idx;
+  pending->cap_out = B.cap_out;
   return VISFD_HIP_OK;
 }
 
-int blob_scan_collect(visfd_hip_ctx* ctx, int set, hipEvent_t done, hipStream_t aux, i64 nx, i64 ny, i64 nvox,
+int blob_scan_collect(visfd_hip_ctx* ctx, const ScanPending& B, hipEvent_t done, hipStream_t aux, i64 nx, i64 ny,
                       int scale_index,
                       float sigma, std::vector<visfd_hip_blob>* minima, std::vector<visfd_hip_blob>* maxima,
                       bool* overflow) {
-  ScanBufs B;
-  VH_TRY(scan_bufs(ctx, set, &B, true, nvox));   // (sizes unchanged since the launch: same pointers)
+  // only what the launch recorded: slot sizes, options and the slots themselves may have changed since (blob_jobs_drain
+  // runs before anything frees or overwrites what `B` points to)
   *overflow = false;
   VH_HIP(hipStreamWaitEvent(aux, done, 0));
   unsigned long long c2[2] = {0, 0};
@@ -379,7 +389,7 @@ int blob_scan_collect(visfd_hip_ctx* ctx, int set, hipEvent_t done, hipStream_t 
   if (c2[0] > B.cap_idx || c2[1] > B.cap_out) { *overflow = true; return VISFD_HIP_OK; }
   std::vector<Cand> h((size_t)c2[1]);
   if (c2[1]) {
-    VH_HIP(hipMemcpyAsync(h.data(), B.cand, sizeof(Cand) * (size_t)c2[1], hipMemcpyDeviceToHost, aux));
+    VH_HIP(hipMemcpyAsync(h.data(), B.survivors, sizeof(Cand) * (size_t)c2[1], hipMemcpyDeviceToHost, aux));
     VH_HIP(hipStreamSynchronize(aux));
   }
   sort_and_append(h, nx, ny, scale_index, sigma, minima, maxima);
@@ -398,6 +408,7 @@ int dev_blob_scan(visfd_hip_ctx* ctx, const float* lo, const float* mid, const f
   if (!want_min) min_thr = -inf;   // nothing is < -inf
   if (!want_max) max_thr = inf;
   hipStream_t st = ctx->stream;
+  VH_TRY(blob_jobs_drain(ctx));   // set 0 and its counters may hold a pending scan of a job (never the caller's: `end` collects first)
   for (int attempt = 0; attempt < 4; attempt++) {
     ScanBufs B;
     VH_TRY(scan_bufs(ctx, 0, &B, false, nx * ny * nz));

@@ -59,6 +59,8 @@ enum Slot {
   WS_NSLOTS
 };
 
+struct BlobJob;   // api.hip: one visfd_hip_blob_dog_begin_dev that has not been ended or aborted yet
+
 }  // namespace vh
 
 // Tuning and test switches: read ONCE from the environment when the context is created (VISFD_HIP_<NAME>) and
@@ -99,9 +101,16 @@ struct visfd_hip_ctx {
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
   std::vector<int> morph_tab;         // the structuring element now in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b)
   int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
+  std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (api.hip: blob_jobs_drain)
 };
 
 namespace vh {
+
+// Collects every scan that live blob jobs of the context (all but `except`) have queued and not fetched yet into the jobs'
+// host lists; afterwards those jobs hold no pointer into the workspace.  Called before anything frees, reallocates or
+// overwrites the buffers a pending scan writes to (WS_CAND, WS_SCANCNT): ws_get when one of them grows, visfd_hip_trim,
+// and every scan launched for another job.  With nothing pending -- the usual case -- it is a loop over an empty list.
+int blob_jobs_drain(visfd_hip_ctx* ctx, const BlobJob* except = nullptr);
 
 // returns a device buffer of at least `bytes` bytes in slot `s` (contents undefined)
 int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out);
@@ -171,9 +180,19 @@ int dev_sub_scale(visfd_hip_ctx* ctx, float* a_inout, const float* b, i64 n, flo
 int dev_sub_square(visfd_hip_ctx* ctx, const float* a, const float* b, float* out, i64 n);   // out = (a-b)*(a-b)
 int dev_scale_clamp_sqrt(visfd_hip_ctx* ctx, float* a_inout, i64 n, float scale);           // a = sqrt(max(a*scale, 0))
 
-int blob_scan_launch(visfd_hip_ctx* ctx, int set, hipEvent_t done, const float* lo, const float* mid, const float* hi,
-                     const float* mask, i64 nx, i64 ny, i64 nz, float min_thr, float max_thr);
-int blob_scan_collect(visfd_hip_ctx* ctx, int set, hipEvent_t done, hipStream_t aux, i64 nx, i64 ny, i64 nvox,
+// What a queued scan of the pipelined form writes to, as decided when it was launched: blob_scan_collect reads these and
+// nothing of the context's current state (slot sizes and options may have changed since).
+struct ScanPending {
+  const unsigned long long* counters = nullptr;   // [0]: candidates, [1]: verified
+  const void* survivors = nullptr;
+  size_t cap_idx = 0, cap_out = 0;
+};
+// `owner`: the job the scan belongs to (the pending scans of every other job of the context are collected first: the
+// buffer sets are shared)
+int blob_scan_launch(visfd_hip_ctx* ctx, const BlobJob* owner, int set, hipEvent_t done, const float* lo, const float* mid,
+                     const float* hi, const float* mask, i64 nx, i64 ny, i64 nz, float min_thr, float max_thr,
+                     ScanPending* pending);
+int blob_scan_collect(visfd_hip_ctx* ctx, const ScanPending& pending, hipEvent_t done, hipStream_t aux, i64 nx, i64 ny,
                       int scale_index,
                       float sigma, std::vector<visfd_hip_blob>* minima, std::vector<visfd_hip_blob>* maxima,
                       bool* overflow);
