@@ -177,6 +177,44 @@ int visfd_hip_morph_table_dev(visfd_hip_ctx*, const float* src, float* dst, cons
 #define VISFD_HIP_MORPH_PATH_XRUNS 1      /* morph_runs_kernel: window maxima of X-runs, zero-sign fix-up of erosions */
 int visfd_hip_morph_last_path(visfd_hip_ctx*, int* path);
 
+/* ---- m2: local minima and maxima with plateaus, _FindExtrema (lib/visfd/morphology_implementation.hpp:57-515) ---- */
+/* A plateau is a maximal set of voxels with mask != 0 joined through neighbour pairs of equal value (-0 == +0; a NaN
+ * voxel is alone); its root is its first voxel in raster order.  It is a minimum unless a member has a lower existing
+ * neighbour, a maximum unless a member has a higher one; a neighbour outside the image or with mask == 0 disqualifies
+ * both unless allow_borders.  connectivity 1, 2, 3: the 6, 18, 26 neighbours with dx^2 + dy^2 + dz^2 <= connectivity
+ * (the reference accepts larger values; here they are VISFD_HIP_EINVAL).  Images of 2^31 - 2 voxels and more are
+ * VISFD_HIP_EINVAL too (the union-find word and the labels are 32-bit).
+ * Lists (host arrays on both faces, each may be NULL): root index ix + nx * (iy + ny * iz), root value, voxels of the
+ * plateau.  Minima with value <= minima_threshold ascending in (value, root index); maxima with value >=
+ * maxima_threshold in exactly the reverse of ascending order (the reference's, ties included).  The thresholds are
+ * taken as given: FindMaxima's replacement of +inf by -inf is the caller's (visfd_hip.hpp does it).
+ * *n_min / *n_max always receive the list lengths.  A capacity of 0 writes nothing of that list; 0 < capacity < length:
+ * VISFD_HIP_ECAPACITY and nothing but the counts is written.
+ * labels (NULL: none; the device in the _dev face): the reference's aaaiDest as int32, numbered by position in the
+ * sorted lists, maxima positive, minima negative (positive when only one kind is sought); voxels with mask == 0 are not
+ * written.  The reference's numbering rules are kept.  labels must not overlap src or mask.
+ * Further limits of the classification launch, VISFD_HIP_EINVAL as well: ny and nz at most 524280, and fewer than 2^24
+ * tiles of 64 x 8 x 8 voxels, ceil(nx/64) * ceil(ny/8) * ceil(nz/8) (only very thin images of near 2^31 voxels get there).
+ * Both faces return with the context's stream idle.  Temporaries: 9 bytes per voxel in the context's workspace, 12 bytes
+ * per list entry and, with labels, 8 more per listed entry; the host face also stages src, mask and labels there (4 bytes
+ * per voxel each).  A call that returns VISFD_HIP_ECAPACITY has done all of the device work, and the repeated call does
+ * it again: give the lists room (visfd_hip.hpp and the Python binding start with max(65536, voxels / 32) entries). */
+#define VISFD_HIP_EXTREMA_MAX_CONNECTIVITY 3
+#define VISFD_HIP_EXTREMA_MAX_VOXELS 2147483645LL
+#define VISFD_HIP_EXTREMA_MAX_NY_NZ 524280
+int visfd_hip_find_extrema(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                           int find_minima, int find_maxima, float minima_threshold, float maxima_threshold,
+                           int connectivity, int allow_borders,
+                           int64_t* min_index, float* min_score, int64_t* min_nvoxels, int64_t min_cap, int64_t* n_min,
+                           int64_t* max_index, float* max_score, int64_t* max_nvoxels, int64_t max_cap, int64_t* n_max,
+                           int32_t* labels);
+int visfd_hip_find_extrema_dev(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                               int find_minima, int find_maxima, float minima_threshold, float maxima_threshold,
+                               int connectivity, int allow_borders,
+                               int64_t* min_index, float* min_score, int64_t* min_nvoxels, int64_t min_cap, int64_t* n_min,
+                               int64_t* max_index, float* max_score, int64_t* max_nvoxels, int64_t max_cap, int64_t* n_max,
+                               int32_t* labels);
+
 /* ---- a6: ApplyDog, lib/visfd/filter3d.hpp:1338-1402 -------------------------------------------- */
 int visfd_hip_apply_dog(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
                         int64_t nx, int64_t ny, int64_t nz, const float sigma_a[3],

@@ -394,6 +394,170 @@ inline void BlackTopHatSphere(float radius, const int image_size[3], float const
                            bmax);
 }
 
+// ---- local minima and maxima with plateaus: lib/visfd/morphology.hpp:56-118, morphology_implementation.hpp:57-796 --
+// The reference's signatures and defaults with Scalar = float.  Lists come back in the reference's order; aaaiDest (any
+// arithmetic Label) receives the label image where mask != 0, converted from the 32-bit labels of the C ABI exactly as
+// the reference converts its ptrdiff_t (images have fewer than 2^31 - 2 voxels, so every label fits).  Connectivity
+// above 3 is refused (visfd_hip.h).
+namespace hip_detail {
+struct ExtremaLists {
+  std::vector<int64_t> index[2], nvoxels[2];   // [0] minima, [1] maxima
+  std::vector<float> score[2];
+};
+template <typename Label>
+inline size_t find_extrema(const int image_size[3], float const* const* const* src, float const* const* const* mask,
+                           bool find_minima, bool find_maxima, float minima_threshold, float maxima_threshold,
+                           int connectivity, bool allow_borders, Label*** dest, ExtremaLists* out) {
+  require_contiguous(src, image_size);
+  require_contiguous(mask, image_size);
+  const size_t nvox = (size_t)image_size[0] * image_size[1] * image_size[2];
+  std::vector<int32_t> labels(dest ? nvox : 0);
+  int64_t n[2] = {0, 0};
+  // a first try with room for one voxel in 32 per list (blurred tomograms list about one in 150); a call that finds more
+  // returns the counts, and the second call -- which repeats the device work -- is sized by them
+  const int64_t cap0 = (int64_t)(nvox / 32) > 65536 ? (int64_t)(nvox / 32) : 65536;
+  int64_t cap[2] = {find_minima ? cap0 : 1, find_maxima ? cap0 : 1};
+  for (;;) {
+    for (int k = 0; k < 2; k++) {
+      out->index[k].resize((size_t)cap[k]);
+      out->score[k].resize((size_t)cap[k]);
+      out->nvoxels[k].resize((size_t)cap[k]);
+    }
+    const int rc = visfd_hip_find_extrema(
+        context(), flat(src), flat(mask), image_size[0], image_size[1], image_size[2], find_minima ? 1 : 0,
+        find_maxima ? 1 : 0, minima_threshold, maxima_threshold, connectivity, allow_borders ? 1 : 0,
+        out->index[0].data(), out->score[0].data(), out->nvoxels[0].data(), cap[0], &n[0], out->index[1].data(),
+        out->score[1].data(), out->nvoxels[1].data(), cap[1], &n[1], dest ? labels.data() : nullptr);
+    if (rc != VISFD_HIP_ECAPACITY) {
+      check(rc);
+      break;
+    }
+    cap[0] = n[0] > cap[0] ? n[0] : cap[0];
+    cap[1] = n[1] > cap[1] ? n[1] : cap[1];
+  }
+  for (int k = 0; k < 2; k++) {
+    out->index[k].resize((size_t)n[k]);
+    out->score[k].resize((size_t)n[k]);
+    out->nvoxels[k].resize((size_t)n[k]);
+  }
+  if (dest) {
+    size_t i = 0;
+    for (int iz = 0; iz < image_size[2]; iz++)
+      for (int iy = 0; iy < image_size[1]; iy++)
+        for (int ix = 0; ix < image_size[0]; ix++, i++)
+          if (!mask || mask[iz][iy][ix] != 0.0f) dest[iz][iy][ix] = (Label)labels[i];
+  }
+  return (size_t)(n[0] + n[1]);
+}
+template <typename T, typename S>
+inline void assign(std::vector<T>* dst, const std::vector<S>& src) {
+  if (!dst) return;
+  dst->resize(src.size());
+  for (size_t k = 0; k < src.size(); k++) (*dst)[k] = (T)src[k];
+}
+template <typename Coordinate>
+inline void assign_crds(std::vector<std::array<Coordinate, 3> >* dst, const std::vector<int64_t>& index,
+                        const int image_size[3]) {
+  if (!dst) return;
+  dst->resize(index.size());
+  for (size_t k = 0; k < index.size(); k++) {
+    size_t i = (size_t)index[k];
+    (*dst)[k][0] = (Coordinate)(i % image_size[0]);
+    i /= image_size[0];
+    (*dst)[k][1] = (Coordinate)(i % image_size[1]);
+    (*dst)[k][2] = (Coordinate)(i / image_size[1]);
+  }
+}
+}  // namespace hip_detail
+
+// both lists, locations as linear indices ix + nx * (iy + ny * iz); a null index list means that kind is not sought
+template <typename IntegerIndex, typename Label>
+size_t _FindExtrema(int const image_size[3], float const* const* const* aaafSource, float const* const* const* aaafMask,
+                    std::vector<IntegerIndex>* pv_minima_indices, std::vector<IntegerIndex>* pv_maxima_indices,
+                    std::vector<float>* pv_minima_scores, std::vector<float>* pv_maxima_scores,
+                    std::vector<IntegerIndex>* pv_minima_nvoxels, std::vector<IntegerIndex>* pv_maxima_nvoxels,
+                    float minima_threshold = std::numeric_limits<float>::infinity(),
+                    float maxima_threshold = -std::numeric_limits<float>::infinity(), int connectivity = 3,
+                    bool allow_borders = true, Label*** aaaiDest = nullptr, std::ostream* = nullptr) {
+  hip_detail::ExtremaLists l;
+  const bool find_minima = pv_minima_indices != nullptr, find_maxima = pv_maxima_indices != nullptr;
+  const size_t n = hip_detail::find_extrema(image_size, aaafSource, aaafMask, find_minima, find_maxima, minima_threshold,
+                                            maxima_threshold, connectivity, allow_borders, aaaiDest, &l);
+  if (find_minima) {
+    hip_detail::assign(pv_minima_indices, l.index[0]);
+    hip_detail::assign(pv_minima_scores, l.score[0]);
+    hip_detail::assign(pv_minima_nvoxels, l.nvoxels[0]);
+  }
+  if (find_maxima) {
+    hip_detail::assign(pv_maxima_indices, l.index[1]);
+    hip_detail::assign(pv_maxima_scores, l.score[1]);
+    hip_detail::assign(pv_maxima_nvoxels, l.nvoxels[1]);
+  }
+  return n;
+}
+// both lists, locations as (ix, iy, iz)
+template <typename Coordinate, typename IntegerIndex, typename Label>
+size_t _FindExtrema(int const image_size[3], float const* const* const* aaafI, float const* const* const* aaafMask,
+                    std::vector<std::array<Coordinate, 3> >* pva_minima_crds,
+                    std::vector<std::array<Coordinate, 3> >* pva_maxima_crds, std::vector<float>* pv_minima_scores,
+                    std::vector<float>* pv_maxima_scores, std::vector<IntegerIndex>* pv_minima_nvoxels,
+                    std::vector<IntegerIndex>* pv_maxima_nvoxels,
+                    float minima_threshold = std::numeric_limits<float>::infinity(),
+                    float maxima_threshold = -std::numeric_limits<float>::infinity(), int connectivity = 3,
+                    bool allow_borders = true, Label*** aaaiDest = nullptr, std::ostream* = nullptr) {
+  hip_detail::ExtremaLists l;
+  const bool find_minima = pva_minima_crds != nullptr, find_maxima = pva_maxima_crds != nullptr;
+  const size_t n = hip_detail::find_extrema(image_size, aaafI, aaafMask, find_minima, find_maxima, minima_threshold,
+                                            maxima_threshold, connectivity, allow_borders, aaaiDest, &l);
+  if (find_minima) {
+    hip_detail::assign_crds(pva_minima_crds, l.index[0], image_size);
+    hip_detail::assign(pv_minima_scores, l.score[0]);
+    hip_detail::assign(pv_minima_nvoxels, l.nvoxels[0]);
+  }
+  if (find_maxima) {
+    hip_detail::assign_crds(pva_maxima_crds, l.index[1], image_size);
+    hip_detail::assign(pv_maxima_scores, l.score[1]);
+    hip_detail::assign(pv_maxima_nvoxels, l.nvoxels[1]);
+  }
+  return n;
+}
+// one kind, locations as (ix, iy, iz).  Seeking maxima, a threshold of +inf means none (morphology_implementation.hpp:775-776).
+template <typename Coordinate, typename IntegerIndex, typename Label>
+size_t _FindExtrema(int const image_size[3], float const* const* const* aaafI, float const* const* const* aaafMask,
+                    std::vector<std::array<Coordinate, 3> >& extrema_crds, std::vector<float>& extrema_scores,
+                    std::vector<IntegerIndex>& extrema_nvoxels, bool seek_minima = true,
+                    float threshold = std::numeric_limits<float>::infinity(), int connectivity = 3,
+                    bool allow_borders = true, Label*** aaaiDest = nullptr, std::ostream* = nullptr) {
+  const float inf = std::numeric_limits<float>::infinity();
+  std::vector<std::array<Coordinate, 3> >* none_crds = nullptr;
+  std::vector<float>* none_scores = nullptr;
+  std::vector<IntegerIndex>* none_nvoxels = nullptr;
+  if (seek_minima)
+    return _FindExtrema(image_size, aaafI, aaafMask, &extrema_crds, none_crds, &extrema_scores, none_scores,
+                        &extrema_nvoxels, none_nvoxels, threshold, -inf, connectivity, allow_borders, aaaiDest);
+  if (threshold == inf) threshold = -inf;
+  return _FindExtrema(image_size, aaafI, aaafMask, none_crds, &extrema_crds, none_scores, &extrema_scores, none_nvoxels,
+                      &extrema_nvoxels, inf, threshold, connectivity, allow_borders, aaaiDest);
+}
+template <typename Coordinate, typename IntegerIndex, typename Label>
+size_t FindMinima(int const image_size[3], float const* const* const* aaafI, float const* const* const* aaafMask,
+                  std::vector<std::array<Coordinate, 3> >& minima_crds, std::vector<float>& minima_scores,
+                  std::vector<IntegerIndex>& minima_nvoxels, float threshold = std::numeric_limits<float>::infinity(),
+                  int connectivity = 3, bool allow_borders = true, Label*** aaaiDest = nullptr,
+                  std::ostream* pReportProgress = nullptr) {
+  return _FindExtrema(image_size, aaafI, aaafMask, minima_crds, minima_scores, minima_nvoxels, true, threshold,
+                      connectivity, allow_borders, aaaiDest, pReportProgress);
+}
+template <typename Coordinate, typename IntegerIndex, typename Label>
+size_t FindMaxima(int const image_size[3], float const* const* const* aaafI, float const* const* const* aaafMask,
+                  std::vector<std::array<Coordinate, 3> >& maxima_crds, std::vector<float>& maxima_scores,
+                  std::vector<IntegerIndex>& maxima_nvoxels, float threshold = std::numeric_limits<float>::infinity(),
+                  int connectivity = 3, bool allow_borders = true, Label*** aaaiDest = nullptr,
+                  std::ostream* pReportProgress = nullptr) {
+  return _FindExtrema(image_size, aaafI, aaafMask, maxima_crds, maxima_scores, maxima_nvoxels, false, threshold,
+                      connectivity, allow_borders, aaaiDest, pReportProgress);
+}
+
 // ---- LocalFluctuations: lib/visfd/filter3d.hpp:1698-1711 (Gaussian weights: exponent must be 2) -------
 inline void LocalFluctuations(const int image_size[3], float const* const* const* src, float*** dest,
                               float const* const* const* mask, const float sigma[3],

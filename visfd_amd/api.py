@@ -44,6 +44,9 @@ class Blob(C.Structure):
 
 _VOL = [_vp, _vp, _vp, _i64, _i64, _i64]  # src, dst, mask, nx, ny, nz  (pointers as void*)
 
+# find_minima, find_maxima, both thresholds, connectivity, allow_borders, then (index, score, nvoxels, cap, n) per kind, labels
+_EXTREMA_TAIL = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + 2 * [_vp, _vp, _vp, _i64, C.POINTER(_i64)] + [_vp]
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -64,6 +67,8 @@ _SIGS = {
     "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_table_dev": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
+    "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_fluctuation_sigmas": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _fp, C.POINTER(C.c_float)]),
     "visfd_hip_gauss_halfwidths": (C.c_int, [_fp, C.c_float, _ip]),
     "visfd_hip_separable3d": (C.c_int, [_vp] + _VOL + [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
@@ -640,6 +645,55 @@ class Context:
                                                 d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
         return dst
 
+    def _find_extrema(self, fn, src, mask, shape, find_minima, find_maxima, minima_threshold, maxima_threshold,
+                      connectivity, allow_borders, labels):
+        """The capacity protocol of visfd_hip_find_extrema[_dev]: a first call with room for max(65536, voxels / 32)
+        entries per list, a second -- which repeats the device work -- with the returned counts if that was too little."""
+        nz, ny, nx = shape
+        cap = 2 * [max(65536, nz * ny * nx // 32)]
+        while True:
+            lists = [(np.empty(c, np.int64), np.empty(c, np.float32), np.empty(c, np.int64)) for c in cap]
+            n = [_i64(), _i64()]
+            tail = []
+            for (i, sc, nv), c, cnt in zip(lists, cap, n):
+                tail += [i.ctypes.data, sc.ctypes.data, nv.ctypes.data, c, C.byref(cnt)]
+            rc = fn(self._h, src, mask, nx, ny, nz, int(bool(find_minima)), int(bool(find_maxima)),
+                    float(minima_threshold), float(maxima_threshold), int(connectivity), int(bool(allow_borders)),
+                    *(tail + [labels]))
+            if rc == 4 and (n[0].value > cap[0] or n[1].value > cap[1]):   # VISFD_HIP_ECAPACITY
+                cap = [max(int(n[0].value), 1), max(int(n[1].value), 1)]
+                continue
+            self._chk(rc)
+            return [tuple(a[:cnt.value].copy() for a in l) for l, cnt in zip(lists, n)]
+
+    def find_extrema(self, src, mask=None, find_minima=True, find_maxima=True, minima_threshold=float("inf"),
+                     maxima_threshold=-float("inf"), connectivity=3, allow_borders=True, want_labels=False, labels=None):
+        """Plateau-aware local minima and maxima (_FindExtrema, morphology_implementation.hpp:57-515) of a numpy
+        volume (nz, ny, nx): -> (minima, maxima[, labels]), each list (root index int64, score float32, voxels int64) in
+        the reference's order; a kind that was not asked for comes back empty.  want_labels / labels: also the int32
+        label image (written into a copy of `labels`, default zeros: voxels with mask == 0 keep those values).
+        FindMaxima's own rule -- a threshold of +inf means none -- is find_maxima_only's."""
+        out = None
+        if want_labels or labels is not None:
+            out = np.zeros(src.shape, np.int32) if labels is None else np.array(labels, np.int32, copy=True, order="C")
+            assert out.shape == src.shape
+        mins, maxs = self._find_extrema(self._L.visfd_hip_find_extrema, _np(src), _np(mask), src.shape, find_minima,
+                                        find_maxima, minima_threshold, maxima_threshold, connectivity, allow_borders,
+                                        None if out is None else out.ctypes.data)
+        return (mins, maxs) if out is None else (mins, maxs, out)
+
+    def find_minima_only(self, src, mask=None, threshold=float("inf"), connectivity=3, allow_borders=True, **kw):
+        """visfd::FindMinima: -> (minima[, labels])."""
+        r = self.find_extrema(src, mask, True, False, threshold, -float("inf"), connectivity, allow_borders, **kw)
+        return r[0] if len(r) == 2 else (r[0], r[2])
+
+    def find_maxima_only(self, src, mask=None, threshold=float("inf"), connectivity=3, allow_borders=True, **kw):
+        """visfd::FindMaxima: -> (maxima[, labels]); a threshold of +inf is taken as -inf, as the reference does."""
+        if threshold == float("inf"):
+            threshold = -float("inf")
+        r = self.find_extrema(src, mask, False, True, float("inf"), threshold, connectivity, allow_borders, **kw)
+        return r[1] if len(r) == 2 else (r[1], r[2])
+
     def morph_last_path(self):
         """The kernel the last morphology call ran: MORPH_PATH_GENERAL or MORPH_PATH_XRUNS (-1 before the first)."""
         p = C.c_int()
@@ -885,6 +939,17 @@ class Context:
 
     def black_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
         self.morph_sphere_dev(MORPH_TOP_HAT_BLACK, src, dst, radius, radius_max, bmax, mask)
+
+    def find_extrema_dev(self, src, mask=None, find_minima=True, find_maxima=True, minima_threshold=float("inf"),
+                         maxima_threshold=-float("inf"), connectivity=3, allow_borders=True, labels=None):
+        """find_extrema on device tensors: -> (minima, maxima) as numpy lists; labels (an int32 cuda tensor, optional) is
+        written in place where mask != 0.  Returns with the stream idle."""
+        if labels is not None:
+            assert labels.is_cuda and labels.is_contiguous() and str(labels.dtype) == "torch.int32" and \
+                tuple(labels.shape) == tuple(src.shape), "labels: contiguous cuda int32 of src's shape"
+        return tuple(self._find_extrema(self._L.visfd_hip_find_extrema_dev, _dev(src), _dev(mask), tuple(src.shape),
+                                        find_minima, find_maxima, minima_threshold, maxima_threshold, connectivity,
+                                        allow_borders, None if labels is None else labels.data_ptr()))
 
     def morph_table_dev(self, op, src, dst, dxyz, b, mask=None):
         nz, ny, nx = src.shape

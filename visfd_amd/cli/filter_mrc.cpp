@@ -19,6 +19,8 @@
 //   -dilate|-dilation R | -erode|-erosion R | -open|-opening R | -close|-closing R | -top-hat-white R | -top-hat-black R
 //   -dilate-binary-soft|-dilation-binary-soft R RMAX BMAX | -erode-binary-soft|-erosion-binary-soft R RMAX BMAX
 //                                                                      (settings.cpp:722-915, handlers.cpp:41-145)
+//   -find-minima FILE | -find-maxima FILE (both may be given) | -neighbor-connectivity N (1, 2 or 3) |
+//   -boundary-extrema | -ignore-boundary-extrema                       (settings.cpp:2202-2259, HandleExtrema)
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is written from the MRC2014 layout description (1024-byte header: nx,ny,nz,mode,
@@ -146,10 +148,15 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until main() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
+  // local minima / maxima (settings.cpp:97-102)
+  bool find_minima = false, find_maxima = false;
+  string find_minima_file, find_maxima_file;
+  int neighbor_connectivity = 3;
+  bool extrema_on_boundary = true;
   float width_a[3] = {0, 0, 0}, width_b[3] = {0, 0, 0}, log_width[3] = {0, 0, 0};
   float template_background_radius[3] = {-1, -1, -1};        // settings.cpp:222-225 (-fluct)
   float template_background_exponent = 2.0f;
@@ -266,6 +273,24 @@ Settings parse(int argc, char** argv) {
       s.morph_op = (f == "-dilate-binary-soft" || f == "-dilation-binary-soft") ? VISFD_HIP_MORPH_DILATE : VISFD_HIP_MORPH_ERODE;
       s.type = Settings::MORPHOLOGY; i += 4;
     }
+    else if (f == "-find-minima" || f == "-find-maxima") {   // settings.cpp:2202-2231 (the wording is the reference's)
+      if (i + 1 >= v.size()) throw VisfdErr("Error: The " + f + " argument must be followed by a number.\n");
+      if (f == "-find-minima") { s.find_minima = true; s.find_minima_file = v[i + 1]; }
+      else { s.find_maxima = true; s.find_maxima_file = v[i + 1]; }
+      s.type = Settings::FIND_EXTREMA; i += 2;
+    }
+    else if (f == "-neighbor-connectivity") {   // settings.cpp:2234-2247
+      const string msg = "Error: The " + f + " argument must be followed by a positive integer.\n";
+      if (i + 1 >= v.size()) throw VisfdErr(msg);
+      try { s.neighbor_connectivity = std::stoi(v[i + 1]); } catch (...) { throw VisfdErr(msg); }
+      if (s.neighbor_connectivity <= 0) throw VisfdErr(msg);
+      if (s.neighbor_connectivity > VISFD_HIP_EXTREMA_MAX_CONNECTIVITY)
+        throw VisfdErr("Error: The " + f + " argument must be 1, 2 or 3 (6, 18 or 26 neighbors) in this program:\n"
+                       "       larger neighborhoods are not supported on the GPU.\n");
+      i += 2;
+    }
+    else if (f == "-boundary-extrema") { s.extrema_on_boundary = true; i += 1; }
+    else if (f == "-ignore-boundary-extrema") { s.extrema_on_boundary = false; i += 1; }
     else if (f == "-gauss-aniso") { need(3); for (int d = 0; d < 3; d++) s.width_a[d] = num(v, i + 1 + d, f); s.type = Settings::GAUSS; i += 4; }
     else if (f == "-dog") {
       need(2);
@@ -916,6 +941,30 @@ int main(int argc, char** argv) {
           WhiteTopHatSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
         default:
           BlackTopHatSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
+      }
+    } else if (s.type == Settings::FIND_EXTREMA) {
+      // HandleExtrema, handlers.cpp:1086-1245 (without the optional thinning by a sphere diameter, :1165-1211: this
+      // program has none of the -sphere* / -diameters flags that would switch it on)
+      std::memset(tomo_out.data(), 0, tomo_out.nvox() * 4);
+      vector<std::array<float, 3> > crds[2];
+      vector<float> scores[2];
+      vector<size_t> nvoxels[2];
+      const size_t num_extrema =
+          _FindExtrema(size, tomo_in.a, M, s.find_minima ? &crds[0] : nullptr, s.find_maxima ? &crds[1] : nullptr,
+                       s.find_minima ? &scores[0] : nullptr, s.find_maxima ? &scores[1] : nullptr,
+                       s.find_minima ? &nvoxels[0] : nullptr, s.find_maxima ? &nvoxels[1] : nullptr, s.score_upper,
+                       s.score_lower, s.neighbor_connectivity, s.extrema_on_boundary, tomo_out.a, &cerr);
+      cerr << "Found " << num_extrema << " extrema" << std::endl;
+      for (int side = 0; side < 2; side++) {
+        const string& fname = side ? s.find_maxima_file : s.find_minima_file;
+        if (crds[side].empty() || !(side ? s.find_maxima : s.find_minima)) continue;   // no file for an empty list
+        std::fstream out;
+        out.open(fname.c_str(), std::ios::out);
+        // "for reading" is the reference's wording for this file it writes (handlers.cpp:1223, :1236)
+        if (!out) throw VisfdErr("Error: unable to open \"" + fname + "\" for reading.\n");
+        for (size_t k = 0; k < crds[side].size(); k++)
+          out << crds[side][k][0] * vw[0] << " " << crds[side][k][1] * vw[1] << " " << crds[side][k][2] * vw[2] << " "
+              << nvoxels[side][k] << " " << scores[side][k] << "\n";
       }
     } else if (s.type == Settings::BLOB_NONMAX) {
       handle_blob_nonmax(s, vw, M, size);

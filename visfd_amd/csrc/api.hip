@@ -1388,4 +1388,42 @@ int visfd_hip_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, cons
   });
 }
 
+// ---- m2: local minima and maxima with plateaus (csrc/extrema.hip) ---------------------------------
+int visfd_hip_find_extrema_dev(visfd_hip_ctx* ctx, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                               int find_minima, int find_maxima, float minima_threshold, float maxima_threshold,
+                               int connectivity, int allow_borders, int64_t* min_index, float* min_score,
+                               int64_t* min_nvoxels, int64_t min_cap, int64_t* n_min, int64_t* max_index, float* max_score,
+                               int64_t* max_nvoxels, int64_t max_cap, int64_t* n_max, int32_t* labels) {
+  const ExtremaArgs a = {src, mask, nx, ny, nz, find_minima, find_maxima, minima_threshold, maxima_threshold, connectivity,
+                         allow_borders, min_index, min_nvoxels, max_index, max_nvoxels, min_score, max_score, min_cap,
+                         max_cap, n_min, n_max, labels};
+  VH_TRY(extrema_check_args(ctx, a));
+  return dev_find_extrema(ctx, a);
+}
+
+int visfd_hip_find_extrema(visfd_hip_ctx* ctx, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                           int find_minima, int find_maxima, float minima_threshold, float maxima_threshold,
+                           int connectivity, int allow_borders, int64_t* min_index, float* min_score, int64_t* min_nvoxels,
+                           int64_t min_cap, int64_t* n_min, int64_t* max_index, float* max_score, int64_t* max_nvoxels,
+                           int64_t max_cap, int64_t* n_max, int32_t* labels) {
+  ExtremaArgs a = {src, mask, nx, ny, nz, find_minima, find_maxima, minima_threshold, maxima_threshold, connectivity,
+                   allow_borders, min_index, min_nvoxels, max_index, max_nvoxels, min_score, max_score, min_cap, max_cap,
+                   n_min, n_max, labels};
+  VH_TRY(extrema_check_args(ctx, a));
+  VH_HIP(hipSetDevice(ctx->device));
+  const size_t n = (size_t)(nx * ny * nz);
+  float *ds, *dm, *dl = nullptr;
+  VH_TRY(upload(ctx, WS_H2D_0, src, n, &ds));
+  VH_TRY(upload(ctx, WS_H2D_1, mask, n, &dm));
+  // the labels (32-bit words like the floats) go up when there is a mask: voxels with mask == 0 keep their values
+  if (labels && mask) VH_TRY(upload(ctx, WS_H2D_2, reinterpret_cast<const float*>(labels), n, &dl));
+  else if (labels) VH_TRY(ws(ctx, WS_H2D_2, n, &dl));
+  a.src = ds;
+  a.mask = dm;
+  a.labels = reinterpret_cast<int32_t*>(dl);
+  VH_TRY(dev_find_extrema(ctx, a));
+  if (labels) VH_TRY(download(ctx, reinterpret_cast<float*>(labels), dl, n));
+  return VISFD_HIP_OK;
+}
+
 }  // extern "C"

@@ -56,6 +56,12 @@ enum Slot {
   WS_MORPH_TAB,                    // morphology: the structuring element on the device (host copy in visfd_hip_ctx::morph_tab)
   WS_MORPH_SRC,                    // morphology: the source with masked voxels replaced by NaN
   WS_MORPH_TMP,                    // morphology: the intermediate image of open / close / the top-hats
+  WS_EXT_FLAGS,                    // extrema: one byte of neighbour facts per voxel (csrc/extrema.hip)
+  WS_EXT_PARENT,                   // extrema: the union-find word of every voxel (int32)
+  WS_EXT_COUNT,                    // extrema: voxels per plateau, at the plateau's root (int32 per voxel)
+  WS_EXT_COUNTERS,                 // extrema: the two list lengths
+  WS_EXT_LIST,                     // extrema: the unsorted lists (index, score, voxels)
+  WS_EXT_RANKS,                    // extrema: listed roots in raster order and their sorted positions, for the label image
   WS_NSLOTS
 };
 
@@ -257,6 +263,25 @@ int dev_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
                     const MorphElem& el, bool dilate, int epi, bool nan_masked, int* path);
 // out = (mask == 0) ? NaN : src
 int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, float* out, i64 n);
+
+// extrema.hip: plateau-aware minima and maxima (visfd_hip_find_extrema[_dev], include/visfd_hip.h)
+struct ExtremaArgs {
+  const float* src;
+  const float* mask;
+  i64 nx, ny, nz;
+  int find_minima, find_maxima;
+  float minima_threshold, maxima_threshold;
+  int connectivity, allow_borders;
+  int64_t *min_index, *min_nvoxels, *max_index, *max_nvoxels;
+  float *min_score, *max_score;
+  int64_t min_cap, max_cap;
+  int64_t *n_min, *n_max;
+  int32_t* labels;
+};
+// everything that can be said without a device, the context last
+int extrema_check_args(const visfd_hip_ctx* ctx, const ExtremaArgs& a);
+// src, mask, labels on the device; the lists on the host.  Returns with the stream idle.
+int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a);
 
 // resample.hip (sizes are {nx, ny, nz}; offset nullable)
 int dev_bin_array3d(visfd_hip_ctx* ctx, const float* src, const int64_t size_src[3], float* dst,
