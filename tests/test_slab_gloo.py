@@ -115,7 +115,7 @@ SEAM_SIGMAS = (1.4954885, 0.74774426, 1.8693607, 2.990977, 3.7387214)
 
 
 def _plan_log_hw_f32(sigma, delta, ratio):
-    """plan_log (csrc/api.hip) restated in float32 numpy: sigma_a/b = (float)(sigma * (1 -/+ delta/2)) with the factor in
+    """plan_log (csrc/api.hip, declared in common.hpp) restated in float32 numpy: sigma_a/b = (float)(sigma * (1 -/+ delta/2)) with the factor in
     double, the half-width floor(ratio * max(sigma_a, sigma_b)) as a float32 product."""
     s, d = float(np.float32(sigma)), float(np.float32(delta))
     sa = np.float32(s * (1.0 - 0.5 * d))

@@ -266,7 +266,7 @@ struct ScanBufs {
 static int scan_bufs(visfd_hip_ctx* ctx, int set, ScanBufs* B, bool pipelined, i64 nvox) {
   // at least 4 M candidates / 1 M survivors, and room for 1 voxel in 32 / 128 (noise volumes at 1024^3 give ~1 in
   // 100 / 1 in 4000 per scale): the pipelined scan then does not overflow on its first call
-  constexpr size_t NSET = 3;   // buffer sets of the pipelined scan (api.hip: blob_dog_dev)
+  constexpr size_t NSET = 3;   // buffer sets of the pipelined scan (blob_job.hip: BlobJob::NSET)
   size_t cap_idx = ctx->slot_bytes[WS_TVAUX] / sizeof(unsigned long long) / NSET;
   if (cap_idx < (1u << 22)) cap_idx = 1u << 22;
   if (cap_idx < (size_t)(nvox / 32)) cap_idx = (size_t)(nvox / 32);

@@ -65,7 +65,7 @@ enum Slot {
   WS_NSLOTS
 };
 
-struct BlobJob;   // api.hip: one visfd_hip_blob_dog_begin_dev that has not been ended or aborted yet
+struct BlobJob;   // blob_job.hip: one visfd_hip_blob_dog_begin_dev that has not been ended or aborted yet
 
 }  // namespace vh
 
@@ -107,7 +107,7 @@ struct visfd_hip_ctx {
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
   std::vector<int> morph_tab;         // the structuring element now in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b)
   int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
-  std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (api.hip: blob_jobs_drain)
+  std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };
 
 namespace vh {
@@ -117,6 +117,7 @@ namespace vh {
 // overwrites the buffers a pending scan writes to (WS_CAND, WS_SCANCNT): ws_get when one of them grows, visfd_hip_trim,
 // and every scan launched for another job.  With nothing pending -- the usual case -- it is a loop over an empty list.
 int blob_jobs_drain(visfd_hip_ctx* ctx, const BlobJob* except = nullptr);
+void blob_jobs_abort(visfd_hip_ctx* ctx);   // visfd_hip_destroy: the context's jobs go with it (their handles then name no live job)
 
 // returns a device buffer of at least `bytes` bytes in slot `s` (contents undefined)
 int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out);
@@ -130,6 +131,10 @@ inline int ws(visfd_hip_ctx* ctx, Slot s, size_t count, T** out) {
 
 inline int check_dims(i64 nx, i64 ny, i64 nz) {
   if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VISFD_HIP_EINVAL, "image dimensions must be positive");
+  return VISFD_HIP_OK;
+}
+inline int check_dims32(i64 nx, i64 ny, i64 nz) {   // for the kernels that index a volume with 32-bit coordinates
+  if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
   return VISFD_HIP_OK;
 }
 
@@ -182,6 +187,18 @@ int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
                     bool fma = false);
 // dst = (a - b) * scale  with two roundings (filter3d.hpp:1387-1390,1495-1498); scale==1: no multiply
 int dev_sub_scale(visfd_hip_ctx* ctx, float* a_inout, const float* b, i64 n, float scale, bool do_scale);
+
+// api.hip: the Gaussian from sigmas and half-widths (the trailing arguments are dev_separable3d's), and ApplyLog
+int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+              const float sigma[3], const int hw[3], bool normalize, SlabInfo slab, float* A_out,
+              const float* minuend = nullptr, float log_scale = 1.0f, bool* epilogue_done = nullptr, bool fma = false);
+struct LogPlan {
+  float sa[3], sb[3], scale;
+  int hw[3];
+};
+LogPlan plan_log(const float sigma[3], float delta, float ratio);
+int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, float* tmp, const float* mask, i64 nx, i64 ny,
+            i64 nz, const float sigma[3], float delta, float ratio, float* A, float* B);
 // LocalFluctuations element-wise steps (filter3d.hpp:1776-1790 and :1819-1846)
 int dev_sub_square(visfd_hip_ctx* ctx, const float* a, const float* b, float* out, i64 n);   // out = (a-b)*(a-b)
 int dev_scale_clamp_sqrt(visfd_hip_ctx* ctx, float* a_inout, i64 n, float scale);           // a = sqrt(max(a*scale, 0))
@@ -263,6 +280,10 @@ int dev_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
                     const MorphElem& el, bool dilate, int epi, bool nan_masked, int* path);
 // out = (mask == 0) ? NaN : src
 int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, float* out, i64 n);
+// the orchestration (tail of morph.hip): an element into WS_MORPH_TAB (`el` describes it), and one op with it
+int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el);
+int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
+              MorphElem el);
 
 // extrema.hip: plateau-aware minima and maxima (visfd_hip_find_extrema[_dev], include/visfd_hip.h)
 struct ExtremaArgs {
@@ -293,6 +314,63 @@ int dev_unbin_array3d(visfd_hip_ctx* ctx, const float* src, const int64_t size_s
 int dev_interleaved_to_planar(visfd_hip_ctx* ctx, const float* aos, float* planar, i64 n, int channels);
 int dev_planar_to_interleaved(visfd_hip_ctx* ctx, const float* planar, float* aos, i64 n, int channels,
                               const float* mask /*nullable: only where mask!=0*/);
+
+// How the host-pointer entry points move the caller's arrays through the workspace slots: every copy is asynchronous on
+// ctx->stream, and `down` ends with the call's synchronisation.
+struct Stage {
+  visfd_hip_ctx* ctx;
+  size_t n;   // voxels; an array has channels * n floats
+
+  // channels * n floats in slot s, filled from the caller's array unless `fill` is null
+  int out(Slot s, float** dev, int channels = 1, const float* fill = nullptr) const {
+    VH_TRY(ws(ctx, s, channels * n, dev));
+    if (fill) VH_HIP(hipMemcpyAsync(*dev, fill, sizeof(float) * channels * n, hipMemcpyHostToDevice, ctx->stream));
+    return VISFD_HIP_OK;
+  }
+  // a nullable host array into slot s: a null one takes no memory and gives a null device pointer
+  int up(Slot s, const float* host, float** dev, int channels = 1) const {
+    *dev = nullptr;
+    return host ? out(s, dev, channels, host) : VISFD_HIP_OK;
+  }
+  int down(float* host, const float* dev, int channels = 1) const {
+    VH_HIP(hipMemcpyAsync(host, dev, sizeof(float) * channels * n, hipMemcpyDeviceToHost, ctx->stream));
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    return VISFD_HIP_OK;
+  }
+  // an interleaved host array into slot s_aos and, channel by channel, into slot s_planar
+  int up_planar(Slot s_aos, Slot s_planar, const float* host, int channels, float** planar, float** aos = nullptr) const {
+    float* a = nullptr;
+    VH_TRY(out(s_aos, &a, channels, host));
+    VH_TRY(out(s_planar, planar, channels));
+    if (aos) *aos = a;
+    return dev_interleaved_to_planar(ctx, a, *planar, (i64)n, channels);
+  }
+  // planar channels back to the caller's interleaved array through the device buffer `aos`.  keep: the caller's values
+  // go up first, so that voxels with mask == 0 (which the interleave skips) come back as they were
+  int down_interleaved(float* host, const float* planar, float* aos, int channels, const float* mask, bool keep) const {
+    if (keep) VH_HIP(hipMemcpyAsync(aos, host, sizeof(float) * channels * n, hipMemcpyHostToDevice, ctx->stream));
+    VH_TRY(dev_planar_to_interleaved(ctx, planar, aos, (i64)n, channels, mask));
+    return down(host, aos, channels);
+  }
+};
+
+// The commonest face: the checks every such face starts with (those that have checked more already pass them again), src
+// and mask up (slots WS_H2D_0 and _1), dst reserved in WS_H2D_2 -- filled from the caller's array when the stage leaves
+// some of its voxels alone or reads it (dst_up) -- `run(src, dst, mask)` on the device copies, and dst down.
+template <typename Run>
+int stage_filter(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, bool dst_up,
+                 Run run) {
+  VH_REQUIRE(ctx && src && dst, "null argument");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(check_dims(nx, ny, nz));
+  const Stage st = {ctx, (size_t)(nx * ny * nz)};
+  float *ds, *dm, *dd;
+  VH_TRY(st.up(WS_H2D_0, src, &ds));
+  VH_TRY(st.up(WS_H2D_1, mask, &dm));
+  VH_TRY(st.out(WS_H2D_2, &dd, 1, dst_up ? dst : nullptr));
+  VH_TRY(run(ds, dd, dm));
+  return st.down(dst, dd);
+}
 
 inline unsigned grid_for(i64 n, int block, i64 cap = (i64)1 << 30) {
   i64 g = (n + block - 1) / block;

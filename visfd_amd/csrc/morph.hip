@@ -1,6 +1,6 @@
 // morph.hip -- grayscale morphology with an arbitrary structuring element: Dilate / Erode
 // (reference lib/visfd/morphology.hpp:134-229), the building block of DilateSphere, ErodeSphere, OpenSphere,
-// CloseSphere and the two top-hats (:241-597; the orchestration is in api.hip).
+// CloseSphere and the two top-hats (:241-597; the orchestration is at the end of this file).
 //
 // Exact by construction: every voxel walks the element in the reference's order and keeps its running value with the
 // reference's compare-select (std::max / std::min: cur = (cur < c) ? c : cur, cur = (c < cur) ? c : cur), so NaN
@@ -18,7 +18,9 @@
 // scalar arithmetic.  A workgroup whose voxels and whole element footprint lie inside the image takes the loop without
 // bounds tests.  Elements whose b are all +0.0f (flat balls) skip the add: f - (+0) == f bit for bit where it can win,
 // and the dilation adds its +0.0f once at the end (the winner is the same; -0 turns into +0 as the reference's f + 0 does).
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "common.hpp"
 
@@ -247,6 +249,91 @@ int dev_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
 #undef VH_MORPH_LAUNCH
   VH_HIP(hipGetLastError());
   *path = VISFD_HIP_MORPH_PATH_GENERAL;
+  return VISFD_HIP_OK;
+}
+
+// puts the element in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b); an element equal to the one already
+// there is not sent again.  Fills `el`: count, bounding box, flatness and, for flat elements made of symmetric X-runs,
+// the run length of every (dy, dz) row (the X-run kernel's input).
+int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el) {
+  VH_REQUIRE(n >= 0 && n < ((i64)1 << 31), "morphology: too many structuring element entries");
+  VH_REQUIRE(n == 0 || (dxyz && b), "null argument");
+  std::vector<int> t((size_t)(4 * n));
+  el->n = n;
+  el->flat = true;
+  int* lo = el->lo;
+  int* hi = el->hi;
+  for (int d = 0; d < 3; d++) lo[d] = hi[d] = 0;
+  for (i64 k = 0; k < n; k++) {
+    for (int d = 0; d < 3; d++) {
+      const int v = dxyz[3 * k + d];
+      VH_REQUIRE(v > -(1 << 30) && v < (1 << 30), "morphology: structuring element offsets must be below 2^30");
+      lo[d] = (k == 0 || v < lo[d]) ? v : lo[d];
+      hi[d] = (k == 0 || v > hi[d]) ? v : hi[d];
+      t[4 * k + d] = v;
+    }
+    int bits;
+    std::memcpy(&bits, &b[k], 4);
+    t[4 * k + 3] = bits;
+    if (bits != 0) el->flat = false;
+  }
+  // X-runs: each (dy, dz) row holds exactly the offsets dx = -L..L (in any order, repeats allowed)
+  el->runs = false;
+  int R = 0;
+  for (int d = 0; d < 3; d++) R = std::max(R, std::max(-lo[d], hi[d]));
+  if (n > 0 && el->flat && R <= MORPH_RUN_MAX_R) {
+    const int S = 2 * R + 1;
+    std::vector<uint32_t> rows((size_t)(S * S), 0u);   // bit dx + R of row (dy, dz)
+    for (i64 k = 0; k < n; k++) rows[(size_t)((t[4 * k + 2] + R) * S + t[4 * k + 1] + R)] |= 1u << (t[4 * k] + R);
+    bool ok = true;
+    for (int r = 0; r < S * S && ok; r++) {
+      el->run_len[r] = -1;
+      if (!rows[r]) continue;
+      int L = 0;
+      while (L < R && (rows[r] >> (R - L - 1) & 1u)) L++;
+      const uint32_t want = ((1u << (2 * L + 1)) - 1u) << (R - L);
+      ok = rows[r] == want;
+      el->run_len[r] = (signed char)L;
+    }
+    el->runs = ok;
+    el->R = R;
+  }
+  if (n == 0 || t == ctx->morph_tab) return VISFD_HIP_OK;
+  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read the element now in the slot
+  int* d = nullptr;
+  VH_TRY(ws(ctx, WS_MORPH_TAB, t.size(), &d));
+  VH_HIP(hipMemcpyAsync(d, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->morph_tab.swap(t);
+  return VISFD_HIP_OK;
+}
+
+// one op with the element in WS_MORPH_TAB.  Open = erode then dilate, close = dilate then erode (morphology.hpp:431-510),
+// both steps with the same mask and element; the top-hats fuse their subtraction into the second step.
+int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
+              MorphElem el) {
+  if (ctx->opt.morph_general) el.runs = false;
+  const i64 nv = nx * ny * nz;
+  const float* s0 = src;
+  if (mask) {
+    float* sn = nullptr;
+    VH_TRY(ws(ctx, WS_MORPH_SRC, (size_t)nv, &sn));
+    VH_TRY(dev_nan_masked(ctx, src, mask, sn, nv));
+    s0 = sn;
+  }
+  int path = 0;
+  if (op == VISFD_HIP_MORPH_DILATE || op == VISFD_HIP_MORPH_ERODE) {
+    VH_TRY(dev_morph_table(ctx, s0, dst, mask, nx, ny, nz, el, op == VISFD_HIP_MORPH_DILATE, 0, false, &path));
+    ctx->morph_last_path = path;
+    return VISFD_HIP_OK;
+  }
+  float* tmp = nullptr;
+  VH_TRY(ws(ctx, WS_MORPH_TMP, (size_t)nv, &tmp));
+  const bool dilate_first = (op == VISFD_HIP_MORPH_CLOSE || op == VISFD_HIP_MORPH_TOP_HAT_BLACK);
+  const int epi = op == VISFD_HIP_MORPH_TOP_HAT_WHITE ? 1 : op == VISFD_HIP_MORPH_TOP_HAT_BLACK ? 2 : 0;
+  VH_TRY(dev_morph_table(ctx, s0, tmp, mask, nx, ny, nz, el, dilate_first, 0, mask != nullptr, &path));
+  VH_TRY(dev_morph_table(ctx, tmp, dst, mask, nx, ny, nz, el, !dilate_first, epi, false, &path));
+  ctx->morph_last_path = path;
   return VISFD_HIP_OK;
 }
 

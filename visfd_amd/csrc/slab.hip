@@ -456,6 +456,22 @@ int visfd_hip_membrane_detect_slab_dev(visfd_hip_slab* s, float* src, float* sal
                                                sigma_tv, exponent, cutoff, 0.0f, 1, src_halo_ready, thr_out);
 }
 
+namespace {
+struct DevBlock {
+  float* p = nullptr;
+  ~DevBlock() { if (p) (void)hipFree(p); }
+};
+// the rank's stored planes on the device: zeros in the ghost planes (the exchange fills them), the owned planes from the host
+int upload_owned(visfd_hip_slab* s, const float* src_owned, i64 nx, i64 ny, float* src) {
+  visfd_hip_ctx* ctx = s->ctx;
+  const i64 plane = nx * ny;
+  VH_HIP(hipMemsetAsync(src, 0, sizeof(float) * (size_t)(plane * s->nz_local), ctx->stream));
+  VH_HIP(hipMemcpyAsync(src + s->own0 * plane, src_owned, sizeof(float) * (size_t)((s->own1 - s->own0) * plane), hipMemcpyHostToDevice,
+                        ctx->stream));
+  return VISFD_HIP_OK;
+}
+}  // namespace
+
 // The same stage for a host that keeps its volume in HOST memory (the filter_mrc program started once per GPU): the owned
 // planes go up, the slab stage runs, the owned planes of the score (and, if asked for, of the vote tensors, six interleaved
 // floats per voxel as visfd_hip_membrane_detect returns them) come back.  Device arrays live for the call only.
@@ -468,10 +484,7 @@ int visfd_hip_membrane_detect_slab_bg(visfd_hip_slab* s, const float* src_owned,
   VH_HIP(hipSetDevice(ctx->device));
   const i64 nzl = s->nz_local, plane = nx * ny, nvl = plane * nzl, nown = (s->own1 - s->own0) * plane;
   VH_TRY(check_dims(nx, ny, nzl));
-  struct Block {
-    float* p = nullptr;
-    ~Block() { if (p) (void)hipFree(p); }
-  } blk;
+  DevBlock blk;
   const bool with_bg = sigma_background > 0.0f;
   const size_t total = (size_t)nvl * (with_bg ? 13 : 12) + (tensor_owned ? (size_t)nown * 12 : 0);
   if (hipMalloc(&blk.p, total * sizeof(float)) != hipSuccess) {
@@ -483,8 +496,7 @@ int visfd_hip_membrane_detect_slab_bg(visfd_hip_slab* s, const float* src_owned,
   float* dirs = sal + nvl;
   float* ten = dirs + 3 * nvl;
   float* scratch = ten + 6 * nvl;
-  VH_HIP(hipMemsetAsync(src, 0, sizeof(float) * (size_t)nvl, ctx->stream));     // ghost planes: filled by the exchange
-  VH_HIP(hipMemcpyAsync(src + s->own0 * plane, src_owned, sizeof(float) * (size_t)nown, hipMemcpyHostToDevice, ctx->stream));
+  VH_TRY(upload_owned(s, src_owned, nx, ny, src));
   float* bgv = with_bg ? blk.p + (total - (size_t)nvl) : nullptr;   // (behind everything else)
   VH_TRY(visfd_hip_membrane_detect_slab_bg_dev(s, src, sal, dirs, ten, scratch, bgv, nx, ny, sigma, ratio, order, best_fraction, sigma_tv,
                                                exponent, cutoff, sigma_background, normalize_background, 0, thr_out));
@@ -512,22 +524,6 @@ int visfd_hip_membrane_detect_slab(visfd_hip_slab* s, const float* src_owned, in
 // merging the ranks' lists (and ratio thresholds, which need the global best score) is the host's job.
 // ---- host-memory faces of the Gaussian and of the blob detector for a host that starts one process per GPU
 // (`filter_mrc ... -slab RANK WORLD IDFILE` with -gauss / -blob): owned planes in, owned planes / owned blobs out ----------
-namespace {
-struct DevBlock {
-  float* p = nullptr;
-  ~DevBlock() { if (p) (void)hipFree(p); }
-};
-// the rank's stored planes on the device: zeros in the ghost planes (the exchange fills them), the owned planes from the host
-int upload_owned(visfd_hip_slab* s, const float* src_owned, i64 nx, i64 ny, float* src) {
-  visfd_hip_ctx* ctx = s->ctx;
-  const i64 plane = nx * ny;
-  VH_HIP(hipMemsetAsync(src, 0, sizeof(float) * (size_t)(plane * s->nz_local), ctx->stream));
-  VH_HIP(hipMemcpyAsync(src + s->own0 * plane, src_owned, sizeof(float) * (size_t)((s->own1 - s->own0) * plane), hipMemcpyHostToDevice,
-                        ctx->stream));
-  return VISFD_HIP_OK;
-}
-}  // namespace
-
 int visfd_hip_apply_gauss_slab(visfd_hip_slab* s, const float* src_owned, int64_t nx, int64_t ny, const float sigma[3],
                                const int hw[3], int normalize, float* dst_owned, float* A_out) {
   VH_REQUIRE(s && src_owned && dst_owned && sigma && hw, "null argument");

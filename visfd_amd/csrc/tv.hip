@@ -177,8 +177,7 @@ int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir, f
                        const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz,
                        i64 z_out0, i64 z_out1, float sigma_tv, int exponent, float cutoff, bool curves) {
   VH_TRY(check_dims(nx, ny, nz));
-  if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31))
-    return fail(VISFD_HIP_EINVAL, "dimension too large");
+  VH_TRY(check_dims32(nx, ny, nz));
   VH_REQUIRE(z_out0 >= 0 && z_out1 <= nz && z_out0 <= z_out1, "bad receiver plane range");
   if (z_out0 == z_out1) return VISFD_HIP_OK;
   const int h = host_tv_halfwidth(sigma_tv, cutoff);
@@ -224,7 +223,7 @@ int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir, f
 int dev_tv_weight_sum(visfd_hip_ctx* ctx, const float* sal, float* den, const float* mask_src, const float* mask_dst, i64 nx,
                       i64 ny, i64 nz, float sigma_tv, float cutoff) {
   VH_TRY(check_dims(nx, ny, nz));
-  if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
+  VH_TRY(check_dims32(nx, ny, nz));
   const int h = host_tv_halfwidth(sigma_tv, cutoff);
   VH_REQUIRE(h >= 0 && h <= 255, "tensor-voting window halfwidth out of range");
   const float4* dtab = nullptr;
