@@ -49,6 +49,18 @@ def volume(gpu):
     return src
 
 
+def _assert_exact_cut(torch, pre, post, thr, fraction, what):
+    """The top-fraction cut of the whole volume is exact, with no sort and no oracle: thr is entry
+    k = floor(float32(n) * float32(fraction)) of the descending order of `pre` (count(v > thr) <= k < count(v >= thr)),
+    and `post` is `pre` with every voxel below thr zeroed, bit for bit."""
+    k = int(np.floor(np.float32(pre.numel()) * np.float32(fraction)))
+    above, at_least = int((pre > thr).sum().item()), int((pre >= thr).sum().item())
+    assert above <= k < at_least, "%s: thr %r is not entry %d of the descending order (%d above it, %d not below it)" % (
+        what, thr, k, above, at_least)
+    want = torch.where(pre < thr, torch.zeros((), dtype=pre.dtype, device=pre.device), pre)
+    assert torch.equal(post.view(torch.int32), want.view(torch.int32)), "%s: thresholded field" % what
+
+
 def _crop(t, lo, hi):
     return t[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]].contiguous().cpu().numpy()
 
@@ -74,7 +86,12 @@ def _check_membrane(gpu, oracle, src, crops, E, dense=0.12, ridge_crops=4, tv_fm
     dirs = torch.zeros((3,) + shape, device=dev)
     ten = torch.empty((6,) + shape, device=dev)
     ctx.ridge_scores_dev(src, sal, smoothed, sigma, ratio, order)
+    ctx.synchronize()
+    pre = sal.clone()
     thr = ctx.threshold_fraction_dev(sal, P["best_fraction"])
+    ctx.synchronize()
+    _assert_exact_cut(torch, pre, sal, thr, P["best_fraction"], "membrane cut")
+    del pre      # (a volume's worth: freed before the voting stage)
     ctx.ridge_directions_dev(smoothed, sal, dirs, sigma, order)
     ctx.synchronize()
     del smoothed
@@ -272,6 +289,7 @@ def test_exact_mode_eigen_census(gpu, volume, oracle):
         raw = s.clone()
         thr[mode] = ctx.threshold_fraction_dev(s, P["best_fraction"])
         ctx.synchronize()
+        _assert_exact_cut(torch, raw, s, thr[mode], P["best_fraction"], "cut with eig_f32=%d" % mode)
         sal[mode] = (raw, s != 0)
         del s
     nvox = volume.numel()
