@@ -95,7 +95,7 @@ struct visfd_hip_options {
 
 struct visfd_hip_ctx {
   visfd_hip_options opt;
-  float* tv_table_dev = nullptr;   // cached vote table (tv_tiled.hip) and what it was built for
+  float* tv_table_dev = nullptr;   // cached vote tables (tv_common.hpp: TvTableLayout) and what they were built for
   float tv_table_key[2] = {0.0f, 0.0f};
   int tv_table_h = -1;
   int device = 0;
@@ -144,24 +144,6 @@ struct Taps {
   float t[2 * MAX_HALFWIDTH + 1];  // t[j + h], j = -h..h
   int h;
 };
-
-// row stride (in float4 entries) of the tiled kernel's vote table: 2h+1 rounded up to 4 modulo 8 (tv_tiled.hip: LDS banks)
-inline int tv_padded_row(int h) {
-  int sp = 2 * h + 1;
-  while ((sp & 7) != 4) sp++;
-  return sp;
-}
-
-// tolerance-mode vote table of tv_box.hip: a slice has 3 zero rows above and below its 2h+1 rows and rows of
-// tv_box_row(h) entries -- at least 3 zero entries behind the 2h+1 of a row, 4 modulo 8 (LDS banks) -- behind 4 guard
-// entries: entry (jy, jx) of slice jz at 4 + (jy + h + 3) * row + (jx + h); everything else is zero, so that the receivers
-// of a 4 x 4 sub-patch a sender does not reach read a zero weight
-inline int tv_box_row(int h) {
-  int sp = 2 * h + 1 + 3;
-  while ((sp & 7) != 4) sp++;
-  return sp;
-}
-inline int tv_box_slice(int h) { return (2 * h + 1 + 6) * tv_box_row(h) + 8; }
 
 // host-side arithmetic (taps.cpp)
 void host_gauss_taps(float sigma, int h, float* t);

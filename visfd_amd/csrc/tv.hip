@@ -12,7 +12,7 @@
 // Device layout: direction is 3 planes, tensor is 6 planes (xx,yy,zz,xy,yz,xz), each nvox floats.
 #include <vector>
 
-#include "common.hpp"
+#include "tv_common.hpp"
 
 namespace vh {
 
@@ -121,57 +121,116 @@ tv_dense_kernel(const float* __restrict__ sal, const float* __restrict__ dir,
 
 }  // namespace
 
-// declared in tv_tiled.hip
-int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten,
-                 const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0,
-                 i64 z_out1, int h, const float4* dtab, int exponent, bool curves, bool weights_only, bool* handled);
-
-// declared in tv_box.hip
-int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
-               const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box,
-               int exponent, bool* handled, bool exact);
-
-
-// The vote table of (sigma_tv, cutoff) on the device: float4 {w, rhat_x, rhat_y, rhat_z} per offset j in z, y, x order
-// (filter3d.hpp:563-578, feature.hpp:2470-2478).  Built on the host once and kept in the context: a launch with the same
-// parameters queues no copy and never waits for the stream.
-static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int h, const float4** out) {
-  const size_t n = 2 * (size_t)h + 1, m = n * n * n;
-  if (ctx->tv_table_dev && ctx->tv_table_h == h && ctx->tv_table_key[0] == sigma_tv && ctx->tv_table_key[1] == cutoff) {
-    *out = reinterpret_cast<const float4*>(ctx->tv_table_dev);
-    return VISFD_HIP_OK;
+// The vote tables of (sigma_tv, cutoff) on the device: float4 {w, rhat_x, rhat_y, rhat_z} per offset j in z, y, x order
+// (filter3d.hpp:563-578, feature.hpp:2470-2478), in the four layouts of tv_common.hpp (TvTableLayout).  Built on the host
+// once and kept in the context: a launch with the same parameters queues no copy and never waits for the stream.
+static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int h, TvTables* out) {
+  const TvTableLayout l = tv_table_layout(h);
+  if (!(ctx->tv_table_dev && ctx->tv_table_h == h && ctx->tv_table_key[0] == sigma_tv && ctx->tv_table_key[1] == cutoff)) {
+    // kernels of an earlier call may still read the old table, and the copy below reads host memory of this call
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t n = 2 * (size_t)h + 1, m = n * n * n;
+    std::vector<float> w(m), rh(3 * m);
+    host_tv_tables(sigma_tv, h, w.data(), rh.data());
+    const size_t sp = (size_t)tv_padded_row(h), spb = (size_t)tv_box_row(h), nslb = (size_t)tv_box_slice(h);
+    std::vector<float4> tab(l.total, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    const float rt2 = 1.41421356237309504880f;
+    for (size_t k = 0; k < m; k++) {
+      tab[l.packed + k] = make_float4(w[k], rh[3 * k], rh[3 * k + 1], rh[3 * k + 2]);
+      tab[l.padded + (k / n) * sp + (k % n)] = tab[l.packed + k];
+      const size_t kb = (k / (n * n)) * nslb + 4 + ((k / n) % n + 3) * spb + (k % n);
+      tab[l.box_tol + kb] = make_float4(w[k], rt2 * rh[3 * k], rt2 * rh[3 * k + 1], rt2 * rh[3 * k + 2]);
+      tab[l.box_exact + kb] = tab[l.packed + k];
+    }
+    float4* dtab = nullptr;
+    ctx->tv_table_dev = nullptr;
+    VH_TRY(ws(ctx, WS_TVTAB, l.total, &dtab));
+    VH_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(float4) * l.total, hipMemcpyHostToDevice, ctx->stream));
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->tv_table_dev = reinterpret_cast<float*>(dtab);
+    ctx->tv_table_h = h;
+    ctx->tv_table_key[0] = sigma_tv;
+    ctx->tv_table_key[1] = cutoff;
   }
-  // kernels of an earlier call may still read the old table, and the copy below reads host memory of this call
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  std::vector<float> w(m), rh(3 * m);
-  host_tv_tables(sigma_tv, h, w.data(), rh.data());
-  // three tables: [0, m) the reference's {w, rhat}, packed (baseline kernel); then the same with rows padded to
-  // tv_padded_row(h) entries (tiled kernel: LDS banks; pad entries are never read); then the tolerance mode's
-  // {w, sqrt(2) rhat} in the slice layout of tv_box.hip (zero rows and zero row tails, which ARE read: common.hpp)
-  const size_t sp = (size_t)tv_padded_row(h), m2 = n * n * sp;
-  // ... and the reference's {w, rhat} once more in that slice layout (the exact form of tv_box.hip)
-  const size_t spb = (size_t)tv_box_row(h), nslb = (size_t)tv_box_slice(h), m3 = (n + 1) * nslb;   // (+ one slice of zeros)
-  std::vector<float4> tab(m + m2 + 2 * m3, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  const float rt2 = 1.41421356237309504880f;
-  for (size_t k = 0; k < m; k++) {
-    tab[k] = make_float4(w[k], rh[3 * k], rh[3 * k + 1], rh[3 * k + 2]);
-    tab[m + (k / n) * sp + (k % n)] = tab[k];
-    const size_t kb = (k / (n * n)) * nslb + 4 + ((k / n) % n + 3) * spb + (k % n);
-    tab[m + m2 + kb] = make_float4(w[k], rt2 * rh[3 * k], rt2 * rh[3 * k + 1], rt2 * rh[3 * k + 2]);
-    tab[m + m2 + m3 + kb] = tab[k];
-  }
-  float4* dtab = nullptr;
-  ctx->tv_table_dev = nullptr;
-  VH_TRY(ws(ctx, WS_TVTAB, m + m2 + 2 * m3, &dtab));
-  VH_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(float4) * (m + m2 + 2 * m3), hipMemcpyHostToDevice, ctx->stream));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->tv_table_dev = reinterpret_cast<float*>(dtab);
-  ctx->tv_table_h = h;
-  ctx->tv_table_key[0] = sigma_tv;
-  ctx->tv_table_key[1] = cutoff;
-  *out = dtab;
+  const float4* const dtab = reinterpret_cast<const float4*>(ctx->tv_table_dev);
+  *out = {dtab + l.packed, dtab + l.padded, dtab + l.box_tol, dtab + l.box_exact, h};
   return VISFD_HIP_OK;
 }
+
+namespace {
+
+struct TvRequest {
+  const float *sal, *dir;
+  float* out;              // six tensor planes, or ONE plane of weight sums (weights_only)
+  const float *mask_src, *mask_dst;
+  i64 nx, ny, nz;
+  i64 z_out0, z_out1;      // receiver planes [z_out0, z_out1)
+  int exponent;
+  bool curves, weights_only;
+};
+
+enum class TvRoute { BoxTol, BoxExact, Tiled, Baseline };
+
+// The routes a request may take under the context's options, in the order they are tried; returns their number.
+int tv_routes(const visfd_hip_options& opt, const TvRequest& rq, TvRoute routes[4]) {
+  int n = 0;
+  const bool box = !opt.tv_dense && !rq.curves && !rq.weights_only;
+  // tolerance mode (option tv_fma): fused multiply-adds, sub-patches with two sender streams, box-tested hit lists
+  // (tv_box.hip); windows and vote forms it does not take fall through to the exact kernels
+  if (box && opt.tv_fma) routes[n++] = TvRoute::BoxTol;
+  // exact arithmetic in the same kernel structure (surfaces, exponent 2 or 4, source mask absent or binary, finite
+  // saliencies; option tv_exact_tiled = 1 keeps the round-2 kernel)
+  if (box && !opt.tv_exact_tiled) routes[n++] = TvRoute::BoxExact;
+  if (!opt.tv_dense) routes[n++] = TvRoute::Tiled;
+  // windows the tiled kernel declines (h = 0, h > 40, slices beyond LDS) and the tv_dense option: the baseline kernel, same
+  // order of accumulation; it takes everything
+  routes[n++] = TvRoute::Baseline;
+  return n;
+}
+
+int tv_baseline(visfd_hip_ctx* ctx, const TvRequest& rq, const TvTables& tab) {
+  TvParams p;
+  p.nx = (int)rq.nx; p.ny = (int)rq.ny; p.nz = (int)rq.nz;
+  p.z_out0 = (int)rq.z_out0; p.z_out1 = (int)rq.z_out1;
+  p.h = tab.h; p.exponent = rq.exponent; p.curves = rq.curves ? 1 : 0; p.weights_only = rq.weights_only ? 1 : 0;
+  const i64 nb = ((rq.nx + BLOCK - 1) / BLOCK) * rq.ny * (rq.z_out1 - rq.z_out0);
+  if (nb > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
+  tv_dense_kernel<<<dim3((unsigned)nb), dim3(BLOCK), 0, ctx->stream>>>(rq.sal, rq.dir, rq.out, rq.mask_src, rq.mask_dst,
+                                                                       tab.packed, p);
+  VH_HIP(hipGetLastError());
+  return VISFD_HIP_OK;
+}
+
+int tv_dispatch(visfd_hip_ctx* ctx, const TvRequest& rq, float sigma_tv, float cutoff) {
+  const int h = host_tv_halfwidth(sigma_tv, cutoff);
+  VH_REQUIRE(h >= 0 && h <= 255, "tensor-voting window halfwidth out of range");
+  TvTables tab;
+  VH_TRY(tv_table_device(ctx, sigma_tv, cutoff, h, &tab));
+  TvRoute routes[4];
+  const int nroutes = tv_routes(ctx->opt, rq, routes);
+  int rc = TV_DECLINED;
+  for (int i = 0; i < nroutes && rc == TV_DECLINED; i++) {
+    switch (routes[i]) {
+      case TvRoute::BoxTol:
+      case TvRoute::BoxExact: {
+        const bool exact = routes[i] == TvRoute::BoxExact;
+        rc = dev_tv_box(ctx, rq.sal, rq.dir, rq.out, rq.mask_src, rq.mask_dst, rq.nx, rq.ny, rq.nz, rq.z_out0, rq.z_out1, h,
+                        exact ? tab.box_exact : tab.box_tol, rq.exponent, exact);
+        break;
+      }
+      case TvRoute::Tiled:
+        rc = dev_tv_tiled(ctx, rq.sal, rq.dir, rq.out, rq.mask_src, rq.mask_dst, rq.nx, rq.ny, rq.nz, rq.z_out0, rq.z_out1, h,
+                          tab.padded, rq.exponent, rq.curves, rq.weights_only);
+        break;
+      case TvRoute::Baseline:
+        rc = tv_baseline(ctx, rq, tab);
+        break;
+    }
+  }
+  return rc;   // (never TV_DECLINED: the baseline, always the last route, does not decline)
+}
+
+}  // namespace
 
 int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten,
                        const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz,
@@ -180,41 +239,8 @@ int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir, f
   VH_TRY(check_dims32(nx, ny, nz));
   VH_REQUIRE(z_out0 >= 0 && z_out1 <= nz && z_out0 <= z_out1, "bad receiver plane range");
   if (z_out0 == z_out1) return VISFD_HIP_OK;
-  const int h = host_tv_halfwidth(sigma_tv, cutoff);
-  VH_REQUIRE(h >= 0 && h <= 255, "tensor-voting window halfwidth out of range");
-  const float4* dtab = nullptr;
-  VH_TRY(tv_table_device(ctx, sigma_tv, cutoff, h, &dtab));
-
-  const size_t m_packed = (size_t)(2 * h + 1) * (2 * h + 1) * (2 * h + 1);
-  const size_t m_padded = (size_t)(2 * h + 1) * (2 * h + 1) * (size_t)tv_padded_row(h);
-  bool handled = false;
-  // tolerance mode (option tv_fma): fused multiply-adds, sub-patches with two sender streams, box-tested hit lists
-  // (tv_box.hip); windows and vote forms it does not take fall through to the exact kernels
-  if (!ctx->opt.tv_dense && ctx->opt.tv_fma && !curves)
-    VH_TRY(dev_tv_box(ctx, sal, dir, ten, mask_src, mask_dst, nx, ny, nz, z_out0, z_out1, h, dtab + m_packed + m_padded, exponent,
-                      &handled, false));
-  if (handled) return VISFD_HIP_OK;
-  // exact arithmetic in the same kernel structure (surfaces, exponent 2 or 4, source mask absent or binary, finite saliencies; option
-  // tv_exact_tiled = 1 keeps the round-2 kernel)
-  if (!ctx->opt.tv_dense && !ctx->opt.tv_exact_tiled && !curves)
-    VH_TRY(dev_tv_box(ctx, sal, dir, ten, mask_src, mask_dst, nx, ny, nz, z_out0, z_out1, h,
-                      dtab + m_packed + m_padded + (size_t)(2 * h + 2) * (size_t)tv_box_slice(h), exponent, &handled, true));
-  if (handled) return VISFD_HIP_OK;
-  if (!ctx->opt.tv_dense)
-    VH_TRY(dev_tv_tiled(ctx, sal, dir, ten, mask_src, mask_dst, nx, ny, nz, z_out0, z_out1, h, dtab + m_packed, exponent, curves,
-                        false, &handled));
-  if (handled) return VISFD_HIP_OK;
-
-  hipStream_t st = ctx->stream;
-  TvParams p;
-  p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
-  p.z_out0 = (int)z_out0; p.z_out1 = (int)z_out1;
-  p.h = h; p.exponent = exponent; p.curves = curves ? 1 : 0; p.weights_only = 0;
-  const i64 nb = ((nx + BLOCK - 1) / BLOCK) * ny * (z_out1 - z_out0);
-  if (nb > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
-  tv_dense_kernel<<<dim3((unsigned)nb), dim3(BLOCK), 0, st>>>(sal, dir, ten, mask_src, mask_dst, dtab, p);
-  VH_HIP(hipGetLastError());
-  return VISFD_HIP_OK;
+  return tv_dispatch(ctx, {sal, dir, ten, mask_src, mask_dst, nx, ny, nz, z_out0, z_out1, exponent, curves, false}, sigma_tv,
+                     cutoff);
 }
 
 // The sum of the weights of the votes every receiver takes (one plane-sized volume): the "denominator" TVDenseStick
@@ -224,26 +250,7 @@ int dev_tv_weight_sum(visfd_hip_ctx* ctx, const float* sal, float* den, const fl
                       i64 ny, i64 nz, float sigma_tv, float cutoff) {
   VH_TRY(check_dims(nx, ny, nz));
   VH_TRY(check_dims32(nx, ny, nz));
-  const int h = host_tv_halfwidth(sigma_tv, cutoff);
-  VH_REQUIRE(h >= 0 && h <= 255, "tensor-voting window halfwidth out of range");
-  const float4* dtab = nullptr;
-  VH_TRY(tv_table_device(ctx, sigma_tv, cutoff, h, &dtab));
-  bool handled = false;
-  if (!ctx->opt.tv_dense)
-    VH_TRY(dev_tv_tiled(ctx, sal, nullptr, den, mask_src, mask_dst, nx, ny, nz, 0, nz, h,
-                        dtab + (size_t)(2 * h + 1) * (2 * h + 1) * (2 * h + 1), 4, false, true, &handled));
-  if (handled) return VISFD_HIP_OK;
-  // windows the tiled kernel declines (h = 0, h > 40, slices beyond LDS) and the tv_dense option: the baseline kernel in
-  // its weights-only form, same order of accumulation
-  TvParams p;
-  p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
-  p.z_out0 = 0; p.z_out1 = (int)nz;
-  p.h = h; p.exponent = 4; p.curves = 0; p.weights_only = 1;
-  const i64 nb = ((nx + BLOCK - 1) / BLOCK) * ny * nz;
-  if (nb > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
-  tv_dense_kernel<<<dim3((unsigned)nb), dim3(BLOCK), 0, ctx->stream>>>(sal, nullptr, den, mask_src, mask_dst, dtab, p);
-  VH_HIP(hipGetLastError());
-  return VISFD_HIP_OK;
+  return tv_dispatch(ctx, {sal, nullptr, den, mask_src, mask_dst, nx, ny, nz, 0, nz, 4, false, true}, sigma_tv, cutoff);
 }
 
 }  // namespace vh

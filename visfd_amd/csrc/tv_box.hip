@@ -12,9 +12,9 @@
 // used 49 % of its lanes (ball of radius h against an 8 x 4 x 2 patch) at ~27 issue slots per vote step.
 //
 // This kernel keeps the skeleton (persistent workgroups claiming units from a global counter, packed lists, mirror-paired
-// planes), takes a 16 x 32 tile of ONE receiver pair per pass (two lists per step instead of the four of two pairs over an
+// planes), takes a 16 x 32 tile (tv_common.hpp: box_tile) of ONE receiver pair per pass (two lists per step instead of the four of two pairs over an
 // 8-wide tile: 224 instead of 358 list entries per step, so a step is one barrier interval; 313 -> 302 ms), lists the
-// senders ONCE for the whole launch (tvl_* kernels below: the round-3
+// senders ONCE for the whole launch (tv_list.hip: the round-3
 // kernels listed every sender plane again in every workgroup that reached it -- 7 region voxels read per receiver column,
 // 12-15 % of a wave's time) and replaces the sweep:
 //
@@ -42,15 +42,14 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.hpp"
+#include "tv_common.hpp"
 
 namespace vh {
 
+using namespace box_tile;   // NT, NW, TX, TY: shared with the sender lists (tv_list.hip)
+
 namespace {
 
-constexpr int NT = 512;
-constexpr int NW = NT / 64;
-constexpr int TX = 16, TY = 4 * NW;    // a workgroup's tile of receivers: 16 x 32 on ONE pair of planes (z, z+1) per pass
 constexpr int NH = TX / 8;             // 8-column halves of the tile: a wave owns four rows of each (two sub-patches per half)
 constexpr int NLIST = 2;               // lists per interval: the sender plane above (A) and the one below (B) the pair
 constexpr int NSUB = 2;                // sub-patches per wave and pair: x 0..3 and x 4..7
@@ -61,14 +60,6 @@ constexpr int YPAD = 3;                // zero rows above and below a table slic
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-template <typename T>
-__device__ __forceinline__ const __attribute__((address_space(3))) T* lds_ptr(unsigned a) {
-  return (const __attribute__((address_space(3))) T*)(uintptr_t)a;
-}
 
 #ifdef VH_TV_STAMPS   // development build (tools/build_variant.py; cross-compiled by tests/test_abi.py): where a wave's time goes
 __device__ unsigned long long g_box_stamps[8];
@@ -87,7 +78,7 @@ struct BoxParams {
   int rw, rh;            // region width = TX + 2h, height = TY + 2h
   int tiles_x, tiles_y;
   int zrun;              // receiver planes per unit of work
-  int zl0, nzl;          // sender planes [zl0, zl0 + nzl) are listed (tvl_* kernels below)
+  int zl0, nzl;          // sender planes [zl0, zl0 + nzl) are listed (tv_list.hip)
   int sp;                // row stride of a table slice in float4 entries (tv_box_row)
   int nsl;               // float4 entries of a table slice (tv_box_slice)
 };
@@ -145,7 +136,8 @@ __device__ __forceinline__ uint2 lds_u2(unsigned a) {
 // of the votes.
 __device__ __forceinline__ u4v lds_u4(unsigned a) { return *(const volatile __attribute__((address_space(3))) u4v*)(uintptr_t)a; }
 
-template <int MODE, bool ZNEG, bool FOLD, int OFF>
+// VOTE: the vote as a type with a static add(T, sender, table entry); OFF: byte offset of the list's entries behind hp.
+template <typename VOTE, int OFF>
 __device__ __forceinline__ void vote_hits(float (&T)[6], unsigned hp, int nst, unsigned r16) {
   u4v h0 = lds_u4(hp + (unsigned)OFF), h1 = lds_u4(hp + (unsigned)(OFF + 16));
   f4v sa = lds_f4(h0.x), ta = lds_f4(r16 - h0.y);
@@ -154,25 +146,87 @@ __device__ __forceinline__ void vote_hits(float (&T)[6], unsigned hp, int nst, u
   for (;;) {   // uniform
     sb = lds_f4(h0.z);
     tb = lds_f4(r16 - h0.w);
-    vote_fma<MODE, ZNEG, FOLD>(T, sa, ta);
+    VOTE::add(T, sa, ta);
     if (++k >= nst) break;
     sa = lds_f4(h1.x);
     ta = lds_f4(r16 - h1.y);
     h0 = lds_u4(hp + (unsigned)(OFF + 32));
-    vote_fma<MODE, ZNEG, FOLD>(T, sb, tb);
+    VOTE::add(T, sb, tb);
     if (++k >= nst) break;
     sb = lds_f4(h1.z);
     tb = lds_f4(r16 - h1.w);
-    vote_fma<MODE, ZNEG, FOLD>(T, sa, ta);
+    VOTE::add(T, sa, ta);
     if (++k >= nst) break;
     sa = lds_f4(h0.x);
     ta = lds_f4(r16 - h0.y);
     h1 = lds_u4(hp + (unsigned)(OFF + 48));
     hp += 32u;
-    vote_fma<MODE, ZNEG, FOLD>(T, sb, tb);
+    VOTE::add(T, sb, tb);
     if (++k >= nst) break;
   }
 }
+template <int MODE, bool ZNEG, bool FOLD>
+struct VoteFma {
+  static __device__ __forceinline__ void add(float (&T)[6], const f4v& snd, const f4v& tw) { vote_fma<MODE, ZNEG, FOLD>(T, snd, tw); }
+};
+
+// ---- what the two kernels share, said once ----------------------------------------------------------------------------------
+// (Tried as helpers too, and undone because the kernels' machine code changed: the prologue (null sender, rho_tab, hit-list fill),
+// the unit claim and decode, the plane_beg / plane_cnt / l_rng setup -- all three take LDS arrays through pointers -- and one
+// struct for the VH_TV_STAMPS / VH_TV_COUNT instrumentation.  Those stay written out in both kernels.)
+
+// The per-lane constants of a phase are RECOMPUTED from the lane number where the phase starts (the empty asm hides the
+// number's origin from the compiler): hoisted out of the step loop they stay live across the vote loops and are spilled.
+__device__ __forceinline__ unsigned fresh_lane() {
+  unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  asm volatile("" : "+v"(ln));
+  return ln;
+}
+
+// PACKED LISTS: the lists of a step (lengths pre[k+1] - pre[k], first global entries pl[k]) are dealt to the threads as ONE
+// sequence, NT positions per interval; list k's share of the interval that starts at `done`: sequence positions = LDS slots
+// [c[k], c[k] + len[k]).  idxc: the global entry of this thread's position -- clamped, for an unconditional load: a load
+// inside a branch is closed by a full s_waitcnt at the join, and the entries' round trip then ended before the slice loads
+// were even issued.
+__device__ __forceinline__ void list_share(const int (&pre)[NLIST + 1], const unsigned (&pl)[NLIST], int done, int tid, int (&c)[NLIST],
+                                           int (&len)[NLIST], bool& have, unsigned& idxc) {
+#pragma unroll
+  for (int k = 0; k < NLIST; k++) {
+    const int lo = min(max(pre[k], done), done + NT), hi = min(pre[k + 1], done + NT);
+    c[k] = lo - done;
+    len[k] = max(hi - lo, 0);
+  }
+  const int g = done + tid;
+  int k_me = 0;
+#pragma unroll
+  for (int k = 1; k < NLIST; k++) k_me += (g >= pre[k]) ? 1 : 0;
+  have = g < pre[NLIST];
+  unsigned idx = pl[0] + (unsigned)g;
+#pragma unroll
+  for (int k = 1; k < NLIST; k++)
+    if (k_me == k) idx = pl[k] + (unsigned)(g - pre[k]);
+  idxc = have ? idx : 0u;
+}
+
+// list entries carry {column within the tile column's window, image row}: the region row here.
+// l_pos: {region position bytes (ex, ey), byte offset of the sender in a table slice: 16 (ey SP + ex)}
+__device__ __forceinline__ void put_entry(float4* l_ent, uint2* l_pos, int tid, const float4& a, unsigned m, int y0, int h, int SP) {
+  l_ent[tid] = a;
+  const unsigned ex = m & 0xffu, ey = (m >> 8) - (unsigned)(y0 - h);
+  l_pos[tid] = make_uint2(ex | (ey << 8), 16u * (ey * (unsigned)SP + ex));
+}
+
+// (a wave's stretch rg = i0 | i1 << 16 of a list, cut to an interval's share: `off` = list position of the share's first LDS slot)
+__device__ __forceinline__ void cut_stretch(unsigned rg, int off, int len, int& i0, int& i1) {
+  i0 = min(max((int)(rg & 0xffffu) - off, 0), len);
+  i1 = min(max((int)(rg >> 16) - off, 0), len);
+}
+
+// THE BOX TEST.  With the sender at region position (ex, ey) and a sub-patch's receivers at x in [bx, bx + 3], y in [by, by + 3],
+// the nearest receiver is max(|ex - (bx + 1.5)| - 1.5, 0) columns and as many rows (with by) away; it is reached if
+// dx^2 + dy^2 <= rr = h^2 - (planes to the nearer receiver plane)^2.  All small integers and halves: exact in float.
+__device__ __forceinline__ float box_gap(float e, float centre) { return fmaxf(__builtin_fabsf(e - centre) - 1.5f, 0.0f); }
+__device__ __forceinline__ bool box_reached(float dx, float dy2, float rr) { return __builtin_fmaf(dx, dx, dy2) <= rr; }
 
 template <int MODE, bool FOLD>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6)))
@@ -253,21 +307,12 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
 
     // (A wave owns the rows 4 w .. 4 w + 3 of both halves.  Round 3's mirrored row blocks -- the second half's rows dealt to the
     // waves in reverse order, against the skew of the waves' vote counts -- measured no difference in this kernel.)
-    // The per-lane constants of a phase are RECOMPUTED from the lane number where the phase starts (the empty asm hides the
-    // number's origin from the compiler): hoisted out of the step loop they stay live across the vote loops and are spilled.
-    auto fresh_lane = [&]() -> unsigned {
-      unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      asm volatile("" : "+v"(ln));
-      return ln;
-    };
 
     float TT[NH][NSUB][6];
 
     // ---- TEST + VOTE: entries [i0, i1) of one list's share of the interval (first LDS slot `base`), 64 at a time.  Lane l
-    // tests entry i0 + 64 c + l against the boxes of both sub-patches: with the sender at region position (ex, ey) and a
-    // sub-patch's receivers at x in [bx, bx + 3], y in [by, by + 3], the nearest receiver is max(|ex - (bx + 1.5)| - 1.5, 0)
-    // columns and as many rows (with by) away; it is reached if dx^2 + dy^2 <= rr = h^2 - (d-1)^2 (the nearer of the two
-    // receiver planes is d - 1 planes from the sender plane).  All small integers: exact in float.
+    // tests entry i0 + 64 c + l against the boxes of both sub-patches (box_gap, box_reached), rr = h^2 - (d-1)^2: the nearer of
+    // the two receiver planes is d - 1 planes from the sender plane.
     auto test_vote = [&](auto ZN, int base, int i0, int i1, unsigned r16, float cy, float rr, unsigned null_e16) {
       constexpr bool ZNEG = decltype(ZN)::value;
       // this wave's hit entries: sub-patch s, stream t at hb + (2 s + t) * HCAP * 8 (the constants are offset fields)
@@ -278,7 +323,7 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
         uint2 pw = make_uint2(0xffffffffu, 0u);           // lanes without an entry: far from every box
         if (e < i1) pw = l_pos[base + e];
         const float exf = (float)(pw.x & 0xffu), eyf = (float)((pw.x >> 8) & 0xffu);
-        const float dy = fmaxf(__builtin_fabsf(eyf - cy) - 1.5f, 0.0f);
+        const float dy = box_gap(eyf, cy);
         const float dy2 = dy * dy;
         const unsigned ent = ent_base + 16u * (unsigned)(base + e);
         // the two 8-column halves of the tile, one after the other (the hit buffers hold one half's two sub-patches)
@@ -288,8 +333,7 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
           int nh[NSUB];
 #pragma unroll
           for (int s = 0; s < NSUB; s++) {
-            const float dx = fmaxf(__builtin_fabsf(exf - (cx0 + 4.0f * (float)s)) - 1.5f, 0.0f);
-            const bool hit = __builtin_fmaf(dx, dx, dy2) <= rr;
+            const bool hit = box_reached(box_gap(exf, cx0 + 4.0f * (float)s), dy2, rr);
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
             nh[s] = __builtin_popcountll(bal);
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
@@ -310,8 +354,8 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
           asm volatile("" ::: "memory");
           const unsigned hp = hb + (fresh_lane() >> 5) * (unsigned)(HCAP * 8);
           __builtin_amdgcn_s_setprio(1);   // a voting wave is on its workgroup's critical path; waves that fill are not (337 -> 333 ms)
-          if (nh[0] > 0) vote_hits<MODE, ZNEG, FOLD, 0>(TT[hh][0], hp, (nh[0] + 1) >> 1, r16);              // (uniform)
-          if (nh[1] > 0) vote_hits<MODE, ZNEG, FOLD, 2 * HCAP * 8>(TT[hh][1], hp, (nh[1] + 1) >> 1, r16);
+          if (nh[0] > 0) vote_hits<VoteFma<MODE, ZNEG, FOLD>, 0>(TT[hh][0], hp, (nh[0] + 1) >> 1, r16);              // (uniform)
+          if (nh[1] > 0) vote_hits<VoteFma<MODE, ZNEG, FOLD>, 2 * HCAP * 8>(TT[hh][1], hp, (nh[1] + 1) >> 1, r16);
           __builtin_amdgcn_s_setprio(0);
           asm volatile("" ::: "memory");
           __builtin_amdgcn_wave_barrier();
@@ -403,27 +447,10 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
 #pragma unroll
         for (int k = 0; k < NLIST; k++) pl[k] = lcnt[k] > 0 ? __builtin_amdgcn_readfirstlane(plane_beg[plane_slot(lsz[k])]) : 0u;
         for (int done = 0; done < total; done += NT) {   // uniform
-          // PACKED LISTS: the lists of a step are dealt to the threads as ONE sequence; list k's share of this interval:
-          // sequence positions = LDS slots [c[k], c[k] + len[k])
           int c[NLIST], len[NLIST];
-#pragma unroll
-          for (int k = 0; k < NLIST; k++) {
-            const int lo = min(max(pre[k], done), done + NT), hi = min(pre[k + 1], done + NT);
-            c[k] = lo - done;
-            len[k] = max(hi - lo, 0);
-          }
-          const int g = done + tid;
-          int k_me = 0;
-#pragma unroll
-          for (int k = 1; k < NLIST; k++) k_me += (g >= pre[k]) ? 1 : 0;
-          const bool have = g < total;
-          unsigned idx = pl[0] + (unsigned)g;
-#pragma unroll
-          for (int k = 1; k < NLIST; k++)
-            if (k_me == k) idx = pl[k] + (unsigned)(g - pre[k]);
-          // (unconditional loads from clamped indices: a load inside a branch is closed by a full s_waitcnt at the join, and
-          //  the entries' round trip then ended before the slice loads below were even issued)
-          const unsigned idxc = have ? idx : 0u;
+          bool have;
+          unsigned idxc;
+          list_share(pre, pl, done, tid, c, len, have, idxc);
           const float4 a = lst_ent[idxc];
           const unsigned m = lst_pos[idxc];
           // the new slice(s) of this step: every load is requested BEFORE the first LDS store waits for one (entries and slice
@@ -452,26 +479,17 @@ tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
               for (int i = ft + 2 * NT; i < nsl; i += NT) dst4[i] = srcB[i];
             }
           }
-          if (have) {   // list entries carry {column within the tile column's window, image row}: the region row here
-            l_ent[tid] = a;
-            const unsigned ex = m & 0xffu, ey = (m >> 8) - (unsigned)(y0 - h);
-            l_pos[tid] = make_uint2(ex | (ey << 8), 16u * (ey * (unsigned)SP + ex));
-          }
+          if (have) put_entry(l_ent, l_pos, tid, a, m, y0, h, SP);
           VH_STAMP(1);
           __syncthreads();   // lists (and slices) complete
           VH_STAMP(2);
-          // entries are in descending row order: of list k, this wave needs those from the first one at or below region row
-          // 4 wv + h + 3 + rho to the last one at or above row 4 wv + h - rho.  Every wave counts both kinds itself, from the
-          // row bytes of the position words in LDS, 64 entries at a time.
           int i0[NLIST], i1[NLIST];
 #pragma unroll
           for (int k = 0; k < NLIST; k++) {   // the wave's stretch of list k (l_rng, list positions) cut to this interval's share
             i0[k] = i1[k] = 0;
             if (len[k] > 0) {   // uniform
               const unsigned rg = __builtin_amdgcn_readfirstlane(l_rng[plane_slot(lsz[k]) * NW + wave]);
-              const int off = c[k] + done - pre[k];     // list position of the share's first LDS slot
-              i0[k] = min(max((int)(rg & 0xffffu) - off, 0), len[k]);
-              i1[k] = min(max((int)(rg >> 16) - off, 0), len[k]);
+              cut_stretch(rg, c[k] + done - pre[k], len[k], i0[k], i1[k]);
             }
           }
           if (i1[0] > i0[0] || i1[1] > i0[1]) {   // uniform
@@ -589,35 +607,10 @@ __device__ __forceinline__ void vote_exact(float (&T)[6], const f4v& snd /* sal,
   acc6_pinned<BASE>(T, p00, p01, p02, p11, p12, p22);
 }
 
-// (the vote loop of vote_hits with the exact vote; one list per half wave, entries at hp)
 template <int MODE, int BASE>
-__device__ __forceinline__ void vote_hits_exact(float (&T)[6], unsigned hp, int nst, unsigned r16) {
-  u4v h0 = lds_u4(hp), h1 = lds_u4(hp + 16u);
-  f4v sa = lds_f4(h0.x), ta = lds_f4(r16 - h0.y);
-  f4v sb, tb;
-  int k = 0;
-  for (;;) {   // uniform
-    sb = lds_f4(h0.z);
-    tb = lds_f4(r16 - h0.w);
-    vote_exact<MODE, BASE>(T, sa, ta);
-    if (++k >= nst) break;
-    sa = lds_f4(h1.x);
-    ta = lds_f4(r16 - h1.y);
-    h0 = lds_u4(hp + 32u);
-    vote_exact<MODE, BASE>(T, sb, tb);
-    if (++k >= nst) break;
-    sb = lds_f4(h1.z);
-    tb = lds_f4(r16 - h1.w);
-    vote_exact<MODE, BASE>(T, sa, ta);
-    if (++k >= nst) break;
-    sa = lds_f4(h0.x);
-    ta = lds_f4(r16 - h0.y);
-    h1 = lds_u4(hp + 48u);
-    hp += 32u;
-    vote_exact<MODE, BASE>(T, sb, tb);
-    if (++k >= nst) break;
-  }
-}
+struct VoteExact {
+  static __device__ __forceinline__ void add(float (&T)[6], const f4v& snd, const f4v& tw) { vote_exact<MODE, BASE>(T, snd, tw); }
+};
 
 template <int MODE>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6)))
@@ -682,12 +675,6 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
     const int z_run1 = min(z_run0 + p.zrun, p.z_out1);
     const int x0 = tile_x * TX, y0 = tile_y * TY;
 
-    auto fresh_lane = [&]() -> unsigned {
-      unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      asm volatile("" : "+v"(ln));
-      return ln;
-    };
-
     float TT[NPAIR][NH][6];
 
     // TEST + VOTE of entries [i0, i1) of one list (LDS slots from `base`) for the receiver pair whose sums are T2: 64 entries
@@ -704,7 +691,7 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
         uint2 pw = make_uint2(0xffffffffu, 0u);
         if (e < i1) pw = l_pos[base + e];
         const float exf = (float)(pw.x & 0xffu), eyf = (float)((pw.x >> 8) & 0xffu);
-        const float dy = fmaxf(__builtin_fabsf(eyf - cy) - 1.5f, 0.0f);
+        const float dy = box_gap(eyf, cy);
         const float dy2 = dy * dy;
         const unsigned ent = ent_base + 16u * (unsigned)(base + e);
         auto half = [&](auto HH) {
@@ -713,8 +700,7 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
           int nh[NSUB];
 #pragma unroll
           for (int s = 0; s < NSUB; s++) {
-            const float dx = fmaxf(__builtin_fabsf(exf - (cx0 + 4.0f * (float)s)) - 1.5f, 0.0f);
-            const bool hit = __builtin_fmaf(dx, dx, dy2) <= rr;     // (small integers and halves: exact either way)
+            const bool hit = box_reached(box_gap(exf, cx0 + 4.0f * (float)s), dy2, rr);
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
             nh[s] = __builtin_popcountll(bal);
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
@@ -733,7 +719,7 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
           if (nst > 0) {   // uniform
             const unsigned hp = hb + (fresh_lane() >> 5) * (unsigned)(HX * 8);
             __builtin_amdgcn_s_setprio(1);
-            vote_hits_exact<MODE, 56 + 12 * qq + 6 * hh>(T2[hh], hp, nst, r16);
+            vote_hits<VoteExact<MODE, 56 + 12 * qq + 6 * hh>, 0>(T2[hh], hp, nst, r16);   // (one list per half wave)
             __builtin_amdgcn_s_setprio(0);
           }
           asm volatile("" ::: "memory");
@@ -823,22 +809,9 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
         int done = 0;
         do {   // uniform; at least one interval (a zero-trip path would make the 24 sums a merge of two register sets)
           int c[NLIST], len[NLIST];
-#pragma unroll
-          for (int k = 0; k < NLIST; k++) {
-            const int lo = min(max(pre[k], done), done + NT), hi = min(pre[k + 1], done + NT);
-            c[k] = lo - done;
-            len[k] = max(hi - lo, 0);
-          }
-          const int g = done + tid;
-          int k_me = 0;
-#pragma unroll
-          for (int k = 1; k < NLIST; k++) k_me += (g >= pre[k]) ? 1 : 0;
-          const bool have = g < total;
-          unsigned idx = pl[0] + (unsigned)g;
-#pragma unroll
-          for (int k = 1; k < NLIST; k++)
-            if (k_me == k) idx = pl[k] + (unsigned)(g - pre[k]);
-          const unsigned idxc = have ? idx : 0u;   // (unconditional loads from a clamped index: see the tolerance kernel)
+          bool have;
+          unsigned idxc;
+          list_share(pre, pl, done, tid, c, len, have, idxc);
           const float4 a = lst_ent[idxc];
           const unsigned m = lst_pos[idxc];
           const int ft = wave * 64 + (int)fresh_lane();
@@ -865,11 +838,7 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
             const float4* src2 = table + (i64)(ld2 ? nk2 - 1 : 2 * h + 1) * nsl;
             for (int i = ft; i < nsl; i += NT) dst4[i] = src2[i];
           }
-          if (have) {
-            l_ent[tid] = a;
-            const unsigned ex = m & 0xffu, ey = (m >> 8) - (unsigned)(y0 - h);
-            l_pos[tid] = make_uint2(ex | (ey << 8), 16u * (ey * (unsigned)SP + ex));
-          }
+          if (have) put_entry(l_ent, l_pos, tid, a, m, y0, h, SP);
           VH_STAMP(1);
           __syncthreads();   // lists (and slices) complete
           VH_STAMP(2);
@@ -879,9 +848,7 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
             i0[k] = i1[k] = 0;
             if (len[k] > 0) {   // uniform
               const unsigned rg = __builtin_amdgcn_readfirstlane(l_rng[(plane_slot(lsz[k]) * NPAIR + k) * NW + wave]);
-              const int off = c[k] + done - pre[k];
-              i0[k] = min(max((int)(rg & 0xffffu) - off, 0), len[k]);
-              i1[k] = min(max((int)(rg >> 16) - off, 0), len[k]);
+              cut_stretch(rg, c[k] + done - pre[k], len[k], i0[k], i1[k]);
             }
           }
           if (i1[0] > i0[0] || i1[1] > i0[1]) {   // uniform
@@ -935,168 +902,6 @@ tv_boxx_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
 #endif
 }
 
-// ---- THE SENDER LISTS, once per launch ---------------------------------------------------------------------------------
-// For every listed plane z and every tile column tx (TX = 16 receiver columns), the salient, unmasked senders of the columns
-// [TX tx - h, TX tx + TX + h) -- everything a tile of that column can reach in x -- as one list in DESCENDING (y, x) (the order
-// the vote kernel's row-range culling needs), 20 bytes per entry: float4 {saliency * 1/4 or 1/2 (* mask value), normal} and one
-// word {x - (TX tx - h), y << 8}.  A sender appears in the lists of the tile columns that reach it (2.5 on average at h = 12).
-// rows[(zl (ny + 1) + y) ntx + tx]: index (into the global entry arrays) of the first entry of list (zl, tx) with a row
-// below y -- so the entries of the rows [ylo, yhi] are [rows[.. yhi + 1 ..], rows[.. ylo ..]).
-// Three kernels: count per (plane, row, tile column); suffix sums per (plane, tile column) with one atomic add per list for
-// its place in the global arrays; write.  A WAVE takes one image row: its salient flags as a bit mask in LDS, every
-// window's count / every sender's place in its windows by popcounts over at most four words.
-struct ListGeo {
-  int nx, ny, nz;
-  int zl0, nzl;   // listed planes [zl0, zl0 + nzl)
-  int ntx, h;
-};
-constexpr int LNT = 256;
-constexpr int LWORDS_MAX = 512;    // nx <= 16384
-
-__device__ __forceinline__ unsigned popc_range(const unsigned* w, int lo, int hi) {   // set bits of [lo, hi), hi - lo <= 96
-  unsigned c = 0;
-  for (int i = lo >> 5; i <= (hi - 1) >> 5 && lo < hi; i++) {
-    unsigned m = w[i];
-    if (i == (lo >> 5)) m &= ~0u << (lo & 31);
-    if (i == ((hi - 1) >> 5) && (hi & 31)) m &= ~0u >> (32 - (hi & 31));
-    c += (unsigned)__builtin_popcount(m);
-  }
-  return c;
-}
-
-template <bool WRITE, int MODE>
-__global__ void __launch_bounds__(LNT)
-tvl_row_kernel(const float* __restrict__ sal, const float* __restrict__ dir, const float* __restrict__ mask_src, ListGeo g,
-               unsigned* __restrict__ rows, float4* __restrict__ ent, unsigned* __restrict__ pos,
-               unsigned* __restrict__ neg_flag /* count pass: set if a listed saliency (times its mask value) is not positive */,
-               int fold /* write pass: records {c, a n} instead of {s, n} (vote_fma) */) {
-  // ONE WAVE PER IMAGE ROW (no workgroup barrier: a wave's bit mask is its own): its salient flags as a bit mask in LDS,
-  // 64 voxels per ballot.  A wave is a chain of memory round trips, so every phase requests LB chunks' worth of loads before
-  // it uses the first (the loops are otherwise one round trip per 64 voxels: 8 ms for the write pass at 1024^3)
-  constexpr int LB = 8;
-  __shared__ unsigned bits_all[LNT / 64][LWORDS_MAX + 4];
-  __shared__ unsigned base_all[WRITE ? LNT / 64 : 1][WRITE ? LWORDS_MAX * 2 + 4 : 1];   // write pass: the row's first entry per list
-  __shared__ unsigned cum_all[WRITE ? LNT / 64 : 1][WRITE ? LWORDS_MAX / 2 + 4 : 1];    // write pass: salient voxels before chunk c
-  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const i64 r = (i64)blockIdx.x * (LNT / 64) + wave;      // row number among the listed rows
-  if (r >= (i64)g.nzl * g.ny) return;                      // (uniform per wave)
-  unsigned* const bits = bits_all[wave];
-  const int y = (int)(r % g.ny), zl = (int)(r / g.ny);
-  const i64 plane = (i64)g.nx * g.ny, nvox = plane * g.nz;
-  const i64 row = (i64)(g.zl0 + zl) * plane + (i64)y * g.nx;
-  const int nchunks = (g.nx + 63) >> 6;
-  unsigned* const rrow = rows + ((size_t)zl * (size_t)(g.ny + 1) + (size_t)y) * (size_t)g.ntx;
-  if (WRITE) {   // (requested first: used after the flags)
-    unsigned* const base = base_all[WRITE ? wave : 0];
-    for (int tx = lane; tx < g.ntx; tx += 64) base[tx] = rrow[g.ntx + tx];
-  }
-  unsigned any = 0, total = 0;
-  unsigned* const cum = cum_all[WRITE ? wave : 0];
-  for (int c0 = 0; c0 < nchunks; c0 += LB) {   // uniform
-    float v[LB], m[LB];
-#pragma unroll
-    for (int k = 0; k < LB; k++) {
-      const int x = 64 * (c0 + k) + lane;
-      v[k] = x < g.nx ? sal[row + x] : 0.0f;
-      m[k] = (mask_src && x < g.nx) ? mask_src[row + x] : 1.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < LB; k++) {
-      if (c0 + k >= nchunks) break;   // uniform
-      const bool f = v[k] != 0.0f && m[k] != 0.0f;
-      const unsigned long long bal = __builtin_amdgcn_ballot_w64(f);
-      if (lane == 0) {
-        bits[2 * (c0 + k)] = (unsigned)bal;
-        bits[2 * (c0 + k) + 1] = (unsigned)(bal >> 32);
-        if (WRITE) cum[c0 + k] = total;
-      }
-      any |= (unsigned)bal | (unsigned)(bal >> 32);
-      if (WRITE) total += (unsigned)__builtin_popcountll(bal);
-      if (!WRITE && f) {
-        const float s = mask_src ? v[k] * m[k] : v[k];
-        if (!(s > 0.0f)) atomicOr(neg_flag, 1u);   // (rare: negative peak heights, masks with negative values, NaN)
-        if (!(__builtin_fabsf(s) <= 3.402823466e38f)) atomicOr(neg_flag, 2u);   // non-finite: the exact form declines
-        if (mask_src && m[k] != 1.0f) atomicOr(neg_flag, 4u);   // a weighted source mask: its value is a factor of the exact vote
-      }
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  if (!WRITE) {
-    for (int tx = lane; tx < g.ntx; tx += 64)
-      rrow[tx] = any ? popc_range(bits, max(TX * tx - g.h, 0), min(TX * tx + TX + g.h, g.nx)) : 0u;
-    return;
-  }
-  if (!any) return;   // (uniform)
-  const unsigned* const base = base_all[WRITE ? wave : 0];
-  // lane j takes the row's j-th salient voxel (all lanes busy: the fold's double-precision roots at 3 live lanes per chunk
-  // were most of this pass)
-  for (unsigned j0 = 0; j0 < total; j0 += 64) {   // uniform
-    const unsigned j = j0 + lane;
-    if (j >= total) break;
-    int lo = 0, hi = nchunks;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= j) lo = mid; else hi = mid;
-    }
-    unsigned k = j - cum[lo];
-    unsigned w = bits[2 * lo];
-    int x = 64 * lo;
-    {
-      const unsigned t = (unsigned)__builtin_popcount(w);
-      if (k >= t) { k -= t; x += 32; w = bits[2 * lo + 1]; }
-    }
-#pragma unroll
-    for (int sft = 16; sft >= 1; sft >>= 1) {
-      const unsigned t = (unsigned)__builtin_popcount(w & ((1u << sft) - 1u));
-      if (k >= t) { k -= t; x += sft; w >>= sft; }
-    }
-    // (MODE 1: the exact form's lists carry the saliency itself)
-    float4 q = make_float4(sal[row + x] * (MODE == 0 ? 0.25f : (MODE == 2 ? 0.5f : 1.0f)), dir[row + x], dir[nvox + row + x], dir[2 * nvox + row + x]);
-    if (mask_src) q.x = q.x * mask_src[row + x];
-    if (fold) {   // a = s^(1/6) (exponent 4) or s^(1/4) (exponent 2), rounded once from double
-      const double r2 = sqrt((double)q.x);
-      const float a = (float)(MODE == 0 ? cbrt(r2) : sqrt(r2));
-      q = make_float4(2.0f * a * a, a * q.y, a * q.z, a * q.w);
-    }
-    // tile columns whose window holds x: TX tx - h <= x < TX tx + TX + h
-    const int t0 = max((x - TX - g.h) / TX + ((x - TX - g.h) >= 0 ? 1 : 0), 0);
-    const int t1 = min((x + g.h) / TX, g.ntx - 1);
-    for (int tx = t0; tx <= t1; tx++) {
-      const int lo_x = TX * tx - g.h, hi_x = min(TX * tx + TX + g.h, g.nx);
-      if (x < lo_x || x >= hi_x) continue;
-      // rows[.. y + 1 ..] = first entry of the rows below y + 1 = first entry of row y; within the row: descending x
-      const unsigned idx = base[tx] + popc_range(bits, x + 1, hi_x);
-      ent[idx] = q;
-      pos[idx] = (unsigned)(x - lo_x) | ((unsigned)y << 8);
-    }
-  }
-}
-
-// one thread per list (zl, tx): counts -> offsets.  Before: rows[zl][y][tx] = entries of row y (y < ny).  After:
-// rows[zl][y][tx] = base + (entries of the rows >= y): the index behind row y's last entry... see the header comment; the
-// list's place `base` in the global arrays comes from one atomic add (the lists' order in memory does not matter).
-__global__ void __launch_bounds__(LNT)
-tvl_scan_kernel(ListGeo g, unsigned* __restrict__ rows, unsigned long long* __restrict__ total) {
-  const int i = blockIdx.x * LNT + threadIdx.x;
-  if (i >= g.nzl * g.ntx) return;
-  const int zl = i / g.ntx, tx = i - zl * g.ntx;
-  unsigned* const col = rows + (size_t)zl * (size_t)(g.ny + 1) * (size_t)g.ntx + tx;
-  unsigned sum = 0;
-  for (int y = 0; y < g.ny; y++) sum += col[(size_t)y * g.ntx];
-  const unsigned base = (unsigned)atomicAdd(total, (unsigned long long)sum);
-  // descending rows: the entries of row y sit behind those of every row above it
-  unsigned run = base;
-  unsigned prev = col[(size_t)(g.ny - 1) * g.ntx];
-  col[(size_t)g.ny * g.ntx] = run;            // rows below ny: the list's first entry
-  for (int y = g.ny - 1; y >= 0; y--) {
-    const unsigned c = prev;
-    if (y > 0) prev = col[(size_t)(y - 1) * g.ntx];
-    run += c;
-    col[(size_t)y * g.ntx] = run;              // first entry of a row below y = behind row y's entries
-  }
-}
-
 // Test aid (context option tv_poison): fills every CU's LDS with NaN bit patterns before the voting kernel runs, so that a
 // vote that uses LDS (or ring memory, or an output voxel) the kernel has not written shows up as NaN on every box -- not
 // only on one whose previous tenant happened to leave such bits behind.
@@ -1107,21 +912,28 @@ __global__ void __launch_bounds__(256) lds_poison_kernel(unsigned* sink) {
   if (pz[(threadIdx.x * 37) % (160 * 256)] == 1u) sink[0] = 1u;
 }
 
+// (one signature: the launcher picks a kernel by the vote's mode -- 0: exponent 4, 2: exponent 2 -- and the lists' form)
+auto box_exact_kernel(int mode) {
+  if (mode == 0) return tv_boxx_kernel<0>;
+  return tv_boxx_kernel<2>;
+}
+auto box_tol_kernel(int mode, bool fold) {
+  if (mode == 0) return fold ? tv_box_kernel<0, true> : tv_box_kernel<0, false>;
+  return fold ? tv_box_kernel<2, true> : tv_box_kernel<2, false>;
+}
+
 }  // namespace
 
 // Tolerance-mode tensor voting (surfaces, exponent 2 or 4).  dtab_box: the {w, sqrt(2) rhat} table on the device in this
-// kernel's slice layout (tv.hip: tv_table_device).
-// exact != 0: the exact form (tv_boxx_kernel) with dtab_box = the reference's {w, rhat} in the same slice layout; it declines
-// weighted source masks (values other than 0 and 1) and non-finite saliencies (the caller falls back to tv_tiled.hip).
+// kernel's slice layout (tv_common.hpp: TvTables::box_tol).
+// exact: the exact form (tv_boxx_kernel) with dtab_box = the reference's {w, rhat} in the same slice layout (box_exact); it
+// declines weighted source masks (values other than 0 and 1) and non-finite saliencies (tv_tiled.hip takes them).
 int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
                const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box,
-               int exponent, bool* handled, bool exact) {
-  *handled = false;
-  if (exponent != 2 && exponent != 4) return VISFD_HIP_OK;
-  // (a source mask of zeros and ones only multiplies the kept senders' weights by 1.0 -- exactly nothing -- so the exact form
-  //  takes it; the count pass of the listing reports any other mask value, see below)
-  if (h < 1 || h > 40) return VISFD_HIP_OK;
-  if (nx * ny >= (1LL << 29) || nx > 32 * LWORDS_MAX || ny >= (1 << 24)) return VISFD_HIP_OK;
+               int exponent, bool exact) {
+  if (exponent != 2 && exponent != 4) return TV_DECLINED;
+  if (h < 1 || h > 40) return TV_DECLINED;
+  if (nx * ny >= (1LL << 29) || nx > TV_LIST_MAX_NX || ny >= (1 << 24)) return TV_DECLINED;
   hipStream_t st = ctx->stream;
   BoxParams p;
   p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
@@ -1129,104 +941,47 @@ int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* te
   p.h = h;
   p.rw = TX + 2 * h;
   p.rh = TY + 2 * h;
-  if (p.rw > 255 || p.rh > 255) return VISFD_HIP_OK;   // window columns and region rows travel as bytes
+  if (p.rw > 255 || p.rh > 255) return TV_DECLINED;   // window columns and region rows travel as bytes
   p.sp = tv_box_row(h);
   p.nsl = tv_box_slice(h);
   const size_t slice_bytes = sizeof(float4) * (size_t)p.nsl;
   p.tiles_x = (int)((nx + TX - 1) / TX);
   p.tiles_y = (int)((ny + TY - 1) / TY);
-  p.zrun = 8;    // (sweep at 1024^3, tools/tv_sweep.py: 2..8 planes 280-281 ms, 16: 283, 32: 290, 64: 296, 128: 306 -- short runs keep the
-                 //  workgroups of the chip on neighbouring planes, whose lists and slices they then share in L2)
-  if (ctx->opt.tv_zrun >= 1 && ctx->opt.tv_zrun <= 4096) p.zrun = ctx->opt.tv_zrun;
-  if ((i64)p.zrun > z_out1 - z_out0) p.zrun = (int)(z_out1 - z_out0);
-  if (p.zrun < 1) p.zrun = 1;
-  const i64 nruns = (z_out1 - z_out0 + p.zrun - 1) / p.zrun;
-  const i64 nblk = (i64)p.tiles_x * p.tiles_y * nruns;
-  if (nblk > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
-  if (nblk <= 0) { *handled = true; return VISFD_HIP_OK; }
+  // (sweep at 1024^3, tools/tv_sweep.py: 2..8 planes 280-281 ms, 16: 283, 32: 290, 64: 296, 128: 306 -- short runs keep the
+  //  workgroups of the chip on neighbouring planes, whose lists and slices they then share in L2)
+  i64 nblk = 0;
+  VH_TRY(tv_plan_units(ctx, 8, p.tiles_x, p.tiles_y, z_out0, z_out1, &p.zrun, &nblk));
+  if (nblk == 0) return VISFD_HIP_OK;
   // two slices + the per-pass table of row stretches ([2h + 4 planes][pairs][waves] words)
   const size_t lds = 2 * slice_bytes + sizeof(unsigned) * (size_t)(2 * h + 4) * NW * (exact ? NPAIR : 1);
   const size_t lds_static = sizeof(float4) * (LSLOTS + 1) + sizeof(uint2) * LSLOTS + sizeof(uint2) * NW * NSUB * 2 * HCAP + 1536;
   static_assert(2 * HCAP == HX, "the two kernels' hit lists take the same LDS");
-  if (lds + lds_static > 150 * 1024) return VISFD_HIP_OK;   // window too wide: the caller falls back
+  if (lds + lds_static > 150 * 1024) return TV_DECLINED;   // window too wide
 
-  // ---- the sender lists of the planes the receiver planes [z_out0, z_out1) reach -------------------------------------------
-  ListGeo g;
-  g.nx = p.nx; g.ny = p.ny; g.nz = p.nz; g.h = h; g.ntx = p.tiles_x;
-  g.zl0 = (int)std::max<i64>(z_out0 - h, 0);
-  g.nzl = (int)(std::min<i64>(z_out1 + h, nz) - g.zl0);
-  p.zl0 = g.zl0; p.nzl = g.nzl;
-  const size_t nrows = (size_t)g.nzl * (size_t)(ny + 1) * (size_t)g.ntx;
-  if ((i64)g.nzl * ny > 0x7fffffffLL) return VISFD_HIP_OK;
-  unsigned* rows = nullptr;
+  // The sender lists.  What their count pass reports decides two things here:
+  //  * the exact form declines a non-finite saliency (the zero-padded slices would spread it) and a weighted source mask
+  //    (fv = w * mask value, feature.hpp:2262-2275; a mask of zeros and ones only multiplies the kept senders' weights by
+  //    1.0 -- exactly nothing -- so it takes that);
+  //  * the tolerance form folds the saliencies into the normals (the 18-instruction vote) if every one is positive
+  //    (option tv_no_fold, tests: the general form on positive saliencies too).
   unsigned* counter = nullptr;
-  VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));
-  if (ws(ctx, WS_TVLIST, nrows, &rows) != VISFD_HIP_OK) { set_error(""); (void)hipGetLastError(); return VISFD_HIP_OK; }
-  unsigned long long* total_dev = reinterpret_cast<unsigned long long*>(counter + 4);
-  VH_HIP(hipMemsetAsync(counter, 0, 16 * sizeof(unsigned), st));
-  const unsigned row_blocks = (unsigned)(((i64)g.nzl * ny + LNT / 64 - 1) / (LNT / 64));
-#define VH_TVL_ROWS(WR, ENT, POS)                                                                                         \
-  do {                                                                                                                    \
-    if (exact) tvl_row_kernel<WR, 1><<<dim3(row_blocks), dim3(LNT), 0, st>>>(sal, dir, mask_src, g, rows, ENT, POS, counter + 6, 0);             \
-    else if (exponent == 4) tvl_row_kernel<WR, 0><<<dim3(row_blocks), dim3(LNT), 0, st>>>(sal, dir, mask_src, g, rows, ENT, POS, counter + 6, fold); \
-    else tvl_row_kernel<WR, 2><<<dim3(row_blocks), dim3(LNT), 0, st>>>(sal, dir, mask_src, g, rows, ENT, POS, counter + 6, fold);             \
-  } while (0)
-  int fold = 0;
-  VH_TVL_ROWS(false, nullptr, nullptr);
-  tvl_scan_kernel<<<dim3((unsigned)(((size_t)g.nzl * g.ntx + LNT - 1) / LNT)), dim3(LNT), 0, st>>>(g, rows, total_dev);
-  VH_HIP(hipGetLastError());
-  // the lists' total length decides the size of the entry arrays: the one place this launch waits for the device
-  unsigned long long tot2[2] = {0, 0};   // {total, (negative flag, -)}: counter words 4..7
-  VH_HIP(hipMemcpyAsync(tot2, total_dev, sizeof(tot2), hipMemcpyDeviceToHost, st));
-  VH_HIP(hipStreamSynchronize(st));
-  const unsigned long long total = tot2[0];
-  fold = ((unsigned)tot2[1] & 1u) ? 0 : 1;   // every listed saliency positive: the 18-instruction vote
-  if (ctx->opt.tv_no_fold) fold = 0;         // (tests: the general form on positive saliencies too)
-  if (exact && ((unsigned)tot2[1] & 2u)) return VISFD_HIP_OK;   // a non-finite saliency: the zero-padded slices would spread it
-  if (exact && ((unsigned)tot2[1] & 4u)) return VISFD_HIP_OK;   // a weighted source mask: fv = w * mask value (feature.hpp:2262-2275)
-  if (total >= (1ull << 32) - 2048) return VISFD_HIP_OK;   // 32-bit entry indices: the caller falls back
-  unsigned char* lists = nullptr;
-  if (ws(ctx, WS_TVSCRATCH, (size_t)(total + 16) * 20, &lists) != VISFD_HIP_OK) { set_error(""); (void)hipGetLastError(); return VISFD_HIP_OK; }
-  float4* const lst_ent = reinterpret_cast<float4*>(lists);
-  unsigned* const lst_pos = reinterpret_cast<unsigned*>(lists + (size_t)(total + 16) * 16);
-  if (ctx->opt.tv_poison) VH_HIP(hipMemsetAsync(lists, 0xff, (size_t)(total + 16) * 20, st));
-  VH_TVL_ROWS(true, lst_ent, lst_pos);
-#undef VH_TVL_ROWS
-  VH_HIP(hipGetLastError());
+  VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));   // word 0: the kernel's unit counter (zeroed with the lists' words); 8: poison sink
+  TvSenderLists L;
+  VH_TRY(tv_sender_lists(ctx, sal, dir, mask_src, nx, ny, nz, z_out0, z_out1, h, exact ? 1 : (exponent == 4 ? 0 : 2),
+                         exact ? (TVL_NON_FINITE | TVL_WEIGHTED_MASK) : 0u, !exact && !ctx->opt.tv_no_fold, counter, &L));
+  p.zl0 = L.zl0; p.nzl = L.nzl;
 
   size_t wg_per_cu = (160 * 1024) / (lds + lds_static);
   if (wg_per_cu > 3) wg_per_cu = 3;   // 6 waves per SIMD (80 VGPRs)
   if (wg_per_cu < 1) wg_per_cu = 1;
-  i64 ngrid = (i64)ctx->num_cus * (i64)wg_per_cu;
-  // slab runs: workgroup slots left free for the transport's kernels while a halo is in flight (slab.hip) -- counted
-  // against THIS kernel's own chip-filling grid
-  if (ctx->opt.tv_reserve_wg > 0) ngrid = std::max<i64>(ngrid - ctx->opt.tv_reserve_wg, 1);
-  if (ctx->opt.tv_max_wg > 0 && ngrid > ctx->opt.tv_max_wg) ngrid = ctx->opt.tv_max_wg;
-  if (ngrid > nblk) ngrid = nblk;
+  const i64 ngrid = tv_plan_grid(ctx, wg_per_cu, nblk);
   if (ctx->opt.tv_poison) {   // tests: everything the kernel may read without having written it becomes NaN
     VH_HIP(hipMemsetAsync(ten, 0xff, sizeof(float) * 6 * (size_t)(nx * ny * nz), st));
-    VH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lds_poison_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    lds_poison_kernel<<<dim3(1024), dim3(256), 160 * 1024, st>>>(counter + 8);
+    VH_TRY(tv_launch_lds(ctx, lds_poison_kernel, 1024, 256, 160 * 1024, counter + 8));
   }
-#define VH_BOX_LAUNCH(MD, FD)                                                                                          \
-  do {                                                                                                                 \
-    VH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tv_box_kernel<MD, FD>),                                  \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    tv_box_kernel<MD, FD><<<dim3((unsigned)ngrid), dim3(NT), lds, st>>>(ten, mask_dst, dtab_box, p, counter, (unsigned)nblk, \
-                                                                       lst_ent, lst_pos, rows);                        \
-  } while (0)
-#define VH_BOXX_LAUNCH(MD)                                                                                             \
-  do {                                                                                                                 \
-    VH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tv_boxx_kernel<MD>),                                     \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    tv_boxx_kernel<MD><<<dim3((unsigned)ngrid), dim3(NT), lds, st>>>(ten, mask_dst, dtab_box, p, counter, (unsigned)nblk, \
-                                                                    lst_ent, lst_pos, rows);                           \
-  } while (0)
-  if (exact)              { if (exponent == 4) VH_BOXX_LAUNCH(0); else VH_BOXX_LAUNCH(2); }
-  else if (exponent == 4) { if (fold) VH_BOX_LAUNCH(0, true); else VH_BOX_LAUNCH(0, false); }
-  else                    { if (fold) VH_BOX_LAUNCH(2, true); else VH_BOX_LAUNCH(2, false); }
-#undef VH_BOX_LAUNCH
-#undef VH_BOXX_LAUNCH
+  const int md = exponent == 4 ? 0 : 2;
+  auto kernel = exact ? box_exact_kernel(md) : box_tol_kernel(md, L.folded);
+  VH_TRY(tv_launch_lds(ctx, kernel, ngrid, NT, lds, ten, mask_dst, dtab_box, p, counter, (unsigned)nblk, L.ent, L.pos, L.rows));
   VH_HIP(hipGetLastError());
 #ifdef VH_TV_COUNT
   {
@@ -1251,7 +1006,6 @@ int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* te
     VH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_box_stamps), z8, sizeof(z8)));
   }
 #endif
-  *handled = true;
   return VISFD_HIP_OK;
 }
 

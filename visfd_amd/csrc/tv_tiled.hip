@@ -37,7 +37,7 @@
 // loads and stores were most of the kernel's 2 TB of memory traffic per 1024^3 launch (profiles/r02_tv_design.txt).
 #include <vector>
 
-#include "common.hpp"
+#include "tv_common.hpp"
 
 namespace vh {
 
@@ -69,15 +69,6 @@ __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t rs, unsigned by
 }
 
 typedef float f4v __attribute__((ext_vector_type(4)));
-
-// LDS (address space 3) pointers as 32-bit integers and back
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-template <typename T>
-__device__ __forceinline__ const __attribute__((address_space(3))) T* lds_ptr(unsigned a) {
-  return (const __attribute__((address_space(3))) T*)(uintptr_t)a;
-}
 
 struct TiledParams {
   int nx, ny, nz;
@@ -623,16 +614,23 @@ tv_tiled_kernel(const float* __restrict__ sal, const float* __restrict__ dir, fl
   }   // next unit
 }
 
+template <bool MASKED_SRC>
+auto tiled_kernel(int mode) {
+  if (mode == 0) return tv_tiled_kernel<MASKED_SRC, 0>;
+  if (mode == 2) return tv_tiled_kernel<MASKED_SRC, 2>;
+  if (mode == 3) return tv_tiled_kernel<MASKED_SRC, 3>;
+  return tv_tiled_kernel<MASKED_SRC, 1>;
+}
+
 }  // namespace
 
 // dtab: the vote table on the device with padded rows (tv.hip: tv_table_device).  weights_only: ten receives ONE plane, the sum of the
 // weights of the votes each receiver takes (the normalisation denominator of feature.hpp:1784-1822) instead of tensors.
 int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten,
                  const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0,
-                 i64 z_out1, int h, const float4* dtab, int exponent, bool curves, bool weights_only, bool* handled) {
-  *handled = false;
-  if (h < 1 || h > 40) return VISFD_HIP_OK;  // table slice in LDS + byte-packed coordinates limits
-  if (nx * ny >= (1LL << 29)) return VISFD_HIP_OK;  // plane descriptors are 32-bit
+                 i64 z_out1, int h, const float4* dtab, int exponent, bool curves, bool weights_only) {
+  if (h < 1 || h > 40) return TV_DECLINED;  // table slice in LDS + byte-packed coordinates limits
+  if (nx * ny >= (1LL << 29)) return TV_DECLINED;  // plane descriptors are 32-bit
   const int n = 2 * h + 1;
   hipStream_t st = ctx->stream;
 
@@ -655,20 +653,16 @@ int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* 
   p.curves = curves ? 1 : 0;
   p.relist = ctx->opt.tv_no_replay ? 1 : 0;
   // units of work: a tile over a run of receiver planes (sender-plane lists are shared within a run)
-  p.zrun = 32;   // sweep at 1024^3: 16: 853 ms, 24-64: 820-833 ms, 128: 838 ms
-  if (ctx->opt.tv_zrun >= 1 && ctx->opt.tv_zrun <= 4096) p.zrun = ctx->opt.tv_zrun;   // tuning aid
-  if ((i64)p.zrun > z_out1 - z_out0) p.zrun = (int)(z_out1 - z_out0);
-  if (p.zrun < 1) p.zrun = 1;
-  const i64 nruns = (z_out1 - z_out0 + p.zrun - 1) / p.zrun;
-  const i64 nblk = (i64)p.tiles_x * p.tiles_y * nruns;
-  if (nblk > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
-  if (nblk <= 0) { *handled = true; return VISFD_HIP_OK; }
+  i64 nblk = 0;
+  VH_TRY(tv_plan_units(ctx, 32 /* sweep at 1024^3: 16: 853 ms, 24-64: 820-833 ms, 128: 838 ms */, p.tiles_x, p.tiles_y, z_out0,
+                       z_out1, &p.zrun, &nblk));
+  if (nblk == 0) return VISFD_HIP_OK;
   const size_t lds = 2 * slice_bytes;   // dynamic part: the slices of jz and jz + 1
   const size_t lds_static = (sizeof(float4) + sizeof(uint2) + sizeof(float) * (mask_src ? 1 : 0)) * (size_t)(NT + 12 * NP + 16) + 2560;
-  if (lds + lds_static > 150 * 1024) return VISFD_HIP_OK;   // window too wide for the LDS slice: baseline kernel
+  if (lds + lds_static > 150 * 1024) return TV_DECLINED;   // window too wide for the LDS slice: baseline kernel
   const int mode = weights_only ? 3 : (curves ? 1 : (exponent == 4 ? 0 : (exponent == 2 ? 2 : 1)));
-  // persistent workgroups (see the kernel): as many as the chip holds at once -- LDS allows 160 KB / (static +
-  // dynamic) per CU, registers eight waves per SIMD = 4 workgroups of 8 waves -- each claiming units from a counter
+  // persistent workgroups (see the kernel; tv_common.hpp: tv_plan_grid) -- LDS allows 160 KB / (static + dynamic) per CU,
+  // registers eight waves per SIMD = 4 workgroups of 8 waves
   unsigned* counter = nullptr;
   VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));
   VH_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned), st));
@@ -676,12 +670,7 @@ int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* 
   const size_t max_wg = mode == 1 ? 1 : 2048 / NT;   // eight waves per SIMD in all
   if (wg_per_cu > max_wg) wg_per_cu = max_wg;
   if (wg_per_cu < 1) wg_per_cu = 1;
-  i64 ngrid = (i64)ctx->num_cus * (i64)wg_per_cu;
-  // slab runs: workgroup slots left free for the transport's kernels while a halo is in flight (slab.hip) -- counted
-  // against THIS kernel's own chip-filling grid
-  if (ctx->opt.tv_reserve_wg > 0) ngrid = std::max<i64>(ngrid - ctx->opt.tv_reserve_wg, 1);
-  if (ctx->opt.tv_max_wg > 0 && ngrid > ctx->opt.tv_max_wg) ngrid = ctx->opt.tv_max_wg;   // tests: many units per workgroup
-  if (ngrid > nblk) ngrid = nblk;
+  i64 ngrid = tv_plan_grid(ctx, wg_per_cu, nblk);
   // scratch rings: (2h+1) planes x (8+2h)(32+2h) entries of 32 bytes per workgroup (2.9 GB for h = 12 on 256 CUs).  Very
   // wide windows are capped at 16 GB (fewer workgroups: their LDS slices allow only one or two per CU anyway); if the
   // allocation fails the grid is halved, and without any ring the caller's baseline kernel takes over.
@@ -694,25 +683,11 @@ int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* 
     set_error("");
     (void)hipGetLastError();
   }
-  if (!scratch) return VISFD_HIP_OK;
-#define VH_TV_LAUNCH(MSK, MD)                                                                        \
-  do {                                                                                               \
-    VH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tv_tiled_kernel<MSK, MD>),             \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
-    tv_tiled_kernel<MSK, MD><<<dim3((unsigned)ngrid), dim3(NT), lds, st>>>(sal, dir, ten, mask_src,  \
-                                                                          mask_dst, dtab, p, counter, \
-                                                                          (unsigned)nblk, scratch);  \
-  } while (0)
-  if (mask_src) {
-    if (mode == 0) VH_TV_LAUNCH(true, 0); else if (mode == 2) VH_TV_LAUNCH(true, 2); else if (mode == 3) VH_TV_LAUNCH(true, 3);
-    else VH_TV_LAUNCH(true, 1);
-  } else {
-    if (mode == 0) VH_TV_LAUNCH(false, 0); else if (mode == 2) VH_TV_LAUNCH(false, 2); else if (mode == 3) VH_TV_LAUNCH(false, 3);
-    else VH_TV_LAUNCH(false, 1);
-  }
-#undef VH_TV_LAUNCH
+  if (!scratch) return TV_DECLINED;
+  const auto kernel = mask_src ? tiled_kernel<true>(mode) : tiled_kernel<false>(mode);
+  VH_TRY(tv_launch_lds(ctx, kernel, ngrid, NT, lds, sal, dir, ten, mask_src, mask_dst, dtab, p, counter,
+                       (unsigned)nblk, scratch));
   VH_HIP(hipGetLastError());
-  *handled = true;
   return VISFD_HIP_OK;
 }
 
