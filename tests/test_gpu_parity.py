@@ -497,6 +497,57 @@ def test_gauss_non_finite_and_sparse_inputs(ctx, oracle, h):
     _same_float_field(ctx.log(src, s3, 0.02, r, mask)[0], oracle.log(src, s3, 0.02, r, mask)[0], "masked LoG h=%d" % h)
 
 
+_EPILOGUE_ROUTES = {
+    "h3": ((3, 3, 3), {}),                       # single sweep; masked: Z pass, then the Y/X sweep
+    "h3_3pass": ((3, 3, 3), {"gauss_3pass": 1}),  # the same windows on the three single-axis passes
+    "aniso": ((3, 4, 2), {}),                    # unequal half-widths: three passes
+    "h9": ((9, 9, 9), {}),                       # too wide for the single sweep: three passes
+}
+_EPILOGUE_WANT = {}   # oracle fields, computed once per (filter, mask, half-widths)
+
+
+@pytest.mark.parametrize("route", list(_EPILOGUE_ROUTES))
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("filt", ["dog", "log"])
+def test_dog_log_epilogue_on_every_route(ctx, oracle, filt, masked, route):
+    """DoG and LoG have no subtraction kernel and no temporary volume: on every route of the separable filter the launch
+    that writes the second Gaussian stores (G_a - G_b) * scale itself.  Each route, masked and not, against the oracle bit for
+    bit; and the workspace a device-pointer LoG leaves behind holds no full volume on the single sweep (normaliser lines
+    only) and four on the masked three-pass route (two intermediates, two denominators) -- ws_get allocates exact sizes."""
+    import torch
+    shape = (30, 37, 52)
+    n = int(np.prod(shape))
+    hw, opts = _EPILOGUE_ROUTES[route]
+    src = volgen.noise_volume(shape, seed=77)
+    mask = volgen.block_mask(shape, seed=9) if masked else None
+    r, delta = oracle.ratio_from_threshold(0.03), 0.02
+    # LoG takes its half-widths from sigma: floor(ratio * sigma * (1 + delta / 2)), put in the middle of hw's interval
+    sigma = tuple((h + 0.5) / (r * (1 + 0.5 * delta)) for h in hw)
+    assert tuple(int(np.floor(np.float32(r) * np.float32(s * (1 + 0.5 * delta)))) for s in sigma) == hw
+    if filt == "dog":
+        args = (tuple(h / 3.1 for h in hw), tuple(h / 2.6 for h in hw), hw, mask)
+    else:
+        args = (sigma, delta, r, mask)
+    key = (filt, masked, hw)
+    if key not in _EPILOGUE_WANT:
+        _EPILOGUE_WANT[key] = getattr(oracle, filt)(src, *args)[0]
+    with ctx.options(**opts):
+        got = getattr(ctx, filt)(src, *args)[0]
+    _same_float_field(got, _EPILOGUE_WANT[key], "%s %s masked=%s" % (filt, route, masked))
+    if filt == "log" and (route, masked) in (("h3", False), ("h9", True)):
+        dev = torch.device("cuda:0")
+        dsrc = torch.from_numpy(src).to(dev)
+        dmask = torch.from_numpy(mask).to(dev) if masked else None
+        dst = torch.empty_like(dsrc)
+        torch.cuda.synchronize()
+        ctx.trim()
+        ctx.log_dev(dsrc, dst, sigma, delta, r, dmask)
+        ctx.synchronize()
+        held = ctx.workspace_bytes()
+        _same_float_field(dst.cpu().numpy(), _EPILOGUE_WANT[key], "log_dev %s masked=%s" % (route, masked))
+        assert held < (5 * 4 * n if masked else 4 * n), "workspace after log_dev: %d bytes, volume %d bytes" % (held, 4 * n)
+
+
 def test_blob_detection_with_non_finite_voxels(ctx, oracle):
     """A NaN voxel poisons the LoG values within a window of it; every comparison with a NaN is false in the reference's
     scan (feature.hpp:245-304), which keeps or drops candidates accordingly: same lists from the GPU."""

@@ -11,8 +11,7 @@
 namespace vh {
 
 int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
-              const float sigma[3], const int hw[3], bool normalize, SlabInfo slab, float* A_out, const float* minuend,
-              float log_scale, bool* epilogue_done, bool fma) {
+              const float sigma[3], const int hw[3], bool normalize, const GaussOpts& o) {
   VH_REQUIRE(ctx && src && dst && sigma && hw, "null argument");
   std::vector<float> t[3];
   for (int d = 0; d < 3; d++) {
@@ -21,27 +20,17 @@ int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mas
     t[d].resize(2 * hw[d] + 1);
     host_gauss_taps(sigma[d], hw[d], t[d].data());
   }
-  return dev_separable3d(ctx, src, dst, mask, nx, ny, nz, t[0].data(), hw[0], t[1].data(), hw[1],
-                         t[2].data(), hw[2], normalize, slab, A_out, minuend, log_scale, epilogue_done, fma);
+  return dev_separable3d(ctx, src, dst, mask, nx, ny, nz, t[0].data(), hw[0], t[1].data(), hw[1], t[2].data(), hw[2],
+                         normalize, o);
 }
 
-// ApplyDog with a caller-provided temp volume (filter3d.hpp:1338-1402); with do_scale it is the body of
-// ApplyLog (filter3d.hpp:1466-1498).  dst = G_a(src); then the second Gaussian writes
-// (dst - G_b(src)) [* scale] straight into dst when the single-sweep kernel applies, else via tmp.
-static int dog_dev(visfd_hip_ctx* ctx, const float* src, float* dst, float* tmp, const float* mask, i64 nx, i64 ny,
-                   i64 nz, const float sa[3], const float sb[3], const int hw[3], float scale, bool do_scale,
-                   float* A, float* B) {
-  const SlabInfo whole = {0, nz};
-  VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sa, hw, true, whole, A));
-  {
-    // the fused epilogue reads and writes the same element of dst in one thread: in-place is safe;
-    // without scaling the multiplier is 1.0f, which is exact
-    bool fused = false;
-    VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sb, hw, true, whole, B, dst, do_scale ? scale : 1.0f, &fused));
-    if (fused) return VISFD_HIP_OK;
-  }
-  VH_TRY(gauss_dev(ctx, src, tmp, mask, nx, ny, nz, sb, hw, true, whole, B));
-  return dev_sub_scale(ctx, dst, tmp, nx * ny * nz, scale, do_scale);
+// ApplyDog (filter3d.hpp:1338-1402); with scale != 1 it is the body of ApplyLog (filter3d.hpp:1466-1498).
+// dst = G_a(src); then the second Gaussian stores (dst - G_b(src)) * scale straight into dst: the launch that writes an
+// element has read its minuend in the same thread, so in place is safe, and a multiplier of 1.0f is exact.
+static int dog_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+                   const float sa[3], const float sb[3], const int hw[3], float scale, float* A, float* B) {
+  VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sa, hw, true, {A}));
+  return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sb, hw, true, {B, dst, scale});
 }
 
 // ApplyLog parameter derivation (filter3d.hpp:1451-1464, :1493)
@@ -56,13 +45,13 @@ LogPlan plan_log(const float sigma[3], float delta, float ratio) {
   return p;
 }
 
-int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, float* tmp, const float* mask, i64 nx, i64 ny,
-            i64 nz, const float sigma[3], float delta, float ratio, float* A, float* B) {
+int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+            const float sigma[3], float delta, float ratio, float* A, float* B) {
   const LogPlan p = plan_log(sigma, delta, ratio);
   for (int d = 0; d < 3; d++)
     VH_REQUIRE(p.hw[d] >= 0 && p.hw[d] <= MAX_HALFWIDTH, "LoG filter halfwidth must be in [0, 64]");
   float a = 0, b = 0;
-  VH_TRY(dog_dev(ctx, src, dst, tmp, mask, nx, ny, nz, p.sa, p.sb, p.hw, p.scale, true, &a, &b));
+  VH_TRY(dog_dev(ctx, src, dst, mask, nx, ny, nz, p.sa, p.sb, p.hw, p.scale, &a, &b));
   if (A) *A = a * p.scale;   // filter3d.hpp:1502-1505
   if (B) *B = b * p.scale;
   return VISFD_HIP_OK;
@@ -87,8 +76,7 @@ int gauss_iso_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float*
   if (out) *out = dst;
   const float sg[3] = {sigma, sigma, sigma};
   const int hw[3] = {hwv, hwv, hwv};
-  const SlabInfo whole = {0, nz};
-  return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sg, hw, normalize, whole, nullptr);
+  return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sg, hw, normalize);
 }
 
 int calc_hessian_dev(visfd_hip_ctx* ctx, const float* src, float* grad, float* hess, const float* mask,
@@ -98,6 +86,14 @@ int calc_hessian_dev(visfd_hip_ctx* ctx, const float* src, float* grad, float* h
   float* S = nullptr;
   VH_TRY(gauss_iso_dev(ctx, src, nullptr, mask, nx, ny, nz, sigma, ratio, true, "filter halfwidth", &S));
   return dev_hessian(ctx, S, mask, nx, ny, nz, sigma, grad, hess);
+}
+
+// Options of the entry points whose output is a float field: the tolerance mode where the context asks for it
+GaussOpts field_opts(const visfd_hip_ctx* ctx, float* A_out) {
+  GaussOpts o;
+  o.A_out = A_out;
+  o.fma = ctx->opt.gauss_fma != 0;
+  return o;
 }
 
 bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
@@ -153,9 +149,7 @@ int visfd_hip_separable3d_dev(visfd_hip_ctx* ctx, const float* src, float* dst, 
                               float* A_out) {
   VH_REQUIRE(ctx && src && dst && tx && ty && tz, "null argument");
   VH_HIP(hipSetDevice(ctx->device));
-  const SlabInfo whole = {0, nz};
-  return dev_separable3d(ctx, src, dst, mask, nx, ny, nz, tx, hx, ty, hy, tz, hz, normalize != 0, whole,
-                         A_out, nullptr, 1.0f, nullptr, ctx->opt.gauss_fma != 0);
+  return dev_separable3d(ctx, src, dst, mask, nx, ny, nz, tx, hx, ty, hy, tz, hz, normalize != 0, field_opts(ctx, A_out));
 }
 
 int visfd_hip_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
@@ -172,9 +166,7 @@ int visfd_hip_apply_gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, 
                               const int hw[3], int normalize, float* A_out) {
   VH_REQUIRE(ctx, "null context");
   VH_HIP(hipSetDevice(ctx->device));
-  const SlabInfo whole = {0, nz};
-  return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sigma, hw, normalize != 0, whole, A_out, nullptr, 1.0f, nullptr,
-                   ctx->opt.gauss_fma != 0);
+  return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sigma, hw, normalize != 0, field_opts(ctx, A_out));
 }
 
 int visfd_hip_apply_gauss_slab_dev(visfd_hip_ctx* ctx, const float* src, float* dst, int64_t nx,
@@ -183,9 +175,10 @@ int visfd_hip_apply_gauss_slab_dev(visfd_hip_ctx* ctx, const float* src, float* 
   VH_REQUIRE(ctx, "null context");
   VH_REQUIRE(z_lo >= 0 && z_lo + nz_local <= nz_global, "slab outside the volume");
   VH_HIP(hipSetDevice(ctx->device));
-  const SlabInfo slab = {z_lo, nz_global};
-  return gauss_dev(ctx, src, dst, nullptr, nx, ny, nz_local, sigma, hw, normalize != 0, slab, A_out, nullptr, 1.0f, nullptr,
-                   ctx->opt.gauss_fma != 0);
+  GaussOpts o = field_opts(ctx, A_out);
+  o.z_lo = z_lo;
+  o.nz_global = nz_global;
+  return gauss_dev(ctx, src, dst, nullptr, nx, ny, nz_local, sigma, hw, normalize != 0, o);
 }
 
 int visfd_hip_apply_gauss(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
@@ -208,12 +201,11 @@ int visfd_hip_local_fluctuations_dev(visfd_hip_ctx* ctx, const float* src, float
   int hw[3];
   halfwidths_from_ratio(sigma, truncate_ratio, hw);    // ApplyGauss(sigma[3], ratio), filter3d.hpp:1240-1247
   const float wpeak = host_gengauss3d_peak(sigma, exponent, truncate_ratio);
-  const SlabInfo whole = {0, nz};
   float* p2 = nullptr;
   VH_TRY(ws(ctx, WS_C, (size_t)n, &p2));
-  VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sigma, hw, normalize != 0, whole, nullptr));   // local average
+  VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sigma, hw, normalize != 0));   // local average
   VH_TRY(dev_sub_square(ctx, src, dst, p2, n));                                                      // (src - avg)^2
-  VH_TRY(gauss_dev(ctx, p2, dst, mask, nx, ny, nz, sigma, hw, normalize != 0, whole, nullptr));    // its local average
+  VH_TRY(gauss_dev(ctx, p2, dst, mask, nx, ny, nz, sigma, hw, normalize != 0));    // its local average
   return dev_scale_clamp_sqrt(ctx, dst, n, wpeak);
 }
 
@@ -245,9 +237,7 @@ int visfd_hip_apply_dog_dev(visfd_hip_ctx* ctx, const float* src, float* dst, co
   VH_REQUIRE(ctx && src && dst && sa && sb && hw, "null argument");
   VH_HIP(hipSetDevice(ctx->device));
   VH_TRY(check_dims(nx, ny, nz));
-  float* tmp = nullptr;
-  VH_TRY(ws(ctx, WS_C, (size_t)(nx * ny * nz), &tmp));
-  return dog_dev(ctx, src, dst, tmp, mask, nx, ny, nz, sa, sb, hw, 1.0f, false, A, B);
+  return dog_dev(ctx, src, dst, mask, nx, ny, nz, sa, sb, hw, 1.0f, A, B);
 }
 
 int visfd_hip_apply_dog(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
@@ -264,9 +254,7 @@ int visfd_hip_apply_log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, co
   VH_REQUIRE(ctx && src && dst && sigma, "null argument");
   VH_HIP(hipSetDevice(ctx->device));
   VH_TRY(check_dims(nx, ny, nz));
-  float* tmp = nullptr;
-  VH_TRY(ws(ctx, WS_C, (size_t)(nx * ny * nz), &tmp));
-  return log_dev(ctx, src, dst, tmp, mask, nx, ny, nz, sigma, delta, ratio, A, B);
+  return log_dev(ctx, src, dst, mask, nx, ny, nz, sigma, delta, ratio, A, B);
 }
 
 int visfd_hip_apply_log(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,

@@ -95,12 +95,11 @@ void blob_jobs_abort(visfd_hip_ctx* ctx) {
 
 namespace {
 
-// the three rolling LoG volumes and the temporary of the two-launch DoG
-int blob_volumes(visfd_hip_ctx* ctx, i64 n, float* vol[3], float** tmp) {
+// the three rolling LoG volumes (a LoG takes no temporary: its second Gaussian subtracts in place as it stores)
+int blob_volumes(visfd_hip_ctx* ctx, i64 n, float* vol[3]) {
   VH_TRY(ws(ctx, WS_LOG0, (size_t)n, &vol[0]));
   VH_TRY(ws(ctx, WS_LOG1, (size_t)n, &vol[1]));
-  VH_TRY(ws(ctx, WS_LOG2, (size_t)n, &vol[2]));
-  return ws(ctx, WS_C, (size_t)n, tmp);
+  return ws(ctx, WS_LOG2, (size_t)n, &vol[2]);
 }
 
 int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz,
@@ -112,8 +111,8 @@ int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 
   *job_out = nullptr;
   const i64 n = nx * ny * nz;
   const float inf = std::numeric_limits<float>::infinity();
-  float *vol[3], *tmp = nullptr;
-  VH_TRY(blob_volumes(ctx, n, vol, &tmp));
+  float* vol[3];
+  VH_TRY(blob_volumes(ctx, n, vol));
   std::unique_ptr<BlobJob> J(new BlobJob(ctx));
   J->src = src; J->mask = mask; J->nx = nx; J->ny = ny; J->nz = nz;
   J->sigma.assign(blob_sigma, blob_sigma + n_sigma);
@@ -135,7 +134,7 @@ int blob_dog_begin(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 
   J->smax.resize((size_t)std::max(n_sigma, 1));
   for (int ir = 0; ir < n_sigma; ir++) {
     const float sg[3] = {blob_sigma[ir] * J->asp[0], blob_sigma[ir] * J->asp[1], blob_sigma[ir] * J->asp[2]};
-    VH_TRY(log_dev(ctx, src, vol[ir % 3], tmp, mask, nx, ny, nz, sg, delta, ratio, nullptr, nullptr));
+    VH_TRY(log_dev(ctx, src, vol[ir % 3], mask, nx, ny, nz, sg, delta, ratio, nullptr, nullptr));
     if (ir < 2 || !J->can_scan) continue;
     VH_TRY(blob_scan_launch(ctx, J.get(), (ir - 1) % BlobJob::NSET, J->ev[(ir - 1) % BlobJob::NSET], vol[(ir - 2) % 3], vol[(ir - 1) % 3],
                             vol[ir % 3], mask, nx, ny, nz, J->scan_min, J->scan_max, &J->pend[(ir - 1) % BlobJob::NSET]));
@@ -168,13 +167,13 @@ int blob_dog_end(BlobJob* job, visfd_hip_blob* minima, int64_t min_cap, int64_t*
     // (the three LoG volumes of the scale are filtered again; the other scales keep their lists)
     if (!J->redo.empty()) {
       const i64 n = J->nx * J->ny * J->nz;
-      float *vol[3], *tmp = nullptr;
-      VH_TRY(blob_volumes(ctx, n, vol, &tmp));
+      float* vol[3];
+      VH_TRY(blob_volumes(ctx, n, vol));
       for (int sc : J->redo) {
         for (int k = 0; k < 3; k++) {
           const int ir = sc - 1 + k;
           const float sg[3] = {J->sigma[(size_t)ir] * J->asp[0], J->sigma[(size_t)ir] * J->asp[1], J->sigma[(size_t)ir] * J->asp[2]};
-          VH_TRY(log_dev(ctx, J->src, vol[k], tmp, J->mask, J->nx, J->ny, J->nz, sg, J->delta, J->ratio, nullptr, nullptr));
+          VH_TRY(log_dev(ctx, J->src, vol[k], J->mask, J->nx, J->ny, J->nz, sg, J->delta, J->ratio, nullptr, nullptr));
         }
         J->smin[(size_t)sc].clear();
         J->smax[(size_t)sc].clear();

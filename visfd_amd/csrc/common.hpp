@@ -73,7 +73,7 @@ struct BlobJob;   // blob_job.hip: one visfd_hip_blob_dog_begin_dev that has not
 // changed afterwards only through visfd_hip_set_option -- no getenv on any hot path.
 struct visfd_hip_options {
   int gauss_3pass = 0;      // 1: the separable filter always takes its three single-axis passes
-  int gauss_cfg = 0;        // development builds: alternative tilings of the single-sweep filter
+  int gauss_cfg = 0;        // development aid, kept for set/get: currently selects nothing
   int gauss_wg_per_cu = 2;  // workgroups per CU the single-sweep filter cuts the volume into
   int tv_dense = 0;         // 1: tensor voting by the baseline kernel (csrc/tv.hip)
   int tv_fma = 0;           // 1: TOLERANCE MODE of tensor voting: fused multiply-adds, results within 1e-5 of the field's scale
@@ -154,33 +154,46 @@ float host_gengauss3d_peak(const float width[3], float m_exp, float ratio);
 i64 host_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, i64 cap);
 
 // ---- device stages (each in its own .hip; all asynchronous on ctx->stream) -------------------
-struct SlabInfo {   // Z-slab placement for multi-GPU runs; whole volume: z_lo=0, nz_global=nz
-  i64 z_lo;
-  i64 nz_global;
+// The optional tail of a Gaussian call.  With a minuend, dst receives (minuend - G(src)) * log_scale -- the DoG/LoG
+// epilogue, applied on every route by the launch that writes dst, which may be the minuend itself.
+struct GaussOpts {
+  float* A_out = nullptr;          // the filter's peak weight (filter3d.hpp:1044-1046)
+  const float* minuend = nullptr;
+  float log_scale = 1.0f;
+  bool fma = false;                // tolerance mode (option gauss_fma) for callers whose output is a float field; ignored with a minuend
+  i64 z_lo = 0, nz_global = 0;     // Z-slab placement of a multi-GPU run: the arrays hold planes [z_lo, z_lo + nz) of nz_global; 0: the whole volume
+};
+int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+                    const float* tx, int hx, const float* ty, int hy, const float* tz, int hz, bool normalize,
+                    const GaussOpts& o = {});
+
+// What a Gaussian launch carries below the tap-building level: gauss.hip fills one per call and routes it to the three
+// single-axis passes or, through the one entry point per compiled half-width, to the single sweep (gauss_fused.hip).
+struct GaussRequest {
+  const float* src;
+  float* dst;
+  i64 nx, ny, nz;
+  Taps tx, ty, tz;
+  const float *Dx, *Dy, *Dz;   // boundary normaliser lines (null without the box normaliser); Dz is indexed by iz + dz_offset
+  i64 dz_offset;
+  bool normalize;              // divide by (Dx*Dy)*Dz
+  bool zpass;                  // single sweep: false runs the Y and X passes only (tz is then not looked at)
+  const float* minuend;        // DoG/LoG epilogue, see GaussOpts
+  float log_scale;
+  bool fma;
+  const float* numer;          // Y/X sweep of a mask denominator: dst = numer / result where result > 0, numer elsewhere
 };
 
-int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx,
-                    i64 ny, i64 nz, const float* tx, int hx, const float* ty, int hy,
-                    const float* tz, int hz, bool normalize, SlabInfo slab, float* A_out,
-                    // optional DoG/LoG epilogue: dst = (minuend - G(src)) * log_scale, fused into the
-                    // single-sweep kernel when it applies (*epilogue_done tells whether it was)
-                    const float* minuend = nullptr, float log_scale = 1.0f, bool* epilogue_done = nullptr,
-                    // tolerance mode (option gauss_fma) for callers whose output is a float field; never with a minuend
-                    bool fma = false);
-// dst = (a - b) * scale  with two roundings (filter3d.hpp:1387-1390,1495-1498); scale==1: no multiply
-int dev_sub_scale(visfd_hip_ctx* ctx, float* a_inout, const float* b, i64 n, float scale, bool do_scale);
-
-// api.hip: the Gaussian from sigmas and half-widths (the trailing arguments are dev_separable3d's), and ApplyLog
+// api.hip: the Gaussian from sigmas and half-widths, and ApplyLog
 int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
-              const float sigma[3], const int hw[3], bool normalize, SlabInfo slab, float* A_out,
-              const float* minuend = nullptr, float log_scale = 1.0f, bool* epilogue_done = nullptr, bool fma = false);
+              const float sigma[3], const int hw[3], bool normalize, const GaussOpts& o = {});
 struct LogPlan {
   float sa[3], sb[3], scale;
   int hw[3];
 };
 LogPlan plan_log(const float sigma[3], float delta, float ratio);
-int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, float* tmp, const float* mask, i64 nx, i64 ny,
-            i64 nz, const float sigma[3], float delta, float ratio, float* A, float* B);
+int log_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+            const float sigma[3], float delta, float ratio, float* A, float* B);
 // LocalFluctuations element-wise steps (filter3d.hpp:1776-1790 and :1819-1846)
 int dev_sub_square(visfd_hip_ctx* ctx, const float* a, const float* b, float* out, i64 n);   // out = (a-b)*(a-b)
 int dev_scale_clamp_sqrt(visfd_hip_ctx* ctx, float* a_inout, i64 n, float scale);           // a = sqrt(max(a*scale, 0))

@@ -1,5 +1,7 @@
-// gauss.hip -- separable 3-D filter (reference lib/visfd/filter3d.hpp:686-1050, ApplySeparable)
-// and the DoG/LoG element-wise epilogue, for gfx950.
+// gauss.hip -- separable 3-D filter (reference lib/visfd/filter3d.hpp:686-1050, ApplySeparable) for gfx950: the three
+// single-axis passes, the routing between them and the single sweep (gauss_fused.hip), and the LocalFluctuations
+// element-wise kernels.  The DoG/LoG epilogue dst = (minuend - G(src)) * scale has no kernel of its own: on every route
+// the launch that writes dst applies it as it stores.
 //
 // Arithmetic contract, kept by every kernel in this file:
 //   * pass order Z -> Y -> X, each pass rounded to float before the next;
@@ -233,17 +235,6 @@ conv_row_kernel(const float* __restrict__ in, float* __restrict__ out, const flo
   }
 }
 
-__global__ void __launch_bounds__(BLOCK)
-sub_scale_kernel(float* __restrict__ a, const float* __restrict__ b, i64 n, float scale, int do_scale) {
-  i64 i = (i64)blockIdx.x * BLOCK + threadIdx.x;
-  const i64 step = (i64)gridDim.x * BLOCK;
-  for (; i < n; i += step) {
-    float d = a[i] - b[i];
-    if (do_scale) d = d * scale;
-    a[i] = d;
-  }
-}
-
 // LocalFluctuations, filter3d.hpp:1776-1790: P = source - average; P *= P (two roundings)
 __global__ void __launch_bounds__(BLOCK)
 sub_square_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, i64 n) {
@@ -352,120 +343,76 @@ int launch_row(visfd_hip_ctx* ctx, const float* in, float* out, const float* den
 
 }  // namespace
 
-// One translation unit per window half-width (gauss_fused.hip compiled with -DVH_FUSED_H=h).
-#define VH_DECL_FUSED(HH)                                                                          \
-  int launch_gauss_fused_h##HH(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny,   \
-                               i64 nz, const Taps& tx, const Taps& ty, const Taps& tz,            \
-                               const float* Dx, const float* Dy, const float* Dz, i64 dz_offset,  \
-                               bool normalize, int cfg, const float* minuend, float log_scale, bool fma);
-VH_DECL_FUSED(1) VH_DECL_FUSED(2) VH_DECL_FUSED(3) VH_DECL_FUSED(4) VH_DECL_FUSED(5)
-VH_DECL_FUSED(6) VH_DECL_FUSED(7) VH_DECL_FUSED(8)
-#undef VH_DECL_FUSED
-#define VH_DECL_FUSED_YX(HH)                                                                       \
-  int launch_gauss_fused_yx_h##HH(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny, \
-                                  i64 nz, const Taps& tx, const Taps& ty, const float* numer,       \
-                                  const float* minuend, float log_scale);
-VH_DECL_FUSED_YX(1) VH_DECL_FUSED_YX(2) VH_DECL_FUSED_YX(3) VH_DECL_FUSED_YX(4) VH_DECL_FUSED_YX(5)
-VH_DECL_FUSED_YX(6) VH_DECL_FUSED_YX(7) VH_DECL_FUSED_YX(8)
-#undef VH_DECL_FUSED_YX
+// gauss_fused.hip, compiled once per window half-width (-DVH_FUSED_H=h): the single-sweep kernel for the request's H
+typedef int FusedLaunch(visfd_hip_ctx* ctx, const GaussRequest& rq);
+FusedLaunch launch_gauss_fused_h1, launch_gauss_fused_h2, launch_gauss_fused_h3, launch_gauss_fused_h4, launch_gauss_fused_h5,
+    launch_gauss_fused_h6, launch_gauss_fused_h7, launch_gauss_fused_h8;
+static FusedLaunch* const fused_launch[9] = {nullptr, launch_gauss_fused_h1, launch_gauss_fused_h2, launch_gauss_fused_h3,
+                                             launch_gauss_fused_h4, launch_gauss_fused_h5, launch_gauss_fused_h6,
+                                             launch_gauss_fused_h7, launch_gauss_fused_h8};
 
-// The single-sweep kernel covers the unmasked case with equal half-widths 1..8 on the three axes (any sigma
-// per axis) and planes below 2 GiB; everything else takes the 3-pass path.  (Beyond h = 8
-// the register ring no longer fits 128 VGPRs: the spilling single-sweep kernels ran at 10 and 16 ms for
-// h = 9 and 10 at 1024^3, three bandwidth-bound passes take 5.3 ms.)
-static int dev_gauss_fused(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny, i64 nz,
-                           const Taps& tx, const Taps& ty, const Taps& tz, const float* Dx,
-                           const float* Dy, const float* Dz, i64 dz_offset, bool normalize,
-                           const float* minuend, float log_scale, bool fma, bool* handled) {
-  *handled = false;
-  const int H = tx.h;
-  if (ty.h != H || tz.h != H || H < 1 || H > 8) return VISFD_HIP_OK;
-  if (nx * ny >= (1LL << 29) || nz >= (1LL << 31)) return VISFD_HIP_OK;
-  if (src == dst) return VISFD_HIP_OK;  // in place: 3-pass path through scratch volumes
-  // the single-sweep kernel's Z pass shares the product of a sample with the taps +j and -j, and all three passes
-  // keep only the taps 0..H (in VGPRs): the taps must be symmetric bit for bit on every axis (every Gaussian is;
-  // arbitrary filters take the 3-pass path)
-  for (int j = 1; j <= H; j++)
-    if (std::memcmp(&tz.t[H + j], &tz.t[H - j], sizeof(float)) != 0 || std::memcmp(&ty.t[H + j], &ty.t[H - j], sizeof(float)) != 0 ||
-        std::memcmp(&tx.t[H + j], &tx.t[H - j], sizeof(float)) != 0)
-      return VISFD_HIP_OK;
-  if (ctx->opt.gauss_3pass) return VISFD_HIP_OK;
-  const int cfg = ctx->opt.gauss_cfg;
-  *handled = true;
-  switch (H) {
-#define VH_CASE(HH) case HH: return launch_gauss_fused_h##HH(ctx, src, dst, nx, ny, nz, tx, ty, tz, Dx, Dy, Dz, dz_offset, normalize, cfg, minuend, log_scale, fma);
-    VH_CASE(1) VH_CASE(2) VH_CASE(3) VH_CASE(4) VH_CASE(5) VH_CASE(6) VH_CASE(7) VH_CASE(8)
-#undef VH_CASE
-  }
-  *handled = false;
-  return VISFD_HIP_OK;
+// Where the single-sweep kernel applies -- to all three passes (rq.zpass) or to the Y and X passes that follow the masked
+// filter's Z pass: equal half-widths 1..8 on the axes it filters (beyond h = 8 the register ring no longer fits 128 VGPRs:
+// the spilling kernels ran at 10 and 16 ms for h = 9 and 10 at 1024^3, three bandwidth-bound passes take 5.3 ms), planes
+// below 2 GiB, not in place (nor onto its numerator), and taps that are symmetric bit for bit: the Z pass shares the product
+// of a sample between the taps +j and -j, and every pass keeps only the taps 0..H in VGPRs (every Gaussian is symmetric;
+// arbitrary filters take the three passes).
+static bool fused_applies(const visfd_hip_ctx* ctx, const GaussRequest& rq) {
+  const int H = rq.tx.h;
+  if (ctx->opt.gauss_3pass || H < 1 || H > 8 || rq.ty.h != H || (rq.zpass && rq.tz.h != H)) return false;
+  if (rq.nx * rq.ny >= (1LL << 29) || rq.nz >= (1LL << 31)) return false;
+  if (rq.src == rq.dst || rq.numer == rq.dst) return false;
+  const Taps* const axis[3] = {&rq.tx, &rq.ty, &rq.tz};
+  for (int a = 0; a < (rq.zpass ? 3 : 2); a++)
+    for (int j = 1; j <= H; j++)
+      if (std::memcmp(&axis[a]->t[H + j], &axis[a]->t[H - j], sizeof(float)) != 0) return false;
+  return true;
 }
 
-// Y and X passes in one sweep (the masked filter after its Z pass): equal half-widths 1..8 in x and y, planes
-// below 2 GiB; numer != null selects the masked-normalisation epilogue.
-static int dev_gauss_fused_yx(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny, i64 nz, const Taps& tx,
-                              const Taps& ty, const float* numer, const float* minuend, float log_scale,
-                              bool* handled) {
-  *handled = false;
-  const int H = tx.h;
-  if (ty.h != H || H < 1 || H > 8) return VISFD_HIP_OK;
-  if (nx * ny >= (1LL << 29) || nz >= (1LL << 31)) return VISFD_HIP_OK;
-  if (src == dst || numer == dst) return VISFD_HIP_OK;
-  for (int j = 1; j <= H; j++)   // the kernel keeps the taps 0..H only
-    if (std::memcmp(&ty.t[H + j], &ty.t[H - j], sizeof(float)) != 0 || std::memcmp(&tx.t[H + j], &tx.t[H - j], sizeof(float)) != 0)
-      return VISFD_HIP_OK;
-  if (ctx->opt.gauss_3pass) return VISFD_HIP_OK;
-  *handled = true;
-  switch (H) {
-#define VH_CASE(HH) case HH: return launch_gauss_fused_yx_h##HH(ctx, src, dst, nx, ny, nz, tx, ty, numer, minuend, log_scale);
-    VH_CASE(1) VH_CASE(2) VH_CASE(3) VH_CASE(4) VH_CASE(5) VH_CASE(6) VH_CASE(7) VH_CASE(8)
-#undef VH_CASE
-  }
-  *handled = false;
-  return VISFD_HIP_OK;
+// A route returns VISFD_HIP_OK, an error, or GAUSS_DECLINED: nothing launched, the caller takes the three passes.
+constexpr int GAUSS_DECLINED = -1;
+static int gauss_fused_route(visfd_hip_ctx* ctx, const GaussRequest& rq) {
+  return fused_applies(ctx, rq) ? fused_launch[rq.tx.h](ctx, rq) : GAUSS_DECLINED;
 }
 
-int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx,
-                    i64 ny, i64 nz, const float* tx, int hx, const float* ty, int hy,
-                    const float* tz, int hz, bool normalize, SlabInfo slab, float* A_out,
-                    const float* minuend, float log_scale, bool* epilogue_done, bool fma) {
-  if (epilogue_done) *epilogue_done = false;
+// With a minuend, dst receives (minuend - G(src)) * log_scale on every route -- the single sweep and the last launch of
+// each three-pass branch store it themselves -- and dst may be the minuend: the intermediate volumes are workspace slots.
+int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+                    const float* tx, int hx, const float* ty, int hy, const float* tz, int hz, bool normalize,
+                    const GaussOpts& o) {
   VH_TRY(check_dims(nx, ny, nz));
-  Taps Tx, Ty, Tz;
-  VH_TRY(fill_taps(&Tx, tx, hx));
-  VH_TRY(fill_taps(&Ty, ty, hy));
-  VH_TRY(fill_taps(&Tz, tz, hz));
-  if (A_out) *A_out = (tx[hx] * ty[hy]) * tz[hz];  // filter3d.hpp:1044-1046
+  GaussRequest rq = {};
+  rq.src = src; rq.dst = dst; rq.nx = nx; rq.ny = ny; rq.nz = nz;
+  VH_TRY(fill_taps(&rq.tx, tx, hx));
+  VH_TRY(fill_taps(&rq.ty, ty, hy));
+  VH_TRY(fill_taps(&rq.tz, tz, hz));
+  if (o.A_out) *o.A_out = (tx[hx] * ty[hy]) * tz[hz];  // filter3d.hpp:1044-1046
+  rq.dz_offset = o.z_lo;
+  rq.normalize = normalize; rq.zpass = true;
+  rq.minuend = o.minuend; rq.log_scale = o.log_scale;
+  rq.fma = o.fma && !o.minuend;
+  const Taps &Tx = rq.tx, &Ty = rq.ty, &Tz = rq.tz;
+  const float* const minuend = o.minuend;
+  const float log_scale = o.log_scale;
   const i64 n = nx * ny * nz;
-  hipStream_t st = ctx->stream;
 
-  // boundary normaliser lines (unmasked case): host arithmetic, a few KB
-  float *Dx = nullptr, *Dy = nullptr, *Dz = nullptr;
+  // boundary normaliser lines (unmasked case)
   if (normalize && !mask) {
     // filled on the device (same float sums as host_conv_ones): no host copy, no stream synchronisation --
     // a dozen Gaussians in a row (blob detection) stay queued back to back
     float* D = nullptr;
-    const i64 total = nx + ny + slab.nz_global;
+    const i64 nz_global = o.nz_global ? o.nz_global : nz;
+    const i64 total = nx + ny + nz_global;
     VH_TRY(ws(ctx, WS_NORM, (size_t)total, &D));
-    norm_lines_kernel<<<dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st>>>(D, nx, ny, slab.nz_global,
-                                                                                            Tx, Ty, Tz);
+    norm_lines_kernel<<<dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(D, nx, ny, nz_global, Tx, Ty, Tz);
     VH_HIP(hipGetLastError());
-    Dx = D; Dy = D + nx; Dz = D + nx + ny;
+    rq.Dx = D; rq.Dy = D + nx; rq.Dz = D + nx + ny;
   }
 
   if (!mask) {
-    bool handled = false;
-    VH_TRY(dev_gauss_fused(ctx, src, dst, nx, ny, nz, Tx, Ty, Tz, Dx, Dy, Dz, slab.z_lo, normalize,
-                           minuend, log_scale, fma && !minuend, &handled));
-    if (handled) {
-      if (epilogue_done) *epilogue_done = (minuend != nullptr);
-      return VISFD_HIP_OK;
-    }
+    const int rc = gauss_fused_route(ctx, rq);
+    if (rc != GAUSS_DECLINED) return rc;
   }
-  // the DoG/LoG epilogue is also folded into the X pass of the three-pass route (the intermediate volumes are
-  // workspace slots, so dst may alias the minuend here as well)
-  if (minuend && !epilogue_done) return fail(VISFD_HIP_EINVAL, "internal: epilogue request without a result flag");
-  if (minuend) *epilogue_done = true;
 
   float *A = nullptr, *B = nullptr;
   VH_TRY(ws(ctx, WS_A, (size_t)n, &A));
@@ -474,45 +421,37 @@ int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
   if (!mask) {
     VH_TRY(launch_march<false>(ctx, 2, src, A, nullptr, nullptr, Tz, nx, ny, nz));
     VH_TRY(launch_march<false>(ctx, 1, A, B, nullptr, nullptr, Ty, nx, ny, nz));
-    if (normalize) VH_TRY(launch_row<NORM_BOX>(ctx, B, dst, nullptr, Dx, Dy, Dz, slab.z_lo, Tx, nx, ny, nz, minuend, log_scale));
-    else VH_TRY(launch_row<NORM_NONE>(ctx, B, dst, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale));
-  } else if (!normalize) {
-    // masked: the Z pass applies the mask (one bandwidth-bound kernel); Y and X then run as one sweep where the
-    // single-sweep kernel applies (36 instead of 52 bytes per voxel for the normalised filter)
-    VH_TRY(launch_march<true>(ctx, 2, src, A, mask, nullptr, Tz, nx, ny, nz));
-    bool yx = false;
-    VH_TRY(dev_gauss_fused_yx(ctx, A, dst, nx, ny, nz, Tx, Ty, nullptr, minuend, log_scale, &yx));
-    if (!yx) {
-      VH_TRY(launch_march<false>(ctx, 1, A, B, nullptr, nullptr, Ty, nx, ny, nz));
-      VH_TRY(launch_row<NORM_NONE>(ctx, B, dst, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale));
-    }
-  } else {
-    float *DA = nullptr, *DB = nullptr;
-    VH_TRY(ws(ctx, WS_DEN_A, (size_t)n, &DA));
-    VH_TRY(ws(ctx, WS_DEN_B, (size_t)n, &DB));
-    VH_TRY(launch_march<true>(ctx, 2, src, A, mask, DA, Tz, nx, ny, nz));
-    bool yx = false;
-    VH_TRY(dev_gauss_fused_yx(ctx, A, B, nx, ny, nz, Tx, Ty, nullptr, nullptr, 1.0f, &yx));       // numerator
-    if (yx) {
-      // denominator through Y and X, divided into the numerator (and the DoG/LoG epilogue) as it is stored
-      VH_TRY(dev_gauss_fused_yx(ctx, DA, dst, nx, ny, nz, Tx, Ty, B, minuend, log_scale, &yx));
-      if (!yx) return fail(VISFD_HIP_EDEVICE, "internal: single-sweep Y/X pass refused its second call");
-    } else {
-      VH_TRY(launch_march<false>(ctx, 1, A, B, nullptr, nullptr, Ty, nx, ny, nz));
-      VH_TRY(launch_march<false>(ctx, 1, DA, DB, nullptr, nullptr, Ty, nx, ny, nz));
-      VH_TRY(launch_row<NORM_NONE>(ctx, DB, DA, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz));
-      VH_TRY(launch_row<NORM_DEN>(ctx, B, dst, DA, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale));
-    }
+    if (normalize) return launch_row<NORM_BOX>(ctx, B, dst, nullptr, rq.Dx, rq.Dy, rq.Dz, rq.dz_offset, Tx, nx, ny, nz, minuend, log_scale);
+    return launch_row<NORM_NONE>(ctx, B, dst, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale);
   }
-  VH_HIP(hipGetLastError());
-  return VISFD_HIP_OK;
-}
-
-int dev_sub_scale(visfd_hip_ctx* ctx, float* a, const float* b, i64 n, float scale, bool do_scale) {
-  const unsigned g = grid_for(n, BLOCK, (i64)ctx->num_cus * 16);
-  sub_scale_kernel<<<dim3(g), dim3(BLOCK), 0, ctx->stream>>>(a, b, n, scale, do_scale ? 1 : 0);
-  VH_HIP(hipGetLastError());
-  return VISFD_HIP_OK;
+  // masked: the Z pass applies the mask (one bandwidth-bound kernel); Y and X then run as one sweep where the single-sweep
+  // kernel applies (36 instead of 52 bytes per voxel for the normalised filter).  yx: the launch that writes dst
+  GaussRequest yx = rq;
+  yx.src = A; yx.zpass = false; yx.normalize = false; yx.fma = false;
+  if (!normalize) {
+    VH_TRY(launch_march<true>(ctx, 2, src, A, mask, nullptr, Tz, nx, ny, nz));
+    const int rc = gauss_fused_route(ctx, yx);
+    if (rc != GAUSS_DECLINED) return rc;
+    VH_TRY(launch_march<false>(ctx, 1, A, B, nullptr, nullptr, Ty, nx, ny, nz));
+    return launch_row<NORM_NONE>(ctx, B, dst, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale);
+  }
+  float *DA = nullptr, *DB = nullptr;
+  VH_TRY(ws(ctx, WS_DEN_A, (size_t)n, &DA));
+  VH_TRY(ws(ctx, WS_DEN_B, (size_t)n, &DB));
+  VH_TRY(launch_march<true>(ctx, 2, src, A, mask, DA, Tz, nx, ny, nz));
+  // the denominator through Y and X, divided into the numerator B (and the DoG/LoG epilogue) as it is stored.  Decided
+  // once, on this launch: the numerator's differs only in workspace pointers
+  yx.src = DA; yx.numer = B;
+  if (fused_applies(ctx, yx)) {
+    GaussRequest num = yx;   // A through Y and X into B, no epilogue of either kind
+    num.src = A; num.dst = B; num.numer = nullptr; num.minuend = nullptr; num.log_scale = 1.0f;
+    VH_TRY(fused_launch[Tx.h](ctx, num));
+    return fused_launch[Tx.h](ctx, yx);
+  }
+  VH_TRY(launch_march<false>(ctx, 1, A, B, nullptr, nullptr, Ty, nx, ny, nz));
+  VH_TRY(launch_march<false>(ctx, 1, DA, DB, nullptr, nullptr, Ty, nx, ny, nz));
+  VH_TRY(launch_row<NORM_NONE>(ctx, DB, DA, nullptr, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz));
+  return launch_row<NORM_DEN>(ctx, B, dst, DA, nullptr, nullptr, nullptr, 0, Tx, nx, ny, nz, minuend, log_scale);
 }
 
 int dev_sub_square(visfd_hip_ctx* ctx, const float* a, const float* b, float* out, i64 n) {

@@ -698,11 +698,10 @@ gauss_fused_kernel(const float* __restrict__ src, float* __restrict__ dst, TapsH
 #endif
 }
 
-template <int H, int TX, int TY, int NT, int XV = 4, int YV = 2>
-int launch_cfg(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny, i64 nz,
-               const Taps& tx, const Taps& ty, const Taps& tz, const float* Dx, const float* Dy,
-               const float* Dz, i64 dz_offset, bool normalize, const float* minuend, float log_scale,
-               bool zpass = true, const float* numer = nullptr, bool fma = false) {
+template <int H, int TX, int TY, int NT, int XV, int YV>
+int launch_cfg(visfd_hip_ctx* ctx, const GaussRequest& rq) {
+  const i64 nx = rq.nx, ny = rq.ny, nz = rq.nz;
+  const Taps &tx = rq.tx, &ty = rq.ty, &tz = rq.zpass ? rq.tz : rq.ty;   // (no Z pass: the kernel does not read its Z taps)
   TapsH<H> a, b, c;
   bool iso = true;
   for (int k = 0; k < 2 * H + 1; k++) {
@@ -731,13 +730,13 @@ int launch_cfg(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny,
   dim3 grid((unsigned)nblk), block(NT);
 #define VH_GO(NORM, ISOV, RAG, ZP, DEN, ...)                                                     \
   gauss_fused_kernel<H, TX, TY, NT, XV, YV, NORM, ISOV, RAG, ZP, DEN, ##__VA_ARGS__><<<grid, block, 0, ctx->stream>>>(  \
-      src, dst, a, b, c, Dx, Dy, Dz, dz_offset, (int)nx, (int)ny, (int)nz, (int)zchunk, tiles_x, tiles_y,  \
-      minuend, log_scale, dz_int, numer)
+      rq.src, rq.dst, a, b, c, rq.Dx, rq.Dy, rq.Dz, rq.dz_offset, (int)nx, (int)ny, (int)nz, (int)zchunk, tiles_x,   \
+      tiles_y, rq.minuend, rq.log_scale, dz_int, rq.numer)
   // anisotropic taps share the ragged-row instantiation (both are the uncommon cases)
   const bool ragged = (nx % XV) != 0;
-  if (!zpass) { if (numer) VH_GO(false, false, true, false, true); else VH_GO(false, false, true, false, false); }
-  else if (normalize && iso && !ragged && fma && !minuend) VH_GO(true, true, false, true, false, true);   // tolerance mode
-  else if (normalize) { if (iso && !ragged) VH_GO(true, true, false, true, false); else VH_GO(true, false, true, true, false); }
+  if (!rq.zpass) { if (rq.numer) VH_GO(false, false, true, false, true); else VH_GO(false, false, true, false, false); }
+  else if (rq.normalize && iso && !ragged && rq.fma && !rq.minuend) VH_GO(true, true, false, true, false, true);   // tolerance mode
+  else if (rq.normalize) { if (iso && !ragged) VH_GO(true, true, false, true, false); else VH_GO(true, false, true, true, false); }
   else                { if (iso && !ragged) VH_GO(false, true, false, true, false); else VH_GO(false, false, true, true, false); }
 #undef VH_GO
   VH_HIP(hipGetLastError());
@@ -760,38 +759,18 @@ int launch_cfg(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny,
 #define VH_CAT2(a, b) a##b
 #define VH_CAT(a, b) VH_CAT2(a, b)
 
-// One entry point per compiled half-width: launch_gauss_fused_h<H>(..., cfg)
-int VH_CAT(launch_gauss_fused_h, VH_FUSED_H)(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx,
-                                            i64 ny, i64 nz, const Taps& tx, const Taps& ty,
-                                            const Taps& tz, const float* Dx, const float* Dy,
-                                            const float* Dz, i64 dz_offset, bool normalize, int cfg,
-                                            const float* minuend, float log_scale, bool fma) {
+// The one entry point of a compiled half-width (gauss.hip holds the table of the eight).  rq.zpass == false: the Y and X
+// passes alone (no box normaliser), with the masked-normalisation epilogue out = rq.numer / result where result > 0 (numer
+// elsewhere) if there is a numerator, and the DoG/LoG epilogue after it.
+int VH_CAT(launch_gauss_fused_h, VH_FUSED_H)(visfd_hip_ctx* ctx, const GaussRequest& rq) {
   constexpr int H = VH_FUSED_H;
-  (void)cfg;
   // tilings picked from sweeps on MI355X (1024^3; profiles/r01_gauss_tiling_sweep.txt): wide tiles cut the
   // halo recomputation of the Z and Y passes (the kernel is VALU-bound), until the register ring
   // (columns per thread x (2H+1)) no longer fits 128 VGPRs; with the 64-wide tile the X pass needs two
   // outputs per lane to fill its wave, and single-column Y tasks pack the rounds better
-  if constexpr (H <= 3)
-    return launch_cfg<H, 128, 16, 512, 4, 2>(ctx, src, dst, nx, ny, nz, tx, ty, tz, Dx, Dy, Dz, dz_offset, normalize, minuend, log_scale, true, nullptr, fma);
-  else if constexpr (H <= 5)
-    return launch_cfg<H, 128, 32, 1024, 4, 2>(ctx, src, dst, nx, ny, nz, tx, ty, tz, Dx, Dy, Dz, dz_offset, normalize, minuend, log_scale, true, nullptr, fma);
-  else
-    return launch_cfg<H, 64, 32, 1024, 2, 1>(ctx, src, dst, nx, ny, nz, tx, ty, tz, Dx, Dy, Dz, dz_offset, normalize, minuend, log_scale, true, nullptr, fma);
-}
-
-// The Y and X passes alone (no Z pass, no box normaliser), optionally with the masked-normalisation epilogue
-// out = numer / result where result > 0 (numer elsewhere) and the DoG/LoG epilogue after it.
-int VH_CAT(launch_gauss_fused_yx_h, VH_FUSED_H)(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny,
-                                               i64 nz, const Taps& tx, const Taps& ty, const float* numer,
-                                               const float* minuend, float log_scale) {
-  constexpr int H = VH_FUSED_H;
-  if constexpr (H <= 3)
-    return launch_cfg<H, 128, 16, 512, 4, 2>(ctx, src, dst, nx, ny, nz, tx, ty, ty, nullptr, nullptr, nullptr, 0, false, minuend, log_scale, false, numer);
-  else if constexpr (H <= 5)
-    return launch_cfg<H, 128, 32, 1024, 4, 2>(ctx, src, dst, nx, ny, nz, tx, ty, ty, nullptr, nullptr, nullptr, 0, false, minuend, log_scale, false, numer);
-  else
-    return launch_cfg<H, 64, 32, 1024, 2, 1>(ctx, src, dst, nx, ny, nz, tx, ty, ty, nullptr, nullptr, nullptr, 0, false, minuend, log_scale, false, numer);
+  if constexpr (H <= 3) return launch_cfg<H, 128, 16, 512, 4, 2>(ctx, rq);
+  else if constexpr (H <= 5) return launch_cfg<H, 128, 32, 1024, 4, 2>(ctx, rq);
+  else return launch_cfg<H, 64, 32, 1024, 2, 1>(ctx, rq);
 }
 
 }  // namespace vh
