@@ -64,7 +64,10 @@ const char* visfd_hip_last_error(void);
 int visfd_hip_abi_version(void);   /* 10: entry points only get added between versions (since 10 was set: the
                                      * morphology entries visfd_hip_sphere_structure, visfd_hip_morph_sphere[_dev],
                                      * visfd_hip_morph_table[_dev] and visfd_hip_morph_last_path; then
-                                     * visfd_hip_blob_jobs_pending and visfd_hip_debug_poison_workspace) */
+                                     * visfd_hip_blob_jobs_pending and visfd_hip_debug_poison_workspace; then the
+                                     * general 3-D filter: visfd_hip_gengauss3d_halfwidths, _gengauss3d_table,
+                                     * _dogg3d_table, _filter3d[_dev], _filter3d_last_path, _apply_ggauss[_dev],
+                                     * _apply_dogg[_dev] and _local_fluctuations_gen[_dev]) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -92,13 +95,15 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *   blob_test_cap    tests: capacity the pipelined blob scan pretends to have (exercises its overflow path)
  *   morph_general    1: morphology always walks the element entry by entry (csrc/morph.hip), never takes the flat X-run
  *                    kernel; results are bit-identical either way
+ *   filter3d_general 1: the general 3-D filter always walks the table entry by entry (csrc/filter3d.hip), never takes the
+ *                    LDS-tiled kernel; results are bit-identical either way
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
 /* bytes of device workspace currently held by the context */
 int64_t visfd_hip_workspace_bytes(visfd_hip_ctx* ctx);
 /* TEST AID: waits for the context's stream, then fills every workspace slot the context holds with 0xFF bytes (NaN as
- * floats, huge as counters) and forgets what it had cached inside them (vote table, structuring element), without freeing
+ * floats, huge as counters) and forgets what it had cached inside them (vote table, structuring element, filter table), without freeing
  * anything.  No stage may depend on what a slot held before the call that uses it, so every result after this call is the
  * same as before it.  What live blob jobs have queued is fetched to the host first, as visfd_hip_trim does. */
 int visfd_hip_debug_poison_workspace(visfd_hip_ctx* ctx);
@@ -133,7 +138,8 @@ int visfd_hip_gauss_halfwidths(const float sigma[3], float truncate_ratio, int h
 /* ---- f4: LocalFluctuations (lib/visfd/filter3d.hpp:1698-1853) ---------------------------------- */
 /* dst = sqrt(max(A * G((src - G(src))^2), 0)), G = ApplyGauss(sigma[3], truncate_ratio) with the same mask and
  * normalize flag, A = the central value of GenFilterGenGauss3D(sigma, exponent, truncate_ratio)
- * (filter3d.hpp:546-640, :1725, :1836).  Only exponent == 2 (the separable case) is provided; src != dst. */
+ * (filter3d.hpp:546-640, :1725, :1836).  Only exponent == 2 (the separable case) is provided here; src != dst.
+ * visfd_hip_local_fluctuations_gen (below) takes any exponent. */
 int visfd_hip_local_fluctuations(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
                                  int64_t nx, int64_t ny, int64_t nz, const float sigma[3], float exponent,
                                  float truncate_ratio, int normalize);
@@ -144,6 +150,70 @@ int visfd_hip_local_fluctuations_dev(visfd_hip_ctx*, const float* src, float* ds
  * sigma = radius / (9 pi / 2)^(1/6); a negative truncate_ratio is replaced by (-log threshold)^(1/exponent). */
 int visfd_hip_fluctuation_sigmas(const float radius[3], float exponent, float truncate_ratio,
                                  float truncate_threshold, float sigma_out[3], float* ratio_out);
+
+/* ---- g1-g5: the general (non-separable) 3-D filter, Filter3D::Apply (lib/visfd/filter3d.hpp:37-530) ----------------
+ * Tables are (2 hx + 1)(2 hy + 1)(2 hz + 1) floats, x fastest, entry H[jz][jy][jx] at ((jz + hz) * (2 hy + 1) + jy + hy) *
+ * (2 hx + 1) + jx + hx.  The table makers are host arithmetic and take no context.  They write nothing when cap == 0
+ * (count only), return VISFD_HIP_ECAPACITY when 0 < cap < *n, and always set *n to the entry count. */
+/* halfwidth[d] = floor(width[d] * ratio); a negative ratio is first replaced by pow(-log(threshold), 1.0 / m_exp)
+ * (bin/filter_mrc/filter3d_variants.hpp:99-103, lib/visfd/filter3d.hpp:631-633) */
+int visfd_hip_gengauss3d_halfwidths(const float width[3], float m_exp, float truncate_ratio, float truncate_threshold,
+                                    int halfwidth_out[3]);
+/* GenFilterGenGauss3D(width, m_exp, truncate_halfwidth) (filter3d.hpp:546-601): exp(-r^m), r = sqrt((x/wx)^2 + (y/wy)^2 +
+ * (z/wz)^2), entries below the smallest face value zeroed, divided by their float sum.  A_out (nullable) = centre entry. */
+int visfd_hip_gengauss3d_table(const float width[3], float m_exp, const int halfwidth[3], float* table, int64_t cap,
+                               int64_t* n, float* A_out);
+/* GenFilterDogg3D(width_a, width_b, m, n, ratio, threshold) (filter3d_variants.hpp:284-345, :441-482): each generalised
+ * Gaussian in its own window, the table's window (halfwidth_out) their per-axis maximum, entries A_entry - B_entry.
+ * A_out, B_out (nullable): the two centre values. */
+int visfd_hip_dogg3d_table(const float width_a[3], const float width_b[3], float m_exp, float n_exp, float truncate_ratio,
+                           float truncate_threshold, int halfwidth_out[3], float* table, int64_t cap, int64_t* n,
+                           float* A_out, float* B_out);
+/* Filter3D::Apply (filter3d.hpp:81-198, :403-458): for every voxel i with mask(i) != 0 (or no mask)
+ *   g = sum_j (H[j] * mask(i - j)) * src(i - j),   den = sum_j H[j] * mask(i - j)
+ * over the senders i - j inside the image with mask != 0, j walked with jz outermost, then jy, then jx, each from -h to +h,
+ * in float, multiply then add; dst = g, or g / den where `normalize` and den > 0.  den_out (nullable) receives den: the
+ * reference's second Apply overload.  Bit-identical to the reference for finite src.
+ * DEFINED HERE, undefined in the reference: a voxel with mask == 0 gets dst = 0 and den = 0 also when no denominator was
+ * asked for (the reference dereferences a null pointer there, filter3d.hpp:182).
+ * THE ONE DIVERGENCE: table entries equal to 0 may be dropped and senders with mask == 0 enter as zero factors, so a NaN
+ * or Inf in src under a zero weight or outside the mask need not spread to its neighbours as it does in the reference
+ * (which of the two kernels runs decides; for finite src both give the reference's bits).
+ * A dst that overlaps src or mask is VISFD_HIP_EINVAL; so are negative half-widths.  `table` is a host array on both
+ * faces; it is kept in the context's workspace and sent again only when it changes. */
+int visfd_hip_filter3d(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                       const float* table, const int halfwidth[3], int normalize, float* den_out);
+int visfd_hip_filter3d_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                           int64_t nz, const float* table, const int halfwidth[3], int normalize, float* den_out);
+/* the kernel the context's last general-filter call ran: VISFD_HIP_FILTER3D_PATH_* (-1 before the first call).  The tiled
+ * kernel takes every window whose source and mask patches, 2 * (64 + 2 hx) * (4 + 2 hy) floats, fit 48 KB of LDS; the
+ * option filter3d_general forces the general one. */
+#define VISFD_HIP_FILTER3D_PATH_GENERAL 0    /* filter3d_kernel: the non-zero entries walked one by one, no LDS */
+#define VISFD_HIP_FILTER3D_PATH_TILED 1      /* filter3d_tiled_kernel: source planes staged in LDS, 8 output planes a thread */
+int visfd_hip_filter3d_last_path(visfd_hip_ctx*, int* path);
+/* HandleGGauss (bin/filter_mrc/handlers.cpp:167-187): the generalised Gaussian table above, applied.  A_out nullable. */
+int visfd_hip_apply_ggauss(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                           int64_t nz, const float width[3], float m_exp, const int halfwidth[3], int normalize,
+                           float* A_out);
+int visfd_hip_apply_ggauss_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                               int64_t nz, const float width[3], float m_exp, const int halfwidth[3], int normalize,
+                               float* A_out);
+/* HandleDogg (handlers.cpp:265-293): the difference-of-generalised-Gaussians table above, applied; never normalised. */
+int visfd_hip_apply_dogg(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                         int64_t nz, const float width_a[3], const float width_b[3], float m_exp, float n_exp,
+                         float truncate_ratio, float truncate_threshold, float* A_out, float* B_out);
+int visfd_hip_apply_dogg_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                             int64_t nz, const float width_a[3], const float width_b[3], float m_exp, float n_exp,
+                             float truncate_ratio, float truncate_threshold, float* A_out, float* B_out);
+/* LocalFluctuations for any exponent (filter3d.hpp:1698-1853): with W = the filter of GenFilterGenGauss3D(sigma, exponent,
+ * floor(sigma * truncate_ratio)) times (float)(1.0 / A), A its centre entry: dst = sqrt(max(A * W((src - W(src))^2), 0)),
+ * both W with the same mask and normalize flag.  Exponent 2 takes the separable path of visfd_hip_local_fluctuations. */
+int visfd_hip_local_fluctuations_gen(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx,
+                                     int64_t ny, int64_t nz, const float sigma[3], float exponent, float truncate_ratio,
+                                     int normalize);
+int visfd_hip_local_fluctuations_gen_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx,
+                                         int64_t ny, int64_t nz, const float sigma[3], float exponent,
+                                         float truncate_ratio, int normalize);
 
 /* ---- m1: grayscale morphology (lib/visfd/morphology.hpp:134-597) ------------------------------- */
 #define VISFD_HIP_MORPH_DILATE 0          /* DilateSphere / Dilate                         morphology.hpp:134-172, 241-330 */

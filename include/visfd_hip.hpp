@@ -17,6 +17,7 @@
 //   TV3D         lib/visfd/feature.hpp:1645-1647, TVDenseStick :1711-1901 (with its normalize / diagonalize_dest steps)
 //   BlobDogNM / _BlobDogNM  bin/filter_mrc/feature_variants.hpp:393-580
 //   Alloc3D / Dealloc3D  lib/visfd/alloc3d.hpp:25, :75
+//   Filter3D     lib/visfd/filter3d.hpp:37-530;  GenFilterGenGauss3D :546-638;  LocalFluctuations[ByRadius] :1698-1926
 //   CompactMultiChannelImage3D  lib/visfd/multichannel_image3d.hpp:41-204
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
 #ifndef VISFD_HIP_HPP
@@ -558,7 +559,145 @@ size_t FindMaxima(int const image_size[3], float const* const* const* aaafI, flo
                       connectivity, allow_borders, aaaiDest, pReportProgress);
 }
 
-// ---- LocalFluctuations: lib/visfd/filter3d.hpp:1698-1711 (Gaussian weights: exponent must be 2) -------
+// ---- Filter3D: lib/visfd/filter3d.hpp:37-530 ---------------------------------------------------------------------------
+// The reference's public face: aaafH indexable [jz][jy][jx] from -halfwidth to +halfwidth, halfwidth, array_size, both
+// Apply overloads (on the GPU: visfd_hip_filter3d), the table arithmetic, copy, move and assignment.  What Apply computes,
+// what it defines where the reference has nothing to say (voxels with mask == 0 get 0, with or without a denominator)
+// and its one divergence (a NaN or Inf under a zero weight or outside the mask does not spread) are in visfd_hip.h.
+template <typename Scalar, typename Integer>
+class Filter3D {
+ public:
+  Scalar*** aaafH;
+  Integer halfwidth[3];
+  Integer array_size[3];
+
+  // filter3d.hpp:81-109: g = sum h * f * mask, divided by the sum of the weights considered when `normalize`
+  void Apply(Integer const size_source[3], Scalar const* const* const* aaafSource, Scalar*** aaafDest,
+             Scalar const* const* const* aaafMask = nullptr, bool normalize = false,
+             std::ostream* pReportProgress = nullptr) const {
+    run(size_source, aaafSource, aaafDest, aaafMask, normalize, nullptr, pReportProgress);
+  }
+  // filter3d.hpp:150-198: never normalises; hands back the denominator where aaafDenominator is given
+  void Apply(Integer const size_source[3], Scalar const* const* const* aaafSource, Scalar*** aaafDest,
+             Scalar const* const* const* aaafMask = nullptr, Scalar*** aaafDenominator = nullptr,
+             std::ostream* pReportProgress = nullptr) const {
+    run(size_source, aaafSource, aaafDest, aaafMask, false, aaafDenominator, pReportProgress);
+  }
+
+  void Normalize() {   // filter3d.hpp:202-214
+    Scalar total = 0.0;
+    for (size_t k = 0; k < data_.size(); k++) total += data_[k];
+    for (size_t k = 0; k < data_.size(); k++) data_[k] /= total;
+  }
+  // filter3d.hpp:274-384; aaafW: optional weights, indexed like aaafH
+  Scalar Average(Scalar const* const* const* aaafW = nullptr) const { return wsum(aaafW, 1) / wsum(aaafW, 0); }
+  Scalar AverageSqr(Scalar const* const* const* aaafW = nullptr) const { return wsum(aaafW, 2) / wsum(aaafW, 0); }
+  Scalar StdDev(Scalar const* const* const* aaafW = nullptr) const {
+    return static_cast<Scalar>(std::sqrt(wsum(aaafW, 2, Average(aaafW)) / wsum(aaafW, 0)));
+  }
+  Scalar Sum(Scalar const* const* const* aaafW = nullptr) const { return wsum(aaafW, 1); }
+  Scalar SumSqr(Scalar const* const* const* aaafW = nullptr) const { return wsum(aaafW, 2); }
+  void AddScalar(Scalar offset) { for (size_t k = 0; k < data_.size(); k++) data_[k] += offset; }
+  void MultiplyScalar(Scalar scale) { for (size_t k = 0; k < data_.size(); k++) data_[k] *= scale; }
+
+  Filter3D() { Init(); }
+  Filter3D(Integer const set_halfwidth[3]) { Init(); Resize(set_halfwidth); }
+  virtual ~Filter3D() {}
+  Filter3D(const Filter3D<Scalar, Integer>& source) {
+    Init();
+    if (source.aaafH) {
+      Resize(source.halfwidth);
+      data_ = source.data_;
+    }
+  }
+  void swap(Filter3D<Scalar, Integer>& other) {
+    data_.swap(other.data_);   // the buffers change owners where they lie: the pointers into them stay good
+    rows_.swap(other.rows_);
+    planes_.swap(other.planes_);
+    std::swap(aaafH, other.aaafH);
+    for (int d = 0; d < 3; d++) {
+      std::swap(halfwidth[d], other.halfwidth[d]);
+      std::swap(array_size[d], other.array_size[d]);
+    }
+  }
+  Filter3D(Filter3D<Scalar, Integer>&& other) { Init(); this->swap(other); }
+  Filter3D<Scalar, Integer>& operator=(Filter3D<Scalar, Integer> source) { this->swap(source); return *this; }
+
+  // the table as the C ABI takes it: (2 hx + 1)(2 hy + 1)(2 hz + 1) numbers, x fastest
+  Scalar* flat_table() { return data_.empty() ? nullptr : &data_[0]; }
+  const Scalar* flat_table() const { return data_.empty() ? nullptr : &data_[0]; }
+
+ private:
+  std::vector<Scalar> data_;
+  std::vector<Scalar*> rows_;
+  std::vector<Scalar**> planes_;
+
+  void Init() {
+    aaafH = nullptr;
+    for (int d = 0; d < 3; d++) halfwidth[d] = array_size[d] = -1;
+  }
+  void Resize(Integer const set_halfwidth[3]) {
+    for (int d = 0; d < 3; d++) {
+      if (set_halfwidth[d] < 0) throw VisfdErr("visfd_hip: filter half-widths must not be negative");
+      halfwidth[d] = set_halfwidth[d];
+      array_size[d] = 1 + 2 * halfwidth[d];
+    }
+    const size_t sx = array_size[0], sy = array_size[1], sz = array_size[2];
+    data_.assign(sx * sy * sz, (Scalar)-1.0e38);   // as the reference fills a new table
+    rows_.resize(sy * sz);
+    planes_.resize(sz);
+    for (size_t k = 0; k < sy * sz; k++) rows_[k] = &data_[0] + k * sx + halfwidth[0];
+    for (size_t k = 0; k < sz; k++) planes_[k] = &rows_[0] + k * sy + halfwidth[1];
+    aaafH = &planes_[0] + halfwidth[2];
+  }
+  // what = 0: sum of w; 1: sum of w * h; 2: sum of w * (h - shift)^2
+  Scalar wsum(Scalar const* const* const* aaafW, int what, Scalar shift = 0.0) const {
+    Scalar sum = 0.0;
+    for (Integer iz = -halfwidth[2]; iz <= halfwidth[2]; iz++)
+      for (Integer iy = -halfwidth[1]; iy <= halfwidth[1]; iy++)
+        for (Integer ix = -halfwidth[0]; ix <= halfwidth[0]; ix++) {
+          const Scalar w = aaafW ? aaafW[iz][iy][ix] : (Scalar)1.0;
+          const Scalar h = aaafH[iz][iy][ix] - shift;
+          sum += what == 0 ? w : what == 1 ? w * h : w * (h * h);
+        }
+    return sum;
+  }
+  void run(Integer const size_source[3], float const* const* const* src, float*** dest, float const* const* const* mask,
+           bool normalize, float*** den, std::ostream* pReportProgress) const {
+    const int size[3] = {(int)size_source[0], (int)size_source[1], (int)size_source[2]};
+    const int hw[3] = {(int)halfwidth[0], (int)halfwidth[1], (int)halfwidth[2]};
+    hip_detail::require_contiguous(src, size);
+    hip_detail::require_contiguous(dest, size);
+    hip_detail::require_contiguous(mask, size);
+    hip_detail::require_contiguous(den, size);
+    if (pReportProgress) *pReportProgress << "  progress: applying the 3-D filter on the GPU" << std::endl;
+    hip_detail::check(visfd_hip_filter3d(hip_detail::context(), hip_detail::flat(src), hip_detail::flat(dest),
+                                         hip_detail::flat(mask), size[0], size[1], size[2], flat_table(), hw,
+                                         normalize ? 1 : 0, hip_detail::flat(den)));
+  }
+};
+
+// lib/visfd/filter3d.hpp:546-601: h(x,y,z) = A*exp(-r^m), r = sqrt((x/s_x)^2 + (y/s_y)^2 + (z/s_z)^2), entries below
+// the smallest face value zeroed, the sum 1
+inline Filter3D<float, int> GenFilterGenGauss3D(const float width[3], float m_exp, const int truncate_halfwidth[3],
+                                                float* pA = nullptr) {
+  Filter3D<float, int> filter(truncate_halfwidth);
+  int64_t n = 0;
+  hip_detail::check(visfd_hip_gengauss3d_table(width, m_exp, truncate_halfwidth, filter.flat_table(),
+                                               (int64_t)filter.array_size[0] * filter.array_size[1] * filter.array_size[2],
+                                               &n, pA));
+  return filter;
+}
+// :618-638: the window is floor(width * filter_cutoff_ratio)
+inline Filter3D<float, int> GenFilterGenGauss3D(const float width[3], float m_exp, const float filter_cutoff_ratio = 2.5,
+                                                float* pA = nullptr) {
+  if (filter_cutoff_ratio < 0) throw VisfdErr("visfd_hip: the filter cutoff ratio must not be negative");
+  int hw[3];
+  hip_detail::check(visfd_hip_gengauss3d_halfwidths(width, m_exp, filter_cutoff_ratio, 0.0f, hw));
+  return GenFilterGenGauss3D(width, m_exp, hw, pA);
+}
+
+// ---- LocalFluctuations: lib/visfd/filter3d.hpp:1698-1711 (any exponent; 2 takes the separable Gaussians) -------
 inline void LocalFluctuations(const int image_size[3], float const* const* const* src, float*** dest,
                               float const* const* const* mask, const float sigma[3],
                               float template_background_exponent = 2, float filter_truncate_ratio = 2.5,
@@ -566,10 +705,10 @@ inline void LocalFluctuations(const int image_size[3], float const* const* const
   hip_detail::require_contiguous(src, image_size);
   hip_detail::require_contiguous(dest, image_size);
   hip_detail::require_contiguous(mask, image_size);
-  hip_detail::check(visfd_hip_local_fluctuations(hip_detail::context(), hip_detail::flat(src), hip_detail::flat(dest),
-                                                 hip_detail::flat(mask), image_size[0], image_size[1], image_size[2],
-                                                 sigma, template_background_exponent, filter_truncate_ratio,
-                                                 normalize ? 1 : 0));
+  hip_detail::check(visfd_hip_local_fluctuations_gen(hip_detail::context(), hip_detail::flat(src), hip_detail::flat(dest),
+                                                     hip_detail::flat(mask), image_size[0], image_size[1], image_size[2],
+                                                     sigma, template_background_exponent, filter_truncate_ratio,
+                                                     normalize ? 1 : 0));
 }
 // ---- LocalFluctuationsByRadius: lib/visfd/filter3d.hpp:1897-1926 and the variant with a decay threshold,
 //      bin/filter_mrc/filter3d_variants.hpp:651-681 (a negative ratio selects the threshold) --------------

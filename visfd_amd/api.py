@@ -24,6 +24,7 @@ DECREASING_EIVALS = 1
 # grayscale morphology ops (VISFD_HIP_MORPH_*, lib/visfd/morphology.hpp:134-597)
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_TOP_HAT_WHITE, MORPH_TOP_HAT_BLACK = range(6)
 MORPH_PATH_GENERAL, MORPH_PATH_XRUNS = 0, 1   # visfd_hip_morph_last_path
+FILTER3D_PATH_GENERAL, FILTER3D_PATH_TILED = 0, 1   # visfd_hip_filter3d_last_path
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -61,12 +62,25 @@ _SIGS = {
     "visfd_hip_ratio_from_threshold": (C.c_float, [C.c_float]),
     "visfd_hip_local_fluctuations": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
     "visfd_hip_local_fluctuations_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
+    "visfd_hip_gengauss3d_halfwidths": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _ip]),
+    "visfd_hip_gengauss3d_table": (C.c_int, [_fp, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64), _fp]),
+    "visfd_hip_dogg3d_table": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _ip, _fp, _i64,
+                                         C.POINTER(C.c_int64), _fp, _fp]),
+    "visfd_hip_filter3d": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _vp]),
+    "visfd_hip_filter3d_dev": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _vp]),
+    "visfd_hip_apply_ggauss": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, _ip, C.c_int, _fp]),
+    "visfd_hip_apply_ggauss_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, _ip, C.c_int, _fp]),
+    "visfd_hip_apply_dogg": (C.c_int, [_vp] + _VOL + [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp]),
+    "visfd_hip_apply_dogg_dev": (C.c_int, [_vp] + _VOL + [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp]),
+    "visfd_hip_local_fluctuations_gen": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
+    "visfd_hip_local_fluctuations_gen_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
     "visfd_hip_sphere_structure": (C.c_int, [C.c_float, C.c_float, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64)]),
     "visfd_hip_morph_sphere": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
     "visfd_hip_morph_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
     "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_table_dev": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_filter3d_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_fluctuation_sigmas": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _fp, C.POINTER(C.c_float)]),
@@ -292,6 +306,50 @@ def sphere_structure(radius, radius_max=0.0, bmax=0.0):
     _chk_host(L, L.visfd_hip_sphere_structure(float(radius), float(radius_max), float(bmax), d.ctypes.data_as(_ip),
                                               b.ctypes.data_as(_fp), len(b), C.byref(n)))
     return d[:n.value].copy(), b[:n.value].copy()
+
+
+def gengauss3d_halfwidths(width, m_exp, truncate_ratio=-1.0, truncate_threshold=0.03):
+    """Window of the generalised Gaussians (filter3d_variants.hpp:99-103, filter3d.hpp:631-633): floor(width * ratio), a
+    negative ratio first replaced by pow(-log(threshold), 1 / m_exp).  -> (hx, hy, hz)"""
+    L = load_library()
+    hw = (C.c_int * 3)()
+    _chk_host(L, L.visfd_hip_gengauss3d_halfwidths(_f3(width), float(m_exp), float(truncate_ratio),
+                                                   float(truncate_threshold), hw))
+    return tuple(hw)
+
+
+def gengauss3d_table(width, m_exp, halfwidth):
+    """GenFilterGenGauss3D(width, m_exp, halfwidth) (filter3d.hpp:546-601) -> (table float32 (2hz+1, 2hy+1, 2hx+1), A)."""
+    L = load_library()
+    hw = [int(h) for h in halfwidth]
+    n = C.c_int64()
+    _chk_host(L, L.visfd_hip_gengauss3d_table(_f3(width), float(m_exp), _i3(hw), None, 0, C.byref(n), None))
+    t = np.empty((2 * hw[2] + 1, 2 * hw[1] + 1, 2 * hw[0] + 1), np.float32)
+    A = C.c_float()
+    _chk_host(L, L.visfd_hip_gengauss3d_table(_f3(width), float(m_exp), _i3(hw), t.ctypes.data_as(_fp), t.size,
+                                              C.byref(n), C.byref(A)))
+    return t, A.value
+
+
+def dogg3d_table(width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03):
+    """GenFilterDogg3D (filter3d_variants.hpp:284-345, :441-482) -> (table float32 (2hz+1, 2hy+1, 2hx+1), A, B)."""
+    L = load_library()
+    args = (_f3(width_a), _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio), float(truncate_threshold))
+    hw = (C.c_int * 3)()
+    n = C.c_int64()
+    _chk_host(L, L.visfd_hip_dogg3d_table(*(args + (hw, None, 0, C.byref(n), None, None))))
+    t = np.empty((2 * hw[2] + 1, 2 * hw[1] + 1, 2 * hw[0] + 1), np.float32)
+    A, B = C.c_float(), C.c_float()
+    _chk_host(L, L.visfd_hip_dogg3d_table(*(args + (hw, t.ctypes.data_as(_fp), t.size, C.byref(n), C.byref(A),
+                                                    C.byref(B)))))
+    return t, A.value, B.value
+
+
+def _filter_table(table):
+    """A 3-D table (2hz+1, 2hy+1, 2hx+1) as the C ABI takes it: (float32 array, (hx, hy, hz))."""
+    t = np.ascontiguousarray(table, np.float32)
+    assert t.ndim == 3 and all(s % 2 == 1 for s in t.shape), "a filter table has an odd number of entries per axis"
+    return t, _i3([(t.shape[2] - 1) // 2, (t.shape[1] - 1) // 2, (t.shape[0] - 1) // 2])
 
 
 def _morph_table(dxyz, b):
@@ -607,6 +665,45 @@ class Context:
                                                        float(exponent), float(ratio), int(normalize)))
         return dst
 
+    def local_fluctuations_gen(self, src, sigma, ratio, mask=None, normalize=True, exponent=2.0):
+        """LocalFluctuations (filter3d.hpp:1698-1853) for any exponent: the dense generalised-Gaussian window unless the
+        exponent is 2, which takes the separable path of local_fluctuations."""
+        nz, ny, nx = src.shape
+        dst = np.empty_like(src)
+        self._chk(self._L.visfd_hip_local_fluctuations_gen(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
+                                                           _f3(sigma), float(exponent), float(ratio), int(normalize)))
+        return dst
+
+    def filter3d(self, src, table, mask=None, normalize=False, want_den=False):
+        """Filter3D::Apply (filter3d.hpp:81-198) with a table (2hz+1, 2hy+1, 2hx+1) indexed [jz][jy][jx]: -> dst, or
+        (dst, den) with want_den (the second Apply overload's denominator).  Voxels with mask == 0 get 0 in both."""
+        nz, ny, nx = src.shape
+        t, hw = _filter_table(table)
+        dst = np.empty_like(src)
+        den = np.empty_like(src) if want_den else None
+        self._chk(self._L.visfd_hip_filter3d(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, t.ctypes.data_as(_fp), hw,
+                                             int(normalize), _np(den)))
+        return (dst, den) if want_den else dst
+
+    def apply_ggauss(self, src, width, m_exp, halfwidth, mask=None, normalize=True):
+        """HandleGGauss (handlers.cpp:167-187): GenFilterGenGauss3D(width, m_exp, halfwidth) applied -> (dst, A)."""
+        nz, ny, nx = src.shape
+        dst = np.empty_like(src)
+        A = C.c_float()
+        self._chk(self._L.visfd_hip_apply_ggauss(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(width),
+                                                 float(m_exp), _i3(halfwidth), int(normalize), C.byref(A)))
+        return dst, A.value
+
+    def apply_dogg(self, src, width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03, mask=None):
+        """HandleDogg (handlers.cpp:265-293): GenFilterDogg3D applied, never normalised -> (dst, A, B)."""
+        nz, ny, nx = src.shape
+        dst = np.empty_like(src)
+        A, B = C.c_float(), C.c_float()
+        self._chk(self._L.visfd_hip_apply_dogg(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(width_a),
+                                               _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio),
+                                               float(truncate_threshold), C.byref(A), C.byref(B)))
+        return dst, A.value, B.value
+
     def morph_sphere(self, op, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
         """DilateSphere / ErodeSphere / OpenSphere / CloseSphere / WhiteTopHatSphere / BlackTopHatSphere (op = MORPH_*,
         morphology.hpp:241-597).  dst (default: a copy of src, as filter_mrc starts its output) keeps its values where
@@ -693,6 +790,12 @@ class Context:
             threshold = -float("inf")
         r = self.find_extrema(src, mask, False, True, float("inf"), threshold, connectivity, allow_borders, **kw)
         return r[1] if len(r) == 2 else (r[1], r[2])
+
+    def filter3d_last_path(self):
+        """The kernel the last general-filter call ran: FILTER3D_PATH_GENERAL or FILTER3D_PATH_TILED (-1 before the first)."""
+        p = C.c_int()
+        self._chk(self._L.visfd_hip_filter3d_last_path(self._h, C.byref(p)))
+        return p.value
 
     def morph_last_path(self):
         """The kernel the last morphology call ran: MORPH_PATH_GENERAL or MORPH_PATH_XRUNS (-1 before the first)."""
@@ -915,6 +1018,34 @@ class Context:
         nz, ny, nx = src.shape
         self._chk(self._L.visfd_hip_local_fluctuations_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
                                                            _f3(sigma), float(exponent), float(ratio), int(normalize)))
+
+    def local_fluctuations_gen_dev(self, src, dst, sigma, ratio, mask=None, normalize=True, exponent=2.0):
+        nz, ny, nx = src.shape
+        self._chk(self._L.visfd_hip_local_fluctuations_gen_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
+                                                               _f3(sigma), float(exponent), float(ratio), int(normalize)))
+
+    def filter3d_dev(self, src, dst, table, mask=None, normalize=False, den=None):
+        """filter3d on device tensors (the table is a host array); den: optional tensor for the denominator."""
+        nz, ny, nx = src.shape
+        t, hw = _filter_table(table)
+        self._chk(self._L.visfd_hip_filter3d_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
+                                                 t.ctypes.data_as(_fp), hw, int(normalize), _dev(den)))
+
+    def apply_ggauss_dev(self, src, dst, width, m_exp, halfwidth, mask=None, normalize=True):
+        nz, ny, nx = src.shape
+        A = C.c_float()
+        self._chk(self._L.visfd_hip_apply_ggauss_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, _f3(width),
+                                                     float(m_exp), _i3(halfwidth), int(normalize), C.byref(A)))
+        return A.value
+
+    def apply_dogg_dev(self, src, dst, width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03,
+                       mask=None):
+        nz, ny, nx = src.shape
+        A, B = C.c_float(), C.c_float()
+        self._chk(self._L.visfd_hip_apply_dogg_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, _f3(width_a),
+                                                   _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio),
+                                                   float(truncate_threshold), C.byref(A), C.byref(B)))
+        return A.value, B.value
 
     def morph_sphere_dev(self, op, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
         """morph_sphere on device tensors; dst is read (top-hats, masked voxels) and written in place."""

@@ -9,6 +9,8 @@
 //   -w WIDTH            voxel width (otherwise cellA[0]/nx from the header, handlers.cpp:2429)
 //   -gauss S | -gauss-aniso SX SY SZ              (settings.cpp:1220-1271, HandleGauss)
 //   -dog A B                                        (settings.cpp:1309-1335, HandleDog)
+//   -ggauss S | -ggauss-aniso SX SY SZ | -dogg A B | -dogg-aniso AX AY AZ BX BY BZ   (HandleGGauss, HandleDogg: the dense filter)
+//   -exponent M | -gauss-exponent M | -exponents M N | -gdog-exponents M N   (settings.cpp:1492-1535; also -fluct's exponent)
 //   -log S | -log-r R | -log-d D | -log-aniso SX SY SZ | -dog-delta D   (HandleLoGDoG)
 //   -blob|-blob-s|-blob-r|-blob-d TYPE FILE MIN MAX GROWTH             (settings.cpp:1648-1764)
 //   -minima-threshold T | -maxima-threshold T                          (settings.cpp:1915,1934)
@@ -148,7 +150,7 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until main() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
@@ -160,6 +162,7 @@ struct Settings {
   float width_a[3] = {0, 0, 0}, width_b[3] = {0, 0, 0}, log_width[3] = {0, 0, 0};
   float template_background_radius[3] = {-1, -1, -1};        // settings.cpp:222-225 (-fluct)
   float template_background_exponent = 2.0f;
+  float m_exp = 2.0f, n_exp = 2.0f;                           // settings.cpp:73-74 (-exponent, -exponents)
   float truncate_ratio = -1.0f, truncate_threshold = 0.03f;   // settings.cpp:81,88
   float delta = 0.02f;                                        // settings.cpp:95
   bool normalize = true;
@@ -291,6 +294,32 @@ Settings parse(int argc, char** argv) {
     }
     else if (f == "-boundary-extrema") { s.extrema_on_boundary = true; i += 1; }
     else if (f == "-ignore-boundary-extrema") { s.extrema_on_boundary = false; i += 1; }
+    else if (f == "-ggauss" || f == "-ggauss-aniso" || f == "-dogg" || f == "-dogg-aniso" || f == "-exponent" ||
+             f == "-gauss-exponent" || f == "-exponents" || f == "-gdog-exponents") {
+      // settings.cpp:1220-1335, :1492-1535: the numbers must be there, not empty and not start with '-'
+      const bool aniso = f == "-ggauss-aniso" || f == "-dogg-aniso", two = f == "-dogg" || f == "-dogg-aniso";
+      const bool expo = f == "-exponent" || f == "-gauss-exponent", expos = f == "-exponents" || f == "-gdog-exponents";
+      const size_t k = expo ? 1 : expos ? 2 : (aniso ? 3 : 1) * (two ? 2 : 1);
+      const string msg = "Error: The " + f + " argument must be followed by " +
+                         (k == 1 ? string(expo ? "a positive number.\n" : "a positive number (\"s\"),\n the Gaussian width\n")
+                                 : expos ? string("two positive numbers.\n")
+                                         : std::to_string(k) + " positive numbers" + (k == 3 ? ":\n s_x  s_y  s_z\n the Gaussian widths in the X, Y, and Z direction.)\n" : ".\n"));
+      float x[6] = {0, 0, 0, 0, 0, 0};
+      for (size_t j = 1; j <= k; j++) {
+        if (i + j >= v.size() || v[i + j].empty() || v[i + j][0] == '-') throw VisfdErr(msg);
+        try { x[j - 1] = std::stof(v[i + j]); } catch (...) { throw VisfdErr(msg); }
+      }
+      if (expo) s.m_exp = s.n_exp = s.template_background_exponent = x[0];
+      else if (expos) { s.m_exp = x[0]; s.n_exp = s.template_background_exponent = x[1]; }   // settings.cpp:1500-1503
+      else {
+        for (int d = 0; d < 3; d++) {
+          s.width_a[d] = aniso ? x[d] : x[0];
+          if (two) s.width_b[d] = aniso ? x[3 + d] : x[1];
+        }
+        s.type = two ? Settings::DOGG : Settings::GGAUSS;
+      }
+      i += k + 1;
+    }
     else if (f == "-gauss-aniso") { need(3); for (int d = 0; d < 3; d++) s.width_a[d] = num(v, i + 1 + d, f); s.type = Settings::GAUSS; i += 4; }
     else if (f == "-dog") {
       need(2);
@@ -868,6 +897,61 @@ int main(int argc, char** argv) {
       // HandleLocalFluctuations, handlers.cpp:1254-1271
       LocalFluctuationsByRadius(size, tomo_in.a, tomo_out.a, M, s.template_background_radius,
                                 s.template_background_exponent, s.truncate_ratio, s.truncate_threshold, s.normalize, &cerr);
+    } else if (s.type == Settings::GGAUSS) {
+      // HandleGGauss, handlers.cpp:167-213
+      int hw[3];
+      float A = 0;
+      hip_detail::check(visfd_hip_gengauss3d_halfwidths(s.width_a, s.m_exp, s.truncate_ratio, s.truncate_threshold, hw));
+      hip_detail::check(visfd_hip_apply_ggauss(hip_detail::context(), tomo_in.data(), tomo_out.data(),
+                                               mask.loaded ? mask.data() : nullptr, size[0], size[1], size[2], s.width_a,
+                                               s.m_exp, hw, s.normalize ? 1 : 0, &A));
+      cerr << " Filter Used:\n"
+              " h(x,y,z)   = A*exp(-((x/a_x)^2 + (y/a_y)^2 + (z/a_z)^2)^(m/2))\n"
+              "  ... where      A = " << A << "\n"
+              "                 m = " << s.m_exp << "\n"
+              "   (a_x, a_y, a_z) = " << "(" << s.width_a[0] << " " << s.width_a[1] << " " << s.width_a[2] << ")\n";
+      cerr << " You can plot a slice of this function\n"
+           << "     in the X direction using:\n"
+              " draw_filter_1D.py -ggauss " << A << " " << s.width_a[0] << " " << s.m_exp << std::endl;
+      if (s.width_a[1] != s.width_a[0] || s.width_a[2] != s.width_a[0]) {
+        cerr << " and in the Y direction using:\n"
+                " draw_filter_1D.py -ggauss " << A << " " << s.width_a[1] << " " << s.m_exp << std::endl;
+        cerr << " and in the Z direction using:\n"
+                " draw_filter_1D.py -ggauss " << A << " " << s.width_a[2] << " " << s.m_exp << std::endl;
+      }
+    } else if (s.type == Settings::DOGG) {
+      // HandleDogg, handlers.cpp:265-293; the report is _GenFilterDogg3D's, filter3d_variants.hpp:347-379
+      cerr << "filter_type = Difference-of-Generalized-Gaussians (DOGG)\n";
+      if (mask.loaded)
+        cerr << "WARNING: -dogg with -mask: the reference program crashes at the first voxel outside the mask\n"
+                "         (it applies the filter with a mask and without a denominator).  This program writes 0 there.\n";
+      float A = 0, B = 0;
+      hip_detail::check(visfd_hip_apply_dogg(hip_detail::context(), tomo_in.data(), tomo_out.data(),
+                                             mask.loaded ? mask.data() : nullptr, size[0], size[1], size[2], s.width_a,
+                                             s.width_b, s.m_exp, s.n_exp, s.truncate_ratio, s.truncate_threshold, &A, &B));
+      cerr << "\n"
+              " Filter Used:\n"
+              " h(x,y,z)   = h_a(x,y,z) - h_b(x,y,z)\n"
+              " h_a(x,y,z) = A*exp(-((x/a_x)^2 + (y/a_y)^2 + (z/a_z)^2)^(m/2))\n"
+              " h_b(x,y,z) = B*exp(-((x/b_x)^2 + (y/b_y)^2 + (z/b_z)^2)^(n/2))\n"
+              "  ... where      A = " << A << "\n"
+              "                 B = " << B << "\n"
+              "                 m = " << s.m_exp << "\n"
+              "                 n = " << s.n_exp << "\n"
+              "   (a_x, a_y, a_z) = " << "(" << s.width_a[0] << " " << s.width_a[1] << " " << s.width_a[2] << ")\n"
+              "   (b_x, b_y, b_z) = " << "(" << s.width_b[0] << " " << s.width_b[1] << " " << s.width_b[2] << ")\n";
+      cerr << " You can plot a slice of this function\n"
+           << "     in the X direction using:\n"
+              " draw_filter_1D.py -dogg " << A << " " << B << " " << s.width_a[0] << " " << s.width_b[0] << " " << s.m_exp
+           << " " << s.n_exp << std::endl;
+      if (s.width_a[1] != s.width_a[0] || s.width_a[2] != s.width_a[0]) {
+        cerr << " and in the Y direction using:\n"
+                " draw_filter_1D.py -dogg " << A << " " << B << " " << s.width_a[1] << " " << s.width_b[1] << " " << s.m_exp
+             << " " << s.n_exp << std::endl;
+        cerr << " and in the Z direction using:\n"
+                " draw_filter_1D.py -dogg " << A << " " << B << " " << s.width_a[2] << " " << s.width_b[2] << " " << s.m_exp
+             << " " << s.n_exp << std::endl;
+      }
     } else if (s.type == Settings::DOG) {
       cerr << "filter_type = Difference of Gaussians (DoG)\n";
       // bin/filter_mrc/filter3d_variants.hpp:542-597: each Gaussian has its own window

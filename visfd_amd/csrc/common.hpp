@@ -62,6 +62,7 @@ enum Slot {
   WS_EXT_COUNTERS,                 // extrema: the two list lengths
   WS_EXT_LIST,                     // extrema: the unsorted lists (index, score, voxels)
   WS_EXT_RANKS,                    // extrema: listed roots in raster order and their sorted positions, for the label image
+  WS_F3D_TAB,                      // general 3-D filter: the table's non-zero entries on the device (what they were built from: visfd_hip_ctx::f3d_raw)
   WS_NSLOTS
 };
 
@@ -90,6 +91,7 @@ struct visfd_hip_options {
   int tv_max_wg = 0;        // cap on the persistent grid (0: fill the chip); tests use it to make workgroups claim many units
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
+  int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int debug = 0;
 };
 
@@ -107,6 +109,12 @@ struct visfd_hip_ctx {
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
   std::vector<int> morph_tab;         // the structuring element now in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b)
   int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
+  std::vector<float> f3d_raw;         // the filter table whose non-zero entries are now in slot WS_F3D_TAB (empty: none),
+  int64_t f3d_key[5] = {};            // its half-widths and the nx, ny its sender offsets were computed for,
+  int64_t f3d_n = 0;                  // the number of those entries, of the columns (jy, jx) that hold one
+  int64_t f3d_ncols = 0;
+  float f3d_den = 0.0f;               // and their float sum in order
+  int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };
 
@@ -151,6 +159,10 @@ void host_conv_ones(i64 n, const float* t, int h, float* out);  // filter applie
 int host_tv_halfwidth(float sigma, float cutoff);
 void host_tv_tables(float sigma, int h, float* w, float* rhat);
 float host_gengauss3d_peak(const float width[3], float m_exp, float ratio);
+void host_gengauss3d_table(const float width[3], float m_exp, const int hw[3], float* table_out, float* A_out);
+void host_gengauss3d_halfwidths(const float width[3], float m_exp, float ratio, float threshold, int hw[3]);
+i64 host_dogg3d_table(const float width_a[3], const float width_b[3], float m_exp, float n_exp, float ratio,
+                      float threshold, int hw[3], float* table_out, i64 cap, float* A_out, float* B_out);
 i64 host_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, i64 cap);
 
 // ---- device stages (each in its own .hip; all asynchronous on ctx->stream) -------------------
@@ -279,6 +291,12 @@ int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, floa
 int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el);
 int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
               MorphElem el);
+
+// filter3d.hip: Filter3D::Apply with an arbitrary table of (2 hx + 1)(2 hy + 1)(2 hz + 1) entries (x fastest), on device
+// arrays.  dst = sum_j (H[j] * mask[i - j]) * src[i - j] in the reference's order, divided by den = sum_j H[j] * mask[i - j]
+// where `normalize` and den > 0; den_out (nullable) receives den.  Voxels with mask == 0 get dst = 0 and den = 0.
+int dev_filter3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+                 const float* table, const int hw[3], bool normalize, float* den_out);
 
 // extrema.hip: plateau-aware minima and maxima (visfd_hip_find_extrema[_dev], include/visfd_hip.h)
 struct ExtremaArgs {

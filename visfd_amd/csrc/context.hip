@@ -51,6 +51,7 @@ const OptionDesc kOptions[] = {
     {"tv_poison", &visfd_hip_options::tv_poison, nullptr}, {"tv_no_fold", &visfd_hip_options::tv_no_fold, nullptr}, {"tv_exact_tiled", &visfd_hip_options::tv_exact_tiled, nullptr}, {"tv_reserve_wg", &visfd_hip_options::tv_reserve_wg, nullptr},
     {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
+    {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {
@@ -81,6 +82,7 @@ void forget_slot_caches(visfd_hip_ctx* ctx) {
   ctx->tv_table_dev = nullptr;   // lives in a workspace slot
   ctx->tv_table_h = -1;
   ctx->morph_tab.clear();        // so does the structuring element
+  ctx->f3d_raw.clear();          // and the general filter's table
 }
 
 }  // namespace
