@@ -67,7 +67,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * visfd_hip_blob_jobs_pending and visfd_hip_debug_poison_workspace; then the
                                      * general 3-D filter: visfd_hip_gengauss3d_halfwidths, _gengauss3d_table,
                                      * _dogg3d_table, _filter3d[_dev], _filter3d_last_path, _apply_ggauss[_dev],
-                                     * _apply_dogg[_dev] and _local_fluctuations_gen[_dev]) */
+                                     * _apply_dogg[_dev] and _local_fluctuations_gen[_dev]; then the drawing entries
+                                     * visfd_hip_draw_spheres[_dev], visfd_hip_draw_regions[_dev] and
+                                     * visfd_hip_draw_last_times) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -97,6 +99,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    kernel; results are bit-identical either way
  *   filter3d_general 1: the general 3-D filter always walks the table entry by entry (csrc/filter3d.hip), never takes the
  *                    LDS-tiled kernel; results are bit-identical either way
+ *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
+ *                    (visfd_hip_draw_last_times); default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -214,6 +218,56 @@ int visfd_hip_local_fluctuations_gen(visfd_hip_ctx*, const float* src, float* ds
 int visfd_hip_local_fluctuations_gen_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask, int64_t nx,
                                          int64_t ny, int64_t nz, const float sigma[3], float exponent,
                                          float truncate_ratio, int normalize);
+
+/* ---- d1-d2: drawing (lib/visfd/draw.hpp:90-457) ------------------------------------------------------------------
+ * Both are bit-identical to the reference for finite inputs. */
+/* DrawSpheres (draw.hpp:238-457).  Every voxel of dst, masked or not, first becomes background * rescale + offset (two float
+ * roundings) or, with background_normalize, ((background - ave) / stddev) * rms * rescale + offset, where ave and stddev are
+ * the reference's float statistics of the background weighted by the mask (0 + offset when stddev is not > 0) and rms the
+ * root mean square of `foreground`.  Then sphere i = 0 .. n-1 in list order overwrites the voxels with mask != 0 whose
+ * squared integer distance r2 from the centre truncated to int satisfies rmin2 <= (float)r2 <= rmax2, rmax2 = (d/2)^2,
+ * rmin2 = (d/2 - th)^2 when th > 0 and d/2 - th > 0, else 0, with foreground[i], divided under foreground_normalize by the
+ * number of such voxels.  So the last sphere in list order wins every voxel it holds.
+ * centers: 3 n floats (x, y, z per sphere, in voxels).  diameters, shell_thicknesses, foreground: n floats each or NULL for
+ * the reference's defaults (diameter 0, thickness = radius: a solid sphere, foreground 1).  All four are HOST arrays on
+ * both faces.  dst may be the background array itself; any other overlap of dst with background or mask is refused.
+ * any_center_outside (nullable): set to 1 when a truncated centre lies outside the image (the reference's warning), else 0.
+ * With background_normalize the statistics are computed on the host (the _dev face copies background and mask down for
+ * them and waits for the stream); otherwise the _dev face is asynchronous.
+ * Refused with VISFD_HIP_EINVAL, dst untouched: a null background (the reference dereferences it), n > 2^31 - 2, a centre
+ * that is not finite or does not fit an int, a diameter that is not finite or whose Rs = ceil(d/2 - 0.5) has
+ * 3 Rs^2 >= 2^31 (the reference's int arithmetic overflows there). */
+int visfd_hip_draw_spheres(visfd_hip_ctx*, float* dst, const float* mask, const float* background, int64_t nx, int64_t ny,
+                           int64_t nz, const float* centers, const float* diameters, const float* shell_thicknesses,
+                           const float* foreground, int64_t n, float background_offset, float background_rescale,
+                           int background_normalize, int foreground_normalize, int* any_center_outside);
+int visfd_hip_draw_spheres_dev(visfd_hip_ctx*, float* dst, const float* mask, const float* background, int64_t nx,
+                               int64_t ny, int64_t nz, const float* centers, const float* diameters,
+                               const float* shell_thicknesses, const float* foreground, int64_t n, float background_offset,
+                               float background_rescale, int background_normalize, int foreground_normalize,
+                               int* any_center_outside);
+/* With the option draw_time set: milliseconds the last DrawSpheres of the context spent in the zero fill of its owner volume,
+ * in the scatter (with the counting pass of foreground_normalize) and in the resolve; -1 before the first timed call. */
+int visfd_hip_draw_last_times(visfd_hip_ctx*, float ms[3]);
+/* SimpleRegion<float> (draw.hpp:46-81) as a plain struct.  c: xmin, xmax, ymin, ymax, zmin, zmax of a rectangle, or
+ * x0, y0, z0, r of a sphere (c[4], c[5] unused), in voxels. */
+#define VISFD_HIP_REGION_RECT 0
+#define VISFD_HIP_REGION_SPHERE 1
+typedef struct visfd_hip_region {
+  int32_t type;
+  float c[6];
+  float value;
+} visfd_hip_region;
+/* DrawRegions (draw.hpp:90-224): the regions act on dst in list order, on voxels with mask != 0 only.  A value that is
+ * not negative (NaN included) is written; a negative one zeroes voxels that are > 0 when negative_means_subtract, and does
+ * nothing otherwise.  When the first region is negative, negative_means_subtract is set and every unmasked voxel of dst is
+ * 0, the unmasked voxels are first set to 1.  `regions` is a HOST array on both faces; the _dev face is asynchronous.
+ * Refused: a sphere whose centre or radius is not finite, whose rounded centre does not fit an int or whose
+ * Ri = ceil(r - 0.5) exceeds 32767. */
+int visfd_hip_draw_regions(visfd_hip_ctx*, float* dst, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                           const visfd_hip_region* regions, int64_t n, int negative_means_subtract);
+int visfd_hip_draw_regions_dev(visfd_hip_ctx*, float* dst, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                               const visfd_hip_region* regions, int64_t n, int negative_means_subtract);
 
 /* ---- m1: grayscale morphology (lib/visfd/morphology.hpp:134-597) ------------------------------- */
 #define VISFD_HIP_MORPH_DILATE 0          /* DilateSphere / Dilate                         morphology.hpp:134-172, 241-330 */

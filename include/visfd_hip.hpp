@@ -32,6 +32,7 @@
 #include <ostream>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -835,6 +836,92 @@ inline void UnbinArray3D(int const size_source[3], int const size_dest[3], float
   const int64_t ss[3] = {size_source[0], size_source[1], size_source[2]}, ds[3] = {size_dest[0], size_dest[1], size_dest[2]};
   hip_detail::check(visfd_hip_unbin_array3d(hip_detail::context(), hip_detail::flat(aaafSource), ss,
                                             hip_detail::flat(aaafDest), ds, offset));
+}
+
+// ---- drawing: lib/visfd/draw.hpp:46-81, :90-224, :238-457 --------------------------------------------------------
+// A rectangle or a sphere with a brightness; `value` < 0 means "take these voxels away" under negative_means_subtract.
+template <typename Scalar>
+struct SimpleRegion {
+  struct Rect { Scalar xmin, xmax, ymin, ymax, zmin, zmax; };
+  struct Sphere { Scalar x0, y0, z0, r; };
+  enum RegionType { RECT, SPHERE };
+  RegionType type;
+  union { Rect rect; Sphere sphere; } data;
+  Scalar value;
+  SimpleRegion() : type(RECT), value(1) {   // an empty rectangle
+    data.rect.xmin = 0; data.rect.xmax = -1;
+    data.rect.ymin = 0; data.rect.ymax = -1;
+    data.rect.zmin = 0; data.rect.zmax = -1;
+  }
+};
+
+template <typename Scalar>
+void DrawRegions(int const image_size[3], Scalar*** aaafDest, Scalar const* const* const* aaafMask,
+                 std::vector<SimpleRegion<Scalar> > vRegions, bool negative_means_subtract = false) {
+  static_assert(std::is_same<Scalar, float>::value, "visfd_hip draws float images");
+  hip_detail::require_contiguous(aaafDest, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  std::vector<visfd_hip_region> r(vRegions.size());
+  for (size_t i = 0; i < r.size(); i++) {
+    const SimpleRegion<Scalar>& g = vRegions[i];
+    r[i].value = g.value;
+    for (int k = 0; k < 6; k++) r[i].c[k] = 0.0f;
+    if (g.type == SimpleRegion<Scalar>::SPHERE) {
+      r[i].type = VISFD_HIP_REGION_SPHERE;
+      r[i].c[0] = g.data.sphere.x0; r[i].c[1] = g.data.sphere.y0; r[i].c[2] = g.data.sphere.z0; r[i].c[3] = g.data.sphere.r;
+    } else {
+      r[i].type = VISFD_HIP_REGION_RECT;
+      r[i].c[0] = g.data.rect.xmin; r[i].c[1] = g.data.rect.xmax; r[i].c[2] = g.data.rect.ymin;
+      r[i].c[3] = g.data.rect.ymax; r[i].c[4] = g.data.rect.zmin; r[i].c[5] = g.data.rect.zmax;
+    }
+  }
+  hip_detail::check(visfd_hip_draw_regions(hip_detail::context(), hip_detail::flat(aaafDest), hip_detail::flat(aaafMask),
+                                           image_size[0], image_size[1], image_size[2], r.empty() ? nullptr : r.data(),
+                                           (int64_t)r.size(), negative_means_subtract ? 1 : 0));
+}
+
+// aaafDest may be aaafBackground.  A null background is an error here (the reference dereferences it).
+template <typename Scalar>
+void DrawSpheres(int const image_size[3], Scalar*** aaafDest, Scalar const* const* const* aaafMask,
+                 const std::vector<std::array<Scalar, 3> >& centers, const std::vector<Scalar>* pDiameters = nullptr,
+                 const std::vector<Scalar>* pShellThicknesses = nullptr,
+                 const std::vector<Scalar>* pVoxelIntensitiesForeground = nullptr,
+                 Scalar const* const* const* aaafBackground = nullptr, Scalar voxel_intensity_background_offset = 0.0,
+                 Scalar voxel_intensity_background_rescale = 1.0, bool voxel_intensity_background_normalize = false,
+                 bool voxel_intensity_foreground_normalize = false, std::ostream* pReportProgress = nullptr) {
+  static_assert(std::is_same<Scalar, float>::value, "visfd_hip draws float images");
+  hip_detail::require_contiguous(aaafDest, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  hip_detail::require_contiguous(aaafBackground, image_size);
+  const size_t n = centers.size();
+  if ((pDiameters && pDiameters->size() != n) || (pShellThicknesses && pShellThicknesses->size() != n) ||
+      (pVoxelIntensitiesForeground && pVoxelIntensitiesForeground->size() != n))
+    throw VisfdErr("Error: DrawSpheres: the sphere lists differ in length.\n");
+  std::vector<float> c(3 * n);
+  for (size_t i = 0; i < n; i++) { c[3 * i] = centers[i][0]; c[3 * i + 1] = centers[i][1]; c[3 * i + 2] = centers[i][2]; }
+  if (pReportProgress)   // draw.hpp:360-386
+    for (size_t i = 0; i < n; i++) {
+      const float d = pDiameters ? (*pDiameters)[i] : 0.0f;
+      *pReportProgress << "processing coordinates " << i + 1 << " / " << n << ": x,y,z(in_voxels)=" << centers[i][0] << ","
+                       << centers[i][1] << "," << centers[i][2] << ", diameter=" << d
+                       << ", th=" << (pShellThicknesses ? (*pShellThicknesses)[i] : d / 2) << "\n";
+    }
+  int outside = 0;
+  hip_detail::check(visfd_hip_draw_spheres(
+      hip_detail::context(), hip_detail::flat(aaafDest), hip_detail::flat(aaafMask), hip_detail::flat(aaafBackground),
+      image_size[0], image_size[1], image_size[2], n ? c.data() : nullptr, pDiameters && n ? pDiameters->data() : nullptr,
+      pShellThicknesses && n ? pShellThicknesses->data() : nullptr,
+      pVoxelIntensitiesForeground && n ? pVoxelIntensitiesForeground->data() : nullptr, (int64_t)n,
+      voxel_intensity_background_offset, voxel_intensity_background_rescale, voxel_intensity_background_normalize ? 1 : 0,
+      voxel_intensity_foreground_normalize ? 1 : 0, &outside));
+  if (pReportProgress && outside)   // draw.hpp:447-455
+    *pReportProgress << "------------------------------------------------------------------------------\n"
+                        "WARNING:\n"
+                        "    Some coordinates in the text file lie outside the boundaries of the image.\n"
+                        "    Did you remember to set the voxel width correctly?\n"
+                        "    (Did you use the \"-w\" argument?)\n"
+                        "--------------------------------------------------------------------------=---\n"
+                     << std::endl;
 }
 
 // ---- blob list post-processing: lib/visfd/visfd_utils.hpp:49-55,95-118; feature.hpp:519-616,720-969 ------

@@ -43,6 +43,16 @@ class Blob(C.Structure):
                 ("sigma", C.c_float), ("score", C.c_float)]
 
 
+class Region(C.Structure):   # visfd_hip_region: a SimpleRegion<float> (draw.hpp:46-81)
+    _fields_ = [("type", C.c_int32), ("c", C.c_float * 6), ("value", C.c_float)]
+
+
+REGION_RECT, REGION_SPHERE = 0, 1
+
+# dst, mask, background, sizes, centers, diameters, thicknesses, foreground, n, offset, rescale, two flags, any_center_outside
+_DRAW_SPHERES = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_int, C.c_int, _ip]
+_DRAW_REGIONS = [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(Region), _i64, C.c_int]
+
 _VOL = [_vp, _vp, _vp, _i64, _i64, _i64]  # src, dst, mask, nx, ny, nz  (pointers as void*)
 
 # find_minima, find_maxima, both thresholds, connectivity, allow_borders, then (index, score, nvoxels, cap, n) per kind, labels
@@ -74,6 +84,11 @@ _SIGS = {
     "visfd_hip_apply_dogg_dev": (C.c_int, [_vp] + _VOL + [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp]),
     "visfd_hip_local_fluctuations_gen": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
     "visfd_hip_local_fluctuations_gen_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
+    "visfd_hip_draw_spheres": (C.c_int, _DRAW_SPHERES),
+    "visfd_hip_draw_spheres_dev": (C.c_int, _DRAW_SPHERES),
+    "visfd_hip_draw_regions": (C.c_int, _DRAW_REGIONS),
+    "visfd_hip_draw_regions_dev": (C.c_int, _DRAW_REGIONS),
+    "visfd_hip_draw_last_times": (C.c_int, [_vp, _fp]),
     "visfd_hip_sphere_structure": (C.c_int, [C.c_float, C.c_float, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64)]),
     "visfd_hip_morph_sphere": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
     "visfd_hip_morph_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
@@ -350,6 +365,37 @@ def _filter_table(table):
     t = np.ascontiguousarray(table, np.float32)
     assert t.ndim == 3 and all(s % 2 == 1 for s in t.shape), "a filter table has an odd number of entries per axis"
     return t, _i3([(t.shape[2] - 1) // 2, (t.shape[1] - 1) // 2, (t.shape[0] - 1) // 2])
+
+
+def _sphere_lists(centers, diameters, shell_thicknesses, foreground):
+    """The four host lists of draw_spheres as ctypes arguments; None stays NULL (the reference's defaults)."""
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
+    n = c.shape[0]
+    keep, ptrs = [c], [c.ctypes.data_as(_fp)]
+    for a in (diameters, shell_thicknesses, foreground):
+        if a is None:
+            ptrs.append(None)
+            continue
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        assert a.shape[0] == n, "one entry per sphere"
+        keep.append(a)
+        ptrs.append(a.ctypes.data_as(_fp))
+    return n, ptrs, keep
+
+
+def _regions(regions):
+    """[(type, (six or four floats), value), ...] or Region objects -> (Region array, n)."""
+    arr = (Region * max(len(regions), 1))()
+    for k, r in enumerate(regions):
+        if isinstance(r, Region):
+            arr[k] = r
+            continue
+        t, c, v = r
+        arr[k].type = int(t)
+        for j, x in enumerate(c):
+            arr[k].c[j] = float(x)
+        arr[k].value = float(v)
+    return arr, len(regions)
 
 
 def _morph_table(dxyz, b):
@@ -704,6 +750,31 @@ class Context:
                                                float(truncate_threshold), C.byref(A), C.byref(B)))
         return dst, A.value, B.value
 
+    def draw_spheres(self, background, centers, diameters=None, shell_thicknesses=None, foreground=None, mask=None,
+                     background_offset=0.0, background_rescale=1.0, background_normalize=False,
+                     foreground_normalize=False, want_outside=False):
+        """DrawSpheres (draw.hpp:238-457): spheres or shells at centers (n, 3) in voxels (x, y, z) over the rescaled
+        background; later spheres overwrite earlier ones.  None lists take the reference's defaults (diameter 0, solid,
+        foreground 1).  -> dst, or (dst, any_center_outside) with want_outside."""
+        nz, ny, nx = background.shape
+        dst = np.empty_like(background)
+        n, p, keep = _sphere_lists(centers, diameters, shell_thicknesses, foreground)
+        outside = C.c_int()
+        self._chk(self._L.visfd_hip_draw_spheres(self._h, _np(dst), _np(mask), _np(background), nx, ny, nz, p[0], p[1], p[2],
+                                                 p[3], n, float(background_offset), float(background_rescale),
+                                                 int(background_normalize), int(foreground_normalize), C.byref(outside)))
+        return (dst, bool(outside.value)) if want_outside else dst
+
+    def draw_regions(self, image, regions, mask=None, negative_means_subtract=False):
+        """DrawRegions (draw.hpp:90-224) on a copy of `image`: regions is a list of (REGION_RECT, (xmin, xmax, ymin, ymax,
+        zmin, zmax), value) and (REGION_SPHERE, (x0, y0, z0, r), value), acting in list order -> the new image."""
+        nz, ny, nx = image.shape
+        dst = np.array(image, np.float32, copy=True, order="C")
+        arr, n = _regions(regions)
+        self._chk(self._L.visfd_hip_draw_regions(self._h, _np(dst), _np(mask), nx, ny, nz, arr, n,
+                                                 int(negative_means_subtract)))
+        return dst
+
     def morph_sphere(self, op, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
         """DilateSphere / ErodeSphere / OpenSphere / CloseSphere / WhiteTopHatSphere / BlackTopHatSphere (op = MORPH_*,
         morphology.hpp:241-597).  dst (default: a copy of src, as filter_mrc starts its output) keeps its values where
@@ -1046,6 +1117,32 @@ class Context:
                                                    _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio),
                                                    float(truncate_threshold), C.byref(A), C.byref(B)))
         return A.value, B.value
+
+    def draw_spheres_dev(self, dst, background, centers, diameters=None, shell_thicknesses=None, foreground=None, mask=None,
+                         background_offset=0.0, background_rescale=1.0, background_normalize=False,
+                         foreground_normalize=False):
+        """draw_spheres on device tensors (the lists are host arrays); dst may be background.  -> any_center_outside"""
+        nz, ny, nx = background.shape
+        n, p, keep = _sphere_lists(centers, diameters, shell_thicknesses, foreground)
+        outside = C.c_int()
+        self._chk(self._L.visfd_hip_draw_spheres_dev(self._h, _dev(dst), _dev(mask), _dev(background), nx, ny, nz, p[0], p[1],
+                                                     p[2], p[3], n, float(background_offset), float(background_rescale),
+                                                     int(background_normalize), int(foreground_normalize),
+                                                     C.byref(outside)))
+        return bool(outside.value)
+
+    def draw_last_times(self):
+        """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""
+        ms = (C.c_float * 3)()
+        self._chk(self._L.visfd_hip_draw_last_times(self._h, ms))
+        return tuple(ms)
+
+    def draw_regions_dev(self, dst, regions, mask=None, negative_means_subtract=False):
+        """draw_regions on a device tensor, in place (the region list is a host array)."""
+        nz, ny, nx = dst.shape
+        arr, n = _regions(regions)
+        self._chk(self._L.visfd_hip_draw_regions_dev(self._h, _dev(dst), _dev(mask), nx, ny, nz, arr, n,
+                                                     int(negative_means_subtract)))
 
     def morph_sphere_dev(self, op, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
         """morph_sphere on device tensors; dst is read (top-hats, masked voxels) and written in place."""

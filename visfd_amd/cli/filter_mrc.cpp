@@ -23,6 +23,16 @@
 //                                                                      (settings.cpp:722-915, handlers.cpp:41-145)
 //   -find-minima FILE | -find-maxima FILE (both may be given) | -neighbor-connectivity N (1, 2 or 3) |
 //   -boundary-extrema | -ignore-boundary-extrema                       (settings.cpp:2202-2259, HandleExtrema)
+//   -draw-spheres|-spheres FILE | -draw-hollow-spheres FILE            (settings.cpp:2306-2340, HandleDrawSpheres)
+//   -diameters|-radii D (and -diameter, -sphere-diameter(s), -radius, -sphere-radius|-radii; "-voxels" forms: D is in voxels)
+//   -spheres-scale R | -sphere-shell-ratio R | -sphere-shell-thickness T | -sphere-shell-thickness-min T | -spheres-score
+//   -background B | -background-scale S | -background-auto | -foreground F | -spheres-normalize | -spheres01
+//                                                                      (settings.cpp:2343-2577; -random-spheres is not provided)
+//   -blob ... -out FILE        also draws the blobs found over the input image (handlers.cpp:933-978)
+//   -mask-rect XMIN XMAX YMIN YMAX ZMIN ZMAX | -mask-sphere X0 Y0 Z0 R | their -subtract forms   (settings.cpp:519-633,
+//                              filter_mrc.cpp:220-286; coordinates in voxels) | -mask-crds-units UNITS (read and, as in the
+//                              reference, without effect: settings.cpp:637-658)
+//   -find-minima / -find-maxima with -diameters D -radial-separation R: extrema closer than that are thinned (handlers.cpp:1165-1211)
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is written from the MRC2014 layout description (1024-byte header: nx,ny,nz,mode,
@@ -150,7 +160,7 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until main() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
@@ -172,6 +182,15 @@ struct Settings {
   string blob_min_file, blob_max_file;
   float score_lower = -std::numeric_limits<float>::infinity();
   float score_upper = std::numeric_limits<float>::infinity();
+  // sphere drawing (settings.cpp:107-120)
+  float sphere_decals_diameter = -1.0f;
+  bool sphere_decals_diameter_in_voxels = false;
+  float sphere_decals_foreground = 1.0f, sphere_decals_background = 0.0f, sphere_decals_background_scale = 1.0f;
+  bool sphere_decals_foreground_use_score = true, sphere_decals_background_norm = false, sphere_decals_foreground_norm = false;
+  float sphere_decals_scale = 1.0f;
+  float sphere_decals_shell_thickness = 1.0f, sphere_decals_shell_thickness_min = 1.0f;
+  bool sphere_decals_shell_thickness_is_ratio = true;
+  vector<SimpleRegion<float> > mask_regions;                  // -mask-rect, -mask-sphere and their -subtract forms, in order
   // blob list post-processing (-discard-blobs)
   vector<string> in_crds_files;
   string out_crds_file;
@@ -225,8 +244,22 @@ float morph_num(const vector<string>& v, size_t i, const string& flag, const cha
   try { return std::stof(v[i]); } catch (...) { throw VisfdErr(msg); }
 }
 
+// the sphere flags' arguments (settings.cpp:2306-2577): present, not empty and, unless the number may be negative, not
+// starting with '-'
+float sphere_num(const vector<string>& v, size_t i, const string& flag, const char* what, bool may_be_negative = false) {
+  const string msg = "Error: The " + flag + " argument must be followed by " + what + "\n";
+  if (i >= v.size() || v[i].empty() || (!may_be_negative && v[i][0] == '-')) throw VisfdErr(msg);
+  try { return std::stof(v[i]); } catch (...) { throw VisfdErr(msg); }
+}
+
+bool one_of(const string& f, std::initializer_list<const char*> names) {
+  for (const char* n : names) if (f == n) return true;
+  return false;
+}
+
 Settings parse(int argc, char** argv) {
   Settings s;
+  bool user_set_thickness_manually = false, user_set_background_scale_manually = false;   // settings.cpp:260-261
   vector<string> v(argv + 1, argv + argc);
   for (size_t i = 0; i < v.size();) {
     const string& f = v[i];
@@ -425,6 +458,111 @@ Settings parse(int argc, char** argv) {
       i += 2;
     }
     else if (f == "-detection-threshold") { need(1); s.hessian_thr = num(v, i + 1, f); s.hessian_thr_is_fraction = false; i += 2; }
+    else if (f == "-draw-spheres" || f == "-spheres" || f == "-draw-hollow-spheres") {   // settings.cpp:2306-2340
+      if (i + 1 >= v.size() || v[i + 1].empty() || v[i + 1][0] == '-')
+        throw VisfdErr("Error: The " + f + " argument must be followed by a file name\n");
+      s.type = Settings::DRAW_SPHERES;
+      s.in_crds_files.push_back(v[i + 1]);
+      if (f == "-draw-hollow-spheres" && !user_set_thickness_manually) {
+        s.sphere_decals_shell_thickness = 0.05f;
+        s.sphere_decals_shell_thickness_is_ratio = true;
+        s.sphere_decals_shell_thickness_min = 1.0f;
+      }
+      i += 2;
+    }
+    else if (one_of(f, {"-diameters", "-diameter", "-sphere-diameters", "-sphere-diameter", "-diameters-voxels", "-diameter-voxels",
+                        "-sphere-diameters-voxels", "-sphere-diameter-voxels"})) {   // settings.cpp:2343-2378
+      s.sphere_decals_diameter = sphere_num(v, i + 1, f, "a number");
+      s.sphere_decals_diameter_in_voxels = f.size() > 7 && f.substr(f.size() - 7) == "-voxels";
+      i += 2;
+    }
+    else if (one_of(f, {"-radii", "-radius", "-sphere-radii", "-sphere-radius", "-radii-voxels", "-radius-voxels",
+                        "-sphere-radii-voxels", "-sphere-radius-voxels"})) {         // settings.cpp:2381-2416
+      s.sphere_decals_diameter = (float)(sphere_num(v, i + 1, f, "a number") * 2.0);
+      s.sphere_decals_diameter_in_voxels = f.size() > 7 && f.substr(f.size() - 7) == "-voxels";
+      i += 2;
+    }
+    else if (f == "-spheres-scale" || f == "-sphere-scale") {                        // settings.cpp:2419-2434
+      s.sphere_decals_scale = sphere_num(v, i + 1, f, "a number:\n"
+                                         "       the ratio of the displyed sphere size to the diameter detected (usually 1).");
+      i += 2;
+    }
+    else if (f == "-sphere-shell-ratio" || f == "-spheres-shell-ratio") {            // settings.cpp:2437-2453
+      s.sphere_decals_shell_thickness = sphere_num(v, i + 1, f, "a numbers:\n"
+                                                   "       -the ratio of the shell thickness to the sphere diameter");
+      s.sphere_decals_shell_thickness_is_ratio = true;
+      user_set_thickness_manually = true;
+      i += 2;
+    }
+    else if (one_of(f, {"-sphere-shell-thickness-min", "-sphere-shell-thicknesses-min", "-spheres-shell-thickness-min",
+                        "-spheres-shell-thicknesses-min"})) {                         // settings.cpp:2456-2472
+      s.sphere_decals_shell_thickness_min = sphere_num(v, i + 1, f, "a number");
+      user_set_thickness_manually = true;
+      i += 2;
+    }
+    else if (one_of(f, {"-sphere-shell-thickness", "-sphere-shell-thicknesses", "-spheres-shell-thickness",
+                        "-spheres-shell-thicknesses"})) {                             // settings.cpp:2475-2492
+      s.sphere_decals_shell_thickness = sphere_num(v, i + 1, f, "a number");
+      s.sphere_decals_shell_thickness_is_ratio = false;
+      user_set_thickness_manually = true;
+      i += 2;
+    }
+    else if (f == "-spheres-score" || f == "-sphere-score") { s.sphere_decals_foreground_use_score = true; i += 1; }
+    else if (f == "-background" || f == "-spheres-background" || f == "-sphere-background") {   // settings.cpp:2502-2518
+      s.sphere_decals_background_scale = 0.0f;
+      s.sphere_decals_background = sphere_num(v, i + 1, f, "a number:\n"
+                                              "       the voxel intensity value outside the sphere (normally 0).", true);
+      i += 2;
+    }
+    else if (f == "-background-scale" || f == "-spheres-background-scale" || f == "-sphere-background-scale") {   // :2521-2538
+      s.sphere_decals_background_scale = sphere_num(v, i + 1, f, "a number, usually between 0 and 1:\n"
+                                                    "       how much to supress fluctuations in the original background image.");
+      user_set_background_scale_manually = true;
+      i += 2;
+    }
+    else if (f == "-foreground" || f == "-spheres-foreground" || f == "-sphere-foreground") {   // settings.cpp:2541-2556
+      s.sphere_decals_foreground_use_score = false;
+      s.sphere_decals_foreground = sphere_num(v, i + 1, f, "a number:\n"
+                                              "       the voxel intensity value on the sphere (normally 1).", true);
+      i += 2;
+    }
+    else if (f == "-background-auto") {                                              // settings.cpp:2558-2564
+      s.sphere_decals_background_norm = true;
+      if (!user_set_background_scale_manually) s.sphere_decals_background_scale = 0.3f;
+      i += 1;
+    }
+    else if (f == "-spheres-normalize" || f == "-sphere-normalize") { s.sphere_decals_foreground_norm = true; i += 1; }
+    else if (one_of(f, {"-spheres01", "-spheres-01", "-sphere01", "-sphere-01"})) { s.sphere_decals_foreground_norm = false; i += 1; }
+    else if (f == "-random-spheres")
+      throw VisfdErr("Error: -random-spheres is not provided by this program (it needs the reference's random numbers).\n");
+    else if (one_of(f, {"-mask-rect", "-mask-rectangle", "-mask-rect-subtract", "-mask-rectangle-subtract", "-mask-sphere",
+                        "-mask-sphere-subtract"})) {                                   // settings.cpp:519-633
+      const bool sphere = f.find("sphere") != string::npos, subtract = f.find("subtract") != string::npos;
+      const size_t k = sphere ? 4 : 6;
+      const string msg = "Error: The " + f + " argument must be followed by " + (sphere ? "4" : "6") + " numbers.\n";
+      float x[6] = {0, 0, 0, 0, 0, 0};
+      for (size_t j = 1; j <= k; j++) {
+        if (i + j >= v.size() || v[i + j].empty()) throw VisfdErr(msg);
+        try { x[j - 1] = std::stof(v[i + j]); } catch (...) { throw VisfdErr(msg); }
+      }
+      SimpleRegion<float> region;
+      region.value = subtract ? -1.0f : 1.0f;
+      if (sphere) {
+        region.type = SimpleRegion<float>::SPHERE;
+        region.data.sphere.x0 = x[0]; region.data.sphere.y0 = x[1]; region.data.sphere.z0 = x[2]; region.data.sphere.r = x[3];
+      } else {
+        region.type = SimpleRegion<float>::RECT;
+        region.data.rect.xmin = x[0]; region.data.rect.xmax = x[1]; region.data.rect.ymin = x[2];
+        region.data.rect.ymax = x[3]; region.data.rect.zmin = x[4]; region.data.rect.zmax = x[5];
+      }
+      s.mask_regions.push_back(region);
+      i += k + 1;
+    }
+    else if (one_of(f, {"-mask-crds-units", "-mask-coords-units", "-mask-coordinates-units", "-mask-rect-units"})) {
+      // settings.cpp:637-658: the reference reads the word and, its two tests being unsatisfiable, changes nothing:
+      // mask coordinates are always voxels
+      need(1); i += 2;
+    }
     else if (f == "-slab") {
       need(3);
       s.slab_rank = (int)num(v, i + 1, f); s.slab_world = (int)num(v, i + 2, f); s.slab_id_file = v[i + 3];
@@ -479,6 +617,9 @@ Settings parse(int argc, char** argv) {
     else throw VisfdErr("Error: Unrecognized (or unsupported on the GPU hot path) argument: \"" + f + "\"\n");
   }
   if (s.in.empty()) throw VisfdErr("Error: You must specify an input file (-in).\n");
+  if (s.slab_world > 0 && (s.type == Settings::DRAW_SPHERES || !s.mask_regions.empty() || (s.type == Settings::BLOB && !s.out.empty())))
+    throw VisfdErr("Error: -slab does not draw: -draw-spheres, the -mask-rect / -mask-sphere flags and \"-blob ... -out\"\n"
+                   "       need the whole image in one process.\n");
   if (!s.must_link_filename.empty()) s.must_link_in_voxels = read_must_link_file(s.must_link_filename, s);
   if (s.type == Settings::SURFACE_RIDGE) s.tv_sigma *= s.width_a[0];   // settings.cpp:3535-3540
   if (s.cluster_connected_voxels && s.type != Settings::SURFACE_RIDGE)
@@ -557,7 +698,7 @@ bool read_must_link_file(const string& path, Settings& s) {
 }
 
 bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vector<float>& diameters,
-                    vector<float>& scores) {
+                    vector<float>& scores, float score_default, float diameter_factor) {
   std::ifstream f(path.c_str());
   if (!f) throw VisfdErr("Error: unable to open \"" + path + "\" for reading.\n");
   bool parens = false;
@@ -587,27 +728,32 @@ bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vec
     crds.push_back(c);
     float d = nums.size() > 3 ? nums[3] : -1.0f;
     if (d < 0) d = -1.0f;
-    diameters.push_back(d);
-    scores.push_back(nums.size() > 4 ? nums[4] : 1.0f);   // default score = sphere_decals_foreground (settings.cpp: 1)
+    diameters.push_back(d * diameter_factor);   // file_io.hpp:470-477: the "no diameter" mark is multiplied too
+    scores.push_back(nums.size() > 4 ? nums[4] : score_default);
     i_line++;
   }
   return parens;
 }
 
-// HandleBlobsNonmaxSuppression, bin/filter_mrc/handlers.cpp:421-617 (without the supervised-learning tail)
-void handle_blob_nonmax(const Settings& s, const float vw[3], float const* const* const* mask, const int size[3]) {
+// HandleBlobsNonmaxSuppression, bin/filter_mrc/handlers.cpp:421-617 (without the supervised-learning tail): the lists of
+// the blob files in voxels, filtered by score, by the mask (when one is passed) and by overlap
+void read_and_filter_blobs(const Settings& s, const float vw[3], float const* const* const* mask, const int size[3],
+                           vector<std::array<float, 3> >& crds, vector<float>& diameters, vector<float>& scores) {
   const float w = vw[0];
   const float inf = std::numeric_limits<float>::infinity();
-  vector<std::array<float, 3> > crds;
-  vector<float> diameters, scores;
   for (size_t I = 0; I < s.in_crds_files.size(); I++) {
     vector<std::array<float, 3> > c;
     vector<float> d, sc;
-    const bool in_voxels = read_blob_file(s.in_crds_files[I], c, d, sc);
+    const bool in_voxels = read_blob_file(s.in_crds_files[I], c, d, sc, s.sphere_decals_foreground, s.sphere_decals_scale);
     if (!in_voxels && w > 0.0f)
       for (size_t i = 0; i < c.size(); i++) {
         for (int k = 0; k < 3; k++) c[i][k] = (float)std::floor((c[i][k] / w) + 0.5);   // handlers.cpp:458
         if (d[i] != -1.0f) d[i] /= w;
+      }
+    if (s.sphere_decals_diameter >= 0)   // handlers.cpp:474-500: -diameters / -radii replace every diameter of the file
+      for (size_t i = 0; i < d.size(); i++) {
+        d[i] = s.sphere_decals_diameter;
+        if (!s.sphere_decals_diameter_in_voxels && w > 0.0f) d[i] /= w;
       }
     crds.insert(crds.end(), c.begin(), c.end());
     diameters.insert(diameters.end(), d.begin(), d.end());
@@ -636,6 +782,13 @@ void handle_blob_nonmax(const Settings& s, const float vw[3], float const* const
                             s.nonmax_max_overlap_small, SORT_DECREASING_MAGNITUDE, &cerr);
   }
   cerr << " " << crds.size() << " blobs remaining" << std::endl;
+}
+
+void handle_blob_nonmax(const Settings& s, const float vw[3], float const* const* const* mask, const int size[3]) {
+  const float w = vw[0];
+  vector<std::array<float, 3> > crds;
+  vector<float> diameters, scores;
+  read_and_filter_blobs(s, vw, mask, size, crds, diameters, scores);
   if (!s.out_crds_file.empty()) {
     const double wp = w > 0.0f ? (double)w : 1.0;
     std::ofstream out(s.out_crds_file.c_str());
@@ -644,6 +797,36 @@ void handle_blob_nonmax(const Settings& s, const float vw[3], float const* const
       out << crds[i][0] * wp << " " << crds[i][1] * wp << " " << crds[i][2] * wp << " " << diameters[i] * wp << " "
           << scores[i] << std::endl;
   }
+}
+
+// The thickness of one drawn shell (handlers.cpp:751-758 and :957-964): a ratio times the diameter, and where that falls
+// below the minimum, 1.0 -- not the minimum; a thickness given in voxels is taken as it is
+float shell_thickness_of(const Settings& s, float diameter) {
+  float th = s.sphere_decals_shell_thickness;
+  if (s.sphere_decals_shell_thickness_is_ratio) {
+    th *= diameter;
+    if (th < s.sphere_decals_shell_thickness_min) th = 1.0f;
+  }
+  return th;
+}
+
+// HandleDrawSpheres, bin/filter_mrc/handlers.cpp:712-780
+void handle_draw_spheres(const Settings& s, const float vw[3], const int size[3], Mrc& tomo_in, Mrc& tomo_out,
+                         float const* const* const* mask) {
+  vector<std::array<float, 3> > crds;
+  vector<float> diameters, scores;
+  read_and_filter_blobs(s, vw, nullptr, size, crds, diameters, scores);   // blobs outside the mask are kept
+  const size_t n = diameters.size();
+  if (!s.sphere_decals_foreground_use_score)
+    for (size_t i = 0; i < n; i++) scores[i] = s.sphere_decals_foreground;
+  vector<float> th(n);
+  for (size_t i = 0; i < n; i++) th[i] = shell_thickness_of(s, diameters[i]);
+  std::reverse(crds.begin(), crds.end());
+  std::reverse(diameters.begin(), diameters.end());
+  std::reverse(th.begin(), th.end());
+  std::reverse(scores.begin(), scores.end());
+  DrawSpheres(size, tomo_out.a, mask, crds, &diameters, &th, &scores, tomo_in.a, s.sphere_decals_background,
+              s.sphere_decals_background_scale, s.sphere_decals_background_norm, s.sphere_decals_foreground_norm);
 }
 
 // HandleBinning, bin/filter_mrc/handlers.cpp:2361-2425: the image (and the mask) shrink by `bin` per axis
@@ -870,6 +1053,28 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < s.blob_diameters.size(); k++) s.blob_diameters[k] /= vw[0];
     s.morph_r /= vw[0];      // filter_mrc.cpp:297-298 (bmax is not a length)
     s.morph_rmax /= vw[0];
+    if (!s.sphere_decals_shell_thickness_is_ratio) s.sphere_decals_shell_thickness /= vw[0];   // filter_mrc.cpp:333-336
+    else s.sphere_decals_shell_thickness /= bin;
+    if (!s.mask_regions.empty()) {   // filter_mrc.cpp:220-286
+      if (!mask.loaded) {
+        mask.alloc(size[0], size[1], size[2]);
+        std::memset(mask.data(), 0, mask.nvox() * 4);
+        std::memcpy(mask.raw_header, tomo_in.raw_header, 1024);
+        for (int d = 0; d < 3; d++) mask.cella[d] = tomo_in.cella[d];
+        mask.loaded = true;
+      }
+      const float scale = (float)(1.0 / bin);   // always voxels (see -mask-crds-units): only binning rescales them
+      for (size_t k = 0; k < s.mask_regions.size(); k++) {
+        SimpleRegion<float>& g = s.mask_regions[k];
+        if (g.type == SimpleRegion<float>::RECT) {
+          g.data.rect.xmin *= scale; g.data.rect.xmax *= scale; g.data.rect.ymin *= scale;
+          g.data.rect.ymax *= scale; g.data.rect.zmin *= scale; g.data.rect.zmax *= scale;
+        } else {
+          g.data.sphere.r *= scale; g.data.sphere.x0 *= scale; g.data.sphere.y0 *= scale; g.data.sphere.z0 *= scale;
+        }
+      }
+      DrawRegions(size, mask.a, static_cast<const float* const* const*>(nullptr), s.mask_regions, true);
+    }
 
     tomo_out.alloc(size[0], size[1], size[2]);
     std::memcpy(tomo_out.data(), tomo_in.data(), tomo_in.nvox() * 4);   // filter_mrc.cpp:398
@@ -993,15 +1198,21 @@ int main(int argc, char** argv) {
       BlobDogD(size, tomo_in.a, M, s.blob_diameters, &cmin, &cmax, &dmin, &dmax, &smin, &smax, s.blob_aspect_ratio, s.delta, ratio,
                s.score_upper, s.score_lower, false, &cerr);
       // physical units + sort by score (handlers.cpp:853-909), ties keep list order
+      vector<float> draw_d[2], draw_s[2];   // what the picture below is drawn from: physical diameters, sorted where a file is written
       for (int side = 0; side < 2; side++) {
         const string fname = (side ? s.blob_max_file : s.blob_min_file).empty() ? string() : (side ? s.blob_max_file : s.blob_min_file) + slab_suffix;
-        if (fname.empty()) continue;
         vector<std::array<float, 3> >& c = side ? cmax : cmin;
         vector<float>& dia = side ? dmax : dmin;
         vector<float>& sc = side ? smax : smin;
         vector<size_t> idx(c.size());
         for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t p, size_t q) { return side ? sc[p] > sc[q] : sc[p] < sc[q]; });
+        if (!fname.empty())
+          std::stable_sort(idx.begin(), idx.end(), [&](size_t p, size_t q) { return side ? sc[p] > sc[q] : sc[p] < sc[q]; });
+        for (size_t k = 0; k < idx.size(); k++) {
+          draw_d[side].push_back(dia[idx[k]] * vw[0]);
+          draw_s[side].push_back(sc[idx[k]]);
+        }
+        if (fname.empty()) continue;
         std::ofstream out(fname.c_str());
         if (!out) throw VisfdErr("Error: unable to open \"" + fname + "\" for writing.\n");
         for (size_t k = 0; k < idx.size(); k++) {
@@ -1009,6 +1220,26 @@ int main(int argc, char** argv) {
           out << c[i][0] * vw[0] << " " << c[i][1] * vw[1] << " " << c[i][2] * vw[2] << " " << dia[i] * vw[0] << " "
               << sc[i] << "\n";
         }
+      }
+      if (!s.out.empty()) {
+        // handlers.cpp:933-978: every blob as a shell over the input image, minima first, then maxima reversed.  The
+        // reference sorts the diameters and scores it writes to a file and leaves the voxel coordinates in detection
+        // order, then draws from both: so does this.
+        vector<std::array<float, 3> > crds(cmin);
+        crds.insert(crds.end(), cmax.rbegin(), cmax.rend());
+        vector<float> dia(draw_d[0]), sc(draw_s[0]);
+        dia.insert(dia.end(), draw_d[1].rbegin(), draw_d[1].rend());
+        sc.insert(sc.end(), draw_s[1].rbegin(), draw_s[1].rend());
+        vector<float> th(crds.size());
+        for (size_t i = 0; i < crds.size(); i++) {
+          dia[i] = dia[i] / vw[0];
+          th[i] = s.sphere_decals_shell_thickness;
+          if (s.sphere_decals_shell_thickness_is_ratio) th[i] *= dia[i];
+          dia[i] *= s.sphere_decals_scale;
+          if (th[i] < s.sphere_decals_shell_thickness_min) th[i] = 1.0f;
+        }
+        DrawSpheres(size, tomo_out.a, M, crds, &dia, &th, &sc, tomo_in.a, s.sphere_decals_background,
+                    s.sphere_decals_background_scale, s.sphere_decals_background_norm, false);
       }
     } else if (s.type == Settings::MORPHOLOGY) {
       // HandleDilation ... HandleTopHatBlack, handlers.cpp:41-145: tomo_out starts as a copy of the input (the top-hats read it)
@@ -1027,8 +1258,7 @@ int main(int argc, char** argv) {
           BlackTopHatSphere(s.morph_r, size, tomo_in.a, tomo_out.a, M, s.morph_rmax, s.morph_bmax, &cerr); break;
       }
     } else if (s.type == Settings::FIND_EXTREMA) {
-      // HandleExtrema, handlers.cpp:1086-1245 (without the optional thinning by a sphere diameter, :1165-1211: this
-      // program has none of the -sphere* / -diameters flags that would switch it on)
+      // HandleExtrema, handlers.cpp:1086-1245
       std::memset(tomo_out.data(), 0, tomo_out.nvox() * 4);
       vector<std::array<float, 3> > crds[2];
       vector<float> scores[2];
@@ -1039,6 +1269,17 @@ int main(int argc, char** argv) {
                        s.find_minima ? &nvoxels[0] : nullptr, s.find_maxima ? &nvoxels[1] : nullptr, s.score_upper,
                        s.score_lower, s.neighbor_connectivity, s.extrema_on_boundary, tomo_out.a, &cerr);
       cerr << "Found " << num_extrema << " extrema" << std::endl;
+      // handlers.cpp:1165-1211: extrema closer than a diameter (as given: it is not divided by the voxel width) times the
+      // separation ratio are thinned, the better score staying.  The voxel counts are not thinned with them: entry k of
+      // the thinned list is written with count k of the full one, as in the reference.
+      if (s.sphere_decals_diameter > 0 && s.nonmax_min_radial_separation_ratio > 0.0f)
+        for (int side = 0; side < 2; side++) {
+          vector<float> diam(crds[side].size(), s.sphere_decals_diameter * s.nonmax_min_radial_separation_ratio);
+          if (!crds[side].empty() && M) DiscardMaskedBlobs(crds[side], diam, scores[side], M, size);
+          DiscardOverlappingBlobs(crds[side], diam, scores[side], s.nonmax_min_radial_separation_ratio,
+                                  s.nonmax_max_overlap_large, s.nonmax_max_overlap_small,
+                                  side ? SORT_DECREASING : SORT_INCREASING, &cerr);
+        }
       for (int side = 0; side < 2; side++) {
         const string& fname = side ? s.find_maxima_file : s.find_minima_file;
         if (crds[side].empty() || !(side ? s.find_maxima : s.find_minima)) continue;   // no file for an empty list
@@ -1052,6 +1293,8 @@ int main(int argc, char** argv) {
       }
     } else if (s.type == Settings::BLOB_NONMAX) {
       handle_blob_nonmax(s, vw, M, size);
+    } else if (s.type == Settings::DRAW_SPHERES) {
+      handle_draw_spheres(s, vw, size, tomo_in, tomo_out, M);
     } else if (s.type == Settings::SURFACE_RIDGE) {
       cerr << "filter_type = surface ridge detector\n";
       const int order = s.ridges_are_maxima ? VISFD_HIP_INCREASING_EIVALS : VISFD_HIP_DECREASING_EIVALS;  // handlers.cpp:1524-1535
@@ -1177,7 +1420,7 @@ int main(int argc, char** argv) {
       if (mask.loaded) unbin_image(mask, size_orig, cella_orig);
     }
     // filter_mrc.cpp:765-776: after everything else, voxels outside the mask take the "masked" brightness
-    if (mask.loaded && s.type != Settings::BLOB && s.type != Settings::BLOB_NONMAX) {
+    if (mask.loaded && s.type != Settings::BLOB_NONMAX) {
       float* o = tomo_out.data();
       const float* mp = mask.data();
       for (size_t i = 0; i < tomo_out.nvox(); i++)

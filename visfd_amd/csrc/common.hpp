@@ -63,6 +63,8 @@ enum Slot {
   WS_EXT_LIST,                     // extrema: the unsorted lists (index, score, voxels)
   WS_EXT_RANKS,                    // extrema: listed roots in raster order and their sorted positions, for the label image
   WS_F3D_TAB,                      // general 3-D filter: the table's non-zero entries on the device (what they were built from: visfd_hip_ctx::f3d_raw)
+  WS_DRAW_OWNER,                   // DrawSpheres: the owner volume, one uint32 per voxel: the last sphere that holds it, plus one (csrc/draw.hip)
+  WS_DRAW_TAB,                     // DrawSpheres: per-sphere values, counts, clipped boxes and running row counts; DrawRegions: its one flag
   WS_NSLOTS
 };
 
@@ -92,6 +94,7 @@ struct visfd_hip_options {
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
+  int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
 };
 
@@ -115,6 +118,7 @@ struct visfd_hip_ctx {
   int64_t f3d_ncols = 0;
   float f3d_den = 0.0f;               // and their float sum in order
   int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
+  float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };
 

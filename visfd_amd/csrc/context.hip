@@ -52,6 +52,7 @@ const OptionDesc kOptions[] = {
     {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
+    {"draw_time", &visfd_hip_options::draw_time, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {
