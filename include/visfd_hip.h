@@ -69,7 +69,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * _dogg3d_table, _filter3d[_dev], _filter3d_last_path, _apply_ggauss[_dev],
                                      * _apply_dogg[_dev] and _local_fluctuations_gen[_dev]; then the drawing entries
                                      * visfd_hip_draw_spheres[_dev], visfd_hip_draw_regions[_dev] and
-                                     * visfd_hip_draw_last_times) */
+                                     * visfd_hip_draw_last_times; then the watershed: visfd_hip_watershed_host,
+                                     * visfd_hip_watershed[_dev] and visfd_hip_watershed_last_stats) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -101,6 +102,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    LDS-tiled kernel; results are bit-identical either way
  *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
  *                    (visfd_hip_draw_last_times); default 0
+ *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
+ *                    markers they always do); labels and lists are identical either way; default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -338,6 +341,51 @@ int visfd_hip_find_extrema_dev(visfd_hip_ctx*, const float* src, const float* ma
                                int64_t* min_index, float* min_score, int64_t* min_nvoxels, int64_t min_cap, int64_t* n_min,
                                int64_t* max_index, float* max_score, int64_t* max_nvoxels, int64_t max_cap, int64_t* n_max,
                                int32_t* labels);
+
+/* ---- m3: watershed segmentation, Watershed (lib/visfd/segmentation.hpp:65-559) --------------------------------------- */
+/* Meyer's flood from the image's local minima (start_from_minima) or maxima, or from markers.  s = value, or -value when
+ * starting from maxima; a voxel is eligible when mask != 0 and s <= SIGN * halt_threshold.  The seeds are the plateaus
+ * that visfd_hip_find_extrema lists with that threshold and allow_borders, numbered 0 .. n-1 in its list order; basin k
+ * is labelled k + 1.  With show_boundaries a voxel that meets an already labelled voxel of another basin becomes
+ * boundary.  labels (int32) is written everywhere: basin numbers, label_boundary on boundaries, label_undefined on
+ * unmasked voxels that are not eligible (or were never reached), and -1 where mask == 0 whatever label_undefined is (the
+ * reference initialises its image to -1 and relabels unmasked voxels only).  DESIGN.md 4.8 states the result as a function
+ * of each voxel's neighbourhood; without markers the context faces compute that on the device (csrc/watershed.hip).
+ * markers (int32, NULL: none): the seeds are then the first voxel in raster order of each distinct positive label on a
+ * voxel with mask != 0, numbered by first appearance, and basins get their marker's label back at the end (the reference's
+ * relabelling with its quirks: unmapped labels become label_undefined).  Marked calls run the sequential flood on the
+ * host on every face (the _dev face copies down and back and waits for the stream).
+ * halt_threshold is taken as given: Watershed's replacement of +inf by -inf when starting from maxima is the caller's
+ * (visfd_hip.hpp and filter_mrc do it).  connectivity 1, 2, 3 as for visfd_hip_find_extrema, whose size limits hold too.
+ * basin_index / basin_score (host arrays on every face, each may be NULL): the seeds' voxel index ix + nx * (iy + ny * iz)
+ * and value.  *n_basins receives the count on every return but VISFD_HIP_EINVAL and device failures (the image is refused
+ * before its seeds are sought); basin_cap == 0 writes nothing of the lists; 0 < basin_cap < count: VISFD_HIP_ECAPACITY,
+ * and nothing but the count is written (labels neither).
+ * VISFD_HIP_EINVAL, labels untouched: an unmasked NaN voxel or a NaN threshold (the flood's heap order is then no strict
+ * weak order); connectivity outside 1..3; the size limits; more than 2^24 basins (the reference carries the basin through a
+ * float); labels overlapping src, mask or markers.
+ * Both context faces return with the context's stream idle.  Temporaries of the device path: 10 bytes per voxel (kind,
+ * link, carried basin, one byte of feeder marks and then boundary states) next to the 9 of the seed search, 4 bytes per basin; the host face stages src,
+ * mask and labels (4 bytes per voxel each).  visfd_hip_watershed_host needs no context and no device. */
+#define VISFD_HIP_WATERSHED_MAX_BASINS 16777216
+int visfd_hip_watershed_host(const float* src, const float* mask, const int32_t* markers, int64_t nx, int64_t ny, int64_t nz,
+                             float halt_threshold, int start_from_minima, int connectivity, int show_boundaries,
+                             int32_t label_boundary, int32_t label_undefined, int32_t* labels,
+                             int64_t* basin_index, float* basin_score, int64_t basin_cap, int64_t* n_basins);
+int visfd_hip_watershed(visfd_hip_ctx*, const float* src, const float* mask, const int32_t* markers, int64_t nx, int64_t ny,
+                        int64_t nz, float halt_threshold, int start_from_minima, int connectivity, int show_boundaries,
+                        int32_t label_boundary, int32_t label_undefined, int32_t* labels,
+                        int64_t* basin_index, float* basin_score, int64_t basin_cap, int64_t* n_basins);
+int visfd_hip_watershed_dev(visfd_hip_ctx*, const float* src, const float* mask, const int32_t* markers, int64_t nx,
+                            int64_t ny, int64_t nz, float halt_threshold, int start_from_minima, int connectivity,
+                            int show_boundaries, int32_t label_boundary, int32_t label_undefined, int32_t* labels,
+                            int64_t* basin_index, float* basin_score, int64_t basin_cap, int64_t* n_basins);
+/* the context's last successful watershed call: out[0] the path it took, out[1] label rounds (launches of the propagation
+ * kernel, the final unchanged one included), out[2] boundary rounds, out[3] basins; all -1 before the first call, rounds 0
+ * on the host path */
+#define VISFD_HIP_WATERSHED_PATH_HOST 0
+#define VISFD_HIP_WATERSHED_PATH_DEVICE 1
+int visfd_hip_watershed_last_stats(visfd_hip_ctx*, int64_t out[4]);
 
 /* ---- a6: ApplyDog, lib/visfd/filter3d.hpp:1338-1402 -------------------------------------------- */
 int visfd_hip_apply_dog(visfd_hip_ctx*, const float* src, float* dst, const float* mask,

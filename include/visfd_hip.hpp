@@ -17,6 +17,7 @@
 //   TV3D         lib/visfd/feature.hpp:1645-1647, TVDenseStick :1711-1901 (with its normalize / diagonalize_dest steps)
 //   BlobDogNM / _BlobDogNM  bin/filter_mrc/feature_variants.hpp:393-580
 //   Alloc3D / Dealloc3D  lib/visfd/alloc3d.hpp:25, :75
+//   Watershed    lib/visfd/segmentation.hpp:65-82
 //   Filter3D     lib/visfd/filter3d.hpp:37-530;  GenFilterGenGauss3D :546-638;  LocalFluctuations[ByRadius] :1698-1926
 //   CompactMultiChannelImage3D  lib/visfd/multichannel_image3d.hpp:41-204
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
@@ -558,6 +559,67 @@ size_t FindMaxima(int const image_size[3], float const* const* const* aaafI, flo
                   std::ostream* pReportProgress = nullptr) {
   return _FindExtrema(image_size, aaafI, aaafMask, maxima_crds, maxima_scores, maxima_nvoxels, false, threshold,
                       connectivity, allow_borders, aaaiDest, pReportProgress);
+}
+
+// ---- watershed segmentation: lib/visfd/segmentation.hpp:65-559 -------------------------------------------------------------
+// The reference's signature and defaults with Scalar = float and any integer Label.  aaaiDest is written everywhere: basin
+// k of the seed list as k + 1 (or its marker's label), label_boundary, label_undefined, and -1 where the mask is 0.  Labels
+// travel through the C ABI as int32: marker labels, label_boundary and label_undefined outside its range are refused.
+// Without markers the labels are computed on the GPU; with markers the sequential flood runs on the host (visfd_hip.h).
+// The progress stream is ignored.
+template <typename Label, typename Coordinate>
+size_t Watershed(int const image_size[3], float const* const* const* aaafSource, Label*** aaaiDest,
+                 float const* const* const* aaafMask, Label const* const* const* aaaiMarkers = nullptr,
+                 float halt_threshold = std::numeric_limits<float>::infinity(), bool start_from_minima = true,
+                 int connectivity = 1, bool show_boundaries = true, Label label_boundary = 0, Label label_undefined = -1,
+                 std::vector<std::array<Coordinate, 3> >* pv_basin_locations = nullptr,
+                 std::vector<float>* pv_basin_scores = nullptr, std::ostream* = nullptr) {
+  hip_detail::require_contiguous(aaafSource, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  const float inf = std::numeric_limits<float>::infinity();
+  if (!start_from_minima && halt_threshold == inf) halt_threshold = -inf;   // segmentation.hpp:125-134
+  const size_t nvox = (size_t)image_size[0] * image_size[1] * image_size[2];
+  const long long lo = std::numeric_limits<int32_t>::min(), hi = std::numeric_limits<int32_t>::max();
+  if ((long long)label_boundary < lo || (long long)label_boundary > hi || (long long)label_undefined < lo ||
+      (long long)label_undefined > hi)
+    throw VisfdErr("visfd_hip: Watershed: label_boundary and label_undefined must fit 32 bits");
+  std::vector<int32_t> labels(nvox), markers(aaaiMarkers ? nvox : 0);
+  if (aaaiMarkers) {
+    size_t i = 0;
+    for (int iz = 0; iz < image_size[2]; iz++)
+      for (int iy = 0; iy < image_size[1]; iy++)
+        for (int ix = 0; ix < image_size[0]; ix++, i++) {
+          const long long m = (long long)aaaiMarkers[iz][iy][ix];
+          if (m > hi) throw VisfdErr("visfd_hip: Watershed: marker labels must fit 32 bits");
+          markers[i] = m < 0 ? -1 : (int32_t)m;   // entries <= 0 are ignored alike
+        }
+  }
+  const int64_t cap0 = (int64_t)(nvox / 32) > 65536 ? (int64_t)(nvox / 32) : 65536;
+  std::vector<int64_t> index((size_t)cap0);
+  std::vector<float> score((size_t)cap0);
+  int64_t n = 0;
+  for (;;) {
+    const int rc = visfd_hip_watershed(hip_detail::context(), hip_detail::flat(aaafSource), hip_detail::flat(aaafMask),
+                                       aaaiMarkers ? markers.data() : nullptr, image_size[0], image_size[1], image_size[2],
+                                       halt_threshold, start_from_minima ? 1 : 0, connectivity, show_boundaries ? 1 : 0,
+                                       (int32_t)label_boundary, (int32_t)label_undefined, labels.data(), index.data(),
+                                       score.data(), (int64_t)index.size(), &n);
+    if (rc != VISFD_HIP_ECAPACITY) {
+      hip_detail::check(rc);
+      break;
+    }
+    index.resize((size_t)n);
+    score.resize((size_t)n);
+  }
+  index.resize((size_t)n);
+  score.resize((size_t)n);
+  hip_detail::assign_crds(pv_basin_locations, index, image_size);
+  hip_detail::assign(pv_basin_scores, score);
+  size_t i = 0;
+  for (int iz = 0; iz < image_size[2]; iz++)
+    for (int iy = 0; iy < image_size[1]; iy++)
+      for (int ix = 0; ix < image_size[0]; ix++, i++) aaaiDest[iz][iy][ix] = (Label)labels[i];
+  return (size_t)n;
 }
 
 // ---- Filter3D: lib/visfd/filter3d.hpp:37-530 ---------------------------------------------------------------------------

@@ -58,6 +58,11 @@ _VOL = [_vp, _vp, _vp, _i64, _i64, _i64]  # src, dst, mask, nx, ny, nz  (pointer
 # find_minima, find_maxima, both thresholds, connectivity, allow_borders, then (index, score, nvoxels, cap, n) per kind, labels
 _EXTREMA_TAIL = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + 2 * [_vp, _vp, _vp, _i64, C.POINTER(_i64)] + [_vp]
 
+# src, mask, markers, nx, ny, nz, halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary,
+# label_undefined, labels, basin_index, basin_score, basin_cap, n_basins
+_WATERSHED = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
+              C.POINTER(_i64)]
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -98,6 +103,10 @@ _SIGS = {
     "visfd_hip_filter3d_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
+    "visfd_hip_watershed_host": (C.c_int, _WATERSHED),
+    "visfd_hip_watershed": (C.c_int, [_vp] + _WATERSHED),
+    "visfd_hip_watershed_dev": (C.c_int, [_vp] + _WATERSHED),
+    "visfd_hip_watershed_last_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
     "visfd_hip_fluctuation_sigmas": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _fp, C.POINTER(C.c_float)]),
     "visfd_hip_gauss_halfwidths": (C.c_int, [_fp, C.c_float, _ip]),
     "visfd_hip_separable3d": (C.c_int, [_vp] + _VOL + [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
@@ -249,6 +258,51 @@ def load_library():
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+WATERSHED_PATH_HOST, WATERSHED_PATH_DEVICE = 0, 1
+
+
+def _watershed(call, src, mask, markers, shape, labels, halt_threshold, start_from_minima, connectivity, show_boundaries,
+               label_boundary, label_undefined):
+    """The capacity protocol of the watershed entry points (as for find_extrema): -> (basin index int64, score float32).
+    `call(*tail)` gets everything after the context.  halt_threshold None: no threshold (+inf, or -inf from maxima)."""
+    nz, ny, nx = shape
+    if halt_threshold is None:
+        halt_threshold = float("inf") if start_from_minima else -float("inf")
+    cap = max(65536, nz * ny * nx // 32)
+    while True:
+        index, score, n = np.empty(cap, np.int64), np.empty(cap, np.float32), _i64()
+        rc = call(src, mask, markers, nx, ny, nz, float(halt_threshold), int(bool(start_from_minima)), int(connectivity),
+                  int(bool(show_boundaries)), int(label_boundary), int(label_undefined), labels, index.ctypes.data,
+                  score.ctypes.data, cap, C.byref(n))
+        if rc == 4 and n.value > cap:   # VISFD_HIP_ECAPACITY
+            cap = int(n.value)
+            continue
+        if rc != 0:
+            raise VisfdHipError(rc, load_library().visfd_hip_last_error().decode())
+        return index[:n.value].copy(), score[:n.value].copy()
+
+
+def _markers_np(markers, shape):
+    if markers is None:
+        return None
+    assert isinstance(markers, np.ndarray) and markers.dtype == np.int32 and markers.flags["C_CONTIGUOUS"] and \
+        markers.shape == tuple(shape), "markers: C int32 of src's shape"
+    return markers
+
+
+def watershed_host(src, mask=None, markers=None, halt_threshold=None, start_from_minima=True, connectivity=1,
+                   show_boundaries=True, label_boundary=0, label_undefined=-1):
+    """visfd::Watershed by the sequential flood on the host (visfd_hip_watershed_host: no context, no device), with or
+    without markers (int32, entries <= 0 ignored): -> (labels int32, basin index int64, basin score float32)."""
+    L = load_library()
+    markers = _markers_np(markers, src.shape)
+    labels = np.empty(src.shape, np.int32)
+    index, score = _watershed(L.visfd_hip_watershed_host, _np(src), _np(mask), None if markers is None else markers.ctypes.data,
+                              src.shape, labels.ctypes.data, halt_threshold, start_from_minima, connectivity, show_boundaries,
+                              label_boundary, label_undefined)
+    return labels, index, score
 
 
 def _np(a):
@@ -861,6 +915,38 @@ class Context:
             threshold = -float("inf")
         r = self.find_extrema(src, mask, False, True, float("inf"), threshold, connectivity, allow_borders, **kw)
         return r[1] if len(r) == 2 else (r[1], r[2])
+
+    def watershed(self, src, mask=None, markers=None, halt_threshold=None, start_from_minima=True, connectivity=1,
+                  show_boundaries=True, label_boundary=0, label_undefined=-1):
+        """visfd::Watershed (segmentation.hpp:65-559) of a numpy volume (nz, ny, nx): -> (labels int32, basin index int64,
+        basin score float32).  Basin k of the seed list is labelled k + 1, boundaries label_boundary, unmasked voxels
+        beyond the threshold label_undefined, voxels with mask == 0 hold -1.  halt_threshold None: none.  Without markers
+        the labels are computed on the device; with markers (int32, entries <= 0 ignored), or under the option
+        watershed_host, by the sequential flood on the host."""
+        markers = _markers_np(markers, src.shape)
+        labels = np.empty(src.shape, np.int32)
+        index, score = _watershed(lambda *t: self._L.visfd_hip_watershed(self._h, *t), _np(src), _np(mask),
+                                  None if markers is None else markers.ctypes.data, src.shape, labels.ctypes.data,
+                                  halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary,
+                                  label_undefined)
+        return labels, index, score
+
+    def watershed_dev(self, src, labels, mask=None, markers=None, halt_threshold=None, start_from_minima=True, connectivity=1,
+                      show_boundaries=True, label_boundary=0, label_undefined=-1):
+        """watershed on device tensors: labels (and markers) contiguous cuda int32 of src's shape, labels written in place
+        everywhere; -> (basin index, basin score) as numpy lists.  Returns with the stream idle."""
+        for t in (labels, markers):
+            assert t is None or (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.int32" and
+                                 tuple(t.shape) == tuple(src.shape)), "labels / markers: contiguous cuda int32 of src's shape"
+        return _watershed(lambda *t: self._L.visfd_hip_watershed_dev(self._h, *t), _dev(src), _dev(mask),
+                          None if markers is None else markers.data_ptr(), tuple(src.shape), labels.data_ptr(),
+                          halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary, label_undefined)
+
+    def watershed_last_stats(self):
+        """(path, label rounds, boundary rounds, basins) of the last watershed call; path WATERSHED_PATH_HOST or _DEVICE."""
+        out = (_i64 * 4)()
+        self._chk(self._L.visfd_hip_watershed_last_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def filter3d_last_path(self):
         """The kernel the last general-filter call ran: FILTER3D_PATH_GENERAL or FILTER3D_PATH_TILED (-1 before the first)."""

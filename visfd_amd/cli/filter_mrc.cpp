@@ -160,7 +160,7 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES, WATERSHED } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until main() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
@@ -169,6 +169,12 @@ struct Settings {
   string find_minima_file, find_maxima_file;
   int neighbor_connectivity = 3;
   bool extrema_on_boundary = true;
+  // watershed segmentation (settings.cpp:156-162)
+  bool clusters_begin_at_maxima = false;
+  float watershed_threshold = std::numeric_limits<float>::infinity();
+  bool watershed_show_boundaries = true;
+  float watershed_boundary_label = 0.0f;
+  string watershed_markers_filename;
   float width_a[3] = {0, 0, 0}, width_b[3] = {0, 0, 0}, log_width[3] = {0, 0, 0};
   float template_background_radius[3] = {-1, -1, -1};        // settings.cpp:222-225 (-fluct)
   float template_background_exponent = 2.0f;
@@ -260,6 +266,7 @@ bool one_of(const string& f, std::initializer_list<const char*> names) {
 Settings parse(int argc, char** argv) {
   Settings s;
   bool user_set_thickness_manually = false, user_set_background_scale_manually = false;   // settings.cpp:260-261
+  bool user_set_watershed_threshold_manually = false;
   vector<string> v(argv + 1, argv + argc);
   for (size_t i = 0; i < v.size();) {
     const string& f = v[i];
@@ -327,6 +334,39 @@ Settings parse(int argc, char** argv) {
     }
     else if (f == "-boundary-extrema") { s.extrema_on_boundary = true; i += 1; }
     else if (f == "-ignore-boundary-extrema") { s.extrema_on_boundary = false; i += 1; }
+    else if (f == "-watershed") {   // settings.cpp:2581-2608: the kind resets the threshold unless one was given before it
+      const float inf = std::numeric_limits<float>::infinity();
+      const string kind = (i + 1 < v.size() && !v[i + 1].empty() && v[i + 1][0] != '-') ? v[i + 1] : "";
+      if (kind == "min" || kind == "minima") {
+        s.clusters_begin_at_maxima = false;
+        if (!user_set_watershed_threshold_manually) s.watershed_threshold = inf;
+      } else if (kind == "max" || kind == "maxima") {
+        s.clusters_begin_at_maxima = true;
+        if (!user_set_watershed_threshold_manually) s.watershed_threshold = -inf;
+      } else {
+        // the reference's text verbatim (settings.cpp:2602-2605), its stray "width" included: the flag takes the kind only
+        throw VisfdErr("Error: The " + f + " argument must be followed by an argument:  \"type\"  \"width\"\n"
+                       "       The \"type\" argument must be either \"minima\" or \"maxima\".\n"
+                       "       (It depends on whether you want to detect dark or bright objects.)\n");
+      }
+      s.type = Settings::WATERSHED; i += 2;
+    }
+    else if (f == "-watershed-threshold" || f == "-watershed-boundary") {   // settings.cpp:2612-2663
+      const string msg = "Error: The " + f + " argument must be followed by a number\n";
+      if (i + 1 >= v.size() || v[i + 1].empty()) throw VisfdErr(msg);
+      float x = 0.0f;
+      try { x = std::stof(v[i + 1]); } catch (...) { throw VisfdErr(msg); }
+      if (f == "-watershed-threshold") { user_set_watershed_threshold_manually = true; s.watershed_threshold = x; }
+      else s.watershed_boundary_label = x;
+      s.type = Settings::WATERSHED; i += 2;
+    }
+    else if (f == "-watershed-show-boundaries") { s.watershed_show_boundaries = true; s.type = Settings::WATERSHED; i += 1; }
+    else if (f == "-watershed-hide-boundaries") { s.watershed_show_boundaries = false; s.type = Settings::WATERSHED; i += 1; }
+    else if (f == "-markers") {   // settings.cpp:2667-2680
+      if (i + 1 >= v.size() || v[i + 1].empty())
+        throw VisfdErr("Error: The " + f + " argument must be followed by an image file name\n");
+      s.watershed_markers_filename = v[i + 1]; i += 2;
+    }
     else if (f == "-ggauss" || f == "-ggauss-aniso" || f == "-dogg" || f == "-dogg-aniso" || f == "-exponent" ||
              f == "-gauss-exponent" || f == "-exponents" || f == "-gdog-exponents") {
       // settings.cpp:1220-1335, :1492-1535: the numbers must be there, not empty and not start with '-'
@@ -1291,6 +1331,51 @@ int main(int argc, char** argv) {
           out << crds[side][k][0] * vw[0] << " " << crds[side][k][1] * vw[1] << " " << crds[side][k][2] * vw[2] << " "
               << nvoxels[side][k] << " " << scores[side][k] << "\n";
       }
+    } else if (s.type == Settings::WATERSHED) {
+      // HandleWatershed, handlers.cpp:1280-1391: Watershed is called with label_undefined = -1 whatever -undefined-out
+      // says; the labels become floats, -1 the largest label plus one (or the -undefined-out value), and voxels outside the
+      // mask take the -mask-out value below like every other output
+      const size_t n = tomo_in.nvox();
+      vector<int32_t> labels(n), markers;
+      if (!s.watershed_markers_filename.empty()) {
+        Mrc mk;
+        cerr << "Reading tomogram \"" << s.watershed_markers_filename << "\"\n";
+        mk.read(s.watershed_markers_filename);
+        if (mk.nx != size[0] || mk.ny != size[1] || mk.nz != size[2])
+          throw VisfdErr("Error: \"" + s.watershed_markers_filename + "\" does not have the size of the input image.\n");
+        markers.resize(n);
+        for (size_t i = 0; i < n; i++) markers[i] = (int32_t)std::round(mk.data()[i]);
+      }
+      int32_t*** dest = Alloc3D<int32_t>(size);
+      int32_t*** mark = nullptr;
+      if (!markers.empty()) {
+        mark = Alloc3D<int32_t>(size);
+        std::memcpy(&mark[0][0][0], markers.data(), n * 4);
+      }
+      vector<std::array<float, 3> > extrema_crds;
+      vector<float> extrema_scores;
+      size_t num_basins = 0;
+      try {
+        num_basins = Watershed(size, tomo_in.a, dest, M, static_cast<int32_t const* const* const*>(mark),
+                               s.watershed_threshold, !s.clusters_begin_at_maxima, s.neighbor_connectivity,
+                               s.watershed_show_boundaries, (int32_t)s.watershed_boundary_label, (int32_t)-1, &extrema_crds,
+                               &extrema_scores, &cerr);
+      } catch (...) {
+        Dealloc3D(dest);
+        Dealloc3D(mark);
+        throw;
+      }
+      cerr << "Number of basins found: " << num_basins << "\n";
+      const int32_t* lab = &dest[0][0][0];
+      int32_t max_label = lab[0];
+      for (size_t i = 0; i < n; i++) max_label = std::max(max_label, lab[i]);
+      float* o = tomo_out.data();
+      for (size_t i = 0; i < n; i++) {
+        o[i] = (float)lab[i];
+        if (lab[i] == -1) o[i] = s.undefined_voxels_are_max ? (float)(max_label + 1) : s.undefined_voxel_brightness;
+      }
+      Dealloc3D(dest);
+      Dealloc3D(mark);
     } else if (s.type == Settings::BLOB_NONMAX) {
       handle_blob_nonmax(s, vw, M, size);
     } else if (s.type == Settings::DRAW_SPHERES) {

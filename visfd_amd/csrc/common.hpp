@@ -65,6 +65,12 @@ enum Slot {
   WS_F3D_TAB,                      // general 3-D filter: the table's non-zero entries on the device (what they were built from: visfd_hip_ctx::f3d_raw)
   WS_DRAW_OWNER,                   // DrawSpheres: the owner volume, one uint32 per voxel: the last sphere that holds it, plus one (csrc/draw.hip)
   WS_DRAW_TAB,                     // DrawSpheres: per-sphere values, counts, clipped boxes and running row counts; DrawRegions: its one flag
+  WS_WSH_KIND,                     // watershed: one byte per voxel: ineligible / interior / chain / join, and what the merge pass adds (csrc/watershed.hip)
+  WS_WSH_LINK,                     // watershed: union-find parent or down pointer (int32), then the voxel's node; reused for the qualifying-neighbour bits
+  WS_WSH_C,                        // watershed: the carried basin (int32 per voxel)
+  WS_WSH_STATE,                    // watershed: boundary state, one byte per voxel
+  WS_WSH_SEEDS,                    // watershed: the seeds' root indices in list order
+  WS_WSH_FLAGS,                    // watershed: the NaN flag and the per-round change flag
   WS_NSLOTS
 };
 
@@ -94,6 +100,7 @@ struct visfd_hip_options {
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
+  int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
 };
@@ -119,6 +126,7 @@ struct visfd_hip_ctx {
   float f3d_den = 0.0f;               // and their float sum in order
   int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
+  int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };
 
@@ -144,6 +152,12 @@ inline int ws(visfd_hip_ctx* ctx, Slot s, size_t count, T** out) {
 inline int check_dims(i64 nx, i64 ny, i64 nz) {
   if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VISFD_HIP_EINVAL, "image dimensions must be positive");
   return VISFD_HIP_OK;
+}
+// two byte ranges share a byte (a null pointer shares none)
+inline bool overlap_bytes(const void* a, size_t na, const void* b, size_t nb) {
+  const char* p = static_cast<const char*>(a);
+  const char* q = static_cast<const char*>(b);
+  return p && q && p < q + nb && q < p + na;
 }
 inline int check_dims32(i64 nx, i64 ny, i64 nz) {   // for the kernels that index a volume with 32-bit coordinates
   if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
@@ -320,6 +334,11 @@ struct ExtremaArgs {
 int extrema_check_args(const visfd_hip_ctx* ctx, const ExtremaArgs& a);
 // src, mask, labels on the device; the lists on the host.  Returns with the stream idle.
 int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a);
+
+// The watershed's seeds: the whole sorted list of one kind of extremum (borders allowed), the plateaus' roots and values.
+// Returns with the stream idle.
+int dev_extrema_seeds(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, bool minima,
+                      float threshold, int connectivity, std::vector<int>* index, std::vector<float>* score);
 
 // resample.hip (sizes are {nx, ny, nz}; offset nullable)
 int dev_bin_array3d(visfd_hip_ctx* ctx, const float* src, const int64_t size_src[3], float* dst,

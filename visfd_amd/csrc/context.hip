@@ -53,6 +53,7 @@ const OptionDesc kOptions[] = {
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
+    {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {

@@ -29,17 +29,14 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "tile.hpp"
+#include "union_find.hpp"
 
 namespace vh {
 
 namespace {
 
 constexpr unsigned F_LOWER = 1u, F_HIGHER = 2u, F_EQUAL = 4u, F_MISSING = 8u, F_MASKED = 0x80u;
-constexpr unsigned NAN_BITS = 0x7fc00000u;    // every NaN of the source enters LDS as this one (all of them compare alike)
-constexpr unsigned GONE_BITS = 0x7fc00001u;   // a voxel outside the image or with mask == 0
-
-constexpr int TX = 64, TY = 8, TZ = 8;        // outputs of a workgroup (256 threads: one x, two y, eight z each)
-constexpr int LX = TX + 2, LY = TY + 2, LZ = TZ + 2;
 
 struct Rec {   // one list entry as the list kernel writes it
   int index;
@@ -52,23 +49,10 @@ __global__ void __launch_bounds__(256)
 classify_kernel(const float* __restrict__ src, const float* __restrict__ mask, unsigned char* __restrict__ flags,
                 int* __restrict__ parent, int* __restrict__ count, int nx, int ny, int nz) {
   __shared__ unsigned tile[LZ * LY * LX];
-  const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TX + tx;
+  const int tx = threadIdx.x, ty = threadIdx.y;
   const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY, z0 = blockIdx.z * TZ;
   const i64 plane = (i64)nx * ny;
-  for (int k = tid; k < LZ * LY * LX; k += 256) {
-    const int lx = k % LX, ly = (k / LX) % LY, lz = k / (LX * LY);
-    const int X = x0 - 1 + lx, Y = y0 - 1 + ly, Z = z0 - 1 + lz;
-    unsigned b = GONE_BITS;
-    if ((unsigned)X < (unsigned)nx && (unsigned)Y < (unsigned)ny && (unsigned)Z < (unsigned)nz) {
-      const i64 i = (i64)Z * plane + (i64)Y * nx + X;
-      if (!mask || mask[i] != 0.0f) {
-        const float v = src[i];
-        b = (v == v) ? __float_as_uint(v) : NAN_BITS;
-      }
-    }
-    tile[k] = b;
-  }
-  __syncthreads();
+  load_tile(src, mask, 0u, tile, nx, ny, nz);
   const int x = x0 + tx;
   if (x >= nx) return;
 #pragma unroll
@@ -108,39 +92,6 @@ classify_kernel(const float* __restrict__ src, const float* __restrict__ mask, u
         count[i] = 0;
       }
     }
-  }
-}
-
-__device__ __forceinline__ int ld_parent(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x's tree; every second link on the way is shortened to its grandparent (atomicMin: a link only ever moves
-// to a smaller index, and never away from a smaller one that a concurrent hook has just put there)
-__device__ __forceinline__ int find_halving(int* parent, int x) {
-  for (;;) {
-    const int p = ld_parent(parent + x);
-    if (p == x) return x;
-    const int gp = ld_parent(parent + p);
-    if (gp == p) return p;
-    atomicMin(parent + x, gp);
-    x = gp;
-  }
-}
-
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-  for (;;) {
-    a = find_halving(parent, a);
-    b = find_halving(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(parent + a, b);   // a > b: hook a under b if a still is a root
-    if (old == a) return;
-    a = old;   // a had a parent already (now min(old, b)): what is left to join is old's tree and b's
   }
 }
 
@@ -295,10 +246,6 @@ write_labels_kernel(const unsigned char* __restrict__ flags, const int* __restri
   }
 }
 
-struct ExtremaList {
-  std::vector<Rec> rec;   // in output order
-};
-
 // ascending in (score, raster position), the order std::sort gives the reference's (score, position) tuples: +0 and -0
 // tie (no NaN is ever listed); the maxima are that order reversed
 void sort_list(std::vector<Rec>& v, bool maxima) {
@@ -325,12 +272,6 @@ int put_ranks(visfd_hip_ctx* ctx, const std::vector<Rec>& sorted, std::vector<in
   return VISFD_HIP_OK;
 }
 
-bool overlap_bytes(const void* a, size_t na, const void* b, size_t nb) {
-  const char* p = static_cast<const char*>(a);
-  const char* q = static_cast<const char*>(b);
-  return p && q && p < q + nb && q < p + na;
-}
-
 }  // namespace
 
 // everything that can be said without a device, the context last
@@ -342,7 +283,7 @@ int extrema_check_args(const visfd_hip_ctx* ctx, const ExtremaArgs& a) {
   VH_REQUIRE(a.nx <= lim && a.ny <= lim && a.nz <= lim && a.nx * a.ny <= lim && a.nx * a.ny * a.nz <= lim,
              "find_extrema: the image must have fewer than 2^31 - 2 voxels");
   // the classification pass is one launch of 64 x 8 x 8 tiles: 65535 tiles along y and z, 2^24 workgroups in all
-  const i64 tiles = ((a.nx + TX - 1) / TX) * ((a.ny + TY - 1) / TY) * ((a.nz + TZ - 1) / TZ);
+  const i64 tiles = tile_count(a.nx, a.ny, a.nz);
   VH_REQUIRE(a.ny <= VISFD_HIP_EXTREMA_MAX_NY_NZ && a.nz <= VISFD_HIP_EXTREMA_MAX_NY_NZ && tiles < ((i64)1 << 24),
              "find_extrema: ny and nz must be at most 524280, and the image at most 2^24 - 1 tiles of 64 x 8 x 8 voxels");
   VH_REQUIRE(a.find_minima || a.find_maxima, "find_extrema: neither minima nor maxima asked for");
@@ -379,34 +320,74 @@ int classify_and_merge(visfd_hip_ctx* ctx, const float* src, const float* mask, 
 
 }  // namespace
 
-// src, mask, labels on the device; the lists on the host.  Returns with the stream idle.
-int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a) {
-  VH_HIP(hipSetDevice(ctx->device));
-  const i64 nv = a.nx * a.ny * a.nz;
-  const unsigned g = grid_for(nv, 256, (i64)ctx->num_cus * 16);
+namespace {
+
+// what the search leaves on the device, and its two lists
+struct Found {
   unsigned char* flags = nullptr;
   int *parent = nullptr, *count = nullptr;
   unsigned long long* counters = nullptr;
-  VH_TRY(ws(ctx, WS_EXT_FLAGS, (size_t)((nv + 3) / 4 * 4), &flags));
-  VH_TRY(ws(ctx, WS_EXT_PARENT, (size_t)nv, &parent));
-  VH_TRY(ws(ctx, WS_EXT_COUNT, (size_t)nv, &count));
-  VH_TRY(ws(ctx, WS_EXT_COUNTERS, 2, &counters));
-  if (a.connectivity == 1) VH_TRY(classify_and_merge<1>(ctx, a.src, a.mask, flags, parent, count, a.nx, a.ny, a.nz, g));
-  if (a.connectivity == 2) VH_TRY(classify_and_merge<2>(ctx, a.src, a.mask, flags, parent, count, a.nx, a.ny, a.nz, g));
-  if (a.connectivity == 3) VH_TRY(classify_and_merge<3>(ctx, a.src, a.mask, flags, parent, count, a.nx, a.ny, a.nz, g));
-  flatten_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(flags, parent, nv);
+  unsigned g = 1;
+  unsigned long long n[2] = {0, 0};
+  std::vector<Rec> mins, maxs;   // in output order
+};
+
+// classification, plateaus and the two list lengths; returns with the stream idle
+int count_stage(visfd_hip_ctx* ctx, const ExtremaArgs& a, Found& f) {
+  VH_HIP(hipSetDevice(ctx->device));
+  const i64 nv = a.nx * a.ny * a.nz;
+  const unsigned g = f.g = grid_for(nv, 256, (i64)ctx->num_cus * 16);
+  VH_TRY(ws(ctx, WS_EXT_FLAGS, (size_t)((nv + 3) / 4 * 4), &f.flags));
+  VH_TRY(ws(ctx, WS_EXT_PARENT, (size_t)nv, &f.parent));
+  VH_TRY(ws(ctx, WS_EXT_COUNT, (size_t)nv, &f.count));
+  VH_TRY(ws(ctx, WS_EXT_COUNTERS, 2, &f.counters));
+  if (a.connectivity == 1) VH_TRY(classify_and_merge<1>(ctx, a.src, a.mask, f.flags, f.parent, f.count, a.nx, a.ny, a.nz, g));
+  if (a.connectivity == 2) VH_TRY(classify_and_merge<2>(ctx, a.src, a.mask, f.flags, f.parent, f.count, a.nx, a.ny, a.nz, g));
+  if (a.connectivity == 3) VH_TRY(classify_and_merge<3>(ctx, a.src, a.mask, f.flags, f.parent, f.count, a.nx, a.ny, a.nz, g));
+  flatten_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(f.flags, f.parent, nv);
   VH_HIP(hipGetLastError());
-  reduce_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(flags, parent, count, nv);
+  reduce_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(f.flags, f.parent, f.count, nv);
   VH_HIP(hipGetLastError());
 
-  unsigned long long n[2] = {0, 0};
-  VH_HIP(hipMemsetAsync(counters, 0, sizeof(n), ctx->stream));
-  list_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(a.src, flags, parent, count, nv, a.find_minima, a.find_maxima,
-                                                      a.minima_threshold, a.maxima_threshold, a.allow_borders, counters,
+  VH_HIP(hipMemsetAsync(f.counters, 0, sizeof(f.n), ctx->stream));
+  list_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(a.src, f.flags, f.parent, f.count, nv, a.find_minima, a.find_maxima,
+                                                      a.minima_threshold, a.maxima_threshold, a.allow_borders, f.counters,
                                                       nullptr, nullptr);
   VH_HIP(hipGetLastError());
-  VH_HIP(hipMemcpyAsync(n, counters, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+  VH_HIP(hipMemcpyAsync(f.n, f.counters, sizeof(f.n), hipMemcpyDeviceToHost, ctx->stream));
   VH_HIP(hipStreamSynchronize(ctx->stream));
+  return VISFD_HIP_OK;
+}
+
+// the lists themselves, sorted; returns with the stream idle
+int list_stage(visfd_hip_ctx* ctx, const ExtremaArgs& a, Found& f) {
+  const i64 nv = a.nx * a.ny * a.nz;
+  const unsigned long long* n = f.n;
+  Rec* recs = nullptr;
+  VH_TRY(ws(ctx, WS_EXT_LIST, (size_t)(n[0] + n[1]), &recs));
+  VH_HIP(hipMemsetAsync(f.counters, 0, sizeof(f.n), ctx->stream));
+  list_kernel<<<dim3(f.g), dim3(256), 0, ctx->stream>>>(a.src, f.flags, f.parent, f.count, nv, a.find_minima, a.find_maxima,
+                                                        a.minima_threshold, a.maxima_threshold, a.allow_borders, f.counters,
+                                                        recs, recs + n[0]);
+  VH_HIP(hipGetLastError());
+  f.mins.resize((size_t)n[0]);
+  f.maxs.resize((size_t)n[1]);
+  if (n[0]) VH_HIP(hipMemcpyAsync(f.mins.data(), recs, sizeof(Rec) * n[0], hipMemcpyDeviceToHost, ctx->stream));
+  if (n[1]) VH_HIP(hipMemcpyAsync(f.maxs.data(), recs + n[0], sizeof(Rec) * n[1], hipMemcpyDeviceToHost, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  sort_list(f.mins, false);
+  sort_list(f.maxs, true);
+  return VISFD_HIP_OK;
+}
+
+}  // namespace
+
+// src, mask, labels on the device; the lists on the host.  Returns with the stream idle.
+int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a) {
+  Found f;
+  VH_TRY(count_stage(ctx, a, f));
+  const i64 nv = a.nx * a.ny * a.nz;
+  const unsigned long long* n = f.n;
   if (a.n_min) *a.n_min = (int64_t)n[0];
   if (a.n_max) *a.n_max = (int64_t)n[1];
   const bool short_min = a.min_cap > 0 && (unsigned long long)a.min_cap < n[0];
@@ -415,21 +396,9 @@ int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a) {
   const bool want_min = a.find_minima && (a.min_cap > 0 || a.labels), want_max = a.find_maxima && (a.max_cap > 0 || a.labels);
   if (!want_min && !want_max) return VISFD_HIP_OK;   // counting only
 
-  Rec* recs = nullptr;
-  VH_TRY(ws(ctx, WS_EXT_LIST, (size_t)(n[0] + n[1]), &recs));
-  VH_HIP(hipMemsetAsync(counters, 0, sizeof(n), ctx->stream));
-  list_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(a.src, flags, parent, count, nv, a.find_minima, a.find_maxima,
-                                                      a.minima_threshold, a.maxima_threshold, a.allow_borders, counters,
-                                                      recs, recs + n[0]);
-  VH_HIP(hipGetLastError());
-  std::vector<Rec> mins((size_t)n[0]), maxs((size_t)n[1]);
-  if (n[0]) VH_HIP(hipMemcpyAsync(mins.data(), recs, sizeof(Rec) * n[0], hipMemcpyDeviceToHost, ctx->stream));
-  if (n[1]) VH_HIP(hipMemcpyAsync(maxs.data(), recs + n[0], sizeof(Rec) * n[1], hipMemcpyDeviceToHost, ctx->stream));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  sort_list(mins, false);
-  sort_list(maxs, true);
-  if (a.min_cap > 0) copy_out(mins, a.min_index, a.min_score, a.min_nvoxels);
-  if (a.max_cap > 0) copy_out(maxs, a.max_index, a.max_score, a.max_nvoxels);
+  VH_TRY(list_stage(ctx, a, f));
+  if (a.min_cap > 0) copy_out(f.mins, a.min_index, a.min_score, a.min_nvoxels);
+  if (a.max_cap > 0) copy_out(f.maxs, a.max_index, a.max_score, a.max_nvoxels);
   if (!a.labels) return VISFD_HIP_OK;
 
   int* ranks = nullptr;
@@ -437,13 +406,41 @@ int dev_find_extrema(visfd_hip_ctx* ctx, const ExtremaArgs& a) {
   std::vector<int> hmin, hmax;
   int* rmin = ranks;
   int* rmax = ranks + 2 * n[0];
-  VH_TRY(put_ranks(ctx, mins, hmin, rmin));
-  VH_TRY(put_ranks(ctx, maxs, hmax, rmax));
-  write_labels_kernel<<<dim3(g), dim3(256), 0, ctx->stream>>>(flags, parent, nv, a.allow_borders, rmin, rmin + n[0], (int)n[0],
-                                                              rmax, rmax + n[1], (int)n[1],
-                                                              (a.find_minima && a.find_maxima) ? 0 : 1, a.labels);
+  VH_TRY(put_ranks(ctx, f.mins, hmin, rmin));
+  VH_TRY(put_ranks(ctx, f.maxs, hmax, rmax));
+  write_labels_kernel<<<dim3(f.g), dim3(256), 0, ctx->stream>>>(f.flags, f.parent, nv, a.allow_borders, rmin, rmin + n[0],
+                                                                (int)n[0], rmax, rmax + n[1], (int)n[1],
+                                                                (a.find_minima && a.find_maxima) ? 0 : 1, a.labels);
   VH_HIP(hipGetLastError());
   VH_HIP(hipStreamSynchronize(ctx->stream));   // hmin / hmax go out of scope
+  return VISFD_HIP_OK;
+}
+
+// The watershed's seeds (watershed.hip): the whole sorted list of one kind, borders allowed, whatever its length -- the
+// plateaus' roots and their values.  Returns with the stream idle.
+int dev_extrema_seeds(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, bool minima,
+                      float threshold, int connectivity, std::vector<int>* index, std::vector<float>* score) {
+  ExtremaArgs a = {};
+  a.src = src;
+  a.mask = mask;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.find_minima = minima;
+  a.find_maxima = !minima;
+  a.minima_threshold = a.maxima_threshold = threshold;
+  a.connectivity = connectivity;
+  a.allow_borders = 1;
+  Found f;
+  VH_TRY(count_stage(ctx, a, f));
+  VH_TRY(list_stage(ctx, a, f));
+  const std::vector<Rec>& v = minima ? f.mins : f.maxs;
+  index->resize(v.size());
+  score->resize(v.size());
+  for (size_t k = 0; k < v.size(); k++) {
+    (*index)[k] = v[k].index;
+    (*score)[k] = v[k].score;
+  }
   return VISFD_HIP_OK;
 }
 
