@@ -88,7 +88,8 @@ CLI_BIN = os.path.join(HERE, "cli", "filter_mrc")
 
 def build_cli(verbose=True):
     """The filter_mrc drop-in: plain C++11 host code on top of the C ABI (no HIP in this file)."""
-    deps = [CLI_SRC, os.path.join(ROOT, "include", "visfd_hip.hpp"), os.path.join(ROOT, "include", "visfd_hip.h"), LIB]
+    deps = [CLI_SRC, os.path.join(HERE, "cli", "mrc.hpp"), os.path.join(HERE, "cli", "settings.hpp"),
+            os.path.join(ROOT, "include", "visfd_hip.hpp"), os.path.join(ROOT, "include", "visfd_hip.h"), LIB]
     if os.path.exists(CLI_BIN) and _mtime(CLI_BIN) >= max(_mtime(d) for d in deps):
         return CLI_BIN
     cmd = ["g++", "-std=c++11", "-O2", "-Wall", "-o", CLI_BIN, CLI_SRC, "-L" + HERE, "-lvisfd_hip",
