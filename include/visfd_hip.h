@@ -70,7 +70,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * _apply_dogg[_dev] and _local_fluctuations_gen[_dev]; then the drawing entries
                                      * visfd_hip_draw_spheres[_dev], visfd_hip_draw_regions[_dev] and
                                      * visfd_hip_draw_last_times; then the watershed: visfd_hip_watershed_host,
-                                     * visfd_hip_watershed[_dev] and visfd_hip_watershed_last_stats) */
+                                     * visfd_hip_watershed[_dev] and visfd_hip_watershed_last_stats; then the median
+                                     * filter: visfd_hip_median_footprint, visfd_hip_median_sphere[_dev],
+                                     * visfd_hip_median_table[_dev] and visfd_hip_median_last_path) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -100,6 +102,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    kernel; results are bit-identical either way
  *   filter3d_general 1: the general 3-D filter always walks the table entry by entry (csrc/filter3d.hip), never takes the
  *                    LDS-tiled kernel; results are bit-identical either way
+ *   median_general   1: the median filter always walks the footprint in global memory (csrc/median.hip), never takes the
+ *                    LDS-tiled kernel; results are bit-identical either way
  *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
  *                    (visfd_hip_draw_last_times); default 0
  *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
@@ -110,7 +114,7 @@ int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_ou
 /* bytes of device workspace currently held by the context */
 int64_t visfd_hip_workspace_bytes(visfd_hip_ctx* ctx);
 /* TEST AID: waits for the context's stream, then fills every workspace slot the context holds with 0xFF bytes (NaN as
- * floats, huge as counters) and forgets what it had cached inside them (vote table, structuring element, filter table), without freeing
+ * floats, huge as counters) and forgets what it had cached inside them (vote table, structuring element, filter table, median footprint), without freeing
  * anything.  No stage may depend on what a slot held before the call that uses it, so every result after this call is the
  * same as before it.  What live blob jobs have queued is fetched to the host first, as visfd_hip_trim does. */
 int visfd_hip_debug_poison_workspace(visfd_hip_ctx* ctx);
@@ -303,6 +307,40 @@ int visfd_hip_morph_table_dev(visfd_hip_ctx*, const float* src, float* dst, cons
 #define VISFD_HIP_MORPH_PATH_GENERAL 0    /* morph_kernel: the element walked entry by entry */
 #define VISFD_HIP_MORPH_PATH_XRUNS 1      /* morph_runs_kernel: window maxima of X-runs, zero-sign fix-up of erosions */
 int visfd_hip_morph_last_path(visfd_hip_ctx*, int* path);
+
+/* ---- m1b: the median filter, Median / MedianSphere (lib/visfd/filter3d.hpp:1577-1674) -------------- */
+/* The reference's footprint loop does not terminate once a neighbour is skipped, so the semantics are stated here.
+ * A voxel with mask == 0 is not written (dst keeps its value).  Any other voxel collects the source values at voxel +
+ * entry for every footprint entry that lies inside the image and, with a mask, has mask != 0; duplicates count as often
+ * as they appear and the centre need not be an entry.  With n values collected it gets the value of rank n / 2 (0-based,
+ * ascending: the upper median for even n, what std::nth_element(begin, begin + n / 2, begin + n) leaves there), and
+ * +0.0f when n == 0.  The order is total on bit patterns: a float with bits u has the key ~u if its sign bit is set, else
+ * u | 0x80000000, and keys compare as unsigned integers -- operator< for finite values and infinities, -0 before +0, NaNs
+ * by sign and payload below -inf or above +inf -- so every result is defined to the bit for every input.
+ * Limits, which keep one launch bounded (beyond them: VISFD_HIP_EINVAL): radius >= 0 and ceil(radius) <= 16; a table has
+ * 1 <= n <= 32768 entries with |d| <= 16 per axis; ny <= 262140 (65535 rows of workgroups of 4 voxels in y; nx and nz
+ * only need to be below 2^30).  A dst that overlaps src or mask is VISFD_HIP_EINVAL. */
+#define VISFD_HIP_MEDIAN_MAX_RADIUS 16
+#define VISFD_HIP_MEDIAN_MAX_ENTRIES 32768
+/* The footprint of MedianSphere (filter3d.hpp:1652-1662), host arithmetic: with Ri = ceil(radius), every (ix, iy, iz) of
+ * [-Ri, Ri]^3 with (float)sqrt((double)(ix^2 + iy^2 + iz^2)) <= radius, iz outermost, then iy, then ix, 3 ints each.
+ * *n = the number of entries; the first min(n, cap) are written (cap == 0: count only; 0 < cap < n:
+ * VISFD_HIP_ECAPACITY). */
+int visfd_hip_median_footprint(float radius, int* dxyz, int64_t cap, int64_t* n);
+int visfd_hip_median_sphere(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                            int64_t nx, int64_t ny, int64_t nz, float radius);
+int visfd_hip_median_sphere_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                                int64_t nx, int64_t ny, int64_t nz, float radius);
+/* an arbitrary footprint of n entries (dx, dy, dz), 3 ints each (a host array on both faces) */
+int visfd_hip_median_table(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                           int64_t nx, int64_t ny, int64_t nz, const int* dxyz, int64_t n);
+int visfd_hip_median_table_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
+                               int64_t nx, int64_t ny, int64_t nz, const int* dxyz, int64_t n);
+/* the kernel the context's last median call ran: VISFD_HIP_MEDIAN_PATH_* (-1 before the first call) */
+#define VISFD_HIP_MEDIAN_PATH_GENERAL 0   /* median_general_kernel: neighbours from global memory, tested per entry */
+#define VISFD_HIP_MEDIAN_PATH_TILED 1     /* median_tiled_kernel: 64 x 4 x 4 outputs and their bounding box in LDS (64 KiB:
+                                           * balls up to radius 5) */
+int visfd_hip_median_last_path(visfd_hip_ctx*, int* path);
 
 /* ---- m2: local minima and maxima with plateaus, _FindExtrema (lib/visfd/morphology_implementation.hpp:57-515) ---- */
 /* A plateau is a maximal set of voxels with mask != 0 joined through neighbour pairs of equal value (-0 == +0; a NaN

@@ -397,6 +397,36 @@ inline void BlackTopHatSphere(float radius, const int image_size[3], float const
                            bmax);
 }
 
+// ---- the median filter: lib/visfd/filter3d.hpp:1577-1674 ----------------------------------------------------------
+// The reference's signatures.  Its footprint loop does not end once a neighbour is skipped; the semantics here are the
+// ones include/visfd_hip.h states (rank n / 2 of the neighbours inside the image with mask != 0; dest keeps its values
+// where mask == 0).
+inline void Median(std::vector<std::tuple<int, int, int> > footprint, const int image_size[3],
+                   float const* const* const* aaafSource, float*** aaafDest,
+                   float const* const* const* aaafMask = nullptr, std::ostream* = nullptr) {
+  hip_detail::require_contiguous(aaafSource, image_size);
+  hip_detail::require_contiguous(aaafDest, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  std::vector<int> dxyz;
+  dxyz.reserve(3 * footprint.size());
+  for (size_t k = 0; k < footprint.size(); k++) {
+    dxyz.push_back(std::get<0>(footprint[k]));
+    dxyz.push_back(std::get<1>(footprint[k]));
+    dxyz.push_back(std::get<2>(footprint[k]));
+  }
+  hip_detail::check(visfd_hip_median_table(hip_detail::context(), hip_detail::flat(aaafSource), hip_detail::flat(aaafDest),
+                                           hip_detail::flat(aaafMask), image_size[0], image_size[1], image_size[2],
+                                           dxyz.empty() ? nullptr : &dxyz[0], (int64_t)footprint.size()));
+}
+inline void MedianSphere(float radius, int const image_size[3], float const* const* const* aaafSource, float*** aaafDest,
+                         float const* const* const* aaafMask = nullptr, std::ostream* = nullptr) {
+  hip_detail::require_contiguous(aaafSource, image_size);
+  hip_detail::require_contiguous(aaafDest, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  hip_detail::check(visfd_hip_median_sphere(hip_detail::context(), hip_detail::flat(aaafSource), hip_detail::flat(aaafDest),
+                                            hip_detail::flat(aaafMask), image_size[0], image_size[1], image_size[2], radius));
+}
+
 // ---- local minima and maxima with plateaus: lib/visfd/morphology.hpp:56-118, morphology_implementation.hpp:57-796 --
 // The reference's signatures and defaults with Scalar = float.  Lists come back in the reference's order; aaaiDest (any
 // arithmetic Label) receives the label image where mask != 0, converted from the 32-bit labels of the C ABI exactly as

@@ -24,6 +24,7 @@ DECREASING_EIVALS = 1
 # grayscale morphology ops (VISFD_HIP_MORPH_*, lib/visfd/morphology.hpp:134-597)
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_TOP_HAT_WHITE, MORPH_TOP_HAT_BLACK = range(6)
 MORPH_PATH_GENERAL, MORPH_PATH_XRUNS = 0, 1   # visfd_hip_morph_last_path
+MEDIAN_PATH_GENERAL, MEDIAN_PATH_TILED = 0, 1   # visfd_hip_median_last_path
 FILTER3D_PATH_GENERAL, FILTER3D_PATH_TILED = 0, 1   # visfd_hip_filter3d_last_path
 
 _fp = C.POINTER(C.c_float)
@@ -100,6 +101,12 @@ _SIGS = {
     "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_table_dev": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
     "visfd_hip_morph_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_median_footprint": (C.c_int, [C.c_float, _ip, _i64, C.POINTER(C.c_int64)]),
+    "visfd_hip_median_sphere": (C.c_int, [_vp] + _VOL + [C.c_float]),
+    "visfd_hip_median_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_float]),
+    "visfd_hip_median_table": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
+    "visfd_hip_median_table_dev": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
+    "visfd_hip_median_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_filter3d_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
@@ -375,6 +382,17 @@ def sphere_structure(radius, radius_max=0.0, bmax=0.0):
     _chk_host(L, L.visfd_hip_sphere_structure(float(radius), float(radius_max), float(bmax), d.ctypes.data_as(_ip),
                                               b.ctypes.data_as(_fp), len(b), C.byref(n)))
     return d[:n.value].copy(), b[:n.value].copy()
+
+
+def median_footprint(radius):
+    """The footprint of MedianSphere (filter3d.hpp:1652-1662): dxyz int32 (n, 3) in the reference's order (dz outermost,
+    then dy, then dx)."""
+    L = load_library()
+    n = C.c_int64()
+    _chk_host(L, L.visfd_hip_median_footprint(float(radius), None, 0, C.byref(n)))
+    d = np.zeros((n.value, 3), np.int32)
+    _chk_host(L, L.visfd_hip_median_footprint(float(radius), d.ctypes.data_as(_ip), len(d), C.byref(n)))
+    return d
 
 
 def gengauss3d_halfwidths(width, m_exp, truncate_ratio=-1.0, truncate_threshold=0.03):
@@ -867,6 +885,25 @@ class Context:
                                                 d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
         return dst
 
+    def median_sphere(self, src, radius, mask=None, dst=None):
+        """MedianSphere (filter3d.hpp:1639-1674, semantics in include/visfd_hip.h): the value of rank n // 2 among the n
+        neighbours within `radius` voxels that lie in the image and have mask != 0.  dst (default: a copy of src, as
+        filter_mrc starts its output) keeps its values where mask == 0; a new array is returned."""
+        nz, ny, nx = src.shape
+        dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
+        self._chk(self._L.visfd_hip_median_sphere(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, float(radius)))
+        return dst
+
+    def median_table(self, src, dxyz, mask=None, dst=None):
+        """Median (filter3d.hpp:1577-1630) with an arbitrary footprint: dxyz (n, 3) offsets; duplicates count as often as
+        they appear and the centre need not be among them."""
+        nz, ny, nx = src.shape
+        d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
+        dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
+        self._chk(self._L.visfd_hip_median_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
+                                                 d.ctypes.data_as(_ip), len(d)))
+        return dst
+
     def _find_extrema(self, fn, src, mask, shape, find_minima, find_maxima, minima_threshold, maxima_threshold,
                       connectivity, allow_borders, labels):
         """The capacity protocol of visfd_hip_find_extrema[_dev]: a first call with room for max(65536, voxels / 32)
@@ -958,6 +995,12 @@ class Context:
         """The kernel the last morphology call ran: MORPH_PATH_GENERAL or MORPH_PATH_XRUNS (-1 before the first)."""
         p = C.c_int()
         self._chk(self._L.visfd_hip_morph_last_path(self._h, C.byref(p)))
+        return p.value
+
+    def median_last_path(self):
+        """The kernel the last median call ran: MEDIAN_PATH_GENERAL or MEDIAN_PATH_TILED (-1 before the first)."""
+        p = C.c_int()
+        self._chk(self._L.visfd_hip_median_last_path(self._h, C.byref(p)))
         return p.value
 
     def dilate(self, src, dxyz, b, mask=None, dst=None):
@@ -1270,6 +1313,17 @@ class Context:
         d, bb = _morph_table(dxyz, b)
         self._chk(self._L.visfd_hip_morph_table_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, int(op),
                                                     d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
+
+    def median_sphere_dev(self, src, dst, radius, mask=None):
+        """median_sphere on device tensors; dst keeps its values where mask == 0 and is written in place."""
+        nz, ny, nx = src.shape
+        self._chk(self._L.visfd_hip_median_sphere_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, float(radius)))
+
+    def median_table_dev(self, src, dst, dxyz, mask=None):
+        nz, ny, nx = src.shape
+        d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
+        self._chk(self._L.visfd_hip_median_table_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
+                                                     d.ctypes.data_as(_ip), len(d)))
 
     def dilate_dev(self, src, dst, dxyz, b, mask=None):
         self.morph_table_dev(MORPH_DILATE, src, dst, dxyz, b, mask)

@@ -109,6 +109,15 @@ int morph_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* m
   return VISFD_HIP_OK;
 }
 
+int median_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz) {
+  VH_REQUIRE(ctx && src && dst, "null argument");
+  VH_TRY(check_dims(nx, ny, nz));
+  VH_REQUIRE(!overlaps(src, dst, nx * ny * nz), "the median filter cannot run in place (dst overlaps src)");
+  VH_REQUIRE(!overlaps(mask, dst, nx * ny * nz), "median: dst overlaps mask");
+  VH_HIP(hipSetDevice(ctx->device));
+  return VISFD_HIP_OK;
+}
+
 }  // namespace
 }  // namespace vh
 
@@ -712,6 +721,72 @@ int visfd_hip_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, cons
   VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_ERODE));
   return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
     return visfd_hip_morph_table_dev(ctx, ds, dd, dm, nx, ny, nz, op, dxyz, b, n);
+  });
+}
+
+// ---- m1b: the median filter (lib/visfd/filter3d.hpp:1577-1674; kernels and dispatch in median.hip) ----------------
+int visfd_hip_median_last_path(visfd_hip_ctx* ctx, int* path) {
+  VH_REQUIRE(ctx && path, "null argument");
+  *path = ctx->median_last_path;
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_median_footprint(float radius, int* dxyz, int64_t cap, int64_t* n) {
+  VH_REQUIRE(n && cap >= 0 && (cap == 0 || dxyz), "bad argument");
+  VH_REQUIRE(radius >= 0.0f, "the median radius must be a nonnegative number");
+  VH_REQUIRE(std::ceil(radius) <= (float)VISFD_HIP_MEDIAN_MAX_RADIUS, "the median radius must be at most 16 voxels");
+  const int Ri = (int)std::ceil(radius);
+  int64_t m = 0;
+  for (int iz = -Ri; iz <= Ri; iz++)
+    for (int iy = -Ri; iy <= Ri; iy++)
+      for (int ix = -Ri; ix <= Ri; ix++) {
+        const float r = (float)std::sqrt((double)(ix * ix + iy * iy + iz * iz));   // filter3d.hpp:1657
+        if (!(r <= radius)) continue;
+        if (m < cap) {
+          dxyz[3 * m] = ix;
+          dxyz[3 * m + 1] = iy;
+          dxyz[3 * m + 2] = iz;
+        }
+        m++;
+      }
+  *n = m;
+  if (cap > 0 && cap < m) return fail(VISFD_HIP_ECAPACITY, "median footprint has more entries than cap");
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_median_table_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
+                               int64_t ny, int64_t nz, const int* dxyz, int64_t n) {
+  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  MedianTab mt;
+  VH_TRY(median_put_table(ctx, dxyz, n, &mt));
+  return median_run(ctx, src, dst, mask, nx, ny, nz, mt);
+}
+
+int visfd_hip_median_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
+                                int64_t ny, int64_t nz, float radius) {
+  int64_t n = 0;   // the arrays are checked by the table entry
+  VH_TRY(visfd_hip_median_footprint(radius, nullptr, 0, &n));
+  std::vector<int> dxyz((size_t)(3 * n));
+  VH_TRY(visfd_hip_median_footprint(radius, dxyz.data(), n, &n));
+  return visfd_hip_median_table_dev(ctx, src, dst, mask, nx, ny, nz, dxyz.data(), n);
+}
+
+// the host faces: dst goes up too (masked voxels keep their values)
+int visfd_hip_median_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                            int64_t nz, float radius) {
+  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  int64_t n = 0;
+  VH_TRY(visfd_hip_median_footprint(radius, nullptr, 0, &n));   // a bad radius is refused before anything is staged
+  return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
+    return visfd_hip_median_sphere_dev(ctx, ds, dd, dm, nx, ny, nz, radius);
+  });
+}
+
+int visfd_hip_median_table(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
+                           int64_t nz, const int* dxyz, int64_t n) {
+  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
+    return visfd_hip_median_table_dev(ctx, ds, dd, dm, nx, ny, nz, dxyz, n);
   });
 }
 

@@ -71,6 +71,7 @@ enum Slot {
   WS_WSH_STATE,                    // watershed: boundary state, one byte per voxel
   WS_WSH_SEEDS,                    // watershed: the seeds' root indices in list order
   WS_WSH_FLAGS,                    // watershed: the NaN flag and the per-round change flag
+  WS_MEDIAN_TAB,                   // median filter: the footprint on the device (host copy in visfd_hip_ctx::median_tab); csrc/median.hip
   WS_NSLOTS
 };
 
@@ -100,6 +101,7 @@ struct visfd_hip_options {
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
+  int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
@@ -125,6 +127,8 @@ struct visfd_hip_ctx {
   int64_t f3d_ncols = 0;
   float f3d_den = 0.0f;               // and their float sum in order
   int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
+  std::vector<int> median_tab;        // the footprint now in slot WS_MEDIAN_TAB (n entries dx, dy, dz, 0, then n LDS cell offsets)
+  int median_last_path = -1;          // the kernel the last median call ran (VISFD_HIP_MEDIAN_PATH_*)
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
@@ -309,6 +313,21 @@ int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, floa
 int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el);
 int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
               MorphElem el);
+
+// median.hip: a footprint as the median kernels see it (the entries themselves are in slot WS_MEDIAN_TAB): the entry
+// count, the bounding box of the offsets and the extent W x H x D of the tiled kernel's LDS image for that box.
+struct MedianTab {
+  i64 n = 0;
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  int W = 0, H = 0, D = 0;
+};
+// a footprint of n entries (dx, dy, dz; host array) into WS_MEDIAN_TAB (`mt` describes it), and the median of src with it:
+// voxels with mask == 0 are left untouched, neighbours outside the image or with mask == 0 are not collected, a voxel
+// that collects nothing gets +0.0f.  The route is the LDS-tiled kernel where the bounding box fits its budget and the
+// option median_general is off, else the general walk (ctx->median_last_path says which).
+int median_put_table(visfd_hip_ctx* ctx, const int* dxyz, i64 n, MedianTab* mt);
+int median_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
+               const MedianTab& mt);
 
 // filter3d.hip: Filter3D::Apply with an arbitrary table of (2 hx + 1)(2 hy + 1)(2 hz + 1) entries (x fastest), on device
 // arrays.  dst = sum_j (H[j] * mask[i - j]) * src[i - j] in the reference's order, divided by den = sum_j H[j] * mask[i - j]

@@ -52,6 +52,7 @@ const OptionDesc kOptions[] = {
     {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
+    {"median_general", &visfd_hip_options::median_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
 };
@@ -85,6 +86,7 @@ void forget_slot_caches(visfd_hip_ctx* ctx) {
   ctx->tv_table_h = -1;
   ctx->morph_tab.clear();        // so does the structuring element
   ctx->f3d_raw.clear();          // and the general filter's table
+  ctx->median_tab.clear();       // and the median's footprint
 }
 
 }  // namespace
