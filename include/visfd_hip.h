@@ -72,7 +72,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * visfd_hip_draw_last_times; then the watershed: visfd_hip_watershed_host,
                                      * visfd_hip_watershed[_dev] and visfd_hip_watershed_last_stats; then the median
                                      * filter: visfd_hip_median_footprint, visfd_hip_median_sphere[_dev],
-                                     * visfd_hip_median_table[_dev] and visfd_hip_median_last_path) */
+                                     * visfd_hip_median_table[_dev] and visfd_hip_median_last_path; then the image
+                                     * statistics and intensity maps: visfd_hip_image_stats[_dev|_host] and
+                                     * visfd_hip_intensity_map[_dev|_host]) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -104,6 +106,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    LDS-tiled kernel; results are bit-identical either way
  *   median_general   1: the median filter always walks the footprint in global memory (csrc/median.hip), never takes the
  *                    LDS-tiled kernel; results are bit-identical either way
+ *   stats_blocks     workgroups of the statistics / intensity-map kernel (csrc/intensity.hip; 0, the default: eight per CU, and
+ *                    never more than the image has work for); results are bit-identical for every value
  *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
  *                    (visfd_hip_draw_last_times); default 0
  *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
@@ -341,6 +345,90 @@ int visfd_hip_median_table_dev(visfd_hip_ctx*, const float* src, float* dst, con
 #define VISFD_HIP_MEDIAN_PATH_TILED 1     /* median_tiled_kernel: 64 x 4 x 4 outputs and their bounding box in LDS (64 KiB:
                                            * balls up to radius 5) */
 int visfd_hip_median_last_path(visfd_hip_ctx*, int* path);
+
+/* ---- m1c: image statistics and the intensity maps that end every filter_mrc run (bin/filter_mrc/filter_mrc.cpp:746-786,
+ * handlers.cpp:1003-1081, lib/threshold/threshold.hpp, MrcSimple::Invert / Rescale01 / FindMinMaxMean) -------------- */
+/* Statistics of the voxels with mask == NULL || mask != 0.
+ *   count        how many voxels that is
+ *   n_nonfinite  how many of them are NaN or +-inf; when this is not 0 the fields below are unspecified
+ *   min, max     by the total order on bit patterns (-0 before +0)
+ *   sum          the EXACT sum of the values, rounded once to double (round to nearest even): what Python's math.fsum
+ *                returns.  The device adds integers -- per exponent field the mantissas of the positive and of the negative
+ *                values in 64-bit words -- so the result depends neither on the launch geometry nor on arrival order; the
+ *                host combines the 255 bins in multi-word integer arithmetic.
+ *   order_free   1 when a double sum of the values is provably the same in EVERY order of additions: all values are
+ *                multiples of 2^q and sum |x| < 2^(q + 53), so every partial sum of every order is a multiple of 2^q below
+ *                2^(q + 53), hence a double, hence exact.  Then sum / count is bit for bit the mean FindMinMaxMean and
+ *                Invert compute serially (mrc_simple.cpp:396-481).  0: not proven (a serial sum may round differently).
+ * count == 0 gives sum = 0, min = max = 0 and order_free = 1. */
+typedef struct visfd_hip_stats {
+  int64_t count;
+  int64_t n_nonfinite;
+  double sum;
+  float min, max;
+  int32_t order_free;
+  int32_t reserved;
+} visfd_hip_stats;
+int visfd_hip_image_stats(visfd_hip_ctx*, const float* src, const float* mask, int64_t n, visfd_hip_stats* out);
+/* src and mask on the device, `out` on the host; returns with the stream idle */
+int visfd_hip_image_stats_dev(visfd_hip_ctx*, const float* src, const float* mask, int64_t n, visfd_hip_stats* out);
+/* the same bins filled by a plain host loop and the same combine: no context, no device */
+int visfd_hip_image_stats_host(const float* src, const float* mask, int64_t n, visfd_hip_stats* out);
+
+/* One pass that applies, per voxel and in the reference's order, the stages `p` switches on:
+ *   1. invert      out = (float)(2.0 * ave - (double)out) where mask != 0                (MrcSimple::Invert)
+ *   2. map         one of VISFD_HIP_MAP_*.  The threshold family READS `in` AND OVERWRITES out (so an inversion is lost, and so
+ *                  is whatever a filter wrote to out: handlers.cpp:1044-1077); RESCALE acts on out: out * t[0], then + t[1],
+ *                  each rounded to float
+ *   3. mask_fill   out = masked_value where mask == 0                                    (filter_mrc.cpp:771-776)
+ *   4. rescale01   out = rescale_a + ((rescale_b - rescale_a) * (out - dmin)) / (dmax - dmin), left to right in float, on
+ *                  every voxel                                                           (MrcSimple::Rescale01)
+ * The maps, with I = in[voxel], a, b, c, d = t[0..3], every operation rounded to float (threshold.hpp with Number = float):
+ *   STEP      I > a ? out_b : out_a
+ *   THRESH2   g = (I - a) / (b - a) when (a <= I && I < b) || (b < I && I <= a), else 1 when (I - a) * (b - a) > 0, else 0;
+ *             out_a + g * (out_b - out_a).  Clipping is THRESH2 with out_a = a and out_b = b (not min(max(I, a), b): the
+ *             bits differ)
+ *   THRESH4   Threshold4 (threshold.hpp:117-169), including its early return of g itself when b == c == d; thresholds that
+ *             are neither increasing nor decreasing (the reference asserts) give the first ramp's g
+ *   RANGE     SelectIntensityRange: 1 or 0, out_a and out_b unused as in the reference (threshold.hpp:206-229)
+ *   GAUSS     (float)(out_a + (double)(out_b - out_a) * exp(-0.5 * xr * xr)), xr = (I - a) / b in float, the rest in
+ *             double.  The device's double exp may differ from the host library's in its last bit: results are within one
+ *             float ulp of the reference's, everything else on this page is bit for bit.
+ * in == out is allowed (in may be NULL when no threshold map is on: it is then not read); any other overlap of out with in
+ * or mask is VISFD_HIP_EINVAL.  mask may be NULL: every voxel then counts as mask != 0.  Loads and stores are 16 bytes wide
+ * where the arrays' addresses agree modulo 16, with a scalar head and tail; arrays need 4-byte alignment only.
+ * stats_out (nullable): the statistics of what was written, under the mask when p->stats_mask, else of every voxel; the
+ * call then returns with the stream idle (without it the _dev face only queues the kernel). */
+#define VISFD_HIP_MAP_NONE 0
+#define VISFD_HIP_MAP_STEP 1
+#define VISFD_HIP_MAP_THRESH2 2
+#define VISFD_HIP_MAP_THRESH4 3
+#define VISFD_HIP_MAP_RANGE 4
+#define VISFD_HIP_MAP_GAUSS 5
+#define VISFD_HIP_MAP_RESCALE 6
+typedef struct visfd_hip_intensity {
+  int32_t invert;       /* stage 1 on / off */
+  int32_t map;          /* stage 2: VISFD_HIP_MAP_* */
+  int32_t mask_fill;    /* stage 3 on / off */
+  int32_t rescale01;    /* stage 4 on / off */
+  int32_t stats_mask;   /* stats_out: 1 under the mask, 0 of every voxel */
+  int32_t reserved;
+  double ave;           /* stage 1: the mean to invert about */
+  float t[4];           /* stage 2: a, b, c, d (GAUSS: x0, sigma; RESCALE: factor, offset) */
+  float out_a, out_b;   /* stage 2 */
+  float masked_value;   /* stage 3 */
+  float dmin, dmax;     /* stage 4 */
+  float rescale_a, rescale_b;
+  float reserved2;
+} visfd_hip_intensity;
+int visfd_hip_intensity_map(visfd_hip_ctx*, const float* in, float* out, const float* mask,
+                            int64_t nx, int64_t ny, int64_t nz, const visfd_hip_intensity* p, visfd_hip_stats* stats_out);
+int visfd_hip_intensity_map_dev(visfd_hip_ctx*, const float* in, float* out, const float* mask,
+                                int64_t nx, int64_t ny, int64_t nz, const visfd_hip_intensity* p, visfd_hip_stats* stats_out);
+/* the same stages by a plain host loop (the scalar functions of csrc/intensity.hpp compiled for the host): no context, no
+ * device; stats_out as above */
+int visfd_hip_intensity_map_host(const float* in, float* out, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                 const visfd_hip_intensity* p, visfd_hip_stats* stats_out);
 
 /* ---- m2: local minima and maxima with plateaus, _FindExtrema (lib/visfd/morphology_implementation.hpp:57-515) ---- */
 /* A plateau is a maximal set of voxels with mask != 0 joined through neighbour pairs of equal value (-0 == +0; a NaN

@@ -20,6 +20,7 @@
 //   Watershed    lib/visfd/segmentation.hpp:65-82
 //   Filter3D     lib/visfd/filter3d.hpp:37-530;  GenFilterGenGauss3D :546-638;  LocalFluctuations[ByRadius] :1698-1926
 //   CompactMultiChannelImage3D  lib/visfd/multichannel_image3d.hpp:41-204
+//   Threshold2, Threshold4, SelectIntensityRange, SelectIntensityRangeGauss  lib/threshold/threshold.hpp:52-258
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
 #ifndef VISFD_HIP_HPP
 #define VISFD_HIP_HPP
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "visfd_hip.h"
+#include "../visfd_amd/csrc/intensity.hpp"   // the scalar intensity maps, shared with the kernels
 
 namespace visfd {
 
@@ -425,6 +427,43 @@ inline void MedianSphere(float radius, int const image_size[3], float const* con
   hip_detail::require_contiguous(aaafMask, image_size);
   hip_detail::check(visfd_hip_median_sphere(hip_detail::context(), hip_detail::flat(aaafSource), hip_detail::flat(aaafDest),
                                             hip_detail::flat(aaafMask), image_size[0], image_size[1], image_size[2], radius));
+}
+
+// ---- intensity maps: lib/threshold/threshold.hpp (Number = float), and the image-level calls of include/visfd_hip.h m1c --
+// The reference's names, arguments and defaults; the arithmetic is csrc/intensity.hpp's, the one the kernels run.
+inline float Threshold2(float intensity, float threshold_01_a, float threshold_01_b, float outA = 0, float outB = 1) {
+  return vh_intensity::threshold2(intensity, threshold_01_a, threshold_01_b, outA, outB);
+}
+inline float Threshold4(float intensity, float threshold_01_a, float threshold_01_b, float threshold_10_a,
+                        float threshold_10_b, float outA = 0, float outB = 1) {
+  return vh_intensity::threshold4(intensity, threshold_01_a, threshold_01_b, threshold_10_a, threshold_10_b, outA, outB);
+}
+// (the reference takes outA and outB and returns 1 or 0 whatever they are)
+inline float SelectIntensityRange(float intensity, float range_a, float range_b, float = 0, float = 1) {
+  return vh_intensity::select_range(intensity, range_a, range_b);
+}
+inline float SelectIntensityRangeGauss(float intensity, float x0, float sigma, float outA = 0, float outB = 1) {
+  return vh_intensity::gauss(intensity, x0, sigma, outA, outB);
+}
+// count, extremes and the exact sum of the voxels with mask != 0 (visfd_hip_image_stats)
+inline visfd_hip_stats ImageStats(const int image_size[3], float const* const* const* aaafI,
+                                  float const* const* const* aaafMask = nullptr) {
+  hip_detail::require_contiguous(aaafI, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  visfd_hip_stats st;
+  hip_detail::check(visfd_hip_image_stats(hip_detail::context(), hip_detail::flat(aaafI), hip_detail::flat(aaafMask),
+                                          (int64_t)image_size[0] * image_size[1] * image_size[2], &st));
+  return st;
+}
+// one pass of the stages of `p` over aaafOut, in place (visfd_hip_intensity_map); aaafIn: the threshold maps' input, which
+// may be aaafOut itself
+inline void IntensityMap(const int image_size[3], float const* const* const* aaafIn, float*** aaafOut,
+                         float const* const* const* aaafMask, const visfd_hip_intensity& p, visfd_hip_stats* stats = nullptr) {
+  hip_detail::require_contiguous(aaafIn, image_size);
+  hip_detail::require_contiguous(aaafOut, image_size);
+  hip_detail::require_contiguous(aaafMask, image_size);
+  hip_detail::check(visfd_hip_intensity_map(hip_detail::context(), hip_detail::flat(aaafIn), hip_detail::flat(aaafOut),
+                                            hip_detail::flat(aaafMask), image_size[0], image_size[1], image_size[2], &p, stats));
 }
 
 // ---- local minima and maxima with plateaus: lib/visfd/morphology.hpp:56-118, morphology_implementation.hpp:57-796 --

@@ -50,6 +50,46 @@ class Region(C.Structure):   # visfd_hip_region: a SimpleRegion<float> (draw.hpp
 
 REGION_RECT, REGION_SPHERE = 0, 1
 
+
+class Stats(C.Structure):   # visfd_hip_stats
+    _fields_ = [("count", C.c_int64), ("n_nonfinite", C.c_int64), ("sum", C.c_double), ("min", C.c_float),
+                ("max", C.c_float), ("order_free", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("count", "n_nonfinite", "sum", "min", "max", "order_free")}
+
+
+class Intensity(C.Structure):   # visfd_hip_intensity: the stages of one intensity-map pass (include/visfd_hip.h)
+    _fields_ = [("invert", C.c_int32), ("map", C.c_int32), ("mask_fill", C.c_int32), ("rescale01", C.c_int32),
+                ("stats_mask", C.c_int32), ("reserved", C.c_int32), ("ave", C.c_double), ("t", C.c_float * 4),
+                ("out_a", C.c_float), ("out_b", C.c_float), ("masked_value", C.c_float), ("dmin", C.c_float),
+                ("dmax", C.c_float), ("rescale_a", C.c_float), ("rescale_b", C.c_float), ("reserved2", C.c_float)]
+
+
+MAP_NONE, MAP_STEP, MAP_THRESH2, MAP_THRESH4, MAP_RANGE, MAP_GAUSS, MAP_RESCALE = range(7)   # VISFD_HIP_MAP_*
+
+
+def intensity(map=MAP_NONE, t=(), out_a=0.0, out_b=1.0, invert_ave=None, masked_value=None, rescale01=None,
+              stats_mask=False):
+    """A visfd_hip_intensity.  map, t, out_a, out_b: the map and its numbers (MAP_RESCALE: t = (factor, offset));
+    invert_ave: invert about this mean where mask != 0; masked_value: the value of voxels with mask == 0;
+    rescale01 = (dmin, dmax, a, b): out = a + ((b - a) * (out - dmin)) / (dmax - dmin); stats_mask: statistics under the
+    mask.  Stages run in that order (MrcSimple::Invert, HandleThresholds, the mask fill, MrcSimple::Rescale01)."""
+    p = Intensity()
+    p.map = int(map)
+    for k, x in enumerate(t):
+        p.t[k] = float(x)
+    p.out_a, p.out_b = float(out_a), float(out_b)
+    if invert_ave is not None:
+        p.invert, p.ave = 1, float(invert_ave)
+    if masked_value is not None:
+        p.mask_fill, p.masked_value = 1, float(masked_value)
+    if rescale01 is not None:
+        p.rescale01 = 1
+        p.dmin, p.dmax, p.rescale_a, p.rescale_b = [float(x) for x in rescale01]
+    p.stats_mask = int(bool(stats_mask))
+    return p
+
 # dst, mask, background, sizes, centers, diameters, thicknesses, foreground, n, offset, rescale, two flags, any_center_outside
 _DRAW_SPHERES = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_int, C.c_int, _ip]
 _DRAW_REGIONS = [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(Region), _i64, C.c_int]
@@ -107,6 +147,12 @@ _SIGS = {
     "visfd_hip_median_table": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
     "visfd_hip_median_table_dev": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
     "visfd_hip_median_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_image_stats": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
+    "visfd_hip_image_stats_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
+    "visfd_hip_image_stats_host": (C.c_int, [_vp, _vp, _i64, C.POINTER(Stats)]),
+    "visfd_hip_intensity_map": (C.c_int, [_vp] + _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
+    "visfd_hip_intensity_map_dev": (C.c_int, [_vp] + _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
+    "visfd_hip_intensity_map_host": (C.c_int, _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
     "visfd_hip_filter3d_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
     "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
@@ -393,6 +439,24 @@ def median_footprint(radius):
     d = np.zeros((n.value, 3), np.int32)
     _chk_host(L, L.visfd_hip_median_footprint(float(radius), d.ctypes.data_as(_ip), len(d), C.byref(n)))
     return d
+
+
+def image_stats_host(src, mask=None):
+    """visfd_hip_image_stats_host: the statistics of Context.image_stats from a plain host loop (no device) -> dict."""
+    L = load_library()
+    st = Stats()
+    _chk_host(L, L.visfd_hip_image_stats_host(_np(src), _np(mask), src.size, C.byref(st)))
+    return st.as_dict()
+
+
+def intensity_map_host(p, out, src=None, mask=None, want_stats=False):
+    """visfd_hip_intensity_map_host: Context.intensity_map by a plain host loop (no device); `out` is written in place."""
+    L = load_library()
+    nz, ny, nx = out.shape
+    st = Stats()
+    _chk_host(L, L.visfd_hip_intensity_map_host(_np(src), _np(out), _np(mask), nx, ny, nz, C.byref(p),
+                                                C.byref(st) if want_stats else None))
+    return st.as_dict() if want_stats else None
 
 
 def gengauss3d_halfwidths(width, m_exp, truncate_ratio=-1.0, truncate_threshold=0.03):
@@ -903,6 +967,31 @@ class Context:
         self._chk(self._L.visfd_hip_median_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
                                                  d.ctypes.data_as(_ip), len(d)))
         return dst
+
+    def image_stats(self, src, mask=None):
+        """Statistics of the voxels with mask != 0 (all without a mask): dict of count, n_nonfinite, min, max, the exact
+        sum rounded once to double (math.fsum's) and order_free (include/visfd_hip.h).  numpy arrays or torch device
+        tensors of any shape; returns with the stream idle."""
+        st = Stats()
+        if isinstance(src, np.ndarray):
+            self._chk(self._L.visfd_hip_image_stats(self._h, _np(src), _np(mask), src.size, C.byref(st)))
+        else:
+            self._chk(self._L.visfd_hip_image_stats_dev(self._h, _dev(src), _dev(mask), src.numel(), C.byref(st)))
+        return st.as_dict()
+
+    def intensity_map(self, p, out, src=None, mask=None, want_stats=False):
+        """One pass of the stages of `p` (api.intensity(...)) over `out`, IN PLACE: invert, one map (the threshold family
+        reads `src`, which may be `out` itself), mask fill, Rescale01.  3-D numpy arrays or torch device tensors.
+        want_stats: -> the statistics of what was written (the call then waits for the stream), else None."""
+        nz, ny, nx = out.shape
+        st = Stats()
+        sp = C.byref(st) if want_stats else None
+        if isinstance(out, np.ndarray):
+            self._chk(self._L.visfd_hip_intensity_map(self._h, _np(src), _np(out), _np(mask), nx, ny, nz, C.byref(p), sp))
+        else:
+            self._chk(self._L.visfd_hip_intensity_map_dev(self._h, _dev(src), _dev(out), _dev(mask), nx, ny, nz,
+                                                          C.byref(p), sp))
+        return st.as_dict() if want_stats else None
 
     def _find_extrema(self, fn, src, mask, shape, find_minima, find_maxima, minima_threshold, maxima_threshold,
                       connectivity, allow_borders, labels):

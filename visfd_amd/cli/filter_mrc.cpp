@@ -33,6 +33,11 @@
 //                              filter_mrc.cpp:220-286; coordinates in voxels) | -mask-crds-units UNITS (read and, as in the
 //                              reference, without effect: settings.cpp:637-658)
 //   -find-minima / -find-maxima with -diameters D -radial-separation R: extrema closer than that are thinned (handlers.cpp:1165-1211)
+//   -invert|-inv | -thresh T | -thresh2 A B | -thresh4 A B C D | -thresh-interval A B | -thresh-gauss X0 SIGMA (each also
+//   as -...-out) | -thresh-range|-thresh-range-out OUTA OUTB | -clip A B | -cl A B (in standard deviations about the mean) |
+//   -rescale M O | -fill V | -rescale-min-max MAX MIN | -no-rescale|-norescale | -mask-select V
+//                              the tail of every run (settings.cpp:954-1186, filter_mrc.cpp:746-786, HandleThresholds);
+//                              the threshold family maps the INPUT image, as in the reference
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is in mrc.hpp, the settings and the parser of the flags above in settings.hpp; both are part of
@@ -389,6 +394,10 @@ void load(Run& r) {
     r.mask.read(s.mask);
     if (r.mask.nx != r.tomo_in.nx || r.mask.ny != r.tomo_in.ny || r.mask.nz != r.tomo_in.nz)
       throw VisfdErr("Error: The size of the mask image does not match the size of the input image.\n");
+    if (s.use_mask_select) {   // filter_mrc.cpp:100-107: the voxels of one label become the mask
+      float* mp = r.mask.data();
+      for (size_t i = 0; i < r.mask.nvox(); i++) mp[i] = (mp[i] == s.mask_select) ? 1.0f : 0.0f;
+    }
   }
   r.size[0] = r.tomo_in.nx; r.size[1] = r.tomo_in.ny; r.size[2] = r.tomo_in.nz;
   for (int d = 0; d < 3; d++) { r.size_orig[d] = r.size[d]; r.cella_orig[d] = r.tomo_in.cella[d]; }
@@ -914,7 +923,118 @@ bool handle_membrane(Run& r) {
   return true;
 }
 
-// What ends every run but a -slab one: back to the input's size, the -mask-out value outside the mask, the output file
+// -cl (handlers.cpp:1015-1032): AverageArr and StdDevArr add in float, weighted by the mask's values, in scan order
+// (visfd_utils.hpp:685-790).  Such sums depend on their order by nature, so they are formed here, on the host, in that order.
+void clipping_sigma_thresholds(Run& r, float* a, float* b) {
+  const float* h = r.tomo_in.data();
+  const float* w = r.mask_flat();
+  const size_t n = r.tomo_in.nvox();
+  float total = 0.0f, denom = 0.0f;
+  for (size_t i = 0; i < n; i++) {
+    float x = h[i];
+    if (w) { x *= w[i]; denom += w[i]; }
+    else denom += 1.0f;
+    total += x;
+  }
+  const float ave = total / denom;
+  total = denom = 0.0f;
+  for (size_t i = 0; i < n; i++) {
+    float x = h[i] - ave;
+    x *= x;
+    if (w) { x *= w[i]; denom += w[i]; }
+    else denom += 1.0f;
+    total += x;
+  }
+  const float stddev = std::sqrt(total / denom);
+  *a = ave + r.s.in_threshold_01_a * stddev;
+  *b = ave + r.s.in_threshold_01_b * stddev;
+  cerr << "ave=" << ave << ", stddev=" << stddev << std::endl;
+  cerr << "  Clipping intensities between [" << *a << ", " << *b << "]" << std::endl;
+}
+
+// The reference's tail (filter_mrc.cpp:746-786): -invert, one intensity map, the -mask-out value outside the mask,
+// -rescale-min-max, each where asked for, in at most one statistics pass and two map passes on the device.
+void intensity_tail(Run& r, bool mask_fill) {
+  const Settings& s = r.s;
+  visfd_hip_ctx* ctx = hip_detail::context();
+  float* out = r.tomo_out.data();
+  const float* mp = r.mask_flat();
+  const size_t n = r.tomo_out.nvox();
+  const int64_t nx = r.tomo_out.nx, ny = r.tomo_out.ny, nz = r.tomo_out.nz;
+  visfd_hip_intensity p;
+  std::memset(&p, 0, sizeof(p));
+  if (s.invert_output) {   // MrcSimple::Invert: about the mean of the voxels inside the mask
+    visfd_hip_stats st;
+    hip_detail::check(visfd_hip_image_stats(ctx, out, mp, (int64_t)n, &st));
+    p.invert = 1;
+    if (st.n_nonfinite == 0 && st.order_free) p.ave = st.sum / (double)st.count;
+    else {
+      cerr << "-invert: summing on the host in scan order (no proof that the sum of this image is the same in every order)\n";
+      double sum = 0.0;
+      long cnt = 0;
+      for (size_t i = 0; i < n; i++)
+        if (!mp || mp[i] != 0.0f) { sum += out[i]; cnt++; }
+      p.ave = sum / cnt;
+    }
+  }
+  if (s.use_intensity_map) {   // HandleThresholds, handlers.cpp:1003-1081
+    cerr << "Applying thresholds" << std::endl;
+    p.out_a = s.out_thresh_a_value;
+    p.out_b = s.out_thresh_b_value;
+    if (s.use_rescale_multiply) {
+      p.map = VISFD_HIP_MAP_RESCALE;
+      p.t[0] = s.out_rescale_multiply; p.t[1] = s.out_rescale_offset;
+    } else if (s.use_gauss_thresholds) {
+      p.map = VISFD_HIP_MAP_GAUSS;
+      p.t[0] = s.out_thresh_gauss_x0; p.t[1] = s.out_thresh_gauss_sigma;
+    } else if (!s.use_dual_thresholds) {
+      float a = s.in_threshold_01_a, b = s.in_threshold_01_b;
+      if (s.out_thresh2_use_clipping_sigma) clipping_sigma_thresholds(r, &a, &b);
+      p.t[0] = a; p.t[1] = b;
+      if (a == b) p.map = VISFD_HIP_MAP_STEP;
+      else {
+        p.map = VISFD_HIP_MAP_THRESH2;
+        if (s.out_thresh2_use_clipping) { p.out_a = a; p.out_b = b; }
+      }
+    } else {
+      p.map = VISFD_HIP_MAP_THRESH4;
+      p.t[0] = s.in_threshold_01_a; p.t[1] = s.in_threshold_01_b; p.t[2] = s.in_threshold_10_a; p.t[3] = s.in_threshold_10_b;
+    }
+    if (s.threshold_map() && (s.type != Settings::NONE || s.invert_output))
+      cerr << "NOTE: " << s.threshold_flag << " maps the INPUT image, as in the reference: what the filter"
+           << (s.invert_output ? " and -invert" : "") << " wrote to the output is overwritten.\n";
+  }
+  if (mask_fill) { p.mask_fill = 1; p.masked_value = s.masked_voxel_brightness; }
+  const bool one_pass = p.invert || p.map != VISFD_HIP_MAP_NONE || p.mask_fill;
+  if (!s.rescale_min_max_out) {
+    if (one_pass) hip_detail::check(visfd_hip_intensity_map(ctx, r.tomo_in.data(), out, mp, nx, ny, nz, &p, nullptr));
+    return;
+  }
+  // MrcSimple::Rescale01: the extremes of what the stages above leave inside the mask, then every voxel
+  visfd_hip_stats st;
+  p.stats_mask = 1;
+  if (one_pass) hip_detail::check(visfd_hip_intensity_map(ctx, r.tomo_in.data(), out, mp, nx, ny, nz, &p, &st));
+  else hip_detail::check(visfd_hip_image_stats(ctx, out, mp, (int64_t)n, &st));
+  float dmin = st.min, dmax = st.max;
+  if (st.n_nonfinite != 0) {   // FindMinMaxMean's comparisons in scan order (mrc_simple.cpp:396-424)
+    double lo = 0.0, hi = -1.0;
+    for (size_t i = 0; i < n; i++) {
+      if (mp && mp[i] == 0.0f) continue;
+      if (lo > hi) lo = hi = out[i];
+      else { if (out[i] > hi) hi = out[i]; if (out[i] < lo) lo = out[i]; }
+    }
+    dmin = (float)lo; dmax = (float)hi;
+  }
+  visfd_hip_intensity q;
+  std::memset(&q, 0, sizeof(q));
+  q.rescale01 = 1;
+  q.dmin = dmin; q.dmax = dmax;
+  q.rescale_a = s.out_rescale_min; q.rescale_b = s.out_rescale_max;
+  hip_detail::check(visfd_hip_intensity_map(ctx, nullptr, out, nullptr, nx, ny, nz, &q, nullptr));
+}
+
+// What ends every run but a -slab one: back to the input's size, the reference's tail (-invert, an intensity map, the
+// -mask-out value outside the mask, -rescale-min-max), the output file
 void finish(Run& r) {
   const Settings& s = r.s;
   if (s.type == Settings::SURFACE_RIDGE && r.bin > 1 && !s.bin_explicit) {   // handlers.cpp:2315-2355
@@ -925,7 +1045,8 @@ void finish(Run& r) {
     if (r.mask.loaded) unbin_image(r.mask, r.size_orig, r.cella_orig);
   }
   // filter_mrc.cpp:765-776: after everything else, voxels outside the mask take the "masked" brightness
-  if (r.mask.loaded && s.type != Settings::BLOB_NONMAX) {
+  if (s.has_tail()) intensity_tail(r, r.mask.loaded && s.type != Settings::BLOB_NONMAX);
+  else if (r.mask.loaded && s.type != Settings::BLOB_NONMAX) {
     float* o = r.tomo_out.data();
     const float* mp = r.mask.data();
     for (size_t i = 0; i < r.tomo_out.nvox(); i++)

@@ -99,6 +99,23 @@ struct Settings {
   //   VISFD_HIP_DEVICE=r filter_mrc ... -slab r WORLD IDFILE -out out_r.rec
   int slab_rank = -1, slab_world = 0;
   string slab_id_file;
+  // the tail of every run (settings.cpp:34-40, :181-202): -invert, one intensity map, -rescale-min-max; -mask-select
+  bool invert_output = false;
+  bool use_intensity_map = false, use_dual_thresholds = false, use_rescale_multiply = false, use_gauss_thresholds = false;
+  float in_threshold_01_a = 0.0f, in_threshold_01_b = 0.0f, in_threshold_10_a = 0.0f, in_threshold_10_b = 0.0f;
+  bool out_thresh2_use_clipping = false, out_thresh2_use_clipping_sigma = false;
+  float out_thresh_a_value = 0.0f, out_thresh_b_value = 1.0f;
+  float out_thresh_gauss_x0 = 0.0f, out_thresh_gauss_sigma = 1.0f;
+  float out_rescale_multiply = 1.0f, out_rescale_offset = 0.0f;
+  bool rescale_min_max_out = false;
+  float out_rescale_min = 0.0f, out_rescale_max = 1.0f;
+  bool use_mask_select = false;
+  int mask_select = 1;
+  string threshold_flag;       // the last flag of the threshold family (the maps that read the input image), for messages
+  string tail_flag;            // the first flag of the tail that was given (empty: none), for messages
+  // the map reads the input image and overwrites the output (handlers.cpp:1044-1077); -rescale / -fill win over it
+  bool threshold_map() const { return use_intensity_map && !use_rescale_multiply; }
+  bool has_tail() const { return invert_output || use_intensity_map || rescale_min_max_out; }
 };
 
 bool read_must_link_file(const string& path, Settings& s);
@@ -452,6 +469,73 @@ Settings parse(int argc, char** argv) {
       // mask coordinates are always voxels
       need(1); i += 2;
     }
+    // ---- the tail: settings.cpp:954-1186 (texts verbatim) and :502-515 ----
+    else if (f == "-rescale" || f == "-thresh-range" || f == "-thresh-range-out" || f == "-rescale-min-max") {
+      const string msg = after(f, "2 numbers:\n outA  outB\n"
+                                  "  (the desired minimum and maximum voxel intensity values for the final image)");
+      const float x = number(v, i + 1, msg, true), y = number(v, i + 2, msg, true);
+      if (f == "-rescale") { s.use_intensity_map = s.use_rescale_multiply = true; s.out_rescale_multiply = x; s.out_rescale_offset = y; }
+      else if (f == "-rescale-min-max") { s.rescale_min_max_out = true; s.out_rescale_max = x; s.out_rescale_min = y; }   // the first is the maximum
+      else { s.out_thresh_a_value = x; s.out_thresh_b_value = y; }
+      if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 3;
+    }
+    else if (f == "-fill") {
+      s.out_rescale_offset = number(v, i + 1, "Error: The " + f + " argument must be followed by a number.", true);
+      s.use_intensity_map = s.use_rescale_multiply = true;
+      s.out_rescale_multiply = 0.0f;
+      if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 2;
+    }
+    else if (f == "-no-rescale" || f == "-norescale") {
+      s.rescale_min_max_out = false; s.in_threshold_01_a = s.in_threshold_01_b = 1.0f; i += 1;
+    }
+    else if (f == "-invert" || f == "-inv") { s.invert_output = true; if (s.tail_flag.empty()) s.tail_flag = f; i += 1; }
+    else if (f == "-thresh" || f == "-thresh-out") {
+      s.in_threshold_01_a = s.in_threshold_01_b = number(v, i + 1, after(f, "1 number."), true);
+      s.use_intensity_map = true; s.use_dual_thresholds = false;
+      s.threshold_flag = f; if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 2;
+    }
+    else if (f == "-thresh2" || f == "-thresh2-out" || f == "-clip" || f == "-cl") {
+      const string msg = after(f, "2 numbers.");
+      const float x = number(v, i + 1, msg, true), y = number(v, i + 2, msg, true);
+      s.use_intensity_map = true; s.use_dual_thresholds = false;
+      s.in_threshold_01_a = x; s.in_threshold_01_b = y;
+      s.out_thresh2_use_clipping = f == "-clip" || f == "-cl";
+      if (s.out_thresh2_use_clipping) s.out_thresh2_use_clipping_sigma = f == "-cl";
+      s.threshold_flag = f; if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 3;
+    }
+    else if (f == "-thresh4" || f == "-thresh4-out") {
+      const string msg = after(f, "4 numbers\n       (These numbers must be either in increasing or decreasing order.)");
+      float x[4];
+      for (size_t k = 0; k < 4; k++) x[k] = number(v, i + 1 + k, msg, true);
+      if (!((x[0] <= x[1] && x[1] <= x[2] && x[2] <= x[3]) || (x[0] >= x[1] && x[1] >= x[2] && x[2] >= x[3]))) throw VisfdErr(msg);
+      s.use_intensity_map = s.use_dual_thresholds = true;
+      s.in_threshold_01_a = x[0]; s.in_threshold_01_b = x[1]; s.in_threshold_10_a = x[2]; s.in_threshold_10_b = x[3];
+      s.threshold_flag = f; if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 5;
+    }
+    else if (f == "-thresh-interval" || f == "-thresh-interval-out" || f == "-thresh-gauss" || f == "-thresh-gauss-out") {
+      const string msg = after(f, "4 numbers.");   // (the reference's count; both flags take two)
+      const float x = number(v, i + 1, msg, true), y = number(v, i + 2, msg, true);
+      s.use_intensity_map = true;
+      if (f == "-thresh-interval" || f == "-thresh-interval-out") {
+        s.use_dual_thresholds = true;
+        s.in_threshold_01_a = s.in_threshold_01_b = x; s.in_threshold_10_a = s.in_threshold_10_b = y;
+      } else { s.use_gauss_thresholds = true; s.out_thresh_gauss_x0 = x; s.out_thresh_gauss_sigma = y; }
+      s.threshold_flag = f; if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 3;
+    }
+    else if (f == "-mask-select") {
+      const string msg = after(f, "an integer.");
+      if (i + 1 >= v.size() || v[i + 1].empty()) throw VisfdErr(msg);
+      try { s.mask_select = std::stoi(v[i + 1]); } catch (...) { throw VisfdErr(msg); }
+      s.use_mask_select = true;
+      if (s.tail_flag.empty()) s.tail_flag = f;
+      i += 2;
+    }
     else if (f == "-slab") {
       need(3);
       s.slab_rank = (int)num(1); s.slab_world = (int)num(2); s.slab_id_file = v[i + 3];
@@ -509,6 +593,13 @@ Settings parse(int argc, char** argv) {
   if (s.slab_world > 0 && (s.type == Settings::DRAW_SPHERES || !s.mask_regions.empty() || (s.type == Settings::BLOB && !s.out.empty())))
     throw VisfdErr("Error: -slab does not draw: -draw-spheres, the -mask-rect / -mask-sphere flags and \"-blob ... -out\"\n"
                    "       need the whole image in one process.\n");
+  if (s.slab_world > 0 && !s.tail_flag.empty())
+    throw VisfdErr("Error: -slab runs with -gauss, -blob and -membrane ... -tv alone: " + s.tail_flag + " (like every flag of\n"
+                   "       -invert, the intensity maps, -rescale-min-max and -mask-select) needs the whole image in one process.\n");
+  if (s.type == Settings::SURFACE_RIDGE && s.threshold_map())
+    throw VisfdErr("Error: " + s.threshold_flag + " does not combine with -membrane: it maps the INPUT image, which the reference\n"
+                   "       has overwritten on that path (handlers.cpp:1932, :2398).  Of the intensity maps, -membrane runs\n"
+                   "       take -rescale, -fill, -invert and -rescale-min-max, which act on the output.\n");
   if (!s.must_link_filename.empty()) s.must_link_in_voxels = read_must_link_file(s.must_link_filename, s);
   if (s.type == Settings::SURFACE_RIDGE) s.tv_sigma *= s.width_a[0];   // settings.cpp:3535-3540
   if (s.cluster_connected_voxels && s.type != Settings::SURFACE_RIDGE)

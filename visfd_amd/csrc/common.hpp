@@ -72,6 +72,7 @@ enum Slot {
   WS_WSH_SEEDS,                    // watershed: the seeds' root indices in list order
   WS_WSH_FLAGS,                    // watershed: the NaN flag and the per-round change flag
   WS_MEDIAN_TAB,                   // median filter: the footprint on the device (host copy in visfd_hip_ctx::median_tab); csrc/median.hip
+  WS_INTENSITY,                    // image statistics: the integer bins of one pass (csrc/intensity.hip), zeroed by every call that uses them
   WS_NSLOTS
 };
 
@@ -103,6 +104,7 @@ struct visfd_hip_options {
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
+  int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
 };

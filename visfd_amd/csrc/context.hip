@@ -54,6 +54,7 @@ const OptionDesc kOptions[] = {
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
     {"median_general", &visfd_hip_options::median_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
+    {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
