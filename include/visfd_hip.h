@@ -74,7 +74,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * filter: visfd_hip_median_footprint, visfd_hip_median_sphere[_dev],
                                      * visfd_hip_median_table[_dev] and visfd_hip_median_last_path; then the image
                                      * statistics and intensity maps: visfd_hip_image_stats[_dev|_host] and
-                                     * visfd_hip_intensity_map[_dev|_host]) */
+                                     * visfd_hip_intensity_map[_dev|_host]; then the distance maps:
+                                     * visfd_hip_distance_sq[_dev], visfd_hip_distance_to_points[_dev],
+                                     * visfd_hip_distance_from_points[_dev] and visfd_hip_distance_last_path) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -106,6 +108,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    LDS-tiled kernel; results are bit-identical either way
  *   median_general   1: the median filter always walks the footprint in global memory (csrc/median.hip), never takes the
  *                    LDS-tiled kernel; results are bit-identical either way
+ *   distance_general 1: the distance maps always take the brute-force walks (csrc/distance.hip: every voxel against every
+ *                    seed, every query point against every selected voxel), never the separable transform; results are
+ *                    bit-identical either way
  *   stats_blocks     workgroups of the statistics / intensity-map kernel (csrc/intensity.hip; 0, the default: eight per CU, and
  *                    never more than the image has work for); results are bit-identical for every value
  *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
@@ -345,6 +350,43 @@ int visfd_hip_median_table_dev(visfd_hip_ctx*, const float* src, float* dst, con
 #define VISFD_HIP_MEDIAN_PATH_TILED 1     /* median_tiled_kernel: 64 x 4 x 4 outputs and their bounding box in LDS (64 KiB:
                                            * balls up to radius 5) */
 int visfd_hip_median_last_path(visfd_hip_ctx*, int* path);
+
+/* ---- exact distance maps (bin/filter_mrc/handlers_unsupported.cpp:1393-1550: -distance-points, -distance-to-voxels) ---- */
+/* The integer quantity behind both handlers, bit for bit:
+ *     dsq(v) = min(cap, min over seeds s of |v - s|^2),   cap = (nx + ny + nz)^2   (the reference's start value)
+ * Seeds are the voxels with mask != 0 (mask nullable) and lo <= src <= hi (a NaN voxel is never one; src nullable: no voxel
+ * is) and the `npoints` listed points (x, y, z as int32 triples, ALWAYS A HOST ARRAY), which may lie anywhere, outside the
+ * image too.  nx + ny + nz must be at most 46340 (beyond it cap overflows the reference's int): VISFD_HIP_EINVAL.
+ * The device work is an exact separable Euclidean distance transform, O(voxels) whatever the number of seeds; only listed
+ * or query points OUTSIDE the image cost O(voxels x such points).  Voxels are cubes: the float forms use one voxel width
+ * (the reference uses voxel_width[0]); anisotropic voxels are not provided.
+ *
+ * visfd_hip_distance_sq[_dev]            dsq (int32, nz*ny*nx) from the seeds above
+ * visfd_hip_distance_to_points[_dev]     dst = sqrtf((float)dsq * (w * w)), every step rounded to float, from the listed
+ *                                        points alone, where mask != 0; dst keeps its value where mask == 0.  dst must not
+ *                                        overlap mask (VISFD_HIP_EINVAL)
+ * visfd_hip_distance_from_points[_dev]   the roles swapped: out[k] (HOST array of npoints floats on both faces) is the same
+ *                                        float formula for the distance from listed point k to the nearest selected voxel
+ *                                        (cap's distance when none is selected); returns with the stream idle */
+#define VISFD_HIP_DISTANCE_MAX_DIM_SUM 46340
+int visfd_hip_distance_sq(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                          float lo, float hi, const int32_t* points, int64_t npoints, int32_t* dsq);
+int visfd_hip_distance_sq_dev(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                              float lo, float hi, const int32_t* points, int64_t npoints, int32_t* dsq);
+int visfd_hip_distance_to_points(visfd_hip_ctx*, float* dst, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                 const int32_t* points, int64_t npoints, float voxel_width);
+int visfd_hip_distance_to_points_dev(visfd_hip_ctx*, float* dst, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                     const int32_t* points, int64_t npoints, float voxel_width);
+int visfd_hip_distance_from_points(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                   float lo, float hi, const int32_t* points, int64_t npoints, float voxel_width,
+                                   float* out);
+int visfd_hip_distance_from_points_dev(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny,
+                                       int64_t nz, float lo, float hi, const int32_t* points, int64_t npoints,
+                                       float voxel_width, float* out);
+/* what the context's last distance call ran: VISFD_HIP_DISTANCE_PATH_* (-1 before the first call) */
+#define VISFD_HIP_DISTANCE_PATH_GENERAL 0     /* the brute-force walks (option distance_general) */
+#define VISFD_HIP_DISTANCE_PATH_TRANSFORM 1   /* the separable transform: a row pass and two lower-envelope passes */
+int visfd_hip_distance_last_path(visfd_hip_ctx*, int* path);
 
 /* ---- m1c: image statistics and the intensity maps that end every filter_mrc run (bin/filter_mrc/filter_mrc.cpp:746-786,
  * handlers.cpp:1003-1081, lib/threshold/threshold.hpp, MrcSimple::Invert / Rescale01 / FindMinMaxMean) -------------- */

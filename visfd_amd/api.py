@@ -26,6 +26,8 @@ MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_TOP_HAT_WHITE, MORPH_T
 MORPH_PATH_GENERAL, MORPH_PATH_XRUNS = 0, 1   # visfd_hip_morph_last_path
 MEDIAN_PATH_GENERAL, MEDIAN_PATH_TILED = 0, 1   # visfd_hip_median_last_path
 FILTER3D_PATH_GENERAL, FILTER3D_PATH_TILED = 0, 1   # visfd_hip_filter3d_last_path
+DISTANCE_PATH_GENERAL, DISTANCE_PATH_TRANSFORM = 0, 1   # visfd_hip_distance_last_path
+DISTANCE_MAX_DIM_SUM = 46340   # VISFD_HIP_DISTANCE_MAX_DIM_SUM
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -104,6 +106,9 @@ _EXTREMA_TAIL = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + 2 *
 _WATERSHED = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
               C.POINTER(_i64)]
 
+# ctx, src, mask, nx, ny, nz, lo, hi, points (host int32 triples), npoints, dsq
+_DIST_SQ = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, _vp, _i64, _vp]
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -147,6 +152,13 @@ _SIGS = {
     "visfd_hip_median_table": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
     "visfd_hip_median_table_dev": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
     "visfd_hip_median_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_distance_sq": (C.c_int, _DIST_SQ),
+    "visfd_hip_distance_sq_dev": (C.c_int, _DIST_SQ),
+    "visfd_hip_distance_to_points": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_float]),
+    "visfd_hip_distance_to_points_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_float]),
+    "visfd_hip_distance_from_points": (C.c_int, _DIST_SQ[:-1] + [C.c_float, _vp]),
+    "visfd_hip_distance_from_points_dev": (C.c_int, _DIST_SQ[:-1] + [C.c_float, _vp]),
+    "visfd_hip_distance_last_path": (C.c_int, [_vp, _ip]),
     "visfd_hip_image_stats": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
     "visfd_hip_image_stats_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
     "visfd_hip_image_stats_host": (C.c_int, [_vp, _vp, _i64, C.POINTER(Stats)]),
@@ -370,6 +382,13 @@ def _dev(t):
         return None
     assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float32", "need contiguous cuda float32"
     return t.data_ptr()
+
+
+def _points(points):
+    """(n, 3) int32 rows x, y, z on the host (None: no points)"""
+    if points is None:
+        return np.zeros((0, 3), np.int32)
+    return np.ascontiguousarray(points, np.int32).reshape(-1, 3)
 
 
 def _f3(v):
@@ -967,6 +986,59 @@ class Context:
         self._chk(self._L.visfd_hip_median_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
                                                  d.ctypes.data_as(_ip), len(d)))
         return dst
+
+    def distance_sq(self, shape=None, points=None, src=None, mask=None, lo=-np.inf, hi=np.inf):
+        """The exact squared distance map (include/visfd_hip.h): int32 min((nx + ny + nz)^2, |v - s|^2 over the seeds s).
+        Seeds: the voxels of `src` with mask != 0 and lo <= src <= hi (src None: none) and the integer `points` ((n, 3)
+        rows x, y, z; anywhere).  shape = (nz, ny, nx) when there is no src.  numpy arrays -> numpy; torch device
+        tensors -> a torch int32 tensor."""
+        nz, ny, nx = src.shape if src is not None else shape
+        pts = _points(points)
+        if src is None or isinstance(src, np.ndarray):
+            dsq = np.empty((nz, ny, nx), np.int32)
+            self._chk(self._L.visfd_hip_distance_sq(self._h, _np(src), _np(mask), nx, ny, nz, float(lo), float(hi),
+                                                    pts.ctypes.data, len(pts), dsq.ctypes.data))
+            return dsq
+        import torch
+        dsq = torch.empty((nz, ny, nx), dtype=torch.int32, device=src.device)
+        self._chk(self._L.visfd_hip_distance_sq_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(lo), float(hi),
+                                                    pts.ctypes.data, len(pts), dsq.data_ptr()))
+        return dsq
+
+    def distance_to_points(self, dst, points, voxel_width=1.0, mask=None):
+        """-distance-points: sqrtf((float)dsq * (w * w)) of the distance to the nearest of `points` where mask != 0; `dst`
+        (3-D float32) keeps its values where mask == 0.  numpy: a new array is returned; torch device tensors: dst is
+        written in place and returned."""
+        nz, ny, nx = dst.shape
+        pts = _points(points)
+        if isinstance(dst, np.ndarray):
+            dst = np.array(dst, np.float32, copy=True, order="C")
+            self._chk(self._L.visfd_hip_distance_to_points(self._h, _np(dst), _np(mask), nx, ny, nz, pts.ctypes.data, len(pts),
+                                                           float(voxel_width)))
+        else:
+            self._chk(self._L.visfd_hip_distance_to_points_dev(self._h, _dev(dst), _dev(mask), nx, ny, nz, pts.ctypes.data,
+                                                               len(pts), float(voxel_width)))
+        return dst
+
+    def distance_from_points(self, src, points, lo, hi, voxel_width=1.0, mask=None):
+        """-distance-to-voxels: for every point the float distance to the nearest voxel with mask != 0 and lo <= src <= hi
+        (the distance of (nx + ny + nz)^2 when there is none) -> float32 numpy array, one per point."""
+        nz, ny, nx = src.shape
+        pts = _points(points)
+        out = np.empty(len(pts), np.float32)
+        if isinstance(src, np.ndarray):
+            fn, a, m = self._L.visfd_hip_distance_from_points, _np(src), _np(mask)
+        else:
+            fn, a, m = self._L.visfd_hip_distance_from_points_dev, _dev(src), _dev(mask)
+        self._chk(fn(self._h, a, m, nx, ny, nz, float(lo), float(hi), pts.ctypes.data, len(pts), float(voxel_width),
+                     out.ctypes.data))
+        return out
+
+    def distance_last_path(self):
+        """What the last distance call ran: DISTANCE_PATH_GENERAL or DISTANCE_PATH_TRANSFORM (-1 before the first)."""
+        p = C.c_int(-1)
+        self._chk(self._L.visfd_hip_distance_last_path(self._h, C.byref(p)))
+        return int(p.value)
 
     def image_stats(self, src, mask=None):
         """Statistics of the voxels with mask != 0 (all without a mask): dict of count, n_nonfinite, min, max, the exact

@@ -38,6 +38,9 @@
 //   -rescale M O | -fill V | -rescale-min-max MAX MIN | -no-rescale|-norescale | -mask-select V
 //                              the tail of every run (settings.cpp:954-1186, filter_mrc.cpp:746-786, HandleThresholds);
 //                              the threshold family maps the INPUT image, as in the reference
+//   -distance-points FILE (may be repeated: the files' points are appended) | -distance-to-voxels PTS OUT A B
+//                              exact distance maps (settings.cpp:2262-2283, HandleDistanceToPoints,
+//                              HandleDistancePointsToFeature); nx + ny + nz <= 46340; not under -slab
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is in mrc.hpp, the settings and the parser of the flags above in settings.hpp; both are part of
@@ -74,8 +77,10 @@ struct Run {
 
 // Blob list file (bin/filter_mrc/file_io.hpp:413-493): 3-5 numbers per line (x y z [diameter [score]]), '#'
 // starts a comment; coordinates written IMOD-style in parentheses mean "units of voxels".  Returns that flag.
+// imod_from_one: the coordinates of a line with parentheses become floor(x) - 1, as the reference's reader leaves them
+// (file_io.hpp:201-204: IMOD counts voxels from 1); the distance handlers ask for it.
 bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vector<float>& diameters,
-                    vector<float>& scores, float score_default, float diameter_factor) {
+                    vector<float>& scores, float score_default, float diameter_factor, bool imod_from_one = false) {
   std::ifstream f(path.c_str());
   if (!f) throw VisfdErr("Error: unable to open \"" + path + "\" for reading.\n");
   bool parens = false;
@@ -84,8 +89,9 @@ bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vec
   while (std::getline(f, line)) {
     const size_t hash = line.find('#');
     if (hash != string::npos) line.erase(hash);
+    bool line_parens = false;
     for (size_t k = 0; k < line.size(); k++) {
-      if (line[k] == '(' || line[k] == ')') { parens = true; line[k] = ' '; }
+      if (line[k] == '(' || line[k] == ')') { parens = line_parens = true; line[k] = ' '; }
       else if (line[k] == ',') line[k] = ' ';
     }
     std::istringstream in(line);
@@ -102,6 +108,8 @@ bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vec
       throw VisfdErr(msg.str());
     }
     std::array<float, 3> c = {{nums[0], nums[1], nums[2]}};
+    if (imod_from_one && line_parens)
+      for (int k = 0; k < 3; k++) c[k] = std::floor(c[k]) - 1.0f;
     crds.push_back(c);
     float d = nums.size() > 3 ? nums[3] : -1.0f;
     if (d < 0) d = -1.0f;
@@ -206,6 +214,54 @@ void handle_draw_spheres(Run& r) {
   std::reverse(scores.begin(), scores.end());
   DrawSpheres(r.size, r.tomo_out.a, r.mask3d(), crds, &diameters, &th, &scores, r.tomo_in.a, s.sphere_decals_background,
               s.sphere_decals_background_scale, s.sphere_decals_background_norm, s.sphere_decals_foreground_norm);
+}
+
+// The integer points of the coordinate files of -distance-points / -distance-to-voxels, the handlers' expression
+// literally (handlers_unsupported.cpp:1402-1423): a file in voxels has 1 subtracted from every coordinate (on top of what
+// the reader did to its lines in parentheses), any other is divided by the voxel width of the axis; then
+// floor(c + 0.5), the sum in double.
+vector<int32_t> read_integer_points(const Run& r) {
+  const Settings& s = r.s;
+  vector<int32_t> pts;
+  for (size_t I = 0; I < s.in_crds_files.size(); I++) {
+    vector<std::array<float, 3> > c;
+    vector<float> d, sc;
+    const bool in_voxels = read_blob_file(s.in_crds_files[I], c, d, sc, s.sphere_decals_foreground, s.sphere_decals_scale, true);
+    for (size_t i = 0; i < c.size(); i++)
+      for (int k = 0; k < 3; k++) {
+        if (in_voxels) c[i][k] -= 1;
+        else c[i][k] /= r.vw[k];
+        const double v = std::floor(c[i][k] + 0.5);
+        // (the reference converts the double to int whatever its size; beyond int32 the point is farther than any cap)
+        pts.push_back(v >= 2147483647.0 ? 2147483647 : v <= -2147483648.0 ? (int32_t)-2147483647 - 1 : (int32_t)v);
+      }
+  }
+  return pts;
+}
+
+// HandleDistanceToPoints, handlers_unsupported.cpp:1393-1465: where mask != 0 the output becomes the distance to the
+// nearest point, in units of voxel_width[0]
+void handle_distance_points(Run& r) {
+  const vector<int32_t> pts = read_integer_points(r);
+  cerr << " ------ calculating distance to points ------\n" << std::endl;
+  hip_detail::check(visfd_hip_distance_to_points(hip_detail::context(), r.tomo_out.data(), r.mask_flat(), r.size[0], r.size[1],
+                                                 r.size[2], pts.data(), (int64_t)(pts.size() / 3), r.vw[0]));
+}
+
+// HandleDistancePointsToFeature, handlers_unsupported.cpp:1470-1550: one line per point, the distance to the nearest voxel
+// inside the mask whose brightness lies in [A, B]; the image is left as it is
+void handle_distance_to_voxels(Run& r) {
+  const Settings& s = r.s;
+  const vector<int32_t> pts = read_integer_points(r);
+  cerr << " ------ calculating distance from points to feature ------\n" << std::endl;
+  vector<float> dist(pts.size() / 3);
+  hip_detail::check(visfd_hip_distance_from_points(hip_detail::context(), r.tomo_in.data(), r.mask_flat(), r.size[0], r.size[1],
+                                                   r.size[2], s.out_thresh_a_value, s.out_thresh_b_value, pts.data(),
+                                                   (int64_t)dist.size(), r.vw[0], dist.data()));
+  std::fstream out;
+  out.open(s.out_distances_file.c_str(), std::ios::out);
+  if (!out) throw VisfdErr("Error: unable to open \"" + s.out_distances_file + "\" for writing.\n");
+  for (size_t i = 0; i < dist.size(); i++) out << dist[i] << std::endl;
 }
 
 // HandleBinning, bin/filter_mrc/handlers.cpp:2361-2425: the image (and the mask) shrink by `bin` per axis
@@ -1082,6 +1138,8 @@ int main(int argc, char** argv) {
       case Settings::WATERSHED: handle_watershed(r); break;
       case Settings::BLOB_NONMAX: handle_blob_nonmax(r); break;
       case Settings::DRAW_SPHERES: handle_draw_spheres(r); break;
+      case Settings::DISTANCE_TO_POINTS: handle_distance_points(r); break;
+      case Settings::DISTANCE_TO_VOXELS: handle_distance_to_voxels(r); break;
       case Settings::SURFACE_RIDGE: whole_image = handle_membrane(r); break;
     }
     if (whole_image) finish(r);

@@ -25,7 +25,7 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES, WATERSHED } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES, WATERSHED, DISTANCE_TO_POINTS, DISTANCE_TO_VOXELS } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until prepare() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
@@ -65,6 +65,7 @@ struct Settings {
   // blob list post-processing (-discard-blobs)
   vector<string> in_crds_files;
   string out_crds_file;
+  string out_distances_file;                                  // -distance-to-voxels (settings.cpp:2272-2283)
   float nonmax_min_radial_separation_ratio = 0.0f;            // settings.cpp:137
   float nonmax_max_overlap_large = std::numeric_limits<float>::infinity();
   float nonmax_max_overlap_small = std::numeric_limits<float>::infinity();
@@ -442,6 +443,23 @@ Settings parse(int argc, char** argv) {
     }
     else if (f == "-spheres-normalize" || f == "-sphere-normalize") { s.sphere_decals_foreground_norm = true; i += 1; }
     else if (one_of(f, {"-spheres01", "-spheres-01", "-sphere01", "-sphere-01"})) { s.sphere_decals_foreground_norm = false; i += 1; }
+    else if (f == "-distance-points") {                                                // settings.cpp:2262-2269
+      if (i + 1 >= v.size()) throw VisfdErr("Error: The " + f + " argument must be followed by a file name.\n");
+      s.type = Settings::DISTANCE_TO_POINTS;
+      s.in_crds_files.push_back(v[i + 1]);
+      i += 2;
+    }
+    else if (f == "-distance-to-voxels") {                                             // settings.cpp:2272-2283
+      const string msg = "Error: The " + f + " argument must be followed by two file names and two numbers:\n"
+                         "       InFile OutFile BrightnessSelectMin BrightnessSelectMax\n";
+      if (i + 4 >= v.size()) throw VisfdErr(msg);
+      s.type = Settings::DISTANCE_TO_VOXELS;
+      s.in_crds_files.push_back(v[i + 1]);
+      s.out_distances_file = v[i + 2];
+      try { s.out_thresh_a_value = std::stof(v[i + 3]); s.out_thresh_b_value = std::stof(v[i + 4]); }
+      catch (...) { throw VisfdErr(msg); }
+      i += 5;
+    }
     else if (f == "-random-spheres")
       throw VisfdErr("Error: -random-spheres is not provided by this program (it needs the reference's random numbers).\n");
     else if (one_of(f, {"-mask-rect", "-mask-rectangle", "-mask-rect-subtract", "-mask-rectangle-subtract", "-mask-sphere",
@@ -593,6 +611,10 @@ Settings parse(int argc, char** argv) {
   if (s.slab_world > 0 && (s.type == Settings::DRAW_SPHERES || !s.mask_regions.empty() || (s.type == Settings::BLOB && !s.out.empty())))
     throw VisfdErr("Error: -slab does not draw: -draw-spheres, the -mask-rect / -mask-sphere flags and \"-blob ... -out\"\n"
                    "       need the whole image in one process.\n");
+  if (s.slab_world > 0 && (s.type == Settings::DISTANCE_TO_POINTS || s.type == Settings::DISTANCE_TO_VOXELS))
+    throw VisfdErr(string("Error: -slab does not combine with ") +
+                   (s.type == Settings::DISTANCE_TO_POINTS ? "-distance-points" : "-distance-to-voxels") +
+                   ": a distance map needs the whole image in one process.\n");
   if (s.slab_world > 0 && !s.tail_flag.empty())
     throw VisfdErr("Error: -slab runs with -gauss, -blob and -membrane ... -tv alone: " + s.tail_flag + " (like every flag of\n"
                    "       -invert, the intensity maps, -rescale-min-max and -mask-select) needs the whole image in one process.\n");

@@ -73,6 +73,9 @@ enum Slot {
   WS_WSH_FLAGS,                    // watershed: the NaN flag and the per-round change flag
   WS_MEDIAN_TAB,                   // median filter: the footprint on the device (host copy in visfd_hip_ctx::median_tab); csrc/median.hip
   WS_INTENSITY,                    // image statistics: the integer bins of one pass (csrc/intensity.hip), zeroed by every call that uses them
+  WS_DIST_DSQ,                     // distance maps: the int32 squared distances behind the float outputs (csrc/distance.hip)
+  WS_DIST_STACK,                   // distance maps: the envelope passes' stacks, per wave [entry][lane] of int2
+  WS_DIST_POINTS,                  // distance maps: the listed points that can matter; query points and their results
   WS_NSLOTS
 };
 
@@ -103,6 +106,7 @@ struct visfd_hip_options {
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
+  int distance_general = 0; // 1: distance maps by the brute-force walks (csrc/distance.hip), never by the separable transform
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
@@ -131,6 +135,7 @@ struct visfd_hip_ctx {
   int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
   std::vector<int> median_tab;        // the footprint now in slot WS_MEDIAN_TAB (n entries dx, dy, dz, 0, then n LDS cell offsets)
   int median_last_path = -1;          // the kernel the last median call ran (VISFD_HIP_MEDIAN_PATH_*)
+  int distance_last_path = -1;        // what the last distance call ran (VISFD_HIP_DISTANCE_PATH_*)
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
@@ -330,6 +335,12 @@ struct MedianTab {
 int median_put_table(visfd_hip_ctx* ctx, const int* dxyz, i64 n, MedianTab* mt);
 int median_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
                const MedianTab& mt);
+
+// distance.hip: dsq = min((nx + ny + nz)^2, squared distance to the nearest seed), int32 on the device.  Seeds: the voxels
+// with mask != 0 and lo <= src <= hi (src nullable: none) and the `npoints` listed points (x, y, z; HOST array; anywhere).
+// The separable transform, or the brute-force walks under the option distance_general (ctx->distance_last_path).
+int dev_distance_sq(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, float lo, float hi,
+                    const int32_t* points, i64 npoints, int32_t* dsq);
 
 // filter3d.hip: Filter3D::Apply with an arbitrary table of (2 hx + 1)(2 hy + 1)(2 hz + 1) entries (x fastest), on device
 // arrays.  dst = sum_j (H[j] * mask[i - j]) * src[i - j] in the reference's order, divided by den = sum_j H[j] * mask[i - j]

@@ -53,6 +53,7 @@ const OptionDesc kOptions[] = {
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
     {"median_general", &visfd_hip_options::median_general, nullptr},
+    {"distance_general", &visfd_hip_options::distance_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
