@@ -81,6 +81,11 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
  *   gauss_wg_per_cu  workgroups per CU the single-sweep filter cuts the volume into (default 2)
+ *   log_pair         both Gaussians of an unmasked DoG / LoG / BlobDog scale in two shared launches (csrc/gauss_pair.hip; one
+ *                    half-width 6..10 on the three axes): 0 never, 1 (default) for the half-widths its table lists, 2 wherever
+ *                    it applies; results are bit-identical either way
+ *   log_pair_chunk   march length of those two launches along z and y (0, the default: 256 and 512); results are
+ *                    bit-identical for every value
  *   tv_dense         1: tensor voting by the baseline kernel
  *   tv_fma           1: TOLERANCE MODE of tensor voting (surfaces, angular exponent 2 or 4): the vote chain with fused
  *                    multiply-adds.  Tensors are then within 1e-5 of the field's scale of the reference's instead of

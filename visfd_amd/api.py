@@ -1501,6 +1501,9 @@ class Context:
         return A.value
 
     def log_dev(self, src, dst, sigma, delta, ratio, mask=None):
+        """ApplyLog on device tensors; dst may be src.  Unmasked scales with one half-width 7..10 run both Gaussians in two
+        shared launches (csrc/gauss_pair.hip); options log_pair (0 never, 1 by its table, 2 wherever it applies) and
+        log_pair_chunk (march length, for tests).  The bits are the same on every route."""
         nz, ny, nx = src.shape
         self._chk(self._L.visfd_hip_apply_log_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
                                                   _f3(sigma), float(delta), float(ratio), None, None))

@@ -24,11 +24,35 @@ int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mas
                          normalize, o);
 }
 
+// Unmasked, both Gaussians first try the pair route (gauss_pair.hip), which declines everything it does not cover --
+// arguments the calls below refuse included.
+static int log_pair_try(visfd_hip_ctx* ctx, const float* src, float* dst, i64 nx, i64 ny, i64 nz, const float sa[3],
+                        const float sb[3], const int hw[3], float scale, float* A, float* B) {
+  if (!ctx || !src || !dst || !sa || !sb || !hw || ctx->opt.log_pair == 0) return GAUSS_DECLINED;
+  LogPairRequest rq = {};
+  rq.src = src; rq.dst = dst; rq.nx = nx; rq.ny = ny; rq.nz = nz; rq.scale = scale;
+  for (int d = 0; d < 3; d++) {
+    if (!(sa[d] >= 0.0f) || !(sb[d] >= 0.0f) || hw[d] < 0 || hw[d] > MAX_HALFWIDTH) return GAUSS_DECLINED;
+    rq.a[d].h = rq.b[d].h = hw[d];
+    host_gauss_taps(sa[d], hw[d], rq.a[d].t);
+    host_gauss_taps(sb[d], hw[d], rq.b[d].t);
+  }
+  const int rc = log_pair_route(ctx, rq);
+  if (rc != VISFD_HIP_OK) return rc;
+  if (A) *A = (rq.a[0].t[hw[0]] * rq.a[1].t[hw[1]]) * rq.a[2].t[hw[2]];   // filter3d.hpp:1044-1046
+  if (B) *B = (rq.b[0].t[hw[0]] * rq.b[1].t[hw[1]]) * rq.b[2].t[hw[2]];
+  return VISFD_HIP_OK;
+}
+
 // ApplyDog (filter3d.hpp:1338-1402); with scale != 1 it is the body of ApplyLog (filter3d.hpp:1466-1498).
 // dst = G_a(src); then the second Gaussian stores (dst - G_b(src)) * scale straight into dst: the launch that writes an
 // element has read its minuend in the same thread, so in place is safe, and a multiplier of 1.0f is exact.
 static int dog_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
                    const float sa[3], const float sb[3], const int hw[3], float scale, float* A, float* B) {
+  if (!mask) {
+    const int rc = log_pair_try(ctx, src, dst, nx, ny, nz, sa, sb, hw, scale, A, B);
+    if (rc != GAUSS_DECLINED) return rc;
+  }
   VH_TRY(gauss_dev(ctx, src, dst, mask, nx, ny, nz, sa, hw, true, {A}));
   return gauss_dev(ctx, src, dst, mask, nx, ny, nz, sb, hw, true, {B, dst, scale});
 }

@@ -89,6 +89,9 @@ struct visfd_hip_options {
   int gauss_3pass = 0;      // 1: the separable filter always takes its three single-axis passes
   int gauss_cfg = 0;        // development aid, kept for set/get: currently selects nothing
   int gauss_wg_per_cu = 2;  // workgroups per CU the single-sweep filter cuts the volume into
+  int log_pair = 1;         // both Gaussians of an unmasked DoG/LoG scale in two shared launches (csrc/gauss_pair.hip): 0 never,
+                            // 1 for the half-widths its table lists, 2 wherever it applies
+  int log_pair_chunk = 0;   // march length of those launches along z and y (0: default); tests put chunk seams into small volumes
   int tv_dense = 0;         // 1: tensor voting by the baseline kernel (csrc/tv.hip)
   int tv_fma = 0;           // 1: TOLERANCE MODE of tensor voting: fused multiply-adds, results within 1e-5 of the field's scale
                             //    instead of bit-identical (surfaces, exponent 2 or 4; everything else stays exact)
@@ -224,6 +227,23 @@ struct GaussRequest {
   bool fma;
   const float* numer;          // Y/X sweep of a mask denominator: dst = numer / result where result > 0, numer elsewhere
 };
+
+// A route returns VISFD_HIP_OK, an error, or GAUSS_DECLINED: nothing launched, the caller takes the next route.
+constexpr int GAUSS_DECLINED = -1;
+// gauss.hip: the boundary normaliser lines Dx | Dy | Dz of one filter into D (nx + ny + nz floats), on the device
+int dev_norm_lines(visfd_hip_ctx* ctx, float* D, i64 nx, i64 ny, i64 nz, const Taps& tx, const Taps& ty, const Taps& tz);
+
+// gauss_pair.hip: dst = (G_a(src) - G_b(src)) * scale, unmasked and normalised, both filters in two shared launches.
+// a[d], b[d]: the taps of the two filters along x, y, z; dst may be src.  Declines what it does not cover.
+struct LogPairRequest {
+  const float* src;
+  float* dst;
+  i64 nx, ny, nz;
+  Taps a[3], b[3];
+  float scale;
+  i64 z_lo, nz_global;   // Z-slab placement, as in GaussOpts
+};
+int log_pair_route(visfd_hip_ctx* ctx, const LogPairRequest& rq);
 
 // api.hip: the Gaussian from sigmas and half-widths, and ApplyLog
 int gauss_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,

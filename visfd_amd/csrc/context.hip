@@ -57,6 +57,8 @@ const OptionDesc kOptions[] = {
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
+    {"log_pair", &visfd_hip_options::log_pair, nullptr},
+    {"log_pair_chunk", &visfd_hip_options::log_pair_chunk, nullptr},
 };
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {

@@ -369,10 +369,16 @@ static bool fused_applies(const visfd_hip_ctx* ctx, const GaussRequest& rq) {
   return true;
 }
 
-// A route returns VISFD_HIP_OK, an error, or GAUSS_DECLINED: nothing launched, the caller takes the three passes.
-constexpr int GAUSS_DECLINED = -1;
+// (GAUSS_DECLINED: nothing launched, the caller takes the three passes)
 static int gauss_fused_route(visfd_hip_ctx* ctx, const GaussRequest& rq) {
   return fused_applies(ctx, rq) ? fused_launch[rq.tx.h](ctx, rq) : GAUSS_DECLINED;
+}
+
+int dev_norm_lines(visfd_hip_ctx* ctx, float* D, i64 nx, i64 ny, i64 nz, const Taps& tx, const Taps& ty, const Taps& tz) {
+  const i64 total = nx + ny + nz;
+  norm_lines_kernel<<<dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(D, nx, ny, nz, tx, ty, tz);
+  VH_HIP(hipGetLastError());
+  return VISFD_HIP_OK;
 }
 
 // With a minuend, dst receives (minuend - G(src)) * log_scale on every route -- the single sweep and the last launch of
@@ -404,8 +410,7 @@ int dev_separable3d(visfd_hip_ctx* ctx, const float* src, float* dst, const floa
     const i64 nz_global = o.nz_global ? o.nz_global : nz;
     const i64 total = nx + ny + nz_global;
     VH_TRY(ws(ctx, WS_NORM, (size_t)total, &D));
-    norm_lines_kernel<<<dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(D, nx, ny, nz_global, Tx, Ty, Tz);
-    VH_HIP(hipGetLastError());
+    VH_TRY(dev_norm_lines(ctx, D, nx, ny, nz_global, Tx, Ty, Tz));
     rq.Dx = D; rq.Dy = D + nx; rq.Dz = D + nx + ny;
   }
 
