@@ -1501,7 +1501,7 @@ class Context:
         return A.value
 
     def log_dev(self, src, dst, sigma, delta, ratio, mask=None):
-        """ApplyLog on device tensors; dst may be src.  Unmasked scales with one half-width 7..10 run both Gaussians in two
+        """ApplyLog on device tensors; dst may be src.  Unmasked scales with one half-width 6..10 run both Gaussians in two
         shared launches (csrc/gauss_pair.hip); options log_pair (0 never, 1 by its table, 2 wherever it applies) and
         log_pair_chunk (march length, for tests).  The bits are the same on every route."""
         nz, ny, nx = src.shape

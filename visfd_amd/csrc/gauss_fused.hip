@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "exact_div.hpp"
 
 #ifndef VH_FUSED_H
 #error "compile with -DVH_FUSED_H=<halfwidth>"
@@ -538,34 +539,17 @@ gauss_fused_kernel(const float* __restrict__ src, float* __restrict__ dst, TapsH
           } else if (NORMALIZE) {
             // dest /= (Dx*Dy)*Dz (filter3d.hpp:1016-1018), one correctly rounded division.  On planes with the
             // interior Dz the divisor is a per-lane constant whose correctly rounded reciprocal y is known, and
-            // the quotient follows from two Newton corrections with exact FMA residuals (Markstein): q1 = q0 +
-            // (a - d q0) y is a faithful quotient, q2 = q1 + (a - d q1) y is the correctly rounded one.  The
-            // residuals are exact only while nothing under- or overflows, hence the range guard; everything
-            // else (first/last H planes, zeros, extreme magnitudes) takes the full-range division.
+            // the quotient follows from two Newton corrections with exact FMA residuals (csrc/exact_div.hpp, which
+            // also has the range guard); everything else (first/last H planes, zeros, extreme magnitudes) takes the
+            // full-range division.
             float d[C::XV];
 #pragma unroll
             for (int k = 0; k < C::XV; k++) d[k] = dxy[k] * dz;
             bool fast = dz_is_int;
-            if (fast) {
-              float hi = __builtin_fmaxf(__builtin_fabsf(a[0]), __builtin_fabsf(a[1]));
-              float lo = __builtin_fminf(__builtin_fabsf(a[0]), __builtin_fabsf(a[1]));
-#pragma unroll
-              for (int k = 2; k < C::XV; k++) {
-                hi = __builtin_fmaxf(hi, __builtin_fabsf(a[k]));
-                lo = __builtin_fminf(lo, __builtin_fabsf(a[k]));
-              }
-              fast = __builtin_amdgcn_ballot_w64(!((hi < 0x1p100f) && (lo >= 0x1p-100f))) == 0ull;
-            }
+            if (fast) fast = __builtin_amdgcn_ballot_w64(!exact_div_in_range<C::XV>(a)) == 0ull;
             if (fast) {
 #pragma unroll
-              for (int k = 0; k < C::XV; k++) {
-                const float y = rcp_int[k];
-                const float q0 = a[k] * y;
-                const float r0 = __builtin_fmaf(-d[k], q0, a[k]);
-                const float q1 = __builtin_fmaf(r0, y, q0);
-                const float r1 = __builtin_fmaf(-d[k], q1, a[k]);
-                a[k] = __builtin_fmaf(r1, y, q1);
-              }
+              for (int k = 0; k < C::XV; k++) a[k] = exact_div(a[k], d[k], rcp_int[k]);
             } else {
 #pragma unroll
               for (int k = 0; k < C::XV; k++) a[k] = a[k] / d[k];

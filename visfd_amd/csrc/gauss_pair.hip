@@ -31,7 +31,7 @@ constexpr int Z_PF = 8;       // planes requested ahead of the one being added
 constexpr int YX_NT = 256;    // pair_yx_kernel: columns per workgroup, X halo included.  Measured at 1024^3, H = 10, one LoG
                               // scale: 128 / 192 / 256 / 320 / 384 columns 8.9 / 9.0 / 8.5-8.8 / 10.5 / 10.1 ms: three or more
                               // workgroups per CU, each in another phase of its turn, keep the SIMDs busy across the barriers
-constexpr int YX_PF = 12;     // rows requested ahead, per filter
+constexpr int YX_PF = 12;     // rows requested ahead, per filter (8 and 16 time the same)
 constexpr int Z_CHUNK = 256;  // default march lengths; every chunk pays a 2H warm-up
 constexpr int Y_CHUNK = 512;
 
@@ -140,14 +140,21 @@ pair_z_kernel(const float* __restrict__ src, float* __restrict__ za, float* __re
 // two rings, exactly as launch 1 marches in z.  One turn of the ring completes W rows of both filters, which go to LDS; the
 // X pass then gathers the 2H+1 window as conv_row_kernel does, four adjacent outputs per task from 16-byte LDS reads,
 // divides each filter by its normaliser and stores the difference.
+//
+// The X task reads nothing from global memory: the normaliser lines it needs, Dx over the tile and Dy over the chunk's rows,
+// are parked in LDS once per workgroup (sKx, sKy), and the tasks are dealt over the quads of the tile that lie inside the
+// image only (the last tile of a row is mostly outside it).  A wave all of whose columns lie outside the image has nothing
+// to march: it zeroes its LDS columns once, requests nothing, and only joins the barriers and the X pass.
 template <int H>
 struct YxCfg {
   static constexpr int W = 2 * H + 1;
   static constexpr int XW = (2 * H + 4 + 3) / 4;          // 16-byte reads that cover the window of four outputs
   static constexpr int TX = YX_NT + 4 - 4 * XW;           // output columns per tile: the last task's reads end inside the row
   static constexpr int QPR = TX / 4;                      // tasks per row
+  static constexpr int LDS = (int)sizeof(float) * (2 * W * YX_NT + 2 * TX + 2 * Y_CHUNK);
   static_assert(TX % 4 == 0 && TX + 2 * H <= YX_NT && TX > 0, "tile width");
-  static_assert(sizeof(float) * 2 * W * YX_NT <= 64 * 1024, "LDS rows of both filters");
+  static_assert(LDS <= 64 * 1024, "LDS rows of both filters and the normaliser lines");
+  static_assert(H > 8 || 4 * LDS <= 160 * 1024, "four workgroups per CU up to H = 8");
 };
 
 template <int H>
@@ -159,6 +166,8 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
   constexpr int W = C::W;
   __shared__ __attribute__((aligned(16))) float sA[W][YX_NT];
   __shared__ __attribute__((aligned(16))) float sB[W][YX_NT];
+  __shared__ __attribute__((aligned(16))) float sKx[2][C::TX];    // Dx of filter a | b over the tile's output columns
+  __shared__ float sKy[2][Y_CHUNK];                               // Dy of filter a | b over the chunk's rows (ychunk <= Y_CHUNK)
   float ta[H + 1], tb[H + 1];
   taps_to_vgprs<H>(tp, ta, tb);
   unsigned b = blockIdx.x;
@@ -170,6 +179,8 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
   const int x0 = bx * C::TX;
   const int xc = x0 - H + tid;   // this thread's column (LDS index tid)
   const bool col_ok = xc >= 0 && xc < nx;
+  // the wave's first column is at or past the end of the row (its last one is never left of the image: x0 >= 0, H < 64)
+  const bool idle = x0 - H + 64 * __builtin_amdgcn_readfirstlane(tid >> 6) >= nx;
   const int ys = by * ychunk;
   const int ye = min(ys + ychunk, ny);
   const int nsteps = ye - ys + 2 * H;
@@ -183,124 +194,155 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
   float ra[W], rb[W], qa[YX_PF], qb[YX_PF];
 #pragma unroll
   for (int m = 0; m < W; m++) ra[m] = rb[m] = 0.0f;
+  if (!idle) {
 #pragma unroll
-  for (int i = 0; i < YX_PF; i++) {
-    qa[i] = pa[row_off(i)];
-    qb[i] = pb[row_off(i)];
+    for (int i = 0; i < YX_PF; i++) {
+      qa[i] = pa[row_off(i)];
+      qb[i] = pb[row_off(i)];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < YX_PF; i++) qa[i] = qb[i] = 0.0f;
+#pragma unroll
+    for (int m = 0; m < W; m++) sA[m][tid] = sB[m][tid] = 0.0f;   // what marching zero extension would leave, up to the zero's sign
   }
   // normaliser lines of each filter: Dx | Dy | Dz(global)
   const float* Dax = Da; const float* Day = Da + nx; const float* Daz = Da + nx + ny + dz_offset;
   const float* Dbx = Db; const float* Dby = Db + nx; const float* Dbz = Db + nx + ny + dz_offset;
   const float daz = Daz[z], dbz = Dbz[z];
+  if (tid < C::TX) {   // (visible to the X pass after the first turn's barrier)
+    const int xi = min(x0 + tid, nx - 1);
+    sKx[0][tid] = Dax[xi];
+    sKx[1][tid] = Dbx[xi];
+  }
+  for (int i = tid; i < ye - ys; i += YX_NT) {
+    sKy[0][i] = Day[ys + i];
+    sKy[1][i] = Dby[ys + i];
+  }
   float* const out_plane = dst + zoff;
+  // X tasks: (row u, quad qd) = task / QV, task % QV over the QV quads of this tile inside the image, task = tid, tid + YX_NT,
+  // ...: kept as a pair that is stepped, so that the (uniform) QV costs one division per kernel
+  const int QV = min(C::QPR, (nx - x0 + 3) >> 2);
+  const int u_first = tid / QV, q_first = tid - u_first * QV;
+  const int u_step = YX_NT / QV, q_step = YX_NT - u_step * QV;
+
+  // one X task: row u of the turn that began at step nb, outputs x0 + 4 qd .. + 3; LDS index of output x0 + i is i + H
+  auto x_task = [&](int u, int qd, int nb) {
+    const int s = nb + u;
+    const int y = ktop + H - s;
+    const int x = x0 + 4 * qd;
+    if (s < 2 * H || y < ys || x >= nx) return;
+    float ga[4], gb[4];
+    {
+      float v[4 * C::XW];
+#pragma unroll
+      for (int k = 0; k < C::XW; k++) {
+        const float4 t4 = *reinterpret_cast<const float4*>(&sA[u][4 * qd + 4 * k]);
+        v[4 * k] = t4.x; v[4 * k + 1] = t4.y; v[4 * k + 2] = t4.z; v[4 * k + 3] = t4.w;
+      }
+#pragma unroll
+      for (int jj = 0; jj < W; jj++) {   // j = jj - H ascending <=> window index descending
+        const float t = ta[jj < H ? H - jj : jj - H];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const float term = t * v[2 * H - jj + k];
+          ga[k] = jj == 0 ? term : ga[k] + term;
+        }
+      }
+    }
+    {
+      float v[4 * C::XW];
+#pragma unroll
+      for (int k = 0; k < C::XW; k++) {
+        const float4 t4 = *reinterpret_cast<const float4*>(&sB[u][4 * qd + 4 * k]);
+        v[4 * k] = t4.x; v[4 * k + 1] = t4.y; v[4 * k + 2] = t4.z; v[4 * k + 3] = t4.w;
+      }
+#pragma unroll
+      for (int jj = 0; jj < W; jj++) {
+        const float t = tb[jj < H ? H - jj : jj - H];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const float term = t * v[2 * H - jj + k];
+          gb[k] = jj == 0 ? term : gb[k] + term;
+        }
+      }
+    }
+    const float4 ka = *reinterpret_cast<const float4*>(&sKx[0][4 * qd]);
+    const float4 kb = *reinterpret_cast<const float4*>(&sKx[1][4 * qd]);
+    const float dxa[4] = {ka.x, ka.y, ka.z, ka.w}, dxb[4] = {kb.x, kb.y, kb.z, kb.w};
+    const float day = sKy[0][y - ys], dby = sKy[1][y - ys];
+    // the sums started from their first product: +0.0 once restores the reference's zero signs (see the header)
+    float da[4], db[4];
+    bool ones = true;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      ga[k] = ga[k] + 0.0f;
+      gb[k] = gb[k] + 0.0f;
+      da[k] = (dxa[k] * day) * daz;   // (Dx*Dy) first, then *Dz (filter3d.hpp:1016-1018)
+      db[k] = (dxb[k] * dby) * dbz;
+      ones = ones && da[k] == 1.0f && db[k] == 1.0f;
+    }
+    // x / 1.0f is x for every x: where every divisor of the wave is exactly 1 (the interior, for about half of all sigmas)
+    // the divisions are skipped, as the single sweep's wave_one does
+    if (__builtin_amdgcn_ballot_w64(!ones) != 0ull) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        ga[k] = ga[k] / da[k];
+        gb[k] = gb[k] / db[k];
+      }
+    }
+    float r[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {   // the DoG/LoG epilogue (filter3d.hpp:1387-1390, :1495-1498): two roundings
+      const float dd = ga[k] - gb[k];
+      r[k] = dd * scale;
+    }
+    float* o = out_plane + (i64)y * nx + x;
+    if (vec_ok && x + 3 < nx) {
+      typedef float v4f __attribute__((ext_vector_type(4)));
+      const v4f r4 = {r[0], r[1], r[2], r[3]};
+      __builtin_nontemporal_store(r4, reinterpret_cast<v4f*>(o));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (x + k < nx) __builtin_nontemporal_store(r[k], &o[k]);
+    }
+  };
+  auto march_step = [&](auto U, int nb) {
+    constexpr int u = decltype(U)::value;
+    const int s = nb + u;
+    const bool in = inside(s);
+    const float xa = in ? qa[0] : 0.0f, xb = in ? qb[0] : 0.0f;
+#pragma unroll
+    for (int i = 0; i + 1 < YX_PF; i++) { qa[i] = qa[i + 1]; qb[i] = qb[i + 1]; }
+    qa[YX_PF - 1] = pa[row_off(s + YX_PF)];
+    qb[YX_PF - 1] = pb[row_off(s + YX_PF)];
+    scatter<H, u>(ra, ta, xa);
+    scatter<H, u>(rb, tb, xb);
+    sA[u][tid] = ra[u];   // row y = ktop + H - s of this turn (not an output row while s < 2H or y < ys)
+    sB[u][tid] = rb[u];
+    __builtin_amdgcn_sched_barrier(0);   // (as in launch 1)
+  };
 
 #pragma nounroll
   for (int nb = 0; nb < nsteps; nb += W) {
-    static_for<0, W>([&](auto U) {
-      constexpr int u = decltype(U)::value;
-      const int s = nb + u;
-      const bool in = inside(s);
-      const float xa = in ? qa[0] : 0.0f, xb = in ? qb[0] : 0.0f;
-#pragma unroll
-      for (int i = 0; i + 1 < YX_PF; i++) { qa[i] = qa[i + 1]; qb[i] = qb[i + 1]; }
-      qa[YX_PF - 1] = pa[row_off(s + YX_PF)];
-      qb[YX_PF - 1] = pb[row_off(s + YX_PF)];
-      scatter<H, u>(ra, ta, xa);
-      scatter<H, u>(rb, tb, xb);
-      sA[u][tid] = ra[u];   // row y = ktop + H - s of this turn (not an output row while s < 2H or y < ys)
-      sB[u][tid] = rb[u];
-      __builtin_amdgcn_sched_barrier(0);   // (as in launch 1)
-    });
+    if (!idle) static_for<0, W>([&](auto U) { march_step(U, nb); });
     __syncthreads();
-    // X pass over the W rows of this turn: task = (row u, four outputs x0 + 4q .. +3); LDS index of output x0 + i is i + H
-    for (int task = tid; task < W * C::QPR; task += YX_NT) {
-      const int u = task / C::QPR, qd = task - u * C::QPR;
-      const int s = nb + u;
-      const int y = ktop + H - s;
-      const int x = x0 + 4 * qd;
-      if (s < 2 * H || y < ys || x >= nx) continue;
-      float ga[4], gb[4];
-      {
-        float v[4 * C::XW];
-#pragma unroll
-        for (int k = 0; k < C::XW; k++) {
-          const float4 t4 = *reinterpret_cast<const float4*>(&sA[u][4 * qd + 4 * k]);
-          v[4 * k] = t4.x; v[4 * k + 1] = t4.y; v[4 * k + 2] = t4.z; v[4 * k + 3] = t4.w;
-        }
-#pragma unroll
-        for (int jj = 0; jj < W; jj++) {   // j = jj - H ascending <=> window index descending
-          const float t = ta[jj < H ? H - jj : jj - H];
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const float term = t * v[2 * H - jj + k];
-            ga[k] = jj == 0 ? term : ga[k] + term;
-          }
-        }
-      }
-      {
-        float v[4 * C::XW];
-#pragma unroll
-        for (int k = 0; k < C::XW; k++) {
-          const float4 t4 = *reinterpret_cast<const float4*>(&sB[u][4 * qd + 4 * k]);
-          v[4 * k] = t4.x; v[4 * k + 1] = t4.y; v[4 * k + 2] = t4.z; v[4 * k + 3] = t4.w;
-        }
-#pragma unroll
-        for (int jj = 0; jj < W; jj++) {
-          const float t = tb[jj < H ? H - jj : jj - H];
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const float term = t * v[2 * H - jj + k];
-            gb[k] = jj == 0 ? term : gb[k] + term;
-          }
-        }
-      }
-      // the sums started from their first product: +0.0 once restores the reference's zero signs (see the header)
-      float da[4], db[4];
-      const float day = Day[y], dby = Dby[y];
-      bool ones = true;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int xi = min(x + k, nx - 1);
-        ga[k] = ga[k] + 0.0f;
-        gb[k] = gb[k] + 0.0f;
-        da[k] = (Dax[xi] * day) * daz;   // (Dx*Dy) first, then *Dz (filter3d.hpp:1016-1018)
-        db[k] = (Dbx[xi] * dby) * dbz;
-        ones = ones && da[k] == 1.0f && db[k] == 1.0f;
-      }
-      // x / 1.0f is x for every x: where every divisor of the wave is exactly 1 (the interior, for about half of all sigmas)
-      // the divisions are skipped, as the single sweep's wave_one does
-      if (__builtin_amdgcn_ballot_w64(!ones) != 0ull) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          ga[k] = ga[k] / da[k];
-          gb[k] = gb[k] / db[k];
-        }
-      }
-      float r[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {   // the DoG/LoG epilogue (filter3d.hpp:1387-1390, :1495-1498): two roundings
-        const float dd = ga[k] - gb[k];
-        r[k] = dd * scale;
-      }
-      float* o = out_plane + (i64)y * nx + x;
-      if (vec_ok && x + 3 < nx) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f r4 = {r[0], r[1], r[2], r[3]};
-        __builtin_nontemporal_store(r4, reinterpret_cast<v4f*>(o));
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (x + k < nx) __builtin_nontemporal_store(r[k], &o[k]);
-      }
+    // X pass over the W rows of this turn
+    for (int u = u_first, qd = q_first; u < W;) {
+      x_task(u, qd, nb);
+      u += u_step;
+      qd += q_step;
+      if (qd >= QV) { qd -= QV; u++; }
     }
     __syncthreads();   // the rows are overwritten by the next turn
   }
 }
 
-// Which half-widths take the route under log_pair = 1: filled from tools/log_pair_time.py (profiles/log_pair_time.txt: one
-// LoG scale at 1024^3, H = 7 / 8 / 9 / 10: -1.1 / -1.4 / -5.1 / -5.2 ms against spreads below 0.2 ms; H = 6: -0.3 ms, left out)
+// Which half-widths take the route under log_pair = 1: filled from tools/log_pair_time.py (profiles/pair_yx_time.txt: one LoG
+// scale at 1024^3, H = 6 / 7 / 8 / 9 / 10: -1.0 / -1.9 / -2.0 / -5.5 / -5.8 ms against spreads below 0.2 ms)
 constexpr int PAIR_H_MIN = 6, PAIR_H_MAX = 10;
-const bool kPairWins[PAIR_H_MAX + 1] = {false, false, false, false, false, false, /*6*/ false, /*7*/ true, /*8*/ true,
+const bool kPairWins[PAIR_H_MAX + 1] = {false, false, false, false, false, false, /*6*/ true, /*7*/ true, /*8*/ true,
                                         /*9*/ true, /*10*/ true};
 
 bool bit_symmetric(const Taps& T) {
@@ -328,7 +370,7 @@ int launch_pair(visfd_hip_ctx* ctx, const LogPairRequest& rq, const float* Da, c
   i64 zchunk = opt_chunk > 0 ? opt_chunk : Z_CHUNK;
   if ((nz + zchunk - 1) / zchunk > 65535) zchunk = (nz + 65534) / 65535;   // chunks ride in blockIdx.y
   const i64 zblocks = (plane + Z_NT - 1) / Z_NT, zchunks = (nz + zchunk - 1) / zchunk;
-  const i64 ychunk = opt_chunk > 0 ? opt_chunk : Y_CHUNK;
+  const i64 ychunk = opt_chunk > 0 && opt_chunk < Y_CHUNK ? opt_chunk : Y_CHUNK;   // (the kernel parks Dy of a chunk in LDS)
   const i64 xtiles = (nx + C::TX - 1) / C::TX, ychunks = (ny + ychunk - 1) / ychunk;
   const i64 yxblocks = xtiles * ychunks * nz;
   if (zblocks > 0x7fffffffLL || yxblocks > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
