@@ -76,7 +76,11 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * statistics and intensity maps: visfd_hip_image_stats[_dev|_host] and
                                      * visfd_hip_intensity_map[_dev|_host]; then the distance maps:
                                      * visfd_hip_distance_sq[_dev], visfd_hip_distance_to_points[_dev],
-                                     * visfd_hip_distance_from_points[_dev] and visfd_hip_distance_last_path) */
+                                     * visfd_hip_distance_from_points[_dev] and visfd_hip_distance_last_path; then the
+                                     * supervised blob thresholds: visfd_hip_find_spheres[_dev|_host],
+                                     * visfd_hip_find_spheres_last_path, visfd_hip_choose_threshold_1d,
+                                     * visfd_hip_find_blob_scores, visfd_hip_choose_blob_score_thresholds[_multi] and
+                                     * visfd_hip_discard_blobs_by_score_supervised) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -122,6 +126,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    (visfd_hip_draw_last_times); default 0
  *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
  *                    markers they always do); labels and lists are identical either way; default 0
+ *   find_spheres_host 1: visfd_hip_find_spheres[_dev] walk the (query, sphere) pairs on the host (the walk of
+ *                    visfd_hip_find_spheres_host) instead of launching the search kernel; ids are identical either way; default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -675,6 +681,78 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
                                         float min_radial_separation_ratio,
                                         float max_volume_overlap_large, float max_volume_overlap_small,
                                         int sort_criteria, int scale);
+
+/* ---- f3, continued: FindSpheres and the supervised score thresholds ("-auto-thresh score -supervised POS NEG") ----
+ * FindSpheres, lib/visfd/visfd_utils.hpp:271-359: for every query point the sphere of the list that holds it, the LAST
+ * one when several do.  The reference paints every sphere into an integer table as large as the bounding box of the
+ * queries and reads the queries off it; here nothing is painted: the answer is, per query, the largest index among the
+ * spheres that contain it, an integer max-reduction over (query, sphere) pairs.  Exact, the reference's arithmetic:
+ *   query q[d]    = (int)crds[i][d], a truncation toward zero (-0.5 becomes 0)
+ *   centre c[d]   = (int)sphere_crds[i][d], also a truncation; centres may lie anywhere, negative included
+ *   R             = max(0, (int)ceil(diameter / 2 - 0.5)): the division in float, the rest in double
+ *   Rsqr          = max(0, (int)ceil(SQR(diameter / 2) - 0.5)): the square in float, the rest in double
+ *   i contains q  iff |q - c| <= R on every axis and |q - c|^2 <= Rsqr (integers).  A diameter <= 1, negative ones
+ *                 included, has R = 0: its sphere is the centre voxel, whatever Rsqr is
+ *   ids[k]        = 1 + the largest containing index, 0 when no sphere contains query k
+ * crds: n_crds x 3 floats, sphere_crds: n_spheres x 3 floats, sphere_diameters: n_spheres floats, ids: n_crds int64.
+ * VISFD_HIP_EINVAL, ids untouched: a query whose truncation is negative (the reference reads outside its table), a
+ * non-finite coordinate or diameter, R > VISFD_HIP_FIND_SPHERES_MAX_R, n_spheres >= 2^31, a null array with a non-zero
+ * count.  n_crds == 0 and n_spheres == 0 are valid (nothing written; all zeros).  Coordinates beyond the int range
+ * saturate (the reference's conversion is undefined there).
+ *   visfd_hip_find_spheres_host   no context, no device: a walk over the pairs
+ *   visfd_hip_find_spheres        host arrays, staged through the context's workspace; the search runs on the device
+ *                                 (csrc/find_spheres.hip); what it checks it checks on the host, before anything is launched
+ *   visfd_hip_find_spheres_dev    device arrays (ids: int64 on the device).  The values are checked by the two
+ *                                 preparation launches, whose one flag word the call waits for; the search itself is
+ *                                 asynchronous on the context's stream
+ * Context option find_spheres_host (VISFD_HIP_FIND_SPHERES_HOST): the two context faces run the host walk instead. */
+#define VISFD_HIP_FIND_SPHERES_MAX_R 46340
+int visfd_hip_find_spheres_host(const float* crds, int64_t n_crds, const float* sphere_crds, const float* sphere_diameters,
+                                int64_t n_spheres, int64_t* ids);
+int visfd_hip_find_spheres(visfd_hip_ctx*, const float* crds, int64_t n_crds, const float* sphere_crds,
+                           const float* sphere_diameters, int64_t n_spheres, int64_t* ids);
+int visfd_hip_find_spheres_dev(visfd_hip_ctx*, const float* crds, int64_t n_crds, const float* sphere_crds,
+                               const float* sphere_diameters, int64_t n_spheres, int64_t* ids);
+/* what the context's last FindSpheres call ran: VISFD_HIP_FIND_SPHERES_PATH_* (-1 before the first call) */
+#define VISFD_HIP_FIND_SPHERES_PATH_DEVICE 0
+#define VISFD_HIP_FIND_SPHERES_PATH_HOST 1     /* option find_spheres_host */
+int visfd_hip_find_spheres_last_path(visfd_hip_ctx*, int* path);
+
+/* ChooseThreshold1D, lib/visfd/visfd_utils.hpp:373-516: the score threshold with the fewest misclassified training
+ * data (accepted[i] != 0: a positive), the median one of those that tie; -+infinity when accepting or rejecting
+ * everything is best.  is_lower_bound == 0: data BELOW the threshold are accepted.  Ties of the (score, index) sort and
+ * the float / double steps of the midpoint are the reference's. */
+int visfd_hip_choose_threshold_1d(const float* scores, const unsigned char* accepted, int64_t n, int is_lower_bound,
+                                  float* threshold);
+/* The four below take a NULLABLE context: with NULL the spheres are searched by visfd_hip_find_spheres_host, otherwise
+ * by visfd_hip_find_spheres on that context.
+ * _FindBlobScores, lib/visfd/feature_implementation.hpp:48-89: a copy of the blob list is sorted by
+ * visfd_hip_sort_blobs(sort_criteria, ascending) -- increasing priority -- and searched; scores[k] is the score of the
+ * blob that holds training point k (-infinity when none does), sphere_ids[k] (nullable) its position in the SORTED list
+ * plus one (0: none). */
+int visfd_hip_find_blob_scores(visfd_hip_ctx*, const float* training_crds, int64_t n_training, const float* blob_crds,
+                               const float* blob_diameters, const float* blob_scores, int64_t n_blobs, int sort_criteria,
+                               float* scores, int64_t* sphere_ids);
+/* ChooseBlobScoreThresholds[Multi], lib/visfd/feature.hpp:988-1111, feature_implementation.hpp:136-457: the training
+ * points (positives first, then negatives; set after set) that lie in a blob take that blob's score, the others are
+ * dropped; the interval [*lower, *upper] is chosen lower bound first and upper bound first, and the attempt with no more
+ * mistakes than the other is kept.  report[4] (nullable) = false positives, negatives, false negatives, positives: the
+ * numbers of the reference's progress report.  No negative or no positive left after dropping: VISFD_HIP_EINVAL, with
+ * the reference's message in visfd_hip_last_error.  The multi form takes the sets' arrays concatenated and their counts. */
+int visfd_hip_choose_blob_score_thresholds(visfd_hip_ctx*, const float* blob_crds, const float* blob_diameters,
+                                           const float* blob_scores, int64_t n_blobs, const float* pos_crds, int64_t n_pos,
+                                           const float* neg_crds, int64_t n_neg, int sort_criteria, float* lower,
+                                           float* upper, int64_t* report);
+int visfd_hip_choose_blob_score_thresholds_multi(visfd_hip_ctx*, int64_t n_sets, const float* blob_crds,
+                                                 const float* blob_diameters, const float* blob_scores,
+                                                 const int64_t* n_blobs, const float* pos_crds, const int64_t* n_pos,
+                                                 const float* neg_crds, const int64_t* n_neg, int sort_criteria,
+                                                 float* lower, float* upper, int64_t* report);
+/* DiscardBlobsByScoreSupervised, lib/visfd/feature.hpp:1124-1180: the thresholds as above, then the blobs with
+ * lower <= score <= upper are kept in list order; *n is updated. */
+int visfd_hip_discard_blobs_by_score_supervised(visfd_hip_ctx*, float* crds, float* diameters, float* scores, int64_t* n,
+                                                const float* pos_crds, int64_t n_pos, const float* neg_crds, int64_t n_neg,
+                                                int sort_criteria, float* lower, float* upper, int64_t* report);
 
 /* ---- f1: LabelConnected, lib/visfd/connect.hpp:168-1427 (host-side: a sequential priority flood) ------
  * Clusters the voxels whose saliency passes `threshold_saliency` into connected "islands", growing from the

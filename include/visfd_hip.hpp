@@ -1134,6 +1134,180 @@ inline void DiscardOverlappingBlobs(std::vector<std::array<float, 3> >& blob_crd
   if (pReportProgress) *pReportProgress << "done.\n";
 }
 
+// ---- FindSpheres and the supervised score thresholds: lib/visfd/visfd_utils.hpp:271-516, feature.hpp:643-697, :988-1180 ----
+// The search over (training point, blob) pairs runs on the device (visfd_hip_find_spheres); the progress lines are the
+// reference's, text for text -- its table is not allocated here, but its stderr says so and programs compare it.
+namespace hip_detail {
+inline std::vector<float> flat_crds(const std::vector<std::array<float, 3> >& crds) {
+  std::vector<float> c(3 * crds.size());
+  for (size_t i = 0; i < crds.size(); i++) { c[3 * i] = crds[i][0]; c[3 * i + 1] = crds[i][1]; c[3 * i + 2] = crds[i][2]; }
+  return c;
+}
+// Which search the supervised wrappers use: the process-wide context, or -- with a null result -- the host walk
+// (filter_mrc sets it for small lists, which then need no GPU)
+inline bool& supervised_on_host() { static bool on_host = false; return on_host; }
+inline visfd_hip_ctx* supervised_context() { return supervised_on_host() ? nullptr : context(); }
+inline void report_find_spheres(std::ostream* p) {
+  if (p) *p << " -- Attempting to allocate space for one more image.       --\n"
+            << " -- (If this crashes your computer, find a computer with   --\n"
+            << " --  more RAM and use \"ulimit\", OR use a smaller image.)   --\n";
+}
+inline void report_sort(std::ostream* p, size_t n_blobs, SortCriteria criteria) {
+  if (p && n_blobs > 0 && criteria != DO_NOT_SORT) *p << "-- Sorting blobs according to their scores... done --" << std::endl;
+}
+// the C ABI's EINVAL for an empty training set carries the reference's exception text: thrown as it is
+inline void check_supervised(int rc) {
+  if (rc == VISFD_HIP_EINVAL && std::string(visfd_hip_last_error()).compare(0, 20, "Error: Empty list of") == 0)
+    throw VisfdErr(visfd_hip_last_error());
+  check(rc);
+}
+// _ChooseThresholdInterval's report, feature_implementation.hpp:240-273
+inline void report_thresholds(std::ostream* p, float lower, float upper, const int64_t report[4]) {
+  if (!p) return;
+  *p << "  threshold lower bound: " << lower << "\n"
+     << "  threshold upper bound: " << upper << "\n";
+  *p << "  number of false positives: " << report[0] << " (out of " << report[1] << " negatives)\n"
+     << "  number of false negatives: " << report[2] << " (out of " << report[3] << " positives)\n"
+     << std::endl;
+}
+}  // namespace hip_detail
+
+// Not in the reference: the wrappers below search on the process-wide context's device; FindSpheresOnHost(true) makes them
+// walk the pairs on the host instead (visfd_hip_find_spheres_host: no context is created, no GPU is needed).
+inline void FindSpheresOnHost(bool on_host) { hip_detail::supervised_on_host() = on_host; }
+
+template <typename Integer>
+inline void FindSpheres(const std::vector<std::array<float, 3> >& crds, std::vector<Integer>& sphere_ids,
+                        const std::vector<std::array<float, 3> >& sphere_center_crds,
+                        const std::vector<float>& sphere_diameters, std::ostream* pReportProgress = nullptr) {
+  if (sphere_diameters.size() != sphere_center_crds.size())
+    throw VisfdErr("Error: sphere coordinate and diameter lists differ in length.\n");
+  hip_detail::report_find_spheres(pReportProgress);
+  const std::vector<float> q = hip_detail::flat_crds(crds), c = hip_detail::flat_crds(sphere_center_crds);
+  std::vector<int64_t> ids(crds.size());
+  visfd_hip_ctx* ctx = hip_detail::supervised_context();
+  hip_detail::check(ctx ? visfd_hip_find_spheres(ctx, q.data(), (int64_t)crds.size(), c.data(), sphere_diameters.data(),
+                                                 (int64_t)sphere_diameters.size(), ids.data())
+                        : visfd_hip_find_spheres_host(q.data(), (int64_t)crds.size(), c.data(), sphere_diameters.data(),
+                                                      (int64_t)sphere_diameters.size(), ids.data()));
+  sphere_ids.clear();
+  for (size_t i = 0; i < ids.size(); i++) sphere_ids.push_back((Integer)ids[i]);
+}
+
+inline float ChooseThreshold1D(const std::vector<float>& training_scores, const std::vector<bool>& training_accepted,
+                               bool threshold_is_lower_bound = true) {
+  std::vector<unsigned char> acc(training_accepted.begin(), training_accepted.end());
+  float thr = 0.0f;
+  hip_detail::check(visfd_hip_choose_threshold_1d(training_scores.data(), acc.data(), (int64_t)training_scores.size(),
+                                                  threshold_is_lower_bound ? 1 : 0, &thr));
+  return thr;
+}
+
+// the survivors are APPENDED to the three out_ vectors, as in the reference
+inline void FindBlobScores(const std::vector<std::array<float, 3> >& in_training_crds,
+                           const std::vector<bool>& in_training_accepted,
+                           std::vector<std::array<float, 3> >& out_training_crds, std::vector<bool>& out_training_accepted,
+                           std::vector<float>& out_training_scores, const std::vector<std::array<float, 3> >& blob_crds,
+                           const std::vector<float>& blob_diameters, const std::vector<float>& blob_scores,
+                           SortCriteria sort_blob_criteria = SORT_DECREASING_MAGNITUDE,
+                           std::ostream* pReportProgress = nullptr) {
+  hip_detail::FlatBlobs f(blob_crds, blob_diameters, blob_scores);
+  const std::vector<float> t = hip_detail::flat_crds(in_training_crds);
+  std::vector<float> scores(in_training_crds.size());
+  std::vector<int64_t> which(in_training_crds.size());
+  hip_detail::report_sort(pReportProgress, blob_crds.size(), sort_blob_criteria);
+  hip_detail::report_find_spheres(pReportProgress);
+  hip_detail::check(visfd_hip_find_blob_scores(hip_detail::supervised_context(), t.data(), (int64_t)in_training_crds.size(),
+                                               f.c.data(), f.d.data(), f.s.data(), (int64_t)blob_crds.size(),
+                                               (int)sort_blob_criteria, scores.data(), which.data()));
+  for (size_t i = 0; i < which.size(); i++)
+    if (which[i] != 0) {
+      out_training_crds.push_back(in_training_crds[i]);
+      out_training_scores.push_back(scores[i]);
+      out_training_accepted.push_back(in_training_accepted[i]);
+    }
+}
+
+inline void ChooseBlobScoreThresholds(const std::vector<std::array<float, 3> >& blob_crds,
+                                      const std::vector<float>& blob_diameters, const std::vector<float>& blob_scores,
+                                      const std::vector<std::array<float, 3> >& training_set_pos,
+                                      const std::vector<std::array<float, 3> >& training_set_neg,
+                                      float* pthreshold_lower_bound = nullptr, float* pthreshold_upper_bound = nullptr,
+                                      SortCriteria sort_blob_criteria = SORT_DECREASING_MAGNITUDE,
+                                      std::ostream* pReportProgress = nullptr) {
+  hip_detail::FlatBlobs f(blob_crds, blob_diameters, blob_scores);
+  const std::vector<float> p = hip_detail::flat_crds(training_set_pos), n = hip_detail::flat_crds(training_set_neg);
+  float lower = 0.0f, upper = 0.0f;
+  int64_t report[4] = {0, 0, 0, 0};
+  hip_detail::report_sort(pReportProgress, blob_crds.size(), sort_blob_criteria);
+  hip_detail::report_find_spheres(pReportProgress);
+  hip_detail::check_supervised(visfd_hip_choose_blob_score_thresholds(
+      hip_detail::supervised_context(), f.c.data(), f.d.data(), f.s.data(), (int64_t)blob_crds.size(), p.data(),
+      (int64_t)training_set_pos.size(), n.data(), (int64_t)training_set_neg.size(), (int)sort_blob_criteria, &lower, &upper,
+      report));
+  if (pReportProgress) *pReportProgress << "  examining training data to determine optimal thresholds\n";
+  if (pthreshold_lower_bound) *pthreshold_lower_bound = lower;
+  if (pthreshold_upper_bound) *pthreshold_upper_bound = upper;
+  hip_detail::report_thresholds(pReportProgress, lower, upper, report);
+}
+
+inline void ChooseBlobScoreThresholdsMulti(const std::vector<std::vector<std::array<float, 3> > >& blob_crds,
+                                           const std::vector<std::vector<float> >& blob_diameters,
+                                           const std::vector<std::vector<float> >& blob_scores,
+                                           const std::vector<std::vector<std::array<float, 3> > >& training_set_pos,
+                                           const std::vector<std::vector<std::array<float, 3> > >& training_set_neg,
+                                           float* pthreshold_lower_bound = nullptr, float* pthreshold_upper_bound = nullptr,
+                                           SortCriteria sort_blob_criteria = SORT_DECREASING_MAGNITUDE,
+                                           std::ostream* pReportProgress = nullptr) {
+  const size_t n_sets = training_set_pos.size();
+  if (training_set_neg.size() != n_sets || blob_crds.size() != n_sets || blob_diameters.size() != n_sets ||
+      blob_scores.size() != n_sets)
+    throw VisfdErr("Error: the lists of training sets and blob lists differ in length.\n");
+  std::vector<float> bc, bd, bs, pc, nc;
+  std::vector<int64_t> nb(n_sets), np(n_sets), nn(n_sets);
+  for (size_t I = 0; I < n_sets; I++) {
+    hip_detail::FlatBlobs f(blob_crds[I], blob_diameters[I], blob_scores[I]);
+    const std::vector<float> p = hip_detail::flat_crds(training_set_pos[I]), n = hip_detail::flat_crds(training_set_neg[I]);
+    bc.insert(bc.end(), f.c.begin(), f.c.end()); bd.insert(bd.end(), f.d.begin(), f.d.end());
+    bs.insert(bs.end(), f.s.begin(), f.s.end());
+    pc.insert(pc.end(), p.begin(), p.end()); nc.insert(nc.end(), n.begin(), n.end());
+    nb[I] = (int64_t)blob_crds[I].size(); np[I] = (int64_t)training_set_pos[I].size(); nn[I] = (int64_t)training_set_neg[I].size();
+    hip_detail::report_sort(pReportProgress, blob_crds[I].size(), sort_blob_criteria);
+    hip_detail::report_find_spheres(pReportProgress);
+  }
+  float lower = 0.0f, upper = 0.0f;
+  int64_t report[4] = {0, 0, 0, 0};
+  hip_detail::check_supervised(visfd_hip_choose_blob_score_thresholds_multi(
+      hip_detail::supervised_context(), (int64_t)n_sets, bc.data(), bd.data(), bs.data(), nb.data(), pc.data(), np.data(),
+      nc.data(), nn.data(), (int)sort_blob_criteria, &lower, &upper, report));
+  if (pReportProgress) *pReportProgress << "  examining training data to determine optimal thresholds\n";
+  if (pthreshold_lower_bound) *pthreshold_lower_bound = lower;
+  if (pthreshold_upper_bound) *pthreshold_upper_bound = upper;
+  hip_detail::report_thresholds(pReportProgress, lower, upper, report);
+}
+
+inline void DiscardBlobsByScoreSupervised(std::vector<std::array<float, 3> >& blob_crds, std::vector<float>& blob_diameters,
+                                          std::vector<float>& blob_scores,
+                                          const std::vector<std::array<float, 3> >& training_set_pos,
+                                          const std::vector<std::array<float, 3> >& training_set_neg,
+                                          SortCriteria sort_blob_criteria = SORT_DECREASING_MAGNITUDE,
+                                          float* pthreshold_lower_bound = nullptr, float* pthreshold_upper_bound = nullptr,
+                                          std::ostream* pReportProgress = nullptr) {
+  float lower = 0.0f, upper = 0.0f;
+  ChooseBlobScoreThresholds(blob_crds, blob_diameters, blob_scores, training_set_pos, training_set_neg, &lower, &upper,
+                            sort_blob_criteria, pReportProgress);
+  if (pthreshold_lower_bound) *pthreshold_lower_bound = lower;
+  if (pthreshold_upper_bound) *pthreshold_upper_bound = upper;
+  if (pReportProgress) *pReportProgress << "  allocating another blob list copy." << std::endl;
+  size_t kept = 0;
+  for (size_t i = 0; i < blob_crds.size(); i++)
+    if (blob_scores[i] >= lower && blob_scores[i] <= upper) {
+      blob_crds[kept] = blob_crds[i]; blob_diameters[kept] = blob_diameters[i]; blob_scores[kept] = blob_scores[i];
+      kept++;
+    }
+  blob_crds.resize(kept); blob_diameters.resize(kept); blob_scores.resize(kept);
+}
+
 // ---- BlobDogNM / _BlobDogNM: bin/filter_mrc/feature_variants.hpp:393-580 --------------------------------------
 // BlobDogD followed by non-max suppression of overlapping blobs (minima best-first by increasing score, maxima by
 // decreasing score); the `_` form takes the filter window either as a ratio or as a decay threshold.

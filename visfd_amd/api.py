@@ -264,6 +264,19 @@ _SIGS = {
     "visfd_hip_discard_masked_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), _vp, _i64, _i64, _i64]),
     "visfd_hip_discard_overlapping_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), C.c_float, C.c_float,
                                                      C.c_float, C.c_int, C.c_int]),
+    # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
+    "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "visfd_hip_find_spheres_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "visfd_hip_find_spheres_last_path": (C.c_int, [_vp, _ip]),
+    "visfd_hip_choose_threshold_1d": (C.c_int, [_vp, _vp, _i64, C.c_int, _fp]),
+    "visfd_hip_find_blob_scores": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
+    "visfd_hip_choose_blob_score_thresholds": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_int, _fp, _fp,
+                                                        _vp]),
+    "visfd_hip_choose_blob_score_thresholds_multi": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                                              _fp, _fp, _vp]),
+    "visfd_hip_discard_blobs_by_score_supervised": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _i64, _vp, _i64,
+                                                             C.c_int, _fp, _fp, _vp]),
     # Z-slab runs (csrc/slab.hip)
     "visfd_hip_slab_unique_id": (C.c_int, [_vp]),
     "visfd_hip_slab_create_rccl": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, C.c_int, C.POINTER(_vp)]),
@@ -737,6 +750,111 @@ def discard_overlapping_blobs(crds, diameters, scores, min_radial_separation_rat
     return c[:n.value], d[:n.value], s[:n.value]
 
 
+# ---- FindSpheres and the supervised score thresholds.  `ctx` (a Context, or None): with None the spheres are searched by
+# the host walk (visfd_hip_find_spheres_host), otherwise on that context's device.
+FIND_SPHERES_PATH_DEVICE, FIND_SPHERES_PATH_HOST = 0, 1   # visfd_hip_find_spheres_last_path
+FIND_SPHERES_MAX_R = 46340   # VISFD_HIP_FIND_SPHERES_MAX_R
+
+
+def _crds(a):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+
+
+def _handle(ctx):
+    return None if ctx is None else ctx._h
+
+
+def find_spheres_host(crds, sphere_crds, sphere_diameters):
+    """FindSpheres (visfd_utils.hpp:271-359) by the host walk: for every point 1 + the index of the LAST sphere that holds
+    it, 0 when none does -> int64 array."""
+    L = load_library()
+    q, c, d = _crds(crds), _crds(sphere_crds), np.ascontiguousarray(sphere_diameters, np.float32)
+    assert len(c) == len(d), "sphere lists differ in length"
+    ids = np.empty(len(q), np.int64)
+    _chk_host(L, L.visfd_hip_find_spheres_host(q.ctypes.data, len(q), c.ctypes.data, d.ctypes.data, len(d), ids.ctypes.data))
+    return ids
+
+
+def choose_threshold_1d(scores, accepted, threshold_is_lower_bound=True):
+    """ChooseThreshold1D (visfd_utils.hpp:373-516) -> float."""
+    L = load_library()
+    s = np.ascontiguousarray(scores, np.float32)
+    a = np.ascontiguousarray(accepted, np.bool_).astype(np.uint8)
+    assert len(s) == len(a), "scores and labels differ in length"
+    thr = C.c_float()
+    _chk_host(L, L.visfd_hip_choose_threshold_1d(s.ctypes.data, a.ctypes.data, len(s), int(bool(threshold_is_lower_bound)),
+                                                 C.byref(thr)))
+    return float(thr.value)
+
+
+def find_blob_scores(training_crds, crds, diameters, scores, criteria=SORT_DECREASING_MAGNITUDE, ctx=None):
+    """_FindBlobScores (feature_implementation.hpp:48-89) -> (scores float32, -inf where no blob holds the point; ids int64:
+    1 + the position of that blob in the list sorted by increasing priority, 0 for none)."""
+    L = load_library()
+    c, d, s = _blob_arrays(crds, diameters, scores)
+    t = _crds(training_crds)
+    out, ids = np.empty(len(t), np.float32), np.empty(len(t), np.int64)
+    _chk_host(L, L.visfd_hip_find_blob_scores(_handle(ctx), t.ctypes.data, len(t), c.ctypes.data, d.ctypes.data, s.ctypes.data,
+                                              len(d), int(criteria), out.ctypes.data, ids.ctypes.data))
+    return out, ids
+
+
+def _thresholds_result(lower, upper, report):
+    return float(lower.value), float(upper.value), {"false_positives": int(report[0]), "negatives": int(report[1]),
+                                                    "false_negatives": int(report[2]), "positives": int(report[3])}
+
+
+def choose_blob_score_thresholds(crds, diameters, scores, training_pos, training_neg, criteria=SORT_DECREASING_MAGNITUDE,
+                                 ctx=None):
+    """ChooseBlobScoreThresholds (feature.hpp:988-1035) -> (lower, upper, report dict).  An empty positive or negative set
+    after the points outside every blob are dropped raises VisfdHipError with the reference's message."""
+    L = load_library()
+    c, d, s = _blob_arrays(crds, diameters, scores)
+    p, n = _crds(training_pos), _crds(training_neg)
+    lower, upper, report = C.c_float(), C.c_float(), np.zeros(4, np.int64)
+    _chk_host(L, L.visfd_hip_choose_blob_score_thresholds(_handle(ctx), c.ctypes.data, d.ctypes.data, s.ctypes.data, len(d),
+                                                          p.ctypes.data, len(p), n.ctypes.data, len(n), int(criteria),
+                                                          C.byref(lower), C.byref(upper), report.ctypes.data))
+    return _thresholds_result(lower, upper, report)
+
+
+def choose_blob_score_thresholds_multi(blob_lists, training_pos, training_neg, criteria=SORT_DECREASING_MAGNITUDE, ctx=None):
+    """ChooseBlobScoreThresholdsMulti (feature.hpp:1063-1111).  blob_lists: one (crds, diameters, scores) per set;
+    training_pos / training_neg: one coordinate array per set -> (lower, upper, report dict)."""
+    L = load_library()
+    assert len(blob_lists) == len(training_pos) == len(training_neg), "one blob list and two training files per set"
+    lists = [_blob_arrays(*b) for b in blob_lists]
+    pos, neg = [_crds(p) for p in training_pos], [_crds(n) for n in training_neg]
+
+    def cat(parts, width):
+        return np.ascontiguousarray(np.concatenate([np.zeros((0, width), np.float32)] + [x.reshape(-1, width) for x in parts]))
+    c, d, s = cat([b[0] for b in lists], 3), cat([b[1] for b in lists], 1), cat([b[2] for b in lists], 1)
+    p, n = cat(pos, 3), cat(neg, 3)
+    nb = np.array([len(b[1]) for b in lists], np.int64)
+    npos, nneg = np.array([len(x) for x in pos], np.int64), np.array([len(x) for x in neg], np.int64)
+    lower, upper, report = C.c_float(), C.c_float(), np.zeros(4, np.int64)
+    _chk_host(L, L.visfd_hip_choose_blob_score_thresholds_multi(
+        _handle(ctx), len(lists), c.ctypes.data, d.ctypes.data, s.ctypes.data, nb.ctypes.data, p.ctypes.data,
+        npos.ctypes.data, n.ctypes.data, nneg.ctypes.data, int(criteria), C.byref(lower), C.byref(upper), report.ctypes.data))
+    return _thresholds_result(lower, upper, report)
+
+
+def discard_blobs_by_score_supervised(crds, diameters, scores, training_pos, training_neg,
+                                      criteria=SORT_DECREASING_MAGNITUDE, ctx=None):
+    """DiscardBlobsByScoreSupervised (feature.hpp:1124-1180) -> (crds, diameters, scores, lower, upper, report dict): the
+    blobs with lower <= score <= upper, in list order."""
+    L = load_library()
+    c, d, s = _blob_arrays(crds, diameters, scores)
+    p, n = _crds(training_pos), _crds(training_neg)
+    count = _i64(len(d))
+    lower, upper, report = C.c_float(), C.c_float(), np.zeros(4, np.int64)
+    _chk_host(L, L.visfd_hip_discard_blobs_by_score_supervised(
+        _handle(ctx), c.ctypes.data, d.ctypes.data, s.ctypes.data, C.byref(count), p.ctypes.data, len(p), n.ctypes.data,
+        len(n), int(criteria), C.byref(lower), C.byref(upper), report.ctypes.data))
+    k = count.value
+    return (c[:k], d[:k], s[:k]) + _thresholds_result(lower, upper, report)
+
+
 _BLOB_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("scale", "<i4"), ("sigma", "<f4"),
                         ("score", "<f4")])
 
@@ -1038,6 +1156,39 @@ class Context:
         """What the last distance call ran: DISTANCE_PATH_GENERAL or DISTANCE_PATH_TRANSFORM (-1 before the first)."""
         p = C.c_int(-1)
         self._chk(self._L.visfd_hip_distance_last_path(self._h, C.byref(p)))
+        return int(p.value)
+
+    def find_spheres(self, crds, sphere_crds, sphere_diameters, ids=None):
+        """FindSpheres (visfd_utils.hpp:271-359) on the device, numpy in and out: for every point 1 + the index of the LAST
+        sphere that holds it, 0 when none does -> int64 array (`ids` itself when one is passed).  Option
+        find_spheres_host: the host walk instead."""
+        q, c, d = _crds(crds), _crds(sphere_crds), np.ascontiguousarray(sphere_diameters, np.float32)
+        assert len(c) == len(d), "sphere lists differ in length"
+        if ids is None:
+            ids = np.empty(len(q), np.int64)
+        assert isinstance(ids, np.ndarray) and ids.dtype == np.int64 and ids.flags["C_CONTIGUOUS"] and ids.size == len(q)
+        self._chk(self._L.visfd_hip_find_spheres(self._h, q.ctypes.data, len(q), c.ctypes.data, d.ctypes.data, len(d),
+                                                 ids.ctypes.data))
+        return ids
+
+    def find_spheres_dev(self, crds, sphere_crds, sphere_diameters, ids=None):
+        """The same on torch device tensors: crds (n, 3), sphere_crds (m, 3), sphere_diameters (m,) float32 -> ids, an
+        int64 device tensor of n entries (written in place when passed).  The search is asynchronous on the context's
+        stream; the values are checked by the preparation launches, whose flag word the call waits for."""
+        import torch
+        n, m = int(crds.shape[0]), int(sphere_diameters.shape[0])
+        assert int(sphere_crds.shape[0]) == m, "sphere lists differ in length"
+        if ids is None:
+            ids = torch.empty(n, dtype=torch.int64, device=crds.device)
+        assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.numel() == n, "ids: n int64 on the device"
+        self._chk(self._L.visfd_hip_find_spheres_dev(self._h, _dev(crds), n, _dev(sphere_crds), _dev(sphere_diameters), m,
+                                                     ids.data_ptr()))
+        return ids
+
+    def find_spheres_last_path(self):
+        """What the last FindSpheres call ran: FIND_SPHERES_PATH_DEVICE or FIND_SPHERES_PATH_HOST (-1 before the first)."""
+        p = C.c_int(-1)
+        self._chk(self._L.visfd_hip_find_spheres_last_path(self._h, C.byref(p)))
         return int(p.value)
 
     def image_stats(self, src, mask=None):

@@ -41,6 +41,22 @@
 //   -distance-points FILE (may be repeated: the files' points are appended) | -distance-to-voxels PTS OUT A B
 //                              exact distance maps (settings.cpp:2262-2283, HandleDistanceToPoints,
 //                              HandleDistancePointsToFeature); nx + ny + nz <= 46340; not under -slab
+//   -auto-thresh score -supervised POS NEG      with -discard-blobs: after the overlap step, the score interval that
+//                              misclassifies the fewest of the training points (files of locations, plain or in IMOD's
+//                              notation) is chosen and the blobs outside it are discarded (settings.cpp:1792-1830,
+//                              handlers.cpp:598-621); one without the other does nothing, as in the reference
+//   -supervised-multi FILE     FILE lists "pos_file neg_file blob_list_file" per image: the interval that suits all sets is
+//                              printed (HandleBlobScoreSupervisedMulti).  The training coordinates are used as read (the
+//                              reference's rescaling loops do nothing here, filter_mrc.cpp:354-370).  Not with -discard-blobs
+//                              or -mask (the reference's refusals) and -- the one deviation -- not with -supervised, where
+//                              the reference reads past its arrays
+//   -spheres-nonmax-radii-range A B | -spheres-nonmax-score-range A B (also -sphere-...)   bounds of -discard-blobs' first
+//                              filter; the radii range is compared with the diameters in voxels as typed (handlers.cpp:547)
+//   -score-upper-bound T | -score-lower-bound T   other spellings of -minima-threshold and -maxima-threshold
+//   -minima-ratio R | -maxima-ratio R | -score-lower-bound-ratio R | -score-upper-bound-ratio R   -blob's thresholds as
+//                              ratios of the extreme score (settings.cpp:1947-1981); not under -slab
+//   The search behind the supervised flags (FindSpheres) walks the pairs on the host for small lists and runs on the GPU
+//   from FIND_SPHERES_MIN_PAIRS pairs on (VISFD_HIP_FIND_SPHERES_MIN_PAIRS overrides; 0: always the GPU).
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is in mrc.hpp, the settings and the parser of the flags above in settings.hpp; both are part of
@@ -120,8 +136,8 @@ bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vec
   return parens;
 }
 
-// HandleBlobsNonmaxSuppression, bin/filter_mrc/handlers.cpp:421-617 (without the supervised-learning tail): the lists of
-// the blob files in voxels, filtered by score, by the mask (when one is passed) and by overlap
+// HandleBlobsNonmaxSuppression, bin/filter_mrc/handlers.cpp:421-596 (its supervised tail is in handle_blob_nonmax): the
+// lists of the blob files in voxels, filtered by score and size, by the mask (when one is passed) and by overlap
 void read_and_filter_blobs(const Run& r, float const* const* const* mask, vector<std::array<float, 3> >& crds,
                            vector<float>& diameters, vector<float>& scores) {
   const Settings& s = r.s;
@@ -146,11 +162,16 @@ void read_and_filter_blobs(const Run& r, float const* const* const* mask, vector
     scores.insert(scores.end(), sc.begin(), sc.end());
   }
   cerr << " --- discarding blobs in files ---\n\n";
-  if (s.score_lower != -inf || s.score_upper != inf) {   // handlers.cpp:503-545
+  // handlers.cpp:516-559: any of the four bounds opens the filter; each report line needs BOTH bounds of its pair
+  if (s.score_lower != -inf || s.score_upper != inf || s.sphere_diameters_lower != -inf || s.sphere_diameters_upper != inf) {
+    if (s.score_lower != -inf && s.score_upper != inf) cerr << "  discarding blobs based on score" << std::endl;
+    if (s.sphere_diameters_lower != -inf && s.sphere_diameters_upper != inf)
+      cerr << "  discarding blobs based on size (diameter)" << std::endl;
     vector<std::array<float, 3> > c;
     vector<float> d, sc;
     for (size_t i = 0; i < crds.size(); i++)
-      if (scores[i] >= s.score_lower && scores[i] <= s.score_upper) {
+      if (scores[i] >= s.score_lower && scores[i] <= s.score_upper && diameters[i] >= s.sphere_diameters_lower &&
+          diameters[i] <= s.sphere_diameters_upper) {
         c.push_back(crds[i]); d.push_back(diameters[i]); sc.push_back(scores[i]);
       }
     crds.swap(c); diameters.swap(d); scores.swap(sc);
@@ -170,12 +191,43 @@ void read_and_filter_blobs(const Run& r, float const* const* const* mask, vector
   cerr << " " << crds.size() << " blobs remaining" << std::endl;
 }
 
+// Which search the supervised tail uses: the walk on the host below this many (training point, blob) pairs, the device
+// from there on.  Small lists -- what -discard-blobs usually sees -- then need no GPU at all.
+// MEASURED on an MI355X (tools/find_spheres_time.py, second table of profiles/find_spheres_time.txt: 200 training points
+// inside blobs, one staged call in a fresh process): the first context costs about 160 ms before the device searches
+// anything, the call itself 1 to 34 ms up to 10^7 blobs; the host walk takes 17.9 ms at 2 * 10^7 pairs, 163 ms at 2 * 10^8
+// and 868 ms at 2 * 10^9.  The two meet near 2.1 * 10^8 pairs; rounded to a power of two.  The host times include the
+// walk's early exit (it goes from the end of the list and stops at the first blob that holds the point), which is what
+// training points inside blobs see; points outside every blob are walked against the whole list, 3 to 4 times slower per
+// nominal pair, and would cross over at that many fewer pairs.
+// The environment variable VISFD_HIP_FIND_SPHERES_MIN_PAIRS overrides it (0: always the device) and makes the program say
+// which search ran.
+const double FIND_SPHERES_MIN_PAIRS = 268435456.0;   // 2^28
+
+void choose_find_spheres_route(size_t n_training, size_t n_blobs) {
+  double min_pairs = FIND_SPHERES_MIN_PAIRS;
+  const char* e = std::getenv("VISFD_HIP_FIND_SPHERES_MIN_PAIRS");
+  if (e) min_pairs = std::atof(e);
+  const bool on_host = (double)n_training * (double)n_blobs < min_pairs;
+  FindSpheresOnHost(on_host);
+  if (e) cerr << "  (find_spheres: " << (on_host ? "host" : "device") << " search)" << std::endl;
+}
+
 void handle_blob_nonmax(Run& r) {
   const Settings& s = r.s;
   const float w = r.vw[0];
   vector<std::array<float, 3> > crds;
   vector<float> diameters, scores;
   read_and_filter_blobs(r, r.mask3d(), crds, diameters, scores);
+  // handlers.cpp:598-621: the supervised tail, always after the overlap step.  -auto-thresh without -supervised, or the
+  // reverse, does nothing, as in the reference
+  if (s.auto_thresh_score && !s.training_pos_crds.empty() && !s.training_neg_crds.empty()) {
+    cerr << "  discarding blobs based on score using training data" << std::endl;
+    choose_find_spheres_route(s.training_pos_crds.size() + s.training_neg_crds.size(), crds.size());
+    DiscardBlobsByScoreSupervised(crds, diameters, scores, s.training_pos_crds, s.training_neg_crds, SORT_DECREASING_MAGNITUDE,
+                                  static_cast<float*>(nullptr), static_cast<float*>(nullptr), &cerr);
+    cerr << " " << crds.size() << " blobs remaining" << std::endl;
+  }
   if (!s.out_crds_file.empty()) {
     const double wp = w > 0.0f ? (double)w : 1.0;
     std::ofstream out(s.out_crds_file.c_str());
@@ -184,6 +236,33 @@ void handle_blob_nonmax(Run& r) {
       out << crds[i][0] * wp << " " << crds[i][1] * wp << " " << crds[i][2] * wp << " " << diameters[i] * wp << " "
           << scores[i] << std::endl;
   }
+}
+
+// HandleBlobScoreSupervisedMulti, bin/filter_mrc/handlers.cpp:648-706: the thresholds that suit several images' blob lists
+// and training sets at once; they are only printed
+void handle_supervised_multi(Run& r) {
+  const Settings& s = r.s;
+  const float w = r.vw[0];
+  const size_t n_sets = s.multi_in_crds_files.size();
+  vector<vector<std::array<float, 3> > > crds(n_sets);
+  vector<vector<float> > diameters(n_sets), scores(n_sets);
+  size_t pairs_training = 0, pairs_blobs = 0;
+  for (size_t I = 0; I < n_sets; I++) {
+    read_blob_file(s.multi_in_crds_files[I], crds[I], diameters[I], scores[I], s.sphere_decals_foreground, s.sphere_decals_scale);
+    if (s.sphere_decals_diameter >= 0)   // -diameters / -radii: the reader's override (file_io.hpp:474-475)
+      for (size_t i = 0; i < diameters[I].size(); i++) diameters[I][i] = s.sphere_decals_diameter;
+    if (w > 0.0f)   // handlers.cpp:685-694: every diameter and coordinate, whatever the file's notation
+      for (size_t i = 0; i < crds[I].size(); i++) {
+        diameters[I][i] /= w;
+        for (int k = 0; k < 3; k++) crds[I][i][k] = (float)std::floor((crds[I][i][k] / w) + 0.5);
+      }
+    pairs_training = std::max(pairs_training, s.multi_training_pos_crds[I].size() + s.multi_training_neg_crds[I].size());
+    pairs_blobs = std::max(pairs_blobs, crds[I].size());
+  }
+  choose_find_spheres_route(pairs_training, pairs_blobs);   // by the largest set
+  float lower, upper;
+  ChooseBlobScoreThresholdsMulti(crds, diameters, scores, s.multi_training_pos_crds, s.multi_training_neg_crds, &lower, &upper,
+                                 SORT_DECREASING_MAGNITUDE, &cerr);
 }
 
 // The thickness of one drawn shell (handlers.cpp:751-758 and :957-964): a ratio times the diameter, and where that falls
@@ -515,6 +594,13 @@ void prepare(Run& r, Settings& s) {
   cerr << "voxel width = " << r.vw[0] << "\n";
   for (size_t k = 0; k < s.must_link_crds.size(); k++)      // filter_mrc.cpp:372-379: physical units -> voxels, or
     s.must_link_crds[k] /= s.must_link_in_voxels ? (float)r.bin : r.vw[k % 3];   // voxels of the unbinned image -> binned
+  // filter_mrc.cpp:340-352: the -supervised points likewise.  The multi sets' loops of the reference (:354-370) are bounded
+  // by the sizes of THESE lists, which are empty whenever multi sets exist (settings.hpp refuses the combination): the
+  // multi coordinates stay as read
+  for (size_t i = 0; i < s.training_pos_crds.size(); i++)
+    for (int d = 0; d < 3; d++) s.training_pos_crds[i][d] /= s.is_training_pos_in_voxels ? (float)r.bin : r.vw[d];
+  for (size_t i = 0; i < s.training_neg_crds.size(); i++)
+    for (int d = 0; d < 3; d++) s.training_neg_crds[i][d] /= s.is_training_neg_in_voxels ? (float)r.bin : r.vw[d];
   for (int d = 0; d < 3; d++) { s.width_a[d] /= r.vw[d]; s.width_b[d] /= r.vw[d]; s.log_width[d] /= r.vw[d]; s.template_background_radius[d] /= r.vw[d]; }
   s.tv_sigma /= r.vw[0];
   for (size_t k = 0; k < s.blob_diameters.size(); k++) s.blob_diameters[k] /= r.vw[0];
@@ -651,7 +737,7 @@ string detect_blobs(Run& r, Blobs& b) {
   const Settings& s = r.s;
   if (s.slab_world == 0) {
     BlobDogD(r.size, r.tomo_in.a, r.mask3d(), s.blob_diameters, &b.c[0], &b.c[1], &b.d[0], &b.d[1], &b.sc[0], &b.sc[1],
-             s.blob_aspect_ratio, s.delta, r.ratio, s.score_upper, s.score_lower, false, &cerr);
+             s.blob_aspect_ratio, s.delta, r.ratio, s.score_upper, s.score_lower, s.score_bounds_are_ratios, &cerr);
     return string();
   }
   vector<visfd_hip_blob> bl[2];
@@ -1137,6 +1223,7 @@ int main(int argc, char** argv) {
       case Settings::FIND_EXTREMA: handle_extrema(r); break;
       case Settings::WATERSHED: handle_watershed(r); break;
       case Settings::BLOB_NONMAX: handle_blob_nonmax(r); break;
+      case Settings::BLOB_NONMAX_SUPERVISED_MULTI: handle_supervised_multi(r); break;
       case Settings::DRAW_SPHERES: handle_draw_spheres(r); break;
       case Settings::DISTANCE_TO_POINTS: handle_distance_points(r); break;
       case Settings::DISTANCE_TO_VOXELS: handle_distance_to_voxels(r); break;

@@ -25,7 +25,7 @@ struct Settings {
   int bin = 0;                 // settings.cpp:48-49: 0 = not specified (automatic), else the factor
   bool bin_explicit = false;
   float masked_voxel_brightness = 0.0f;   // settings.cpp:41-42: voxels with mask == 0 get this value in the output
-  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES, WATERSHED, DISTANCE_TO_POINTS, DISTANCE_TO_VOXELS } type = NONE;
+  enum { NONE, GAUSS, DOG, LOG, BLOB, BLOB_NONMAX, SURFACE_RIDGE, LOCAL_FLUCTUATIONS, MORPHOLOGY, FIND_EXTREMA, GGAUSS, DOGG, DRAW_SPHERES, WATERSHED, DISTANCE_TO_POINTS, DISTANCE_TO_VOXELS, BLOB_NONMAX_SUPERVISED_MULTI } type = NONE;
   // grayscale morphology (settings.cpp:55-57): op is a VISFD_HIP_MORPH_* code; radii in physical units until prepare() divides
   int morph_op = VISFD_HIP_MORPH_DILATE;
   float morph_r = 0.0f, morph_rmax = 0.0f, morph_bmax = 0.0f;
@@ -53,6 +53,16 @@ struct Settings {
   string blob_min_file, blob_max_file;
   float score_lower = -std::numeric_limits<float>::infinity();
   float score_upper = std::numeric_limits<float>::infinity();
+  bool score_bounds_are_ratios = false;                       // settings.cpp:123: -minima-ratio, -maxima-ratio (BlobDogD's ratios of the extreme score)
+  float sphere_diameters_lower = -std::numeric_limits<float>::infinity();   // settings.cpp:124-125: -spheres-nonmax-radii-range; compared
+  float sphere_diameters_upper = std::numeric_limits<float>::infinity();    // with the DIAMETERS in voxels as typed (handlers.cpp:547-548)
+  // supervised score thresholds (settings.cpp:301-322): -auto-thresh score, -supervised POS NEG, -supervised-multi FILE
+  bool auto_thresh_score = false;
+  string training_pos_file, training_neg_file;
+  vector<std::array<float, 3> > training_pos_crds, training_neg_crds;
+  bool is_training_pos_in_voxels = false, is_training_neg_in_voxels = false;
+  vector<string> multi_training_pos_files, multi_training_neg_files, multi_in_crds_files;
+  vector<vector<std::array<float, 3> > > multi_training_pos_crds, multi_training_neg_crds;
   // sphere drawing (settings.cpp:107-120)
   float sphere_decals_diameter = -1.0f;
   bool sphere_decals_diameter_in_voxels = false;
@@ -120,6 +130,9 @@ struct Settings {
 };
 
 bool read_must_link_file(const string& path, Settings& s);
+bool parse_coordinate_line(string line, vector<float>& xyz);
+bool read_coordinates(const string& path, vector<std::array<float, 3> >& crds);
+void read_training_files(Settings& s);
 
 // The one test of a numeric argument: v[i] is there, is not empty, does not start with '-' unless the number may be
 // negative, and parses as a float; anything else is the error `msg`.  The reference words its messages per flag
@@ -341,8 +354,88 @@ Settings parse(int argc, char** argv) {
     }
     else if (f == "-max-volume-overlap") { need(1); s.nonmax_max_overlap_large = num(1); i += 2; }        // settings.cpp:1540
     else if (f == "-max-volume-overlap-small") { need(1); s.nonmax_max_overlap_small = num(1); i += 2; }  // settings.cpp:1561
-    else if (f == "-minima-threshold") { need(1); s.score_upper = num(1); i += 2; }
-    else if (f == "-maxima-threshold") { need(1); s.score_lower = num(1); i += 2; }
+    else if (one_of(f, {"-minima-threshold", "-score-upper-bound", "-maxima-threshold", "-score-lower-bound", "-minima-ratio",
+                        "-score-lower-bound-ratio", "-maxima-ratio", "-score-upper-bound-ratio"})) {   // settings.cpp:1909-1981
+      // (the -ratio spellings are the reference's: -score-lower-bound-ratio sets the UPPER bound, like -minima-ratio)
+      need(1);
+      const bool upper = one_of(f, {"-minima-threshold", "-score-upper-bound", "-minima-ratio", "-score-lower-bound-ratio"});
+      (upper ? s.score_upper : s.score_lower) = num(1);
+      s.score_bounds_are_ratios = f.size() > 6 && f.substr(f.size() - 6) == "-ratio";
+      i += 2;
+    }
+    else if (f == "-spheres-nonmax-radii-range" || f == "-sphere-nonmax-radii-range") {   // settings.cpp:1985-1999
+      const string msg = "Error: The " + f + " argument must be followed by a number number.\n";
+      s.sphere_diameters_lower = number(v, i + 1, msg, false);
+      s.sphere_diameters_upper = number(v, i + 2, msg, false);
+      i += 3;
+    }
+    else if (f == "-spheres-nonmax-score-range" || f == "-sphere-nonmax-score-range") {   // settings.cpp:2003-2016
+      const string msg = "Error: The " + f + " argument must be followed by two numbers.\n";
+      s.score_lower = number(v, i + 1, msg, true);
+      s.score_upper = number(v, i + 2, msg, true);
+      i += 3;
+    }
+    else if (f == "-auto-thresh") {   // settings.cpp:1792-1810
+      s.auto_thresh_score = true;
+      if (i + 1 >= v.size() || v[i + 1] != "score")
+        throw VisfdErr("Error: The " + f + " argument must be followed by \"score\"\n"
+                       "       (In the future, it may be followed by a list of attributes surrounded\n"
+                       "        in quotes.  But currently only the \"score\" attribute is supported.\n"
+                       "        Thresholds for these attributes will be determined automatically.)\n");
+      i += 2;
+    }
+    else if (f == "-supervised") {   // settings.cpp:1814-1830
+      if (i + 2 >= v.size() || v[i + 1].empty() || v[i + 2].empty())
+        throw VisfdErr("Error: The " + f + " argument must be followed by two file names:\n"
+                       "       FILE_POS.txt  FILE_NEG.txt\n"
+                       "       containing positive and negative training data, respectively.\n");
+      s.training_pos_file = v[i + 1];
+      s.training_neg_file = v[i + 2];
+      i += 3;
+    }
+    else if (f == "-supervised-multi") {   // settings.cpp:1834-1905: a file of "pos_file neg_file blob_list_file" lines
+      s.type = Settings::BLOB_NONMAX_SUPERVISED_MULTI;
+      if (i + 1 >= v.size() || v[i + 1].empty())
+        throw VisfdErr("Error: The " + f + " argument must be followed a file name. Example: FILE_TRAINING_SETS.txt\n"
+                       "\n"
+                       "File format details:\n"
+                       " This should be a 3-column text file containing file names.  Example:\n"
+                       "   training_pos_1.txt  training_crds_neg_1.txt  blob_info_1.txt\n"
+                       "   training_pos_2.txt  training_crds_neg_2.txt  blob_info_2.txt\n"
+                       "   training_pos_3.txt  training_crds_neg_3.txt  blob_info_3.txt\n"
+                       "                :                        :                :\n"
+                       "   training_pos_N.txt  training_crds_neg_N.txt  blob_info_N.txt\n"
+                       "\n"
+                       " containing positive and negative training data, and a list of detected blobs\n"
+                       " for each of the N images you want to simultaneously analyze.\n");
+      const string fname = v[i + 1];
+      std::ifstream meta(fname.c_str());   // (a file that cannot be opened reads as empty, as in the reference)
+      string line;
+      size_t i_line = 1;
+      while (std::getline(meta, line)) {
+        const size_t hash = line.find('#');
+        if (hash != string::npos) line = line.substr(0, hash);
+        std::istringstream words(line);
+        vector<string> tokens;
+        string w;
+        while (words >> w) tokens.push_back(w);
+        if (tokens.empty()) continue;   // (the reference does not count such lines either)
+        if (tokens.size() != 3) {
+          std::ostringstream msg;
+          msg << "Error: Format error in file:\n"
+              << "       \"" << fname << "\", line: " << i_line << "\n"
+              << "\n"
+              << "       Expected 3 file names in every line in this file:\n"
+              << "\n"
+              << "       training_pos_file  training_neg_file  blob_info_list.txt\n";
+          throw VisfdErr(msg.str());
+        }
+        s.multi_training_pos_files.push_back(tokens[0]);
+        s.multi_training_neg_files.push_back(tokens[1]);
+        s.multi_in_crds_files.push_back(tokens[2]);
+      }
+      i += 2;
+    }
     else if (f == "-membrane" || f == "-surface-ridge") {
       need(2);
       if (v[i + 1] == "min" || v[i + 1] == "minima") s.ridges_are_maxima = false;
@@ -622,7 +715,11 @@ Settings parse(int argc, char** argv) {
     throw VisfdErr("Error: " + s.threshold_flag + " does not combine with -membrane: it maps the INPUT image, which the reference\n"
                    "       has overwritten on that path (handlers.cpp:1932, :2398).  Of the intensity maps, -membrane runs\n"
                    "       take -rescale, -fill, -invert and -rescale-min-max, which act on the output.\n");
+  if (s.slab_world > 0 && s.score_bounds_are_ratios)
+    throw VisfdErr("Error: -slab takes absolute score thresholds only (-minima-threshold, -maxima-threshold): a ratio of the\n"
+                   "       extreme score (-minima-ratio, -maxima-ratio) needs the blobs of the whole image in one process.\n");
   if (!s.must_link_filename.empty()) s.must_link_in_voxels = read_must_link_file(s.must_link_filename, s);
+  read_training_files(s);
   if (s.type == Settings::SURFACE_RIDGE) s.tv_sigma *= s.width_a[0];   // settings.cpp:3535-3540
   if (s.cluster_connected_voxels && s.type != Settings::SURFACE_RIDGE)
     throw VisfdErr("Error: this build clusters voxels (-connect) only after \"-membrane ... -tv ...\".\n");
@@ -633,6 +730,102 @@ Settings parse(int argc, char** argv) {
   if ((s.cluster_connected_voxels || !s.load_base.empty()) && !(s.tv_sigma > 0))
     throw VisfdErr("Error: -connect and -load-progress need tensor voting (-tv).\n");
   return s;
+}
+
+// One line of a coordinate file (IMODWords2Crds, bin/filter_mrc/file_io.hpp:82-214): the numbers of the line, text after
+// '#' ignored.  IMOD's notation -- "Pixel (x, y, z) = value" or any line whose numbers sit in parentheses -- means 1-based
+// voxel indices: the first three become floor(x) - 1, and what follows "Pixel (...)" is dropped.  Returns whether the line
+// was in that notation.
+bool parse_coordinate_line(string line, vector<float>& xyz) {
+  const size_t hash = line.find('#');
+  if (hash != string::npos) line = line.substr(0, hash);
+  bool parens = false, imod = false;
+  for (size_t k = 0; k < line.size(); k++) {
+    if (line[k] == '(' || line[k] == ')') { parens = true; line[k] = ' '; }
+    else if (line[k] == ',') line[k] = ' ';
+  }
+  std::istringstream ws(line);
+  vector<string> words;
+  string w;
+  while (ws >> w) words.push_back(w);
+  if (!words.empty() && words[0] == "Pixel") { imod = parens = true; words.erase(words.begin()); }
+  xyz.clear();
+  for (size_t d = 0; d < words.size(); d++) {
+    if (d >= 3 && imod) break;                       // "= value" of IMOD's line
+    std::istringstream num(words[d]);
+    float x;
+    if (!(num >> x)) throw VisfdErr("Error: File read error (invalid entry?) on line:\n      " + line + "\n");
+    if (parens && xyz.size() < 3) x = std::floor(x) - 1.0f;   // IMOD counts voxels from 1
+    xyz.push_back(x);
+  }
+  return parens;
+}
+
+// ReadCoordinates, bin/filter_mrc/file_io.hpp:362-398: a list of locations, one per line, plain ("90.3 117.7 230") or in
+// IMOD's notation (parse_coordinate_line); lines without numbers are skipped.  Returns whether any line was in voxels.
+bool read_coordinates(const string& path, vector<std::array<float, 3> >& crds) {
+  std::ifstream f(path.c_str());
+  if (!f) throw VisfdErr("Error: unable to open \"" + path + "\" for reading.\n");
+  bool in_voxels = false;
+  crds.clear();
+  string line;
+  size_t i_line = 0;
+  while (std::getline(f, line)) {
+    i_line++;
+    vector<float> xyz;
+    in_voxels = parse_coordinate_line(line, xyz) || in_voxels;
+    if (xyz.empty()) continue;
+    if (xyz.size() < 3) {
+      std::ostringstream msg;
+      msg << "Format error near line " << i_line << " of file \"" << path << "\"\n";
+      throw VisfdErr(msg.str());
+    }
+    std::array<float, 3> c = {{xyz[0], xyz[1], xyz[2]}};
+    crds.push_back(c);
+  }
+  return in_voxels;
+}
+
+// settings.cpp:3556-3623: the training files of -supervised and -supervised-multi, and the two refusals of the latter
+void read_training_files(Settings& s) {
+  if (!s.training_pos_file.empty()) s.is_training_pos_in_voxels = read_coordinates(s.training_pos_file, s.training_pos_crds);
+  if (!s.training_neg_file.empty()) s.is_training_neg_in_voxels = read_coordinates(s.training_neg_file, s.training_neg_crds);
+  if (s.multi_training_pos_files.empty() && s.multi_training_neg_files.empty()) return;
+  if (!s.in_crds_files.empty() && !s.out_crds_file.empty())
+    throw VisfdErr("Error: This program is too stupid to automatically discard blobs from multiple\n"
+                   "       images in a single invocation.  For this reason,\n"
+                   "       you may not use the \"-supervised-multi\" argument simultaneously with\n"
+                   "       any other arguments which also perform nonmax-suppression of blobs\n"
+                   "       (such as \"-discard-blobs\").  In particular, you must make sure that\n"
+                   "       any overlapping blobs in any of the reference lists of blobs must be\n"
+                   "       removed in advance.  (These blobs are contained in the files referred\n"
+                   "       to in the 3rd column of the file supplied to \"-supervised-multi\".\n"
+                   "       They can be removed by using this program with\"-discard-blobs\"\n"
+                   "       together with \"-radial-separation\", or \"-max-volume-overlap\", and/or\n"
+                   "       \"-max-volume-overlap-small\".  This must be done separately\n"
+                   "       for each of those files in the 3rd column.)\n");
+  if (!s.mask.empty())
+    throw VisfdErr("Error: You may not use the \"-supervised-multi\" argument simultaneously with\n"
+                   "       the \"-mask\" argument.  If you wish to ignore blobs which lie outside\n"
+                   "       the mask, then you must delete the corresponding lines from the\n"
+                   "       blob lists beforehand.  (These are stored in the files indicated\n"
+                   "       by the 3rd column of the file supplied to \"-supervised-multi\"\n"
+                   "       You can do this by running this program using the \"-discard-blobs\"\n"
+                   "       together with the \"-mask\" argument.  This must be done separately\n"
+                   "       on each of these lists of blobs beforehand.)\n");
+  // THE ONE DEVIATION: the reference rescales the multi sets' coordinates in loops bounded by the sizes of the -supervised
+  // lists (filter_mrc.cpp:354-370).  With -supervised-multi alone those loops do nothing -- the coordinates are used as
+  // read, and so they are here -- but together with -supervised they index past the multi arrays.  Refused.
+  if (!s.training_pos_file.empty() || !s.training_neg_file.empty())
+    throw VisfdErr("Error: -supervised-multi does not combine with -supervised: the reference rescales the multi sets'\n"
+                   "       coordinates with the sizes of the -supervised lists and reads past its arrays there.\n");
+  const size_t n_sets = s.multi_training_pos_files.size();
+  s.multi_training_pos_crds.resize(n_sets);
+  s.multi_training_neg_crds.resize(n_sets);
+  for (size_t I = 0; I < n_sets; I++) {
+    read_coordinates(s.multi_training_pos_files[I], s.multi_training_pos_crds[I]);
+    read_coordinates(s.multi_training_neg_files[I], s.multi_training_neg_crds[I]);
+  }
 }
 
 // The -must-link file (bin/filter_mrc/file_io.hpp:82-214, :667-747): groups of locations separated by blank lines; a
@@ -662,28 +855,8 @@ bool read_must_link_file(const string& path, Settings& s) {
   };
   string line;
   while (std::getline(f, line)) {
-    const size_t hash = line.find('#');
-    if (hash != string::npos) line = line.substr(0, hash);
-    bool parens = false, imod = false;
-    for (size_t k = 0; k < line.size(); k++) {
-      if (line[k] == '(' || line[k] == ')') { parens = true; line[k] = ' '; }
-      else if (line[k] == ',') line[k] = ' ';
-    }
-    std::istringstream ws(line);
-    vector<string> words;
-    string w;
-    while (ws >> w) words.push_back(w);
-    if (!words.empty() && words[0] == "Pixel") { imod = parens = true; words.erase(words.begin()); }
     vector<float> xyz;
-    for (size_t d = 0; d < words.size(); d++) {
-      if (d >= 3 && imod) break;                       // "= value" of IMOD's line
-      std::istringstream num(words[d]);
-      float x;
-      if (!(num >> x)) throw VisfdErr("Error: File read error (invalid entry?) on line:\n      " + line + "\n");
-      if (parens && xyz.size() < 3) x = std::floor(x) - 1.0f;   // IMOD counts voxels from 1
-      xyz.push_back(x);
-    }
-    imod_any = imod_any || parens;
+    imod_any = parse_coordinate_line(line, xyz) || imod_any;
     if (xyz.empty()) { close_group(); continue; }
     if (xyz.size() != 3 && xyz.size() != 4)
       throw VisfdErr("Error: Each line of file \"" + path + "\"\n       should contain either 3 numbers, 4 numbers, or 0 numbers.\n");

@@ -1,5 +1,6 @@
 // blob_post.cpp -- blob list post-processing: sorting by score, discarding blobs
-// whose centres are masked out, greedy non-max suppression of overlapping blobs.
+// whose centres are masked out, greedy non-max suppression of overlapping blobs, and (second half of the file) the score
+// thresholds chosen from training points.
 //
 // These are short sequential host algorithms in the reference as well (lib/visfd/feature.hpp:519-616,
 // :720-913, :924-969; sphere overlap lib/visfd/visfd_utils.hpp:95-118); the greedy suppression's
@@ -197,6 +198,236 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
     }
   }
   *n_inout = (int64_t)keep.size();
+  return VISFD_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- the supervised score thresholds: visfd_utils.hpp:373-516, feature_implementation.hpp:48-457, feature.hpp:643-697,
+//      :988-1180.  Short sequential host logic; the one search over (training point, blob) pairs is FindSpheres
+//      (find_spheres.hip), on the device when a context is passed.
+namespace {
+
+// ChooseThreshold1D.  (score, index) tuples sorted ascending, or descending through reverse iterators (ties then go to
+// the LARGER index first); the mistake count starts at Nn -- everything accepted -- and moves by one per datum; of the
+// positions that reach the minimum the median entry is taken.
+float choose_threshold_1d(const std::vector<float>& scores, const std::vector<unsigned char>& accepted, bool lower_bound) {
+  const i64 N = (i64)scores.size();
+  i64 Nn = 0;
+  for (i64 i = 0; i < N; i++) Nn += accepted[(size_t)i] ? 0 : 1;
+  const float SGN = lower_bound ? 1.0f : -1.0f;
+  std::vector<std::pair<float, i64> > key((size_t)N);
+  for (i64 i = 0; i < N; i++) key[(size_t)i] = std::make_pair(scores[(size_t)i], i);
+  if (lower_bound) std::sort(key.begin(), key.end());
+  else std::sort(key.rbegin(), key.rend());
+  i64 min_mistakes = Nn, mistakes = Nn;
+  for (i64 i = 0; i < N; i++) {
+    mistakes += accepted[(size_t)key[(size_t)i].second] ? 1 : -1;
+    if (mistakes < min_mistakes) min_mistakes = mistakes;
+  }
+  std::vector<i64> at_min;
+  mistakes = Nn;
+  for (i64 i = -1; i < N; i++) {
+    if (i >= 0) mistakes += accepted[(size_t)key[(size_t)i].second] ? 1 : -1;
+    if (mistakes == min_mistakes) at_min.push_back(i);
+  }
+  const i64 it = at_min[at_min.size() / 2];
+  // the order of the two tests is the reference's: with N == 0 both hold and the first wins
+  if (it == -1) return -SGN * std::numeric_limits<float>::infinity();
+  if (it == N - 1) return SGN * std::numeric_limits<float>::infinity();
+  // 0.5 * (a + b): the sum in float, the product with the double literal in double, stored as float
+  return (float)(0.5 * (key[(size_t)it].first + key[(size_t)it + 1].first));
+}
+
+struct Interval {
+  float lower, upper;
+  i64 false_pos, n_neg, false_neg, n_pos;
+};
+
+// _ChooseThresholdInterval: lower bound first, then upper bound first; each second threshold is chosen among the data the
+// first one keeps (>= / <=); "<=" between the two mistake counts keeps the first attempt on a tie.
+Interval choose_interval(const std::vector<float>& s, const std::vector<unsigned char>& acc) {
+  const size_t N = s.size();
+  auto second = [&](float first, bool first_is_lower) {
+    std::vector<float> rs;
+    std::vector<unsigned char> ra;
+    for (size_t i = 0; i < N; i++)
+      if (first_is_lower ? s[i] >= first : s[i] <= first) { rs.push_back(s[i]); ra.push_back(acc[i]); }
+    return choose_threshold_1d(rs, ra, !first_is_lower);
+  };
+  auto mistakes = [&](float lo, float hi) {
+    i64 m = 0;
+    for (size_t i = 0; i < N; i++) m += ((acc[i] != 0) != (s[i] >= lo && s[i] <= hi)) ? 1 : 0;
+    return m;
+  };
+  const float lo1 = choose_threshold_1d(s, acc, true), hi1 = second(lo1, true);
+  const float hi2 = choose_threshold_1d(s, acc, false), lo2 = second(hi2, false);
+  Interval r;
+  if (mistakes(lo1, hi1) <= mistakes(lo2, hi2)) { r.lower = lo1; r.upper = hi1; }
+  else { r.lower = lo2; r.upper = hi2; }
+  r.false_pos = r.false_neg = r.n_neg = r.n_pos = 0;
+  for (size_t i = 0; i < N; i++) {
+    const bool in = s[i] >= r.lower && s[i] <= r.upper;
+    if (in && !acc[i]) r.false_pos++;
+    if (!in && acc[i]) r.false_neg++;
+    if (acc[i]) r.n_pos++; else r.n_neg++;
+  }
+  return r;
+}
+
+int find_spheres_with(visfd_hip_ctx* ctx, const float* crds, i64 n_crds, const float* sc, const float* sd, i64 n_spheres,
+                      int64_t* ids) {
+  return ctx ? visfd_hip_find_spheres(ctx, crds, n_crds, sc, sd, n_spheres, ids)
+             : visfd_hip_find_spheres_host(crds, n_crds, sc, sd, n_spheres, ids);
+}
+
+int check_list(const float* c, const float* d, const float* s, i64 n, const char* what) {
+  if (n < 0 || (n > 0 && (!c || !d || !s)))
+    return vh::fail(VISFD_HIP_EINVAL, std::string(what) + ": null list");
+  return VISFD_HIP_OK;
+}
+
+// _FindBlobScores
+int find_blob_scores(visfd_hip_ctx* ctx, const float* tcrds, i64 nt, const float* bc, const float* bd, const float* bs, i64 nb,
+                     int criteria, float* scores, int64_t* ids) {
+  if (criteria < 0 || criteria > VISFD_HIP_SORT_INCREASING_MAGNITUDE)
+    return vh::fail(VISFD_HIP_EINVAL, "find_blob_scores: unknown sort criteria");
+  std::vector<float> c(bc, bc + 3 * nb), d(bd, bd + nb), s(bs, bs + nb);
+  VH_TRY(visfd_hip_sort_blobs(c.data(), d.data(), s.data(), nb, criteria, 1, nullptr));   // increasing priority
+  std::vector<int64_t> which((size_t)nt);
+  VH_TRY(find_spheres_with(ctx, tcrds, nt, c.data(), d.data(), nb, which.data()));
+  for (i64 i = 0; i < nt; i++) {
+    scores[i] = which[(size_t)i] ? s[(size_t)which[(size_t)i] - 1] : -std::numeric_limits<float>::infinity();
+    if (ids) ids[i] = which[(size_t)i];
+  }
+  return VISFD_HIP_OK;
+}
+
+// _ComplainIfTrainingDataEmpty, feature_implementation.hpp:101-116 (the texts verbatim)
+int complain_if_empty(i64 Nn, i64 Np) {
+  if (Nn == 0)
+    return vh::fail(VISFD_HIP_EINVAL,
+                    "Error: Empty list of negative training examples.\n"
+                    "       Either you have provided no examples of data that you want to discard\n"
+                    "          (IE. Your file of negative training examples is empty),\n"
+                    "       OR none of the examples that you provided are sufficiently close to ANY\n"
+                    "       of the blobs in the list of blobs that you are considering discarding.\n"
+                    "       Either provide more negative training examples, or specify your\n"
+                    "       selection threshold(s) manually.\n");
+  if (Np == 0)
+    return vh::fail(VISFD_HIP_EINVAL,
+                    "Error: Empty list of positive training examples.\n"
+                    "       Either you have provided no examples of data that you want to keep\n"
+                    "          (IE. Your file of positive training examples is empty),\n"
+                    "       OR none of the examples that you provided are sufficiently close to ANY\n"
+                    "       of the blobs in the list of blobs that you are considering discarding.\n"
+                    "       Either provide more positive training examples, or specify your\n"
+                    "       selection threshold(s) manually.\n");
+  return VISFD_HIP_OK;
+}
+
+// _ChooseBlobScoreThresholdsMulti (one set: _ChooseBlobScoreThresholds): per set positives first, then negatives; the
+// points no blob holds are dropped; the sets' survivors are concatenated in order
+int choose_thresholds(visfd_hip_ctx* ctx, i64 n_sets, const float* bc, const float* bd, const float* bs, const int64_t* nb,
+                      const float* pc, const int64_t* np, const float* nc, const int64_t* nn, int criteria, Interval* out) {
+  std::vector<float> scores;
+  std::vector<unsigned char> accepted;
+  i64 ob = 0, op = 0, on = 0;
+  for (i64 I = 0; I < n_sets; I++) {
+    VH_TRY(check_list(bc, bd, bs, nb[I], "choose_blob_score_thresholds"));
+    if (np[I] < 0 || nn[I] < 0 || (np[I] > 0 && !pc) || (nn[I] > 0 && !nc))
+      return vh::fail(VISFD_HIP_EINVAL, "choose_blob_score_thresholds: null training list");
+    const i64 nt = np[I] + nn[I];
+    std::vector<float> t((size_t)(3 * nt)), ts((size_t)nt);
+    std::vector<int64_t> which((size_t)nt);
+    if (np[I] > 0) std::memcpy(t.data(), pc + 3 * op, sizeof(float) * 3 * (size_t)np[I]);
+    if (nn[I] > 0) std::memcpy(t.data() + 3 * np[I], nc + 3 * on, sizeof(float) * 3 * (size_t)nn[I]);
+    VH_TRY(find_blob_scores(ctx, t.data(), nt, bc + 3 * ob, bd + ob, bs + ob, nb[I], criteria, ts.data(), which.data()));
+    for (i64 i = 0; i < nt; i++)
+      if (which[(size_t)i] != 0) {   // FindBlobScores, feature.hpp:684-690
+        scores.push_back(ts[(size_t)i]);
+        accepted.push_back(i < np[I] ? 1 : 0);
+      }
+    ob += nb[I]; op += np[I]; on += nn[I];
+  }
+  i64 Np = 0;
+  for (unsigned char a : accepted) Np += a;
+  VH_TRY(complain_if_empty((i64)accepted.size() - Np, Np));
+  *out = choose_interval(scores, accepted);
+  return VISFD_HIP_OK;
+}
+
+void give(const Interval& r, float* lower, float* upper, int64_t* report) {
+  if (lower) *lower = r.lower;
+  if (upper) *upper = r.upper;
+  if (report) { report[0] = r.false_pos; report[1] = r.n_neg; report[2] = r.false_neg; report[3] = r.n_pos; }
+}
+
+}  // namespace
+
+extern "C" {
+
+int visfd_hip_choose_threshold_1d(const float* scores, const unsigned char* accepted, int64_t n, int is_lower_bound,
+                                  float* threshold) {
+  if (n < 0 || !threshold || (n > 0 && (!scores || !accepted)))
+    return vh::fail(VISFD_HIP_EINVAL, "choose_threshold_1d: null argument");
+  *threshold = choose_threshold_1d(std::vector<float>(scores, scores + n), std::vector<unsigned char>(accepted, accepted + n),
+                                   is_lower_bound != 0);
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_find_blob_scores(visfd_hip_ctx* ctx, const float* training_crds, int64_t n_training, const float* blob_crds,
+                               const float* blob_diameters, const float* blob_scores, int64_t n_blobs, int sort_criteria,
+                               float* scores, int64_t* sphere_ids) {
+  VH_TRY(check_list(blob_crds, blob_diameters, blob_scores, n_blobs, "find_blob_scores"));
+  if (n_training < 0 || (n_training > 0 && (!training_crds || !scores)))
+    return vh::fail(VISFD_HIP_EINVAL, "find_blob_scores: null training list");
+  return find_blob_scores(ctx, training_crds, n_training, blob_crds, blob_diameters, blob_scores, n_blobs, sort_criteria,
+                          scores, sphere_ids);
+}
+
+int visfd_hip_choose_blob_score_thresholds_multi(visfd_hip_ctx* ctx, int64_t n_sets, const float* blob_crds,
+                                                 const float* blob_diameters, const float* blob_scores,
+                                                 const int64_t* n_blobs, const float* pos_crds, const int64_t* n_pos,
+                                                 const float* neg_crds, const int64_t* n_neg, int sort_criteria,
+                                                 float* lower, float* upper, int64_t* report) {
+  if (n_sets < 0 || (n_sets > 0 && (!n_blobs || !n_pos || !n_neg)))
+    return vh::fail(VISFD_HIP_EINVAL, "choose_blob_score_thresholds_multi: null counts");
+  Interval r;
+  VH_TRY(choose_thresholds(ctx, n_sets, blob_crds, blob_diameters, blob_scores, n_blobs, pos_crds, n_pos, neg_crds, n_neg,
+                           sort_criteria, &r));
+  give(r, lower, upper, report);
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_choose_blob_score_thresholds(visfd_hip_ctx* ctx, const float* blob_crds, const float* blob_diameters,
+                                           const float* blob_scores, int64_t n_blobs, const float* pos_crds, int64_t n_pos,
+                                           const float* neg_crds, int64_t n_neg, int sort_criteria, float* lower,
+                                           float* upper, int64_t* report) {
+  return visfd_hip_choose_blob_score_thresholds_multi(ctx, 1, blob_crds, blob_diameters, blob_scores, &n_blobs, pos_crds,
+                                                      &n_pos, neg_crds, &n_neg, sort_criteria, lower, upper, report);
+}
+
+int visfd_hip_discard_blobs_by_score_supervised(visfd_hip_ctx* ctx, float* crds, float* diameters, float* scores,
+                                                int64_t* n_inout, const float* pos_crds, int64_t n_pos,
+                                                const float* neg_crds, int64_t n_neg, int sort_criteria, float* lower,
+                                                float* upper, int64_t* report) {
+  if (!n_inout || *n_inout < 0) return vh::fail(VISFD_HIP_EINVAL, "discard_blobs_by_score_supervised: bad count");
+  const i64 n = *n_inout;
+  Interval r;
+  VH_TRY(choose_thresholds(ctx, 1, crds, diameters, scores, &n, pos_crds, &n_pos, neg_crds, &n_neg, sort_criteria, &r));
+  give(r, lower, upper, report);
+  i64 kept = 0;
+  for (i64 i = 0; i < n; i++) {
+    if (!(scores[i] >= r.lower && scores[i] <= r.upper)) continue;
+    if (kept != i) {
+      std::memmove(crds + 3 * kept, crds + 3 * i, 3 * sizeof(float));
+      diameters[kept] = diameters[i];
+      scores[kept] = scores[i];
+    }
+    kept++;
+  }
+  *n_inout = kept;
   return VISFD_HIP_OK;
 }
 

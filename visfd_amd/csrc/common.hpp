@@ -76,6 +76,8 @@ enum Slot {
   WS_DIST_DSQ,                     // distance maps: the int32 squared distances behind the float outputs (csrc/distance.hip)
   WS_DIST_STACK,                   // distance maps: the envelope passes' stacks, per wave [entry][lane] of int2
   WS_DIST_POINTS,                  // distance maps: the listed points that can matter; query points and their results
+  WS_FS_RECORDS,                   // FindSpheres: one 16-byte record (cx, cy, cz, Rsqr) per sphere, padded to whole passes (csrc/find_spheres.hip)
+  WS_FS_QUERIES,                   // FindSpheres: the truncated queries, padded to whole batches, and the flag word of the two preparation launches
   WS_NSLOTS
 };
 
@@ -110,6 +112,7 @@ struct visfd_hip_options {
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
   int distance_general = 0; // 1: distance maps by the brute-force walks (csrc/distance.hip), never by the separable transform
+  int find_spheres_host = 0; // 1: FindSpheres walks the pairs on the host (csrc/find_spheres.hip), never launches the search kernel
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
@@ -139,6 +142,7 @@ struct visfd_hip_ctx {
   std::vector<int> median_tab;        // the footprint now in slot WS_MEDIAN_TAB (n entries dx, dy, dz, 0, then n LDS cell offsets)
   int median_last_path = -1;          // the kernel the last median call ran (VISFD_HIP_MEDIAN_PATH_*)
   int distance_last_path = -1;        // what the last distance call ran (VISFD_HIP_DISTANCE_PATH_*)
+  int find_spheres_last_path = -1;    // what the last FindSpheres call ran (VISFD_HIP_FIND_SPHERES_PATH_*)
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)

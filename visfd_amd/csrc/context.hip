@@ -57,6 +57,7 @@ const OptionDesc kOptions[] = {
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
+    {"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr},
     {"log_pair", &visfd_hip_options::log_pair, nullptr},
     {"log_pair_chunk", &visfd_hip_options::log_pair_chunk, nullptr},
 };
