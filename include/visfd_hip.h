@@ -80,7 +80,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * supervised blob thresholds: visfd_hip_find_spheres[_dev|_host],
                                      * visfd_hip_find_spheres_last_path, visfd_hip_choose_threshold_1d,
                                      * visfd_hip_find_blob_scores, visfd_hip_choose_blob_score_thresholds[_multi] and
-                                     * visfd_hip_discard_blobs_by_score_supervised) */
+                                     * visfd_hip_discard_blobs_by_score_supervised; then LabelConnected's seed search
+                                     * on the device: visfd_hip_label_connected_device_seeds and
+                                     * visfd_hip_label_connected_device_seeds_last) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -795,6 +797,34 @@ int visfd_hip_label_connected_ex(const float* saliency, int64_t* labels, const f
                                  const float* voxel_weights, const float* must_link_crds,
                                  const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
                                  const int* must_link_directions);
+
+/* visfd_hip_label_connected_ex with its SEED SEARCH on a context's device: the same arguments after the context (host
+ * arrays), the same results bit for bit.  Only the seeds -- the plateau-aware extrema of the whole image, the part of the
+ * call that looks at every voxel -- are found on the device, by the kernels of visfd_hip_find_extrema (saliency and mask
+ * are staged through the workspace); the flood from them is the sequential one of the host, unchanged.  This is not a
+ * device implementation of LabelConnected, and it reports no fallback reasons: DESIGN.md 4.13 says what stands in the way
+ * of one and leaves the names such a face would take free.
+ * Refused before anything is allocated or copied (VISFD_HIP_EINVAL): a null context or image, a dimension below 3, an
+ * image of 2^31 voxels or more, connectivity < 1.  Where the device search does not reach -- connectivity above
+ * VISFD_HIP_EXTREMA_MAX_CONNECTIVITY, more than VISFD_HIP_EXTREMA_MAX_VOXELS voxels, ny or nz above
+ * VISFD_HIP_EXTREMA_MAX_NY_NZ, 2^24 tiles of 64 x 8 x 8 or more -- the host searches the seeds as well.
+ * visfd_hip_label_connected_device_seeds_last: where the context's last successful call searched its seeds
+ * (VISFD_HIP_CONNECT_SEEDS_*; -1 before the first) and, nullable, the length of the device's list (-1 on the host). */
+#define VISFD_HIP_CONNECT_SEEDS_DEVICE 0
+#define VISFD_HIP_CONNECT_SEEDS_HOST 1
+int visfd_hip_label_connected_device_seeds(visfd_hip_ctx*, const float* saliency, int64_t* labels, const float* mask,
+                                           int64_t nx, int64_t ny, int64_t nz, float threshold_saliency, float* direction,
+                                           float threshold_vector_saliency, float threshold_vector_neighbor,
+                                           int consider_dot_product_sign, const float* tensor,
+                                           float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                                           int tensor_is_positive_definite_near_target, int connectivity,
+                                           int64_t label_undefined, int sort_by_size, int standardize_directions,
+                                           int start_from_saliency_maxima, int64_t* n_clusters, float* cluster_maxima,
+                                           float* cluster_sizes, float* cluster_saliencies, int64_t cluster_capacity,
+                                           const float* voxel_weights, const float* must_link_crds,
+                                           const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
+                                           const int* must_link_directions);
+int visfd_hip_label_connected_device_seeds_last(visfd_hip_ctx*, int* where, int64_t* n_seeds);
 
 /* Principal eigenvector (eigenvector row 0 of ConvertFlatSym2Evects3 in the given order) of nvox flat tensors
  * [nvox][6] -> direction [nvox][3], computed on the HOST in the reference's arithmetic (the loop of

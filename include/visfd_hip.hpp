@@ -1377,8 +1377,10 @@ inline void _BlobDogNM(int const image_size[3], float const* const* const* aaafS
 typedef enum eRegionSortCriteria { SORT_BY_VALUE, SORT_BY_SIZE } RegionSortCriteria;
 typedef enum eDirectionPairType { SAME_DIRECTION, OPPOSITE_DIRECTION, AUTO } DirectionPairType;
 
-inline size_t LabelConnected(
-    const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
+// Not in the reference: LabelConnected with its seed search on a context's device (visfd_hip_label_connected_device_seeds;
+// the flood stays on the host, the results are the same bits); a null context is the drop-in below.
+inline size_t LabelConnectedDeviceSeeds(
+    visfd_hip_ctx* ctx, const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
     float const* const* const* aaafMask,
     float threshold_saliency = -std::numeric_limits<float>::infinity(),
     std::array<float, 3> const* const* const* aaaafVector = nullptr,
@@ -1439,16 +1441,31 @@ inline size_t LabelConnected(
   }
   std::vector<float> cm(pv_cluster_maxima ? 3 * n : 0), cs(pv_cluster_sizes ? n : 0), csal(pv_cluster_saliencies ? n : 0);
   int64_t n_clusters = 0;
-  hip_detail::check(visfd_hip_label_connected_ex(
-      hip_detail::flat(aaafSaliency), reinterpret_cast<int64_t*>(&aaaiDest[0][0][0]), hip_detail::flat(aaafMask),
-      image_size[0], image_size[1], image_size[2], threshold_saliency, dir, threshold_vector_saliency,
-      threshold_vector_neighbor, consider_dot_product_sign ? 1 : 0, aaaafSymmetricTensor ? ten.data() : nullptr,
-      threshold_tensor_saliency, threshold_tensor_neighbor, tensor_is_positive_definite_near_target ? 1 : 0, connectivity,
-      (int64_t)label_undefined, sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0,
-      start_from_saliency_maxima ? 1 : 0, &n_clusters, cm.empty() ? nullptr : cm.data(), cs.empty() ? nullptr : cs.data(),
-      csal.empty() ? nullptr : csal.data(), (int64_t)n, hip_detail::flat(aaafVoxelWeights),
-      ml_crds.empty() ? nullptr : ml_crds.data(), ml_sizes.empty() ? nullptr : ml_sizes.data(), (int64_t)ml_sizes.size(),
-      ml_dirs.empty() ? nullptr : ml_dirs.data()));
+  int64_t* const dest = reinterpret_cast<int64_t*>(&aaaiDest[0][0][0]);
+  const float* const w = hip_detail::flat(aaafVoxelWeights);
+  const float* const mlc = ml_crds.empty() ? nullptr : ml_crds.data();
+  const int64_t* const mls = ml_sizes.empty() ? nullptr : ml_sizes.data();
+  const int* const mld = ml_dirs.empty() ? nullptr : ml_dirs.data();
+  const int rc =
+      ctx ? visfd_hip_label_connected_device_seeds(
+                ctx, hip_detail::flat(aaafSaliency), dest, hip_detail::flat(aaafMask), image_size[0], image_size[1],
+                image_size[2], threshold_saliency, dir, threshold_vector_saliency, threshold_vector_neighbor,
+                consider_dot_product_sign ? 1 : 0, aaaafSymmetricTensor ? ten.data() : nullptr, threshold_tensor_saliency,
+                threshold_tensor_neighbor, tensor_is_positive_definite_near_target ? 1 : 0, connectivity,
+                (int64_t)label_undefined, sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0,
+                start_from_saliency_maxima ? 1 : 0, &n_clusters, cm.empty() ? nullptr : cm.data(),
+                cs.empty() ? nullptr : cs.data(), csal.empty() ? nullptr : csal.data(), (int64_t)n, w, mlc, mls,
+                (int64_t)ml_sizes.size(), mld)
+          : visfd_hip_label_connected_ex(
+                hip_detail::flat(aaafSaliency), dest, hip_detail::flat(aaafMask), image_size[0], image_size[1],
+                image_size[2], threshold_saliency, dir, threshold_vector_saliency, threshold_vector_neighbor,
+                consider_dot_product_sign ? 1 : 0, aaaafSymmetricTensor ? ten.data() : nullptr, threshold_tensor_saliency,
+                threshold_tensor_neighbor, tensor_is_positive_definite_near_target ? 1 : 0, connectivity,
+                (int64_t)label_undefined, sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0,
+                start_from_saliency_maxima ? 1 : 0, &n_clusters, cm.empty() ? nullptr : cm.data(),
+                cs.empty() ? nullptr : cs.data(), csal.empty() ? nullptr : csal.data(), (int64_t)n, w, mlc, mls,
+                (int64_t)ml_sizes.size(), mld);
+  hip_detail::check(rc);
   if (pReportProgress) *pReportProgress << "Number of clusters found: " << n_clusters << "\n";
   if (pv_cluster_maxima) {
     pv_cluster_maxima->resize((size_t)n_clusters);
@@ -1457,6 +1474,32 @@ inline size_t LabelConnected(
   if (pv_cluster_sizes) pv_cluster_sizes->assign(cs.begin(), cs.begin() + n_clusters);
   if (pv_cluster_saliencies) pv_cluster_saliencies->assign(csal.begin(), csal.begin() + n_clusters);
   return (size_t)n_clusters;
+}
+
+// the reference's signature: everything on the host, no GPU needed
+inline size_t LabelConnected(
+    const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
+    float const* const* const* aaafMask,
+    float threshold_saliency = -std::numeric_limits<float>::infinity(),
+    std::array<float, 3> const* const* const* aaaafVector = nullptr,
+    float threshold_vector_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_vector_neighbor = -std::numeric_limits<float>::infinity(), bool consider_dot_product_sign = true,
+    float* const* const* const* aaaafSymmetricTensor = nullptr,
+    float threshold_tensor_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_tensor_neighbor = -std::numeric_limits<float>::infinity(),
+    bool tensor_is_positive_definite_near_target = true, int connectivity = 1, ptrdiff_t label_undefined = -1,
+    std::vector<std::array<float, 3> >* pv_cluster_maxima = nullptr, std::vector<float>* pv_cluster_sizes = nullptr,
+    std::vector<float>* pv_cluster_saliencies = nullptr, RegionSortCriteria sort_criteria = SORT_BY_SIZE,
+    float const* const* const* aaafVoxelWeights = nullptr, std::array<float, 3>*** aaaafVectorStandardized = nullptr,
+    const std::vector<std::vector<std::array<float, 3> > >* pMustLinkConstraints = nullptr,
+    const std::vector<std::vector<DirectionPairType> >* pMustLinkDirections = nullptr,
+    bool start_from_saliency_maxima = true, std::ostream* pReportProgress = nullptr) {
+  return LabelConnectedDeviceSeeds(nullptr, image_size, aaafSaliency, aaaiDest, aaafMask, threshold_saliency, aaaafVector,
+                        threshold_vector_saliency, threshold_vector_neighbor, consider_dot_product_sign, aaaafSymmetricTensor,
+                        threshold_tensor_saliency, threshold_tensor_neighbor, tensor_is_positive_definite_near_target,
+                        connectivity, label_undefined, pv_cluster_maxima, pv_cluster_sizes, pv_cluster_saliencies,
+                        sort_criteria, aaafVoxelWeights, aaaafVectorStandardized, pMustLinkConstraints, pMustLinkDirections,
+                        start_from_saliency_maxima, pReportProgress);
 }
 
 // ---- eigenvalue order: lib/visfd/eigen3_simple.hpp:36-43 ------------------------------------------------

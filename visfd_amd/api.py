@@ -252,6 +252,12 @@ _SIGS = {
     "visfd_hip_label_connected_ex": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float, C.c_float, C.c_int,
                                                _vp, C.c_float, C.c_float, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # LabelConnected with its seed search on the device (csrc/connect_seeds.hip): the _ex arguments after the context
+    "visfd_hip_label_connected_device_seeds": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float,
+                                                         C.c_float, C.c_int, _vp, C.c_float, C.c_float, C.c_int, C.c_int, _i64,
+                                                         C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp,
+                                                         _vp, _vp, _i64, _vp]),
+    "visfd_hip_label_connected_device_seeds_last": (C.c_int, [_vp, _ip, C.POINTER(_i64)]),
     "visfd_hip_principal_directions_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_tensor_saliency_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_diagonalize_sym3_f32_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -599,25 +605,12 @@ def sigmas_to_diameters(s):
 
 
 # ---- voxel clustering (host-side) ---------------------------------------------------------
-def label_connected(saliency, threshold_saliency, mask=None, direction=None, tensor=None,
-                    threshold_vector_saliency=-np.inf, threshold_vector_neighbor=-np.inf, consider_dot_product_sign=True,
-                    threshold_tensor_saliency=-np.inf, threshold_tensor_neighbor=-np.inf,
-                    tensor_is_positive_definite_near_target=True, connectivity=1, label_undefined=-1, sort_by_size=True,
-                    standardize_directions=False, start_from_saliency_maxima=True, voxel_weights=None, must_link=None,
-                    must_link_directions=None):
-    """LabelConnected (connect.hpp:168-1427).  saliency [nz,ny,nx]; direction [nz,ny,nx,3] (rewritten in place when
-    standardize_directions); tensor [nz,ny,nx,6].  Returns (labels int64 [nz,ny,nx], n_clusters, seed positions
-    [n,3] in final order, sizes [n] and seed saliencies [n] in provisional order)."""
-    L = load_library()
-    nz, ny, nx = saliency.shape
-    labels = np.empty((nz, ny, nx), np.int64)
-    n = _i64(0)
-    cap = int(saliency.size)
-    cm, cs, csal = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
-    for a in (direction, tensor):
-        assert a is None or (a.dtype == np.float32 and a.flags["C_CONTIGUOUS"])
-    # must_link: list of groups, each a list of (x, y, z) locations in voxels; must_link_directions: the same shape of
-    # 0 / 1 / 2 (same / opposite / automatic, connect.hpp DirectionPairType) or None
+CONNECT_SEEDS_DEVICE, CONNECT_SEEDS_HOST = 0, 1   # visfd_hip_label_connected_device_seeds_last
+
+
+def _must_link_arrays(must_link, must_link_directions):
+    """must_link: list of groups, each a list of (x, y, z) locations in voxels; must_link_directions: the same shape of
+    0 / 1 / 2 (same / opposite / automatic, connect.hpp DirectionPairType) or None -> (crds, group sizes, directions, n)"""
     ml_c = ml_n = ml_d = None
     ngroups = 0
     if must_link:
@@ -626,15 +619,41 @@ def label_connected(saliency, threshold_saliency, mask=None, direction=None, ten
         ml_n = np.array([len(g_) for g_ in must_link], np.int64)
         if must_link_directions is not None:
             ml_d = np.ascontiguousarray(np.concatenate([np.asarray(d_, np.int32).ravel() for d_ in must_link_directions]))
+    return ml_c, ml_n, ml_d, ngroups
+
+
+def label_connected(saliency, threshold_saliency, mask=None, direction=None, tensor=None,
+                    threshold_vector_saliency=-np.inf, threshold_vector_neighbor=-np.inf, consider_dot_product_sign=True,
+                    threshold_tensor_saliency=-np.inf, threshold_tensor_neighbor=-np.inf,
+                    tensor_is_positive_definite_near_target=True, connectivity=1, label_undefined=-1, sort_by_size=True,
+                    standardize_directions=False, start_from_saliency_maxima=True, voxel_weights=None, must_link=None,
+                    must_link_directions=None, seeds_ctx=None):
+    """LabelConnected (connect.hpp:168-1427).  saliency [nz,ny,nx]; direction [nz,ny,nx,3] (rewritten in place when
+    standardize_directions); tensor [nz,ny,nx,6].  Returns (labels int64 [nz,ny,nx], n_clusters, seed positions
+    [n,3] in final order, sizes [n] and seed saliencies [n] in provisional order).  seeds_ctx (a Context): the seeds
+    are searched on its device (Context.label_connected_device_seeds_last says whether); the flood runs on the host either
+    way and the results are the same bits."""
+    L = load_library()
+    nz, ny, nx = saliency.shape
+    labels = np.empty((nz, ny, nx), np.int64)
+    n = _i64(0)
+    cap = int(saliency.size)
+    cm, cs, csal = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    for a in (direction, tensor):
+        assert a is None or (a.dtype == np.float32 and a.flags["C_CONTIGUOUS"])
+    ml_c, ml_n, ml_d, ngroups = _must_link_arrays(must_link, must_link_directions)
     ptr = lambda a: None if a is None else a.ctypes.data
-    _chk_host(L, L.visfd_hip_label_connected_ex(
-        _np(saliency), labels.ctypes.data, _np(mask), nx, ny, nz, threshold_saliency,
-        None if direction is None else direction.ctypes.data, threshold_vector_saliency, threshold_vector_neighbor,
-        int(bool(consider_dot_product_sign)), None if tensor is None else tensor.ctypes.data, threshold_tensor_saliency,
-        threshold_tensor_neighbor, int(bool(tensor_is_positive_definite_near_target)), int(connectivity),
-        int(label_undefined), int(bool(sort_by_size)), int(bool(standardize_directions)),
-        int(bool(start_from_saliency_maxima)), C.byref(n), cm.ctypes.data, cs.ctypes.data, csal.ctypes.data, cap,
-        _np(voxel_weights), ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d)))
+    args = (_np(saliency), labels.ctypes.data, _np(mask), nx, ny, nz, threshold_saliency,
+            None if direction is None else direction.ctypes.data, threshold_vector_saliency, threshold_vector_neighbor,
+            int(bool(consider_dot_product_sign)), None if tensor is None else tensor.ctypes.data, threshold_tensor_saliency,
+            threshold_tensor_neighbor, int(bool(tensor_is_positive_definite_near_target)), int(connectivity),
+            int(label_undefined), int(bool(sort_by_size)), int(bool(standardize_directions)),
+            int(bool(start_from_saliency_maxima)), C.byref(n), cm.ctypes.data, cs.ctypes.data, csal.ctypes.data, cap,
+            _np(voxel_weights), ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d))
+    if seeds_ctx is None:
+        _chk_host(L, L.visfd_hip_label_connected_ex(*args))
+    else:
+        _chk_host(L, L.visfd_hip_label_connected_device_seeds(seeds_ctx._h, *args))
     k = n.value
     return labels, k, cm[:k], cs[:k], csal[:k]
 
@@ -1290,6 +1309,18 @@ class Context:
         return _watershed(lambda *t: self._L.visfd_hip_watershed_dev(self._h, *t), _dev(src), _dev(mask),
                           None if markers is None else markers.data_ptr(), tuple(src.shape), labels.data_ptr(),
                           halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary, label_undefined)
+
+    def label_connected_device_seeds(self, saliency, threshold_saliency, **kw):
+        """api.label_connected with the seed search on this context's device (numpy arrays; the flood on the host)."""
+        return label_connected(saliency, threshold_saliency, seeds_ctx=self, **kw)
+
+    def label_connected_device_seeds_last(self):
+        """(where, seeds) of the context's last label_connected_device_seeds: CONNECT_SEEDS_DEVICE and the length of the
+        device's seed list, or CONNECT_SEEDS_HOST and -1 (the image or the connectivity is beyond the device search);
+        (-1, -1) before the first call."""
+        p, n = C.c_int(), _i64()
+        self._chk(self._L.visfd_hip_label_connected_device_seeds_last(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def watershed_last_stats(self):
         """(path, label rounds, boundary rounds, basins) of the last watershed call; path WATERSHED_PATH_HOST or _DEVICE."""

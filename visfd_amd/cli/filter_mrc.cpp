@@ -1020,6 +1020,17 @@ void write_normals_file(Run& r, const vector<float>& saliency, const vector<floa
         << norms[3 * k + 1] << " " << norms[3 * k + 2] << "\n";
 }
 
+// visfd_hip_label_connected_ex behind the signature of visfd_hip_label_connected_device_seeds
+int connect_on_host(visfd_hip_ctx*, const float* saliency, int64_t* labels, const float* mask, int64_t nx, int64_t ny,
+                    int64_t nz, float ts, float* direction, float tvs, float tvn, int signs, const float* tensor, float tts,
+                    float ttn, int posdef, int connectivity, int64_t label_undefined, int sort_by_size, int standardize,
+                    int from_maxima, int64_t* n_clusters, float* cm, float* cs, float* csal, int64_t cap, const float* weights,
+                    const float* ml_crds, const int64_t* ml_sizes, int64_t ml_n, const int* ml_dirs) {
+  return visfd_hip_label_connected_ex(saliency, labels, mask, nx, ny, nz, ts, direction, tvs, tvn, signs, tensor, tts, ttn,
+                                      posdef, connectivity, label_undefined, sort_by_size, standardize, from_maxima, n_clusters,
+                                      cm, cs, csal, cap, weights, ml_crds, ml_sizes, ml_n, ml_dirs);
+}
+
 // -connect (handlers.cpp:1925-2035).  Saliency and directions are recomputed on the host in the reference's own
 // arithmetic (the flood order and the angle thresholds act on them); the vote tensors are exact already.
 void cluster(Run& r, int order, const vector<float>& tensor) {
@@ -1031,8 +1042,17 @@ void cluster(Run& r, int order, const vector<float>& tensor) {
   hip_detail::check(visfd_hip_principal_directions_host(tensor.data(), mptr, (int64_t)n, order, direction.data()));
   vector<int64_t> labels(n);
   int64_t n_clusters = 0;
-  hip_detail::check(visfd_hip_label_connected_ex(
-      r.tomo_out.data(), labels.data(), mptr, r.size[0], r.size[1], r.size[2], s.connect_threshold_saliency,
+  // -load-progress ... -connect needs no GPU for anything else: on a machine without a device the seeds are searched on
+  // the host as well.  Any other failure to get a context (a bad VISFD_HIP_DEVICE, a driver or memory error) is reported
+  // like everywhere else in this program.
+  visfd_hip_ctx* ctx = nullptr;
+  try {
+    ctx = hip_detail::context();
+  } catch (const VisfdErr& e) {
+    if (std::string(e.what()).find("no HIP device available") == std::string::npos) throw;
+  }
+  hip_detail::check((ctx ? visfd_hip_label_connected_device_seeds : connect_on_host)(   // the same labels either way
+      ctx, r.tomo_out.data(), labels.data(), mptr, r.size[0], r.size[1], r.size[2], s.connect_threshold_saliency,
       direction.data(), s.connect_threshold_vector_saliency, s.connect_threshold_vector_neighbor, 0, tensor.data(),
       s.connect_threshold_tensor_saliency, s.connect_threshold_tensor_neighbor, 1, 1, -1, 1, 1, 1, &n_clusters,
       nullptr, nullptr, nullptr, 0, nullptr, s.must_link_crds.empty() ? nullptr : s.must_link_crds.data(),

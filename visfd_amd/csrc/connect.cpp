@@ -3,9 +3,10 @@
 // mutually compatible voxels into "islands", the consumer of the tensor-voting output
 // (bin/filter_mrc/handlers.cpp:1925-2035).
 //
-// This is a sequential priority-flood (Meyer) in the reference and stays on the host here: every
-// step depends on the labels written by the steps before it.  What is reproduced exactly, because the
-// labels depend on it:
+// This is a sequential priority-flood (Meyer) in the reference and stays on the host here.  Labels, lists and the
+// directions of labelled voxels do not in fact depend on the pop order, the directions the flood leaves on unlabelled
+// voxels do (tests/connect_graph_np.py); the seed search has no order in it and visfd_hip_label_connected_device_seeds
+// (connect_seeds.hip) runs it on the device.  What is reproduced exactly, because the labels depend on it:
 //   * seeds: local maxima (or minima) of the saliency including plateaus, found in scan order,
 //     kept if they pass the threshold, ranked by (score, scan rank) -- descending = the exact reverse
 //     of the ascending ranking;
@@ -33,6 +34,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "connect_host.hpp"
 #include "eigen3.hpp"
 
 namespace {
@@ -140,24 +142,34 @@ inline float sqr(float x) { return x * x; }
 
 }  // namespace
 
-extern "C" int visfd_hip_label_connected_ex(const float* saliency, int64_t* labels, const float* mask, int64_t nx64,
-                                            int64_t ny64, int64_t nz64, float threshold_saliency, float* direction,
-                                            float threshold_vector_saliency, float threshold_vector_neighbor,
-                                            int consider_dot_product_sign, const float* tensor,
-                                            float threshold_tensor_saliency, float threshold_tensor_neighbor,
-                                            int tensor_is_positive_definite_near_target, int connectivity,
-                                            int64_t label_undefined, int sort_by_size, int standardize_directions,
-                                            int start_from_saliency_maxima, int64_t* n_clusters_out,
-                                            float* cluster_maxima, float* cluster_sizes, float* cluster_saliencies,
-                                            int64_t cluster_capacity, const float* voxel_weights,
-                                            const float* must_link_crds, const int64_t* must_link_group_sizes,
-                                            int64_t must_link_ngroups, const int* must_link_directions) {
+// what can be said about a call before anything is computed or copied
+int vh::label_connected_check_args(const float* saliency, const int64_t* labels, int64_t nx64, int64_t ny64, int64_t nz64,
+                                   int connectivity) {
   if (!saliency || !labels) return vh::fail(VISFD_HIP_EINVAL, "label_connected: null image");
   VH_TRY(vh::check_dims(nx64, ny64, nz64));
   if (nx64 < 3 || ny64 < 3 || nz64 < 3)   // visfd_utils.hpp:585-587 (asserted there)
     return vh::fail(VISFD_HIP_EINVAL, "label_connected: the image must be at least 3 voxels wide in every direction");
-  if (nx64 * ny64 * nz64 >= (1LL << 31)) return vh::fail(VISFD_HIP_EINVAL, "label_connected: image too large");
+  if (nx64 >= (1LL << 31) || ny64 >= (1LL << 31) || nz64 >= (1LL << 31) || nx64 * ny64 >= (1LL << 31) ||
+      nx64 * ny64 * nz64 >= (1LL << 31))
+    return vh::fail(VISFD_HIP_EINVAL, "label_connected: image too large");
   if (connectivity < 1) return vh::fail(VISFD_HIP_EINVAL, "label_connected: connectivity must be >= 1");
+  return VISFD_HIP_OK;
+}
+
+// The flood.  given_index / given_score (both or neither): the ranked seed list, found elsewhere (csrc/connect_seeds.hip finds
+// it on the device); without them find_extrema above is run.
+int vh::host_label_connected(const float* saliency, int64_t* labels, const float* mask, int64_t nx64, int64_t ny64,
+                             int64_t nz64, float threshold_saliency, float* direction, float threshold_vector_saliency,
+                             float threshold_vector_neighbor, int consider_dot_product_sign, const float* tensor,
+                             float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                             int tensor_is_positive_definite_near_target, int connectivity, int64_t label_undefined,
+                             int sort_by_size, int standardize_directions, int start_from_saliency_maxima,
+                             int64_t* n_clusters_out, float* cluster_maxima, float* cluster_sizes,
+                             float* cluster_saliencies, int64_t cluster_capacity, const float* voxel_weights,
+                             const float* must_link_crds, const int64_t* must_link_group_sizes,
+                             int64_t must_link_ngroups, const int* must_link_directions,
+                             const std::vector<int>* given_index, const std::vector<float>* given_score) {
+  VH_TRY(vh::label_connected_check_args(saliency, labels, nx64, ny64, nz64, connectivity));
   const Grid g = {(int)nx64, (int)ny64, (int)nz64};
   const i64 n = (i64)g.nx * g.ny * g.nz;
   const float* S = saliency;
@@ -177,7 +189,12 @@ extern "C" int visfd_hip_label_connected_ex(const float* saliency, int64_t* labe
 
   std::vector<i64> seed;
   std::vector<float> seed_score;
-  find_extrema(g, S, M, !from_max, threshold_saliency, nb, &seed, &seed_score);
+  if (given_index && given_score) {
+    seed.assign(given_index->begin(), given_index->end());
+    seed_score = *given_score;
+  } else {
+    find_extrema(g, S, M, !from_max, threshold_saliency, nb, &seed, &seed_score);
+  }
   const i64 nseeds = (i64)seed.size();
   const i64 UNDEFINED = nseeds + 1, QUEUED = nseeds + 2;
   for (i64 i = 0; i < n; i++) labels[i] = UNDEFINED;
@@ -447,6 +464,27 @@ extern "C" int visfd_hip_label_connected_ex(const float* saliency, int64_t* labe
     }
   }
   return VISFD_HIP_OK;
+}
+
+extern "C" int visfd_hip_label_connected_ex(const float* saliency, int64_t* labels, const float* mask, int64_t nx64,
+                                            int64_t ny64, int64_t nz64, float threshold_saliency, float* direction,
+                                            float threshold_vector_saliency, float threshold_vector_neighbor,
+                                            int consider_dot_product_sign, const float* tensor,
+                                            float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                                            int tensor_is_positive_definite_near_target, int connectivity,
+                                            int64_t label_undefined, int sort_by_size, int standardize_directions,
+                                            int start_from_saliency_maxima, int64_t* n_clusters_out,
+                                            float* cluster_maxima, float* cluster_sizes, float* cluster_saliencies,
+                                            int64_t cluster_capacity, const float* voxel_weights,
+                                            const float* must_link_crds, const int64_t* must_link_group_sizes,
+                                            int64_t must_link_ngroups, const int* must_link_directions) {
+  return vh::host_label_connected(saliency, labels, mask, nx64, ny64, nz64, threshold_saliency, direction,
+                                  threshold_vector_saliency, threshold_vector_neighbor, consider_dot_product_sign, tensor,
+                                  threshold_tensor_saliency, threshold_tensor_neighbor,
+                                  tensor_is_positive_definite_near_target, connectivity, label_undefined, sort_by_size,
+                                  standardize_directions, start_from_saliency_maxima, n_clusters_out, cluster_maxima,
+                                  cluster_sizes, cluster_saliencies, cluster_capacity, voxel_weights, must_link_crds,
+                                  must_link_group_sizes, must_link_ngroups, must_link_directions, nullptr, nullptr);
 }
 
 extern "C" int visfd_hip_label_connected(const float* saliency, int64_t* labels, const float* mask, int64_t nx64,
