@@ -82,7 +82,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * visfd_hip_find_blob_scores, visfd_hip_choose_blob_score_thresholds[_multi] and
                                      * visfd_hip_discard_blobs_by_score_supervised; then LabelConnected's seed search
                                      * on the device: visfd_hip_label_connected_device_seeds and
-                                     * visfd_hip_label_connected_device_seeds_last) */
+                                     * visfd_hip_label_connected_device_seeds_last; then LabelConnected as a graph
+                                     * problem: visfd_hip_label_connected_graph[_dev|_host], _graph_last and
+                                     * _graph_last_times) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -126,6 +128,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    never more than the image has work for); results are bit-identical for every value
  *   draw_time        1: visfd_hip_draw_spheres[_dev] times its three phases with events and waits for them
  *                    (visfd_hip_draw_last_times); default 0
+ *   connect_time     1: visfd_hip_label_connected_graph[_dev] time their stages on the host clock and wait for the stream
+ *                    at each (visfd_hip_label_connected_graph_last_times); default 0
  *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
  *                    markers they always do); labels and lists are identical either way; default 0
  *   find_spheres_host 1: visfd_hip_find_spheres[_dev] walk the (query, sphere) pairs on the host (the walk of
@@ -825,6 +829,91 @@ int visfd_hip_label_connected_device_seeds(visfd_hip_ctx*, const float* saliency
                                            const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
                                            const int* must_link_directions);
 int visfd_hip_label_connected_device_seeds_last(visfd_hip_ctx*, int* where, int64_t* n_seeds);
+
+/* LabelConnected AS A GRAPH PROBLEM: a voxel is valid when it is unmasked and passes the saliency, tensor
+ * and vector tests; two valid neighbours are joined when their neighbour tests pass in both directions; a cluster is a
+ * connected component of that graph that holds a valid seed.  The arguments are those of
+ * visfd_hip_label_connected_device_seeds.  What a successful call returns:
+ *   - labels, n_clusters, cluster_maxima, cluster_sizes and cluster_saliencies: the same bits as
+ *     visfd_hip_label_connected_ex on the same inputs (masked voxels get n_seeds + 1, as there);
+ *   - with standardize_directions (and signs ignored), the direction of every voxel that ends up labelled: the same bits
+ *     as after visfd_hip_label_connected_ex;
+ *   - the direction of EVERY OTHER voxel, unlabelled or masked: bit for bit what the caller passed in.  This is where
+ *     these entries differ from the four above: the flood also turns the directions of a halo of unlabelled voxels around
+ *     every cluster, in a way its pop order decides, and the entries above reproduce that; these leave the halo alone.
+ *     Nothing in this library reads those directions.
+ * visfd_hip_label_connected_graph       host arrays; the work runs on the context's device (csrc/connect_graph.hip), except
+ *                                       the vector test, which the host runs over the list of candidates the device compacts
+ * visfd_hip_label_connected_graph_dev   saliency, mask, direction, tensor, labels (and voxel_weights) are device arrays, the
+ *                                       per-cluster outputs host arrays; returns with the stream idle
+ * visfd_hip_label_connected_graph_host  no context and no device: a serial walk of the same definition
+ *                                       (its guard on the outward sum is count * max|term| * 2^-20; the device's is the
+ *                                       looser count * B * 2^-20, B = max (|r_x| + |r_y| + |r_z|) * max|n_d|, so the device
+ *                                       may report OUTWARD where the walk does not; the results agree either way)
+ * Calls whose result the pop order does decide carry a reason (VISFD_HIP_CONNECT_REASON_*): both directed tests of a
+ * pair of valid voxels disagree; an edge's dot product is exactly zero while standardising; a component's signs cannot
+ * be made consistent; must-link constraints; voxel weights; a cluster's outward sum is too near zero for its sign to be
+ * certain; connectivity above 3, an image the device's seed search does not take (VISFD_HIP_EXTREMA_MAX_*), or
+ * 2^31 - 2 voxels or more (the union-find word is (index << 1) | sign).  Such a call is handed to the flood (from the
+ * seeds already found; the _dev face on a staged copy), the labelled results are the flood's, and the directions of the
+ * unlabelled and masked voxels are put back to their input bits, so the contract above holds on every path.
+ * Refused before anything is allocated or copied (VISFD_HIP_EINVAL): what visfd_hip_label_connected_device_seeds refuses.
+ * visfd_hip_label_connected_graph_last: what the context's last successful call did -- path (VISFD_HIP_CONNECT_GRAPH_*; -1
+ * before the first), and, each nullable, the reason bits, the number of valid voxels and the number of candidates the
+ * host's vector test looked at (0 without directions; both -1 where the call was handed over before counting).  With a
+ * null context: the calling thread's last visfd_hip_label_connected_graph_host.
+ * visfd_hip_label_connected_graph_last_times: with the option connect_time, the milliseconds of the last device-path
+ * call by stage: seed search, classify and compact, host vector test, edges and union-find, clusters, directions and
+ * the last pass, copies to the device, copies to the host. */
+#define VISFD_HIP_CONNECT_GRAPH_DEVICE 0
+#define VISFD_HIP_CONNECT_GRAPH_HOST_GRAPH 1
+#define VISFD_HIP_CONNECT_GRAPH_FLOOD 2
+#define VISFD_HIP_CONNECT_REASON_ASYMMETRIC 1
+#define VISFD_HIP_CONNECT_REASON_ZERO_DOT 2
+#define VISFD_HIP_CONNECT_REASON_UNBALANCED 4
+#define VISFD_HIP_CONNECT_REASON_MUST_LINK 8
+#define VISFD_HIP_CONNECT_REASON_WEIGHTS 16
+#define VISFD_HIP_CONNECT_REASON_OUTWARD 32
+#define VISFD_HIP_CONNECT_REASON_LIMITS 64
+int visfd_hip_label_connected_graph(visfd_hip_ctx*, const float* saliency, int64_t* labels, const float* mask,
+                                    int64_t nx, int64_t ny, int64_t nz, float threshold_saliency, float* direction,
+                                    float threshold_vector_saliency, float threshold_vector_neighbor,
+                                    int consider_dot_product_sign, const float* tensor,
+                                    float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                                    int tensor_is_positive_definite_near_target, int connectivity,
+                                    int64_t label_undefined, int sort_by_size, int standardize_directions,
+                                    int start_from_saliency_maxima, int64_t* n_clusters, float* cluster_maxima,
+                                    float* cluster_sizes, float* cluster_saliencies, int64_t cluster_capacity,
+                                    const float* voxel_weights, const float* must_link_crds,
+                                    const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
+                                    const int* must_link_directions);
+int visfd_hip_label_connected_graph_dev(visfd_hip_ctx*, const float* saliency, int64_t* labels, const float* mask,
+                                        int64_t nx, int64_t ny, int64_t nz, float threshold_saliency, float* direction,
+                                        float threshold_vector_saliency, float threshold_vector_neighbor,
+                                        int consider_dot_product_sign, const float* tensor,
+                                        float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                                        int tensor_is_positive_definite_near_target, int connectivity,
+                                        int64_t label_undefined, int sort_by_size, int standardize_directions,
+                                        int start_from_saliency_maxima, int64_t* n_clusters, float* cluster_maxima,
+                                        float* cluster_sizes, float* cluster_saliencies, int64_t cluster_capacity,
+                                        const float* voxel_weights, const float* must_link_crds,
+                                        const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
+                                        const int* must_link_directions);
+int visfd_hip_label_connected_graph_host(const float* saliency, int64_t* labels, const float* mask,
+                                         int64_t nx, int64_t ny, int64_t nz, float threshold_saliency, float* direction,
+                                         float threshold_vector_saliency, float threshold_vector_neighbor,
+                                         int consider_dot_product_sign, const float* tensor,
+                                         float threshold_tensor_saliency, float threshold_tensor_neighbor,
+                                         int tensor_is_positive_definite_near_target, int connectivity,
+                                         int64_t label_undefined, int sort_by_size, int standardize_directions,
+                                         int start_from_saliency_maxima, int64_t* n_clusters, float* cluster_maxima,
+                                         float* cluster_sizes, float* cluster_saliencies, int64_t cluster_capacity,
+                                         const float* voxel_weights, const float* must_link_crds,
+                                         const int64_t* must_link_group_sizes, int64_t must_link_ngroups,
+                                         const int* must_link_directions);
+int visfd_hip_label_connected_graph_last(visfd_hip_ctx*, int* path, unsigned* reasons, int64_t* n_valid,
+                                         int64_t* n_undecided);
+int visfd_hip_label_connected_graph_last_times(visfd_hip_ctx*, float ms[8]);
 
 /* Principal eigenvector (eigenvector row 0 of ConvertFlatSym2Evects3 in the given order) of nvox flat tensors
  * [nvox][6] -> direction [nvox][3], computed on the HOST in the reference's arithmetic (the loop of

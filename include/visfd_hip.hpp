@@ -1377,25 +1377,25 @@ inline void _BlobDogNM(int const image_size[3], float const* const* const* aaafS
 typedef enum eRegionSortCriteria { SORT_BY_VALUE, SORT_BY_SIZE } RegionSortCriteria;
 typedef enum eDirectionPairType { SAME_DIRECTION, OPPOSITE_DIRECTION, AUTO } DirectionPairType;
 
-// Not in the reference: LabelConnected with its seed search on a context's device (visfd_hip_label_connected_device_seeds;
-// the flood stays on the host, the results are the same bits); a null context is the drop-in below.
-inline size_t LabelConnectedDeviceSeeds(
-    visfd_hip_ctx* ctx, const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
+namespace hip_detail {
+// What the three functions below share: the reference's arguments as the flat arrays of the C ABI, and the call.
+inline size_t label_connected_entry(
+    bool graph, visfd_hip_ctx* ctx, const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
     float const* const* const* aaafMask,
-    float threshold_saliency = -std::numeric_limits<float>::infinity(),
-    std::array<float, 3> const* const* const* aaaafVector = nullptr,
-    float threshold_vector_saliency = -std::numeric_limits<float>::infinity(),
-    float threshold_vector_neighbor = -std::numeric_limits<float>::infinity(), bool consider_dot_product_sign = true,
-    float* const* const* const* aaaafSymmetricTensor = nullptr,
-    float threshold_tensor_saliency = -std::numeric_limits<float>::infinity(),
-    float threshold_tensor_neighbor = -std::numeric_limits<float>::infinity(),
-    bool tensor_is_positive_definite_near_target = true, int connectivity = 1, ptrdiff_t label_undefined = -1,
-    std::vector<std::array<float, 3> >* pv_cluster_maxima = nullptr, std::vector<float>* pv_cluster_sizes = nullptr,
-    std::vector<float>* pv_cluster_saliencies = nullptr, RegionSortCriteria sort_criteria = SORT_BY_SIZE,
-    float const* const* const* aaafVoxelWeights = nullptr, std::array<float, 3>*** aaaafVectorStandardized = nullptr,
-    const std::vector<std::vector<std::array<float, 3> > >* pMustLinkConstraints = nullptr,
-    const std::vector<std::vector<DirectionPairType> >* pMustLinkDirections = nullptr,
-    bool start_from_saliency_maxima = true, std::ostream* pReportProgress = nullptr) {
+    float threshold_saliency,
+    std::array<float, 3> const* const* const* aaaafVector,
+    float threshold_vector_saliency,
+    float threshold_vector_neighbor, bool consider_dot_product_sign,
+    float* const* const* const* aaaafSymmetricTensor,
+    float threshold_tensor_saliency,
+    float threshold_tensor_neighbor,
+    bool tensor_is_positive_definite_near_target, int connectivity, ptrdiff_t label_undefined,
+    std::vector<std::array<float, 3> >* pv_cluster_maxima, std::vector<float>* pv_cluster_sizes,
+    std::vector<float>* pv_cluster_saliencies, RegionSortCriteria sort_criteria,
+    float const* const* const* aaafVoxelWeights, std::array<float, 3>*** aaaafVectorStandardized,
+    const std::vector<std::vector<std::array<float, 3> > >* pMustLinkConstraints,
+    const std::vector<std::vector<DirectionPairType> >* pMustLinkDirections,
+    bool start_from_saliency_maxima, std::ostream* pReportProgress) {
   static_assert(sizeof(ptrdiff_t) == sizeof(int64_t), "labels travel as 64-bit integers");
   hip_detail::require_contiguous(aaafSaliency, image_size);
   hip_detail::require_contiguous(aaafVoxelWeights, image_size);
@@ -1446,25 +1446,21 @@ inline size_t LabelConnectedDeviceSeeds(
   const float* const mlc = ml_crds.empty() ? nullptr : ml_crds.data();
   const int64_t* const mls = ml_sizes.empty() ? nullptr : ml_sizes.data();
   const int* const mld = ml_dirs.empty() ? nullptr : ml_dirs.data();
-  const int rc =
-      ctx ? visfd_hip_label_connected_device_seeds(
-                ctx, hip_detail::flat(aaafSaliency), dest, hip_detail::flat(aaafMask), image_size[0], image_size[1],
-                image_size[2], threshold_saliency, dir, threshold_vector_saliency, threshold_vector_neighbor,
-                consider_dot_product_sign ? 1 : 0, aaaafSymmetricTensor ? ten.data() : nullptr, threshold_tensor_saliency,
-                threshold_tensor_neighbor, tensor_is_positive_definite_near_target ? 1 : 0, connectivity,
-                (int64_t)label_undefined, sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0,
-                start_from_saliency_maxima ? 1 : 0, &n_clusters, cm.empty() ? nullptr : cm.data(),
-                cs.empty() ? nullptr : cs.data(), csal.empty() ? nullptr : csal.data(), (int64_t)n, w, mlc, mls,
-                (int64_t)ml_sizes.size(), mld)
-          : visfd_hip_label_connected_ex(
-                hip_detail::flat(aaafSaliency), dest, hip_detail::flat(aaafMask), image_size[0], image_size[1],
-                image_size[2], threshold_saliency, dir, threshold_vector_saliency, threshold_vector_neighbor,
-                consider_dot_product_sign ? 1 : 0, aaaafSymmetricTensor ? ten.data() : nullptr, threshold_tensor_saliency,
-                threshold_tensor_neighbor, tensor_is_positive_definite_near_target ? 1 : 0, connectivity,
-                (int64_t)label_undefined, sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0,
-                start_from_saliency_maxima ? 1 : 0, &n_clusters, cm.empty() ? nullptr : cm.data(),
-                cs.empty() ? nullptr : cs.data(), csal.empty() ? nullptr : csal.data(), (int64_t)n, w, mlc, mls,
-                (int64_t)ml_sizes.size(), mld);
+  // one argument list, four entries: the flood (seeds on the host or on ctx's device) or the graph form (on ctx's device,
+  // or its serial host walk)
+#define VISFD_HIP_LC_ARGS                                                                                                   \
+  hip_detail::flat(aaafSaliency), dest, hip_detail::flat(aaafMask), image_size[0], image_size[1], image_size[2],            \
+      threshold_saliency, dir, threshold_vector_saliency, threshold_vector_neighbor, consider_dot_product_sign ? 1 : 0,     \
+      aaaafSymmetricTensor ? ten.data() : nullptr, threshold_tensor_saliency, threshold_tensor_neighbor,                    \
+      tensor_is_positive_definite_near_target ? 1 : 0, connectivity, (int64_t)label_undefined,                              \
+      sort_criteria == SORT_BY_SIZE ? 1 : 0, aaaafVectorStandardized ? 1 : 0, start_from_saliency_maxima ? 1 : 0,           \
+      &n_clusters, cm.empty() ? nullptr : cm.data(), cs.empty() ? nullptr : cs.data(),                                      \
+      csal.empty() ? nullptr : csal.data(), (int64_t)n, w, mlc, mls, (int64_t)ml_sizes.size(), mld
+  const int rc = graph ? (ctx ? visfd_hip_label_connected_graph(ctx, VISFD_HIP_LC_ARGS)
+                              : visfd_hip_label_connected_graph_host(VISFD_HIP_LC_ARGS))
+                       : (ctx ? visfd_hip_label_connected_device_seeds(ctx, VISFD_HIP_LC_ARGS)
+                              : visfd_hip_label_connected_ex(VISFD_HIP_LC_ARGS));
+#undef VISFD_HIP_LC_ARGS
   hip_detail::check(rc);
   if (pReportProgress) *pReportProgress << "Number of clusters found: " << n_clusters << "\n";
   if (pv_cluster_maxima) {
@@ -1474,6 +1470,65 @@ inline size_t LabelConnectedDeviceSeeds(
   if (pv_cluster_sizes) pv_cluster_sizes->assign(cs.begin(), cs.begin() + n_clusters);
   if (pv_cluster_saliencies) pv_cluster_saliencies->assign(csal.begin(), csal.begin() + n_clusters);
   return (size_t)n_clusters;
+}
+}  // namespace hip_detail
+
+// Not in the reference: LabelConnected with its seed search on a context's device (visfd_hip_label_connected_device_seeds;
+// the flood stays on the host, the results are the same bits); a null context is the drop-in below.
+inline size_t LabelConnectedDeviceSeeds(
+    visfd_hip_ctx* ctx, const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
+    float const* const* const* aaafMask,
+    float threshold_saliency = -std::numeric_limits<float>::infinity(),
+    std::array<float, 3> const* const* const* aaaafVector = nullptr,
+    float threshold_vector_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_vector_neighbor = -std::numeric_limits<float>::infinity(), bool consider_dot_product_sign = true,
+    float* const* const* const* aaaafSymmetricTensor = nullptr,
+    float threshold_tensor_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_tensor_neighbor = -std::numeric_limits<float>::infinity(),
+    bool tensor_is_positive_definite_near_target = true, int connectivity = 1, ptrdiff_t label_undefined = -1,
+    std::vector<std::array<float, 3> >* pv_cluster_maxima = nullptr, std::vector<float>* pv_cluster_sizes = nullptr,
+    std::vector<float>* pv_cluster_saliencies = nullptr, RegionSortCriteria sort_criteria = SORT_BY_SIZE,
+    float const* const* const* aaafVoxelWeights = nullptr, std::array<float, 3>*** aaaafVectorStandardized = nullptr,
+    const std::vector<std::vector<std::array<float, 3> > >* pMustLinkConstraints = nullptr,
+    const std::vector<std::vector<DirectionPairType> >* pMustLinkDirections = nullptr,
+    bool start_from_saliency_maxima = true, std::ostream* pReportProgress = nullptr) {
+  return hip_detail::label_connected_entry(false, ctx, image_size, aaafSaliency, aaaiDest, aaafMask, threshold_saliency, aaaafVector,
+                             threshold_vector_saliency, threshold_vector_neighbor, consider_dot_product_sign,
+                             aaaafSymmetricTensor, threshold_tensor_saliency, threshold_tensor_neighbor,
+                             tensor_is_positive_definite_near_target, connectivity, label_undefined, pv_cluster_maxima,
+                             pv_cluster_sizes, pv_cluster_saliencies, sort_criteria, aaafVoxelWeights,
+                             aaaafVectorStandardized, pMustLinkConstraints, pMustLinkDirections, start_from_saliency_maxima,
+                             pReportProgress);
+}
+
+// Not in the reference: LabelConnected as a graph problem (visfd_hip_label_connected_graph), on a context's
+// device or, with a null context, by the serial host walk.  Labels, lists and the directions of labelled voxels are the
+// drop-in's bits; aaaafVectorStandardized keeps the input's directions at every unlabelled or masked voxel (the drop-in
+// turns a halo of them).  visfd_hip_label_connected_graph_last says which path the call took.
+inline size_t LabelConnectedGraph(
+    visfd_hip_ctx* ctx, const int image_size[3], float const* const* const* aaafSaliency, ptrdiff_t*** aaaiDest,
+    float const* const* const* aaafMask,
+    float threshold_saliency = -std::numeric_limits<float>::infinity(),
+    std::array<float, 3> const* const* const* aaaafVector = nullptr,
+    float threshold_vector_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_vector_neighbor = -std::numeric_limits<float>::infinity(), bool consider_dot_product_sign = true,
+    float* const* const* const* aaaafSymmetricTensor = nullptr,
+    float threshold_tensor_saliency = -std::numeric_limits<float>::infinity(),
+    float threshold_tensor_neighbor = -std::numeric_limits<float>::infinity(),
+    bool tensor_is_positive_definite_near_target = true, int connectivity = 1, ptrdiff_t label_undefined = -1,
+    std::vector<std::array<float, 3> >* pv_cluster_maxima = nullptr, std::vector<float>* pv_cluster_sizes = nullptr,
+    std::vector<float>* pv_cluster_saliencies = nullptr, RegionSortCriteria sort_criteria = SORT_BY_SIZE,
+    float const* const* const* aaafVoxelWeights = nullptr, std::array<float, 3>*** aaaafVectorStandardized = nullptr,
+    const std::vector<std::vector<std::array<float, 3> > >* pMustLinkConstraints = nullptr,
+    const std::vector<std::vector<DirectionPairType> >* pMustLinkDirections = nullptr,
+    bool start_from_saliency_maxima = true, std::ostream* pReportProgress = nullptr) {
+  return hip_detail::label_connected_entry(true, ctx, image_size, aaafSaliency, aaaiDest, aaafMask, threshold_saliency, aaaafVector,
+                             threshold_vector_saliency, threshold_vector_neighbor, consider_dot_product_sign,
+                             aaaafSymmetricTensor, threshold_tensor_saliency, threshold_tensor_neighbor,
+                             tensor_is_positive_definite_near_target, connectivity, label_undefined, pv_cluster_maxima,
+                             pv_cluster_sizes, pv_cluster_saliencies, sort_criteria, aaafVoxelWeights,
+                             aaaafVectorStandardized, pMustLinkConstraints, pMustLinkDirections, start_from_saliency_maxima,
+                             pReportProgress);
 }
 
 // the reference's signature: everything on the host, no GPU needed

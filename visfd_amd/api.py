@@ -109,6 +109,10 @@ _WATERSHED = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, C.c_int, C.c_
 # ctx, src, mask, nx, ny, nz, lo, hi, points (host int32 triples), npoints, dsq
 _DIST_SQ = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, _vp, _i64, _vp]
 
+_LABEL_CONNECTED_EX = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float, C.c_float, C.c_int, _vp, C.c_float, C.c_float,
+                       C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                       _i64, _vp]   # visfd_hip_label_connected_ex
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -258,6 +262,13 @@ _SIGS = {
                                                          C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp,
                                                          _vp, _vp, _i64, _vp]),
     "visfd_hip_label_connected_device_seeds_last": (C.c_int, [_vp, _ip, C.POINTER(_i64)]),
+    # LabelConnected as a graph problem (csrc/connect_graph.hip, connect_graph_host.cpp): the _ex arguments, after the context
+    # where there is one
+    "visfd_hip_label_connected_graph": (C.c_int, [_vp] + _LABEL_CONNECTED_EX),
+    "visfd_hip_label_connected_graph_dev": (C.c_int, [_vp] + _LABEL_CONNECTED_EX),
+    "visfd_hip_label_connected_graph_host": (C.c_int, list(_LABEL_CONNECTED_EX)),
+    "visfd_hip_label_connected_graph_last": (C.c_int, [_vp, _ip, C.POINTER(C.c_uint), C.POINTER(_i64), C.POINTER(_i64)]),
+    "visfd_hip_label_connected_graph_last_times": (C.c_int, [_vp, _fp]),
     "visfd_hip_principal_directions_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_tensor_saliency_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_diagonalize_sym3_f32_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -656,6 +667,56 @@ def label_connected(saliency, threshold_saliency, mask=None, direction=None, ten
         _chk_host(L, L.visfd_hip_label_connected_device_seeds(seeds_ctx._h, *args))
     k = n.value
     return labels, k, cm[:k], cs[:k], csal[:k]
+
+
+# visfd_hip_label_connected_graph_last: the path a graph call took, and why a call was handed to the flood
+CONNECT_GRAPH_DEVICE, CONNECT_GRAPH_HOST_GRAPH, CONNECT_GRAPH_FLOOD = 0, 1, 2
+(CONNECT_REASON_ASYMMETRIC, CONNECT_REASON_ZERO_DOT, CONNECT_REASON_UNBALANCED, CONNECT_REASON_MUST_LINK,
+ CONNECT_REASON_WEIGHTS, CONNECT_REASON_OUTWARD, CONNECT_REASON_LIMITS) = (1 << k for k in range(7))
+
+
+def label_connected_graph(saliency, threshold_saliency, mask=None, direction=None, tensor=None,
+                          threshold_vector_saliency=-np.inf, threshold_vector_neighbor=-np.inf, consider_dot_product_sign=True,
+                          threshold_tensor_saliency=-np.inf, threshold_tensor_neighbor=-np.inf,
+                          tensor_is_positive_definite_near_target=True, connectivity=1, label_undefined=-1, sort_by_size=True,
+                          standardize_directions=False, start_from_saliency_maxima=True, voxel_weights=None, must_link=None,
+                          must_link_directions=None, ctx=None):
+    """label_connected as a graph problem (include/visfd_hip.h: visfd_hip_label_connected_graph): the same labels, lists
+    and directions of labelled voxels, bit for bit; the directions of unlabelled and masked voxels stay as they came in.
+    numpy arrays.  ctx (a Context): the work runs on its device (Context.label_connected_graph_last says what it did);
+    None: the serial host walk (label_connected_graph_last() without a context)."""
+    L = load_library()
+    nz, ny, nx = saliency.shape
+    labels = np.empty((nz, ny, nx), np.int64)
+    n = _i64(0)
+    cap = int(saliency.size)
+    cm, cs, csal = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    for a in (direction, tensor):
+        assert a is None or (a.dtype == np.float32 and a.flags["C_CONTIGUOUS"])
+    ml_c, ml_n, ml_d, ngroups = _must_link_arrays(must_link, must_link_directions)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    args = (_np(saliency), labels.ctypes.data, _np(mask), nx, ny, nz, threshold_saliency, ptr(direction),
+            threshold_vector_saliency, threshold_vector_neighbor, int(bool(consider_dot_product_sign)), ptr(tensor),
+            threshold_tensor_saliency, threshold_tensor_neighbor, int(bool(tensor_is_positive_definite_near_target)),
+            int(connectivity), int(label_undefined), int(bool(sort_by_size)), int(bool(standardize_directions)),
+            int(bool(start_from_saliency_maxima)), C.byref(n), cm.ctypes.data, cs.ctypes.data, csal.ctypes.data, cap,
+            _np(voxel_weights), ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d))
+    if ctx is None:
+        _chk_host(L, L.visfd_hip_label_connected_graph_host(*args))
+    else:
+        _chk_host(L, L.visfd_hip_label_connected_graph(ctx._h, *args))
+    k = n.value
+    return labels, k, cm[:k], cs[:k], csal[:k]
+
+
+def label_connected_graph_last(ctx=None):
+    """(path, reasons, valid voxels, candidates of the host's vector test) of the context's last graph call, or of this
+    thread's last host walk: CONNECT_GRAPH_* and CONNECT_REASON_* bits."""
+    L = load_library()
+    p, r, v, u = C.c_int(-1), C.c_uint(0), _i64(-1), _i64(-1)
+    _chk_host(L, L.visfd_hip_label_connected_graph_last(None if ctx is None else ctx._h, C.byref(p), C.byref(r), C.byref(v),
+                                                        C.byref(u)))
+    return p.value, r.value, v.value, u.value
 
 
 def tensor_saliency_host(tensor, order, sal_inout, mask=None):
@@ -1321,6 +1382,49 @@ class Context:
         p, n = C.c_int(), _i64()
         self._chk(self._L.visfd_hip_label_connected_device_seeds_last(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def label_connected_graph(self, saliency, threshold_saliency, **kw):
+        """api.label_connected_graph on this context's device (numpy arrays)."""
+        return label_connected_graph(saliency, threshold_saliency, ctx=self, **kw)
+
+    def label_connected_graph_dev(self, saliency, labels, threshold_saliency, mask=None, direction=None, tensor=None,
+                                  threshold_vector_saliency=-np.inf, threshold_vector_neighbor=-np.inf,
+                                  consider_dot_product_sign=True, threshold_tensor_saliency=-np.inf,
+                                  threshold_tensor_neighbor=-np.inf, tensor_is_positive_definite_near_target=True,
+                                  connectivity=1, label_undefined=-1, sort_by_size=True, standardize_directions=False,
+                                  start_from_saliency_maxima=True, voxel_weights=None, must_link=None,
+                                  must_link_directions=None):
+        """label_connected_graph on device tensors: saliency, mask, voxel_weights float32 [nz,ny,nx], direction [...,3]
+        (rewritten in place at labelled voxels when standardising), tensor [...,6], labels int64 [nz,ny,nx] (written).
+        Returns (n_clusters, seed positions, sizes, seed saliencies) as numpy arrays."""
+        nz, ny, nx = saliency.shape
+        n = _i64(0)
+        cap = int(saliency.numel())
+        cm, cs, csal = np.zeros((cap, 3), np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        ml_c, ml_n, ml_d, ngroups = _must_link_arrays(must_link, must_link_directions)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        assert labels.is_cuda and labels.is_contiguous() and str(labels.dtype) == "torch.int64" and \
+            tuple(labels.shape) == tuple(saliency.shape), "labels: contiguous cuda int64 of the image's shape"
+        self._chk(self._L.visfd_hip_label_connected_graph_dev(
+            self._h, _dev(saliency), labels.data_ptr(), _dev(mask), nx, ny, nz, threshold_saliency, _dev(direction),
+            threshold_vector_saliency, threshold_vector_neighbor, int(bool(consider_dot_product_sign)), _dev(tensor),
+            threshold_tensor_saliency, threshold_tensor_neighbor, int(bool(tensor_is_positive_definite_near_target)),
+            int(connectivity), int(label_undefined), int(bool(sort_by_size)), int(bool(standardize_directions)),
+            int(bool(start_from_saliency_maxima)), C.byref(n), cm.ctypes.data, cs.ctypes.data, csal.ctypes.data, cap,
+            _dev(voxel_weights), ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d)))
+        k = n.value
+        return k, cm[:k], cs[:k], csal[:k]
+
+    def label_connected_graph_last(self):
+        """(path, reasons, valid voxels, candidates of the host's vector test) of the context's last graph call."""
+        return label_connected_graph_last(self)
+
+    def label_connected_graph_last_times(self):
+        """Under the option connect_time: milliseconds of the last device-path graph call by stage (seed search, classify,
+        host vector test, edges, clusters, directions, copies in, copies out)."""
+        ms = (C.c_float * 8)()
+        self._chk(self._L.visfd_hip_label_connected_graph_last_times(self._h, ms))
+        return tuple(ms)
 
     def watershed_last_stats(self):
         """(path, label rounds, boundary rounds, basins) of the last watershed call; path WATERSHED_PATH_HOST or _DEVICE."""

@@ -78,6 +78,13 @@ enum Slot {
   WS_DIST_POINTS,                  // distance maps: the listed points that can matter; query points and their results
   WS_FS_RECORDS,                   // FindSpheres: one 16-byte record (cx, cy, cz, Rsqr) per sphere, padded to whole passes (csrc/find_spheres.hip)
   WS_FS_QUERIES,                   // FindSpheres: the truncated queries, padded to whole batches, and the flag word of the two preparation launches
+  WS_CG_WORD,                      // LabelConnected as a graph (csrc/connect_graph.hip): the parity union-find word of every voxel (uint32)
+  WS_CG_AUX,                       // ... per voxel, meaningful at roots: the lowest seed rank, then the cluster number and the anchor's sign (int32)
+  WS_CG_LIST,                      // ... the listed voxels' indices, then their cluster number and sign (2 x int32 per entry)
+  WS_CG_REC,                       // ... the listed voxels' Hessians and directions for the host's vector test (9 floats per entry), then its bits
+  WS_CG_SEEDS,                     // ... the ranked seeds, their roots, signs and numbers (4 x int32 per seed)
+  WS_CG_CLUSTER,                   // ... per cluster: size, coordinate sums, centre of mass, outward sum, final label, bound (10 x 8 bytes)
+  WS_CG_COUNTERS,                  // ... the two list lengths and the reason flags
   WS_NSLOTS
 };
 
@@ -115,6 +122,7 @@ struct visfd_hip_options {
   int find_spheres_host = 0; // 1: FindSpheres walks the pairs on the host (csrc/find_spheres.hip), never launches the search kernel
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
+  int connect_time = 0;     // 1: visfd_hip_label_connected_graph[_dev] time their stages on the host clock and wait for each (tools/connect_graph_time.py)
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
 };
@@ -146,6 +154,8 @@ struct visfd_hip_ctx {
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
+  int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test
+  float connect_graph_ms[8] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // option connect_time: its stages (csrc/connect_graph.hip: MS_*)
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };
 

@@ -6,7 +6,9 @@
 // This is a sequential priority-flood (Meyer) in the reference and stays on the host here.  Labels, lists and the
 // directions of labelled voxels do not in fact depend on the pop order, the directions the flood leaves on unlabelled
 // voxels do (tests/connect_graph_np.py); the seed search has no order in it and visfd_hip_label_connected_device_seeds
-// (connect_seeds.hip) runs it on the device.  What is reproduced exactly, because the labels depend on it:
+// (connect_seeds.hip) runs it on the device; the entries that compute all but those halo directions as a graph problem,
+// on the device or by a serial walk, are in connect_graph.hip / connect_graph_host.cpp and hand the calls the pop order
+// does decide back to the flood below.  What is reproduced exactly, because the labels depend on it:
 //   * seeds: local maxima (or minima) of the saliency including plateaus, found in scan order,
 //     kept if they pass the threshold, ranked by (score, scan rank) -- descending = the exact reverse
 //     of the ascending ranking;
@@ -154,6 +156,15 @@ int vh::label_connected_check_args(const float* saliency, const int64_t* labels,
     return vh::fail(VISFD_HIP_EINVAL, "label_connected: image too large");
   if (connectivity < 1) return vh::fail(VISFD_HIP_EINVAL, "label_connected: connectivity must be >= 1");
   return VISFD_HIP_OK;
+}
+
+// connect_graph_host.cpp's host walk starts from the same ranked seeds
+void vh::host_find_seeds(const float* saliency, const float* mask, int64_t nx, int64_t ny, int64_t nz, bool seek_minima,
+                         float threshold, int connectivity, std::vector<int>* index, std::vector<float>* score) {
+  const Grid g = {(int)nx, (int)ny, (int)nz};
+  std::vector<i64> found;
+  find_extrema(g, saliency, mask, seek_minima, threshold, neighbour_offsets(connectivity), &found, score);
+  index->assign(found.begin(), found.end());
 }
 
 // The flood.  given_index / given_score (both or neither): the ranked seed list, found elsewhere (csrc/connect_seeds.hip finds
@@ -505,20 +516,7 @@ extern "C" int visfd_hip_label_connected(const float* saliency, int64_t* labels,
                                       cluster_sizes, cluster_saliencies, cluster_capacity, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
-namespace {
-template <typename F>
-void parallel_voxels(int64_t nvox, F work) {
-  unsigned nt = std::thread::hardware_concurrency();
-  if (nt < 1) nt = 1;
-  if ((int64_t)nt > nvox / 4096 + 1) nt = (unsigned)(nvox / 4096 + 1);
-  std::vector<std::thread> pool;
-  const int64_t chunk = (nvox + nt - 1) / nt;
-  for (unsigned t = 1; t < nt; t++)
-    pool.emplace_back(work, std::min<int64_t>(nvox, t * chunk), std::min<int64_t>(nvox, (t + 1) * chunk));
-  work(0, std::min<int64_t>(nvox, chunk));
-  for (size_t t = 0; t < pool.size(); t++) pool[t].join();
-}
-}  // namespace
+using vh::parallel_voxels;
 
 // Post-vote score lambda0 - lambda1 (handlers.cpp:1868-1888) of nvox flat tensors [nvox][6], on the HOST in the
 // reference's arithmetic: the clustering that follows orders and thresholds voxels by this number, so the

@@ -1,7 +1,9 @@
 // connect_host.hpp -- the sequential flood of LabelConnected (connect.cpp) as connect_seeds.hip calls it.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <thread>
 #include <vector>
 
 namespace vh {
@@ -23,5 +25,24 @@ int host_label_connected(const float* saliency, int64_t* labels, const float* ma
                          int64_t cluster_capacity, const float* voxel_weights, const float* must_link_crds,
                          const int64_t* must_link_group_sizes, int64_t must_link_ngroups, const int* must_link_directions,
                          const std::vector<int>* given_index, const std::vector<float>* given_score);
+
+// the ranked seed list the flood would search for itself (plateau-aware extrema that pass the threshold)
+void host_find_seeds(const float* saliency, const float* mask, int64_t nx, int64_t ny, int64_t nz, bool seek_minima,
+                     float threshold, int connectivity, std::vector<int>* index, std::vector<float>* score);
+
+// work(lo, hi) over [0, nvox) split across the host's cores, 16 threads at the most (independent voxels only)
+template <typename F>
+void parallel_voxels(int64_t nvox, F work) {
+  unsigned nt = std::thread::hardware_concurrency();
+  if (nt < 1) nt = 1;
+  if (nt > 16) nt = 16;
+  if ((int64_t)nt > nvox / 4096 + 1) nt = (unsigned)(nvox / 4096 + 1);
+  std::vector<std::thread> pool;
+  const int64_t chunk = (nvox + nt - 1) / nt;
+  for (unsigned t = 1; t < nt; t++)
+    pool.emplace_back(work, std::min<int64_t>(nvox, t * chunk), std::min<int64_t>(nvox, (t + 1) * chunk));
+  work(0, std::min<int64_t>(nvox, chunk));
+  for (size_t t = 0; t < pool.size(); t++) pool[t].join();
+}
 
 }  // namespace vh

@@ -55,6 +55,7 @@ const OptionDesc kOptions[] = {
     {"median_general", &visfd_hip_options::median_general, nullptr},
     {"distance_general", &visfd_hip_options::distance_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
+    {"connect_time", &visfd_hip_options::connect_time, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
     {"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr},

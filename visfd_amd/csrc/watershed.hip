@@ -439,6 +439,11 @@ int watershed_check_args(const WatershedArgs& a) {
   VH_REQUIRE(a.basin_cap >= 0, "watershed: negative list capacity");
   VH_REQUIRE(a.n_basins, "watershed: no place for the number of basins");
   const size_t nv = (size_t)(a.nx * a.ny * a.nz);
+  // the array that labels starts in is named first: a pointer aimed into one array may also run on into whatever the
+  // allocator put behind it, and the message must not depend on where the arrays lie; then the order is src, mask, markers
+  VH_REQUIRE(!overlap_bytes(a.labels, 1, a.src, 4 * nv), "watershed: labels overlap src");
+  VH_REQUIRE(!overlap_bytes(a.labels, 1, a.mask, 4 * nv), "watershed: labels overlap mask");
+  VH_REQUIRE(!overlap_bytes(a.labels, 1, a.markers, 4 * nv), "watershed: labels overlap markers");
   VH_REQUIRE(!overlap_bytes(a.labels, 4 * nv, a.src, 4 * nv), "watershed: labels overlap src");
   VH_REQUIRE(!overlap_bytes(a.labels, 4 * nv, a.mask, 4 * nv), "watershed: labels overlap mask");
   VH_REQUIRE(!overlap_bytes(a.labels, 4 * nv, a.markers, 4 * nv), "watershed: labels overlap markers");
