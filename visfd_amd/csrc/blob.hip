@@ -8,18 +8,20 @@
 // bit-for-bit whenever the three LoG volumes do.
 //
 // Two kernels:
-//   1. candidates: an HBM sweep of the MIDDLE volume only (4 B/voxel).  A workgroup owns a 64 x 8
-//      column tile and marches along z four planes at a time (the next four already requested); each
-//      plane goes through an LDS tile with a one-voxel halo,
-//      each thread takes the min and max of its 3x3 neighbourhood, and a three-plane register ring
+//   1. candidates: an HBM sweep of the MIDDLE volume only (4 B/voxel).  A wave owns 62 columns by 4 rows and marches
+//      along z on its own (three planes requested ahead, no barrier, no LDS tile): the min and max of x-1, x, x+1 come
+//      from the neighbouring lanes, three rows fold into the 3x3 values, and a three-plane register ring
 //      gives the 3x3x3 box min/max.  A voxel is a candidate when it equals the box min (or max)
 //      and passes the sign/threshold tests -- a non-strict superset of the 26-neighbour rule.
+//      (The form before it staged 64 x 8 tiles in LDS, four planes per step behind two workgroup barriers, and ran at
+//      3.1 TB/s with a third of its waves' time spent at those barriers and in the flush: profiles/blob_stall_stamps.txt.)
 //   2. verify: one thread per candidate repeats the reference's exact test on all 80 neighbours
 //      (strict comparisons, masks) and appends the survivors.
 // LoG volumes are smooth, so candidates are a small fraction of the voxels and kernel 2 is cheap.
 #include <algorithm>
 #include <cstdlib>
 #include <limits>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -27,13 +29,20 @@ namespace vh {
 
 namespace {
 
-constexpr int BLOCK = 512;
-constexpr int TX = 64, TY = 8;          // one voxel column per thread
-constexpr int PZ = 4;                   // planes staged per step (and between flushes of the candidate buffer)
-constexpr int BUFCAP = 2 * PZ * BLOCK;  // candidate buffer (32-bit tile-relative codes): flushed when a step might not fit
-constexpr int LW = TX + 2, LH = TY + 2; // LDS tile with halo
+constexpr int BLOCK = 512;              // threads per workgroup of both kernels
+constexpr int SWV = BLOCK / 64;         // candidate sweep: waves per workgroup, stacked in y; no wave ever waits for another
+constexpr int SOX = 62;                 // output columns per wave (lanes 1..62; lanes 0 and 63 hold the x halo)
+constexpr int SR = 4;                   // output rows per wave: SR + 2 rows are loaded per plane
+constexpr int SPF = 3;                  // planes requested ahead (a multiple of 3: the plane ring is indexed statically)
+constexpr int WCAP = 2 * SR * 64;       // candidate indices a wave parks in LDS between two flushes: a step's fit behind the mark
+static_assert(SPF % 3 == 0, "the plane ring is indexed statically");
 
-static_assert(BLOCK == 512 && TX == 64, "candidate codes pack the thread index in 9 bits");
+#ifdef VH_BLOB_STAMPS   // development build (tools/build_variant.py only): where a wave of the candidate sweep spends its time
+__device__ unsigned long long g_blob_stamps[8];
+#define VH_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_last; st_last = t_; } while (0)
+#else
+#define VH_STAMP(i) do { } while (0)
+#endif
 
 struct Cand {
   int ix, iy, iz;
@@ -41,153 +50,164 @@ struct Cand {
   float score;
 };
 
-__global__ void __launch_bounds__(BLOCK)
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, E>(f);
+  }
+}
+
+// the value of the lane below / above (DPP wave shifts; what lane 0 / lane 63 receive is never used)
+__device__ __forceinline__ float lane_below(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float lane_above(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
+}
+
+// A WAVE owns SOX columns by SR rows and marches along z on its own, as the Z march of csrc/gauss_pair.hip does: no barrier
+// and no LDS tile.  Per plane it loads its SR + 2 rows (64 columns: the outputs and one halo column on either side), takes
+// the row-wise min and max of x-1, x, x+1 from its neighbouring lanes, folds three rows into the 3x3 values and keeps those
+// of three planes in a register ring.  The eight waves of a workgroup are stacked in y, so the rows two of them share are
+// requested on the same CU at about the same time.  Candidates (linear voxel indices) are parked in the wave's own LDS
+// strip, counted in a scalar (ballots: no LDS atomic), and written out with ONE global atomic per flush: every wave of the
+// grid adds to the same counter, and atomics on one address are served one at a time by L2.
+__global__ void __launch_bounds__(BLOCK, 6)   // six waves per SIMD: three workgroups per CU
 blob_candidates_kernel(const float* __restrict__ mid, const float* __restrict__ mask, int nx, int ny, int nz,
                        float min_thr, float max_thr, int zchunk, int tiles_x, int tiles_y,
                        unsigned long long* __restrict__ out, unsigned long long capacity,
                        unsigned long long* __restrict__ counter) {
-  constexpr int NLD = (LH * LW + BLOCK - 1) / BLOCK;
-  __shared__ float tile[PZ][NLD * BLOCK];   // (LH * LW used; padded so that every thread's stores are unconditional)
-  // candidates are collected per workgroup and written out with ONE global atomic per flush
-  __shared__ unsigned int buf[BUFCAP];   // (z - zs) << 9 | thread index: one voxel of this workgroup's column
-  __shared__ unsigned int buf_n;
-  __shared__ unsigned long long buf_base;
-  if (threadIdx.x == 0) buf_n = 0;
+  __shared__ unsigned long long buf[SWV][WCAP];
   unsigned b = blockIdx.x;
   const int tile_x = b % tiles_x;
   b /= tiles_x;
   const int tile_y = b % tiles_y;
   const int chunk = b / tiles_y;
-  const int x0 = tile_x * TX, y0 = tile_y * TY;
   const int zs = max(1, chunk * zchunk), ze = min(nz - 1, (chunk + 1) * zchunk);  // interior planes only
   if (zs >= ze) return;
-  const int tid = threadIdx.x;
-  const int lx = tid & (TX - 1), ly = tid >> 6;
-  const int gx = x0 + lx, gy = y0 + ly;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gx = tile_x * SOX + lane;                 // lane 0: the halo column left of the first output (x >= 0)
+  const int yb = tile_y * (SWV * SR) + wave * SR;     // the halo row above this wave's first output row
+  if (yb + 1 > ny - 2) return;                        // no interior row (no barrier in this kernel)
+#ifdef VH_BLOB_STAMPS
+  unsigned long long st_acc[4] = {0, 0, 0, 0};
+  unsigned long long st_last = __builtin_amdgcn_s_memtime();
+#endif
   const i64 plane = (i64)nx * ny;
-  const bool interior = gx >= 1 && gx <= nx - 2 && gy >= 1 && gy <= ny - 2;
+  const bool col_ok = lane >= 1 && lane <= SOX && gx <= nx - 2;   // an interior column that this wave reports
+  unsigned long long* const wbuf = buf[wave];
 
-  // cooperative load of one haloed plane (values outside the image are irrelevant: they only influence
-  // face voxels, which can never be blobs, feature.hpp:245-252).  Split in two so that the global loads
-  // of plane z+2 are in flight while plane z+1 is being compared (the march is latency-bound otherwise):
-  // fetch() reads this thread's (up to NLD) tile elements into registers, stash() writes them to LDS.
-  // Raw buffer loads through one descriptor per plane (planes below 2 GiB: the host checks): an element outside the image
-  // or the tile has an out-of-range offset, a plane outside the volume a zero-length descriptor -- the hardware returns
-  // 0.0 and the loads need no branches.  (Conditional loads are each closed by a full s_waitcnt at their join: the eight
-  // loads of a step then went out in three or four dependent groups, and the sweep ran at memory latency.)
-  unsigned ld_off[NLD];   // BYTE offset inside a plane
+  // Raw buffer loads through one descriptor per plane (planes below 2 GiB: the host checks), the lane's column in the
+  // vector offset and the row in the scalar one.  Every load is inside the volume and none sits in a branch (a conditional
+  // load is closed by a full s_waitcnt at its join): a column or row past the image is clamped to the last one, a plane past
+  // the chunk to plane ze.  What a clamped load returns only reaches face voxels and voxels outside the image, which are
+  // never reported (feature.hpp:245-252).
+  const int col_off = min(gx, nx - 1) * 4;   // BYTE offsets inside a plane
+  int row_off[SR + 2];
 #pragma unroll
-  for (int k = 0; k < NLD; k++) {
-    const int i = tid + k * BLOCK;
-    const int r = i / LW, c = i - r * LW;
-    const int sx = x0 - 1 + c, sy = y0 - 1 + r;
-    ld_off[k] = (i < LH * LW && sx >= 0 && sx < nx && sy >= 0 && sy < ny) ? (unsigned)(sy * nx + sx) * 4u : 0x7ffffff0u;
-  }
+  for (int r = 0; r < SR + 2; r++) row_off[r] = min(yb + r, ny - 1) * nx * 4;
   const int plane_bytes = (int)(plane * 4);
-  auto fetch = [&](int z, float v[NLD]) {
-    const bool zin = z < nz;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(mid + (zin ? (i64)z * plane : 0)), 0,
-                                                                        zin ? plane_bytes : 0, 0x00020000);
+  auto fetch = [&](int z, float (&v)[SR + 2]) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(mid + (i64)min(z, ze) * plane), 0, plane_bytes,
+                                                                        0x00020000);
 #pragma unroll
-    for (int k = 0; k < NLD; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)ld_off[k], 0, 0));
+    for (int r = 0; r < SR + 2; r++) v[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, col_off, row_off[r], 0));
   };
-  auto stash = [&](const float v[NLD], float* dst) {
-#pragma unroll
-    for (int k = 0; k < NLD; k++) dst[tid + k * BLOCK] = v[k];
-  };
-  // min and max over the 3x3 neighbourhood of (lx, ly) in an LDS plane, plus the centre value
-  auto minmax9 = [&](const float* t, float& mn, float& mx, float& centre) {
-    const float* p0 = t + ly * LW + lx;  // top-left of the 3x3 window (halo offset 1 folded in)
-    float a = p0[0], bb = p0[1], c = p0[2];
-    mn = fminf(fminf(a, bb), c); mx = fmaxf(fmaxf(a, bb), c);
-    a = p0[LW]; bb = p0[LW + 1]; c = p0[LW + 2];
-    centre = bb;
-    mn = fminf(mn, fminf(fminf(a, bb), c)); mx = fmaxf(mx, fmaxf(fmaxf(a, bb), c));
-    a = p0[2 * LW]; bb = p0[2 * LW + 1]; c = p0[2 * LW + 2];
-    mn = fminf(mn, fminf(fminf(a, bb), c)); mx = fmaxf(mx, fmaxf(fmaxf(a, bb), c));
+  const int p0 = (yb + 1) * nx + gx;   // in-plane index of this lane's first output
+  unsigned cnt = 0;   // candidates parked in wbuf: uniform
+  auto flush = [&]() {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(counter, (unsigned long long)cnt);
+    base = __shfl(base, 0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // the wave's LDS instructions complete in order: its appends are visible to all its lanes
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (unsigned i = lane; i < cnt; i += 64)
+      if (base + i < capacity) out[base + i] = wbuf[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    cnt = 0;
   };
 
-  // March in steps of PZ planes: the PZ planes after the current one are staged in LDS together (one barrier
-  // per step instead of one per plane) while the global loads of the following PZ planes are already in
-  // flight in registers, so the HBM latency is covered by PZ planes of comparisons.
-  float mn_prev, mx_prev, c_prev, mn_cur, mx_cur, c_cur;
-  // TWO steps of planes in flight, in two register sets used alternately (a step's loads are requested two steps before
-  // they are stashed: one step of comparisons does not cover a loaded HBM round trip)
-  float preA[PZ][NLD], preB[PZ][NLD];
-  fetch(zs - 1, preA[0]);
-  fetch(zs, preA[1]);
-  stash(preA[0], tile[0]);
-  stash(preA[1], tile[1]);
+  // 3x3 min / max and the centre value of three planes: slot t % 3 takes the plane that arrives at step t
+  float m9n[3][SR], m9x[3][SR], ctr[3][SR];
 #pragma unroll
-  for (int k = 0; k < PZ; k++) fetch(zs + 1 + k, preA[k]);
+  for (int k = 0; k < 3; k++)
 #pragma unroll
-  for (int k = 0; k < PZ; k++) fetch(zs + PZ + 1 + k, preB[k]);
-  __syncthreads();
-  minmax9(tile[0], mn_prev, mx_prev, c_prev);
-  minmax9(tile[1], mn_cur, mx_cur, c_cur);
-  __syncthreads();   // both tiles free again
-  // one step: planes z0 .. z0+PZ-1 are compared; `pre` holds planes z0+1 .. z0+PZ and is refilled with z0+2PZ+1 ..
-  auto step = [&](float (&pre)[PZ][NLD], int z0) {
+    for (int j = 0; j < SR; j++) m9n[k][j] = m9x[k][j] = ctr[k][j] = 0.0f;
+  float q[SPF][SR + 2];
 #pragma unroll
-    for (int k = 0; k < PZ; k++) stash(pre[k], tile[k]);                      // planes z0+1 .. z0+PZ
+  for (int i = 0; i < SPF; i++) {
+    fetch(zs - 1 + i, q[i]);
+    __builtin_amdgcn_sched_barrier(0);   // oldest plane first: the wait counts of the loop are those of its entry as well
+  }
+  const int nsteps = ze - zs + 2;   // planes zs-1 .. ze arrive; the step count is rounded up to whole turns of the queue
+  VH_STAMP(0);
+#pragma nounroll
+  for (int nb = 0; nb < nsteps; nb += SPF) {
+    static_for<0, SPF>([&](auto U) {
+      constexpr int u = decltype(U)::value;
+      constexpr int nxt = u % 3, cur = (u + 2) % 3, prv = (u + 1) % 3;
+      const int t = nb + u;   // plane zs - 1 + t arrives; plane z = zs + t - 2 is decided
+      float hn[SR + 2], hx[SR + 2], hc[SR + 2];
 #pragma unroll
-    for (int k = 0; k < PZ; k++) fetch(z0 + 2 * PZ + 1 + k, pre[k]);          // the planes of the step after the next
-    __syncthreads();
+      for (int r = 0; r < SR + 2; r++) {
+        const float v = q[u][r], lo = lane_below(v), hi = lane_above(v);
+        hn[r] = fminf(fminf(lo, v), hi);
+        hx[r] = fmaxf(fmaxf(lo, v), hi);
+        hc[r] = v;
+      }
+      // the requests stay BEHIND the last use of the values they replace: hoisted above it, they land in other registers
+      // and are copied into place at the loop's end, behind a wait for all of them
+      __builtin_amdgcn_sched_barrier(0);
+      fetch(zs - 1 + t + SPF, q[u]);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int k = 0; k < PZ; k++) {
-      const int z = z0 + k;
-      if (z < ze) {   // uniform
-        float mn_nxt, mx_nxt, c_nxt;
-        minmax9(tile[k], mn_nxt, mx_nxt, c_nxt);
-        const float e = c_cur;
-        const float bmin = fminf(fminf(mn_prev, mn_cur), mn_nxt);
-        const float bmax = fmaxf(fmaxf(mx_prev, mx_cur), mx_nxt);
-        const bool is_min = (e == bmin) && (e < 0.0f) && (e < min_thr);
-        const bool is_max = (e == bmax) && (e > 0.0f) && (e > max_thr);
-        {  // append with ONE LDS atomic per wave (ballot + prefix count) instead of one per candidate
-          const i64 v = (i64)z * plane + (i64)gy * nx + gx;
-          bool cand = interior && (is_min || is_max);
+      for (int j = 0; j < SR; j++) {
+        m9n[nxt][j] = fminf(fminf(hn[j], hn[j + 1]), hn[j + 2]);
+        m9x[nxt][j] = fmaxf(fmaxf(hx[j], hx[j + 1]), hx[j + 2]);
+        // a copy of its own: left in the register it was loaded into, the centre value outlives the queue slot by two steps
+        // and every slot's loads are moved into place at the loop's end, behind a wait for all of them
+        asm volatile("v_mov_b32 %0, %1" : "=v"(ctr[nxt][j]) : "v"(hc[j + 1]));
+      }
+      VH_STAMP(1);
+      const int z = zs + t - 2;
+      if (t >= 2 && z < ze) {   // uniform
+#pragma unroll
+        for (int j = 0; j < SR; j++) {
+          const int gy = yb + 1 + j;
+          const float e = ctr[cur][j];
+          const float bmin = fminf(fminf(m9n[prv][j], m9n[cur][j]), m9n[nxt][j]);
+          const float bmax = fmaxf(fmaxf(m9x[prv][j], m9x[cur][j]), m9x[nxt][j]);
+          const bool is_min = (e == bmin) && (e < 0.0f) && (e < min_thr);
+          const bool is_max = (e == bmax) && (e > 0.0f) && (e > max_thr);
+          const i64 v = (i64)z * plane + (p0 + j * nx);
+          bool cand = col_ok && gy <= ny - 2 && (is_min || is_max);
           if (cand && mask && mask[v] == 0.0f) cand = false;
           const unsigned long long bal = __ballot(cand);
-          if (bal != 0ull) {
-            const int lane = tid & 63;
-            const int leader = __ffsll((long long)bal) - 1;
-            unsigned int base = 0;
-            if (lane == leader) base = atomicAdd(&buf_n, (unsigned int)__popcll(bal));
-            base = (unsigned int)__shfl((int)base, leader);
-            if (cand) buf[base + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull))] = ((unsigned int)(z - zs) << 9) | (unsigned int)tid;
+          if (bal != 0ull) {   // uniform
+            if (cand) wbuf[cnt + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = (unsigned long long)v;
+            cnt += (unsigned)__popcll(bal);
           }
         }
-        mn_prev = mn_cur; mx_prev = mx_cur;
-        mn_cur = mn_nxt; mx_cur = mx_nxt; c_cur = c_nxt;
-      }
-    }
-    // Flush the workgroup's candidates with ONE global atomic -- and only when the next step might not fit:
-    // every workgroup of the grid adds to the same counter, and atomics on one address are served one
-    // at a time by L2 (flushing every step made this kernel 3x slower than its memory traffic).
-    // The first barrier also keeps the next step's stash from overwriting tiles that are still being read.
-    __syncthreads();
-    const unsigned int n = buf_n;
-    const bool last = z0 + PZ >= ze;
-    if (n > (unsigned int)(BUFCAP - PZ * BLOCK) || (last && n)) {   // uniform
-      if (tid == 0) buf_base = atomicAdd(counter, (unsigned long long)n);
-      __syncthreads();
-      const unsigned long long base = buf_base;
-      for (unsigned int i = tid; i < n; i += BLOCK)
-        if (base + i < capacity) {
-          const unsigned int code = buf[i];
-          const int t = (int)(code & 511u), zz = zs + (int)(code >> 9);
-          out[base + i] = (unsigned long long)((i64)zz * plane + (i64)(y0 + (t >> 6)) * nx + (x0 + (t & (TX - 1))));
+        VH_STAMP(2);
+        if (cnt > (unsigned)(WCAP - SR * 64)) {   // the next step might not fit
+          flush();
+          VH_STAMP(3);
         }
-      __syncthreads();
-      if (tid == 0) buf_n = 0;   // ordered before the next appends by the next step's barrier
-    }
-  };
-  for (int z0 = zs; z0 < ze; z0 += 2 * PZ) {
-    step(preA, z0);
-    step(preB, z0 + PZ);   // (unconditional -- a second step past the end compares nothing: with a branch here the wait counts
-                           //  at the loop head must assume the shorter path and drain the younger set's loads as well)
+      }
+    });
   }
+  if (cnt) flush();
+  VH_STAMP(3);
+#ifdef VH_BLOB_STAMPS
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) atomicAdd(&g_blob_stamps[i], st_acc[i]);
+  }
+#endif
 }
 
 __global__ void __launch_bounds__(BLOCK)
@@ -336,7 +356,9 @@ static int scan_enqueue(visfd_hip_ctx* ctx, const ScanBufs& B, const float* lo, 
                         const float* mask, i64 nx, i64 ny, i64 nz, float min_thr, float max_thr) {
   hipStream_t st = ctx->stream;
   if (nx * ny >= (1LL << 29)) return fail(VISFD_HIP_EINVAL, "planes of 2 GiB and more are not supported by the blob scan");
-  const int tiles_x = (int)((nx + TX - 1) / TX), tiles_y = (int)((ny + TY - 1) / TY);
+  // interior columns 1 .. nx-2 in strips of SOX, interior rows 1 .. ny-2 in bands of SWV * SR
+  const int tiles_x = (int)std::max<i64>(1, (nx - 2 + SOX - 1) / SOX);
+  const int tiles_y = (int)std::max<i64>(1, (ny - 2 + SWV * SR - 1) / (SWV * SR));
   const i64 tiles = (i64)tiles_x * tiles_y;
   i64 want_chunks = ((i64)ctx->num_cus * 16 + tiles - 1) / tiles;
   if (want_chunks < 1) want_chunks = 1;
@@ -354,6 +376,18 @@ static int scan_enqueue(visfd_hip_ctx* ctx, const ScanBufs& B, const float* lo, 
       B.idx, B.counters, (unsigned long long)B.cap_idx, lo, mid, hi, mask, (int)nx, (int)ny, (int)nz, min_thr, max_thr,
       B.cand, (unsigned long long)B.cap_out, B.counters + 1);
   VH_HIP(hipGetLastError());
+#ifdef VH_BLOB_STAMPS
+  {
+    unsigned long long st8[8], z8[8] = {};
+    VH_HIP(hipStreamSynchronize(st));
+    VH_HIP(hipMemcpyFromSymbol(st8, HIP_SYMBOL(g_blob_stamps), sizeof(st8)));
+    double tot = 0;
+    for (int i = 0; i < 4; i++) tot += (double)st8[i];
+    fprintf(stderr, "[blob scan stamps] share of wave time: prologue %.3f | wait for the plane + row and 3x3 extrema + requests %.3f | "
+            "tests + append %.3f | flush %.3f  (total %.4g ticks)\n", st8[0] / tot, st8[1] / tot, st8[2] / tot, st8[3] / tot, tot);
+    VH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blob_stamps), z8, sizeof(z8)));
+  }
+#endif
   return VISFD_HIP_OK;
 }
 

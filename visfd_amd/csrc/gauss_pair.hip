@@ -35,6 +35,13 @@ constexpr int YX_PF = 12;     // rows requested ahead, per filter (8 and 16 time
 constexpr int Z_CHUNK = 256;  // default march lengths; every chunk pays a 2H warm-up
 constexpr int Y_CHUNK = 512;
 
+#ifdef VH_PAIR_STAMPS   // development build (tools/build_variant.py only): where a wave of pair_yx_kernel spends its time
+__device__ unsigned long long g_pair_stamps[8];
+#define VH_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_last; st_last = t_; } while (0)
+#else
+#define VH_STAMP(i) do { } while (0)
+#endif
+
 // tap |j| of filter a and of filter b
 template <int H>
 struct PairTaps {
@@ -168,6 +175,10 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
   __shared__ __attribute__((aligned(16))) float sB[W][YX_NT];
   __shared__ __attribute__((aligned(16))) float sKx[2][C::TX];    // Dx of filter a | b over the tile's output columns
   __shared__ float sKy[2][Y_CHUNK];                               // Dy of filter a | b over the chunk's rows (ychunk <= Y_CHUNK)
+#ifdef VH_PAIR_STAMPS
+  unsigned long long st_acc[5] = {0, 0, 0, 0, 0};
+  unsigned long long st_last = __builtin_amdgcn_s_memtime();
+#endif
   float ta[H + 1], tb[H + 1];
   taps_to_vgprs<H>(tp, ta, tb);
   unsigned b = blockIdx.x;
@@ -273,23 +284,26 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
     const float day = sKy[0][y - ys], dby = sKy[1][y - ys];
     // the sums started from their first product: +0.0 once restores the reference's zero signs (see the header)
     float da[4], db[4];
-    bool ones = true;
+    bool ones_a = true, ones_b = true;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       ga[k] = ga[k] + 0.0f;
       gb[k] = gb[k] + 0.0f;
       da[k] = (dxa[k] * day) * daz;   // (Dx*Dy) first, then *Dz (filter3d.hpp:1016-1018)
       db[k] = (dxb[k] * dby) * dbz;
-      ones = ones && da[k] == 1.0f && db[k] == 1.0f;
+      ones_a = ones_a && da[k] == 1.0f;
+      ones_b = ones_b && db[k] == 1.0f;
     }
-    // x / 1.0f is x for every x: where every divisor of the wave is exactly 1 (the interior, for about half of all sigmas)
-    // the divisions are skipped, as the single sweep's wave_one does
-    if (__builtin_amdgcn_ballot_w64(!ones) != 0ull) {
+    // x / 1.0f is x for every x: where every divisor of a filter is exactly 1 in the whole wave (the interior, for about half
+    // of all filters) its divisions are skipped, as the single sweep's wave_one does; each filter on its own, so that a scale
+    // with one such filter divides half as often
+    if (__builtin_amdgcn_ballot_w64(!ones_a) != 0ull) {
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        ga[k] = ga[k] / da[k];
-        gb[k] = gb[k] / db[k];
-      }
+      for (int k = 0; k < 4; k++) ga[k] = ga[k] / da[k];
+    }
+    if (__builtin_amdgcn_ballot_w64(!ones_b) != 0ull) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) gb[k] = gb[k] / db[k];
     }
     float r[4];
 #pragma unroll
@@ -324,23 +338,38 @@ pair_yx_kernel(const float* __restrict__ za, const float* __restrict__ zb, float
     __builtin_amdgcn_sched_barrier(0);   // (as in launch 1)
   };
 
+  VH_STAMP(0);
 #pragma nounroll
   for (int nb = 0; nb < nsteps; nb += W) {
     if (!idle) static_for<0, W>([&](auto U) { march_step(U, nb); });
+    VH_STAMP(1);
     __syncthreads();
-    // X pass over the W rows of this turn
+    VH_STAMP(2);
+    // X pass over the W rows of this turn, at a raised issue priority: the waves that are in it hold their whole workgroup
+    // at the second barrier, so they go before the marching waves of the other workgroups on the SIMD
+    __builtin_amdgcn_s_setprio(2);
     for (int u = u_first, qd = q_first; u < W;) {
       x_task(u, qd, nb);
       u += u_step;
       qd += q_step;
       if (qd >= QV) { qd -= QV; u++; }
     }
+    __builtin_amdgcn_s_setprio(0);
+    VH_STAMP(3);
     __syncthreads();   // the rows are overwritten by the next turn
+    VH_STAMP(4);
   }
+#ifdef VH_PAIR_STAMPS
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < 5; i++) atomicAdd(&g_pair_stamps[i], st_acc[i]);
+  }
+#endif
 }
 
 // Which half-widths take the route under log_pair = 1: filled from tools/log_pair_time.py (profiles/pair_yx_time.txt: one LoG
-// scale at 1024^3, H = 6 / 7 / 8 / 9 / 10: -1.0 / -1.9 / -2.0 / -5.5 / -5.8 ms against spreads below 0.2 ms)
+// scale at 1024^3, H = 6 / 7 / 8 / 9 / 10: -1.4 / -1.9 / -2.2 / -5.7 / -6.0 ms against spreads below 0.2 ms).  H = 5 is not
+// instantiated: its single sweeps take 2.6-2.9 ms each, the route's two launches would have to fit into 5.5 ms.
 constexpr int PAIR_H_MIN = 6, PAIR_H_MAX = 10;
 const bool kPairWins[PAIR_H_MAX + 1] = {false, false, false, false, false, false, /*6*/ true, /*7*/ true, /*8*/ true,
                                         /*9*/ true, /*10*/ true};
@@ -382,6 +411,19 @@ int launch_pair(visfd_hip_ctx* ctx, const LogPairRequest& rq, const float* Da, c
                                                                                 (int)ychunk, (int)xtiles, (int)ychunks, rq.scale,
                                                                                 vec_ok);
   VH_HIP(hipGetLastError());
+#ifdef VH_PAIR_STAMPS
+  {
+    unsigned long long st8[8], z8[8] = {};
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    VH_HIP(hipMemcpyFromSymbol(st8, HIP_SYMBOL(g_pair_stamps), sizeof(st8)));
+    double tot = 0;
+    for (int i = 0; i < 5; i++) tot += (double)st8[i];
+    fprintf(stderr, "[pair_yx stamps H=%d] share of wave time: prologue %.3f | march %.3f | wait at barrier 1 %.3f | X tasks %.3f | "
+            "wait at barrier 2 %.3f  (total %.4g ticks over %lld waves)\n", H, st8[0] / tot, st8[1] / tot, st8[2] / tot, st8[3] / tot,
+            st8[4] / tot, tot, (long long)yxblocks * (YX_NT / 64));
+    VH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stamps), z8, sizeof(z8)));
+  }
+#endif
   return VISFD_HIP_OK;
 }
 
