@@ -359,63 +359,15 @@ def test_eigen_solver(ctx, oracle):
         assert err <= 1e-5, "eigenvalues rel err %g" % err
 
 
-def _shoemake_frame(sm):
-    """Shoemake triple -> quaternion -> rotation matrix, the decoding half of the reference's frame round trip
-    (lin3_utils.hpp:311-337 Shoemake2Quaternion, :275-305 Quaternion2Matrix), in float64 for the checks below."""
-    sm = sm.astype(np.float64)
-    t1, t2 = 2 * np.pi * sm[:, 1], 2 * np.pi * sm[:, 2]
-    r1, r2 = np.sqrt(1.0 - sm[:, 0]), np.sqrt(sm[:, 0])
-    q0, q1, q2, q3 = np.sin(t1) * r1, np.cos(t1) * r1, np.sin(t2) * r2, np.cos(t2) * r2
-    M = np.empty((len(sm), 3, 3))
-    M[:, 0, 0] = 1 - 2 * q2 * q2 - 2 * q3 * q3
-    M[:, 1, 1] = 1 - 2 * q1 * q1 - 2 * q3 * q3
-    M[:, 2, 2] = 1 - 2 * q1 * q1 - 2 * q2 * q2
-    M[:, 0, 1] = 2 * (q1 * q2 - q3 * q0)
-    M[:, 1, 0] = 2 * (q1 * q2 + q3 * q0)
-    M[:, 1, 2] = 2 * (q2 * q3 - q1 * q0)
-    M[:, 2, 1] = 2 * (q2 * q3 + q1 * q0)
-    M[:, 0, 2] = 2 * (q1 * q3 + q2 * q0)
-    M[:, 2, 0] = 2 * (q1 * q3 - q2 * q0)
-    return M
-
-
 def test_eigen_solver_frames(ctx, oracle):
     """All six outputs of visfd_hip_diagonalize_flat_sym3 (eigen3_simple.hpp:137-342, lin3_utils.hpp:231-375): the three
     eigenvalues AND the Shoemake triple that encodes the eigenvector frame, on tests/golden/eigen.npz -- random matrices
-    over six orders of magnitude plus the degenerate, diagonal, tiny and huge cases.  The triple is decoded with the
-    reference's formulas and checked three ways: the frame is orthonormal; it diagonalises the matrix
-    (V^T diag(lambda) V = M within 1e-5 of the matrix's scale -- this also pins the arbitrary frames of degenerate
-    matrices); and where the eigenvalues are well separated every eigenvector equals the reference's up to sign."""
+    over six orders of magnitude plus the degenerate, diagonal, tiny and huge cases.  The checks are
+    ridge_np.check_eigen_frames (shared with the eig_f32 mode, tests/test_ridge_gpu.py): the frame is orthonormal; it
+    diagonalises the matrix; and where the eigenvalues are well separated every eigenvector equals the reference's up to sign."""
+    import ridge_np
     g = golden("eigen")
-    mats = g["mats"]
-    full = np.zeros((len(mats), 3, 3), np.float64)
-    for (a, b), k in {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (1, 2): 4, (0, 2): 5}.items():
-        full[:, a, b] = full[:, b, a] = mats[:, k]
-    scale = np.max(np.abs(mats), axis=1).astype(np.float64) + 1e-300
-    for oname, order in (("inc", 0), ("dec", 1)):
-        d = ctx.diagonalize(mats, order)
-        ref = g["diag_" + oname]
-        assert np.all(np.isfinite(d)), "non-finite output"
-        vecs, rvecs = _shoemake_frame(d[:, 3:6]), _shoemake_frame(ref[:, 3:6])     # rows of vecs[i] = eigenvectors
-        V = vecs.astype(np.float64)
-        eye = np.einsum("nij,nkj->nik", V, V)
-        assert np.max(np.abs(eye - np.eye(3))) <= 2e-6, "frame not orthonormal: %g" % np.max(np.abs(eye - np.eye(3)))
-        assert np.all(np.linalg.det(V) > 0.99), "frame is not a proper rotation (eigen3_simple.hpp:316-319)"
-        recon = np.einsum("nki,nk,nkj->nij", V, d[:, :3].astype(np.float64), V)
-        err = np.max(np.abs(recon - full), axis=(1, 2)) / scale
-        assert np.max(err) <= 1e-5, "V^T diag(lambda) V != M: rel err %g at case %d" % (np.max(err), int(np.argmax(err)))
-        # well-separated spectra: the reference's own eigenvectors, up to sign
-        lam = np.sort(ref[:, :3].astype(np.float64), axis=1)
-        gap = np.minimum(lam[:, 1] - lam[:, 0], lam[:, 2] - lam[:, 1]) / scale
-        sep = gap > 1e-2
-        assert sep.sum() > 3000
-        dots = np.abs(np.einsum("nij,nij->ni", V[sep], rvecs[sep].astype(np.float64)))
-        assert np.min(dots) >= 1.0 - 1e-6, "eigenvector differs from the reference's: |cos| = %.9f" % np.min(dots)
-        # exactly degenerate inputs (multiples of the identity, the zero matrix): the reference returns the identity frame
-        for i in range(len(mats)):
-            if mats[i, 0] == mats[i, 1] == mats[i, 2] and not np.any(mats[i, 3:]):
-                assert np.max(np.abs(np.abs(V[i]) - np.eye(3))) <= 1e-6, "frame of a multiple of the identity (case %d)" % i
-                assert_close_rel(d[i, :3], ref[i, :3], 1e-6, "eigenvalues of a multiple of the identity")
+    ridge_np.check_eigen_frames(ctx.diagonalize, g["mats"], {0: g["diag_inc"], 1: g["diag_dec"]})
 
 
 def test_gauss_512_cubed_crops_equal_oracle(ctx, oracle):

@@ -107,6 +107,9 @@ int calc_hessian_dev(visfd_hip_ctx* ctx, const float* src, float* grad, float* h
                      i64 nx, i64 ny, i64 nz, float sigma, float ratio) {
   VH_REQUIRE(ctx && src, "null argument");
   VH_TRY(check_dims(nx, ny, nz));
+  // (dev_hessian says the same; said here, a volume too thin for the stencil is turned away before the Gaussian runs on it)
+  if (nx < 3 || ny < 3 || nz < 3)
+    return fail(VISFD_HIP_EINVAL, "CalcHessian requires an image at least 3 voxels wide in x,y,z");
   float* S = nullptr;
   VH_TRY(gauss_iso_dev(ctx, src, nullptr, mask, nx, ny, nz, sigma, ratio, true, "filter halfwidth", &S));
   return dev_hessian(ctx, S, mask, nx, ny, nz, sigma, grad, hess);
