@@ -84,7 +84,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * on the device: visfd_hip_label_connected_device_seeds and
                                      * visfd_hip_label_connected_device_seeds_last; then LabelConnected as a graph
                                      * problem: visfd_hip_label_connected_graph[_dev|_host], _graph_last and
-                                     * _graph_last_times) */
+                                     * _graph_last_times; then DiscardOverlappingBlobs on the device:
+                                     * visfd_hip_discard_overlapping_blobs_ctx, _dev, _last and
+                                     * _last_times) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -134,6 +136,12 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    markers they always do); labels and lists are identical either way; default 0
  *   find_spheres_host 1: visfd_hip_find_spheres[_dev] walk the (query, sphere) pairs on the host (the walk of
  *                    visfd_hip_find_spheres_host) instead of launching the search kernel; ids are identical either way; default 0
+ *   discard_overlap_host 1: visfd_hip_discard_overlapping_blobs_ctx / _dev run the host entry instead of the rounds on the
+ *                    device (csrc/discard_overlap.hip); lists are identical either way; default 0
+ *   discard_overlap_time 1: those two entries time their phases with stream events
+ *                    (visfd_hip_discard_overlapping_blobs_last_times); default 0
+ *   discard_overlap_max_rounds  rounds after which the host finishes such a list from the states reached; lists are
+ *                    identical for every value; default 256
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -687,6 +695,42 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
                                         float min_radial_separation_ratio,
                                         float max_volume_overlap_large, float max_volume_overlap_small,
                                         int sort_criteria, int scale);
+/* The same on a context's device (csrc/discard_overlap.hip): the reference's bits always, computed on the device for
+ * every list outside the hand-over set.  The greedy walk is order-free -- a blob is kept exactly when no kept blob
+ * BEFORE it in the sorted list both shares a cell of the occupancy grid with it and meets the discard criterion -- so
+ * the device ranks the list (stable radix sort of score or |score|, ties as std::pair orders them), buckets the blobs by
+ * centre cell and settles the recursion in rounds, one launch per round; the round count is the longest chain of
+ * dependencies in the list.
+ *   _ctx   host arrays, staged through the context's workspace
+ *   _dev   device arrays, in place; *n (a HOST word) is read and written.  Both return with the stream idle.
+ * The hand-over set, for which the call runs visfd_hip_discard_overlapping_blobs unchanged and says so: a non-finite
+ * coordinate, diameter or score; a diameter < 0; n >= 2^31; bounds outside the int range; more than 2^27 cells in the
+ * table or in the range of the centre cells.  A list that needs more rounds than the option discard_overlap_max_rounds
+ * (default 256: a cap, random lists need a dozen) is finished by the host walk from the states reached, same bits.
+ * Option discard_overlap_host (VISFD_HIP_DISCARD_OVERLAP_HOST) 1: both faces run the host entry. */
+int visfd_hip_discard_overlapping_blobs_ctx(visfd_hip_ctx*, float* crds, float* diameters, float* scores, int64_t* n,
+                                            float min_radial_separation_ratio, float max_volume_overlap_large,
+                                            float max_volume_overlap_small, int sort_criteria, int scale);
+int visfd_hip_discard_overlapping_blobs_dev(visfd_hip_ctx*, float* crds, float* diameters, float* scores, int64_t* n,
+                                            float min_radial_separation_ratio, float max_volume_overlap_large,
+                                            float max_volume_overlap_small, int sort_criteria, int scale);
+/* the context's last _ctx / _dev call: info[0] path (VISFD_HIP_DISCARD_OVERLAP_PATH_*, -1 before the first call),
+ * [1] reason (VISFD_HIP_DISCARD_OVERLAP_REASON_*), [2] rounds launched, [3] blobs in, [4] blobs kept, [5] pairs that
+ * reached the discard criterion, [6] pairs that reached the exact cell test, [7] table cells */
+#define VISFD_HIP_DISCARD_OVERLAP_PATH_DEVICE 0
+#define VISFD_HIP_DISCARD_OVERLAP_PATH_HOST 1          /* option discard_overlap_host */
+#define VISFD_HIP_DISCARD_OVERLAP_PATH_HANDED_OVER 2   /* the host entry, or the host walk from the device's states */
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_NONE 0
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_NONFINITE 1
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_NEGATIVE 2    /* a diameter < 0 */
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_COUNT 3       /* n >= 2^31 */
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_BOUNDS 4      /* bounds outside the int range */
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_CELLS 5       /* more than 2^27 cells */
+#define VISFD_HIP_DISCARD_OVERLAP_REASON_ROUNDS 6      /* the round cap */
+int visfd_hip_discard_overlapping_blobs_last(visfd_hip_ctx*, int64_t info[8]);
+/* option discard_overlap_time: milliseconds between events on the stream of the last _ctx / _dev call: the reduction with
+ * its wait, ranking and records, buckets, the rounds with their waits, compaction; -1 for a phase that did not run */
+int visfd_hip_discard_overlapping_blobs_last_times(visfd_hip_ctx*, float ms[5]);
 
 /* ---- f3, continued: FindSpheres and the supervised score thresholds ("-auto-thresh score -supervised POS NEG") ----
  * FindSpheres, lib/visfd/visfd_utils.hpp:271-359: for every query point the sphere of the list that holds it, the LAST

@@ -1134,6 +1134,30 @@ inline void DiscardOverlappingBlobs(std::vector<std::array<float, 3> >& blob_crd
   if (pReportProgress) *pReportProgress << "done.\n";
 }
 
+// The same on a context's device (visfd_hip_discard_overlapping_blobs_ctx): the same lists bit for bit, the same progress
+// text.  A null context is the host form above.
+inline void DiscardOverlappingBlobs(visfd_hip_ctx* ctx, std::vector<std::array<float, 3> >& blob_crds,
+                                    std::vector<float>& blob_diameters, std::vector<float>& blob_scores,
+                                    float min_radial_separation_ratio,
+                                    float max_volume_overlap_large = std::numeric_limits<float>::infinity(),
+                                    float max_volume_overlap_small = std::numeric_limits<float>::infinity(),
+                                    SortCriteria sort_blob_criteria = SORT_DECREASING_MAGNITUDE,
+                                    std::ostream* pReportProgress = nullptr, int scale = 6) {
+  if (!ctx) {
+    DiscardOverlappingBlobs(blob_crds, blob_diameters, blob_scores, min_radial_separation_ratio, max_volume_overlap_large,
+                            max_volume_overlap_small, sort_blob_criteria, pReportProgress, scale);
+    return;
+  }
+  hip_detail::FlatBlobs f(blob_crds, blob_diameters, blob_scores);
+  int64_t n = (int64_t)blob_crds.size();
+  if (pReportProgress) *pReportProgress << "  detecting collisions between " << n << " blobs... ";
+  hip_detail::check(visfd_hip_discard_overlapping_blobs_ctx(ctx, f.c.data(), f.d.data(), f.s.data(), &n,
+                                                            min_radial_separation_ratio, max_volume_overlap_large,
+                                                            max_volume_overlap_small, (int)sort_blob_criteria, scale));
+  f.store((size_t)n, blob_crds, blob_diameters, blob_scores);
+  if (pReportProgress) *pReportProgress << "done.\n";
+}
+
 // ---- FindSpheres and the supervised score thresholds: lib/visfd/visfd_utils.hpp:271-516, feature.hpp:643-697, :988-1180 ----
 // The search over (training point, blob) pairs runs on the device (visfd_hip_find_spheres); the progress lines are the
 // reference's, text for text -- its table is not allocated here, but its stderr says so and programs compare it.

@@ -281,6 +281,13 @@ _SIGS = {
     "visfd_hip_discard_masked_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), _vp, _i64, _i64, _i64]),
     "visfd_hip_discard_overlapping_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), C.c_float, C.c_float,
                                                      C.c_float, C.c_int, C.c_int]),
+    # DiscardOverlappingBlobs on the device (csrc/discard_overlap.hip)
+    "visfd_hip_discard_overlapping_blobs_ctx": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), C.c_float, C.c_float,
+                                                         C.c_float, C.c_int, C.c_int]),
+    "visfd_hip_discard_overlapping_blobs_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), C.c_float, C.c_float,
+                                                         C.c_float, C.c_int, C.c_int]),
+    "visfd_hip_discard_overlapping_blobs_last": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "visfd_hip_discard_overlapping_blobs_last_times": (C.c_int, [_vp, _fp]),
     # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
     "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -779,6 +786,13 @@ def _chk_host(L, rc):
         raise VisfdHipError(rc, L.visfd_hip_last_error().decode())
 
 
+# visfd_hip_discard_overlapping_blobs_last (VISFD_HIP_DISCARD_OVERLAP_PATH_*, _REASON_*)
+DISCARD_OVERLAP_PATH_DEVICE, DISCARD_OVERLAP_PATH_HOST, DISCARD_OVERLAP_PATH_HANDED_OVER = 0, 1, 2
+(DISCARD_OVERLAP_REASON_NONE, DISCARD_OVERLAP_REASON_NONFINITE, DISCARD_OVERLAP_REASON_NEGATIVE, DISCARD_OVERLAP_REASON_COUNT,
+ DISCARD_OVERLAP_REASON_BOUNDS, DISCARD_OVERLAP_REASON_CELLS, DISCARD_OVERLAP_REASON_ROUNDS) = range(7)
+DISCARD_OVERLAP_LAST_FIELDS = ("path", "reason", "rounds", "blobs_in", "blobs_kept", "pairs_crit", "pairs_share", "table_cells")
+
+
 def _blob_arrays(crds, diameters, scores):
     c = np.ascontiguousarray(crds, np.float32).reshape(-1, 3).copy()
     d = np.ascontiguousarray(diameters, np.float32).copy()
@@ -819,8 +833,13 @@ def discard_masked_blobs(crds, diameters, scores, mask):
 
 
 def discard_overlapping_blobs(crds, diameters, scores, min_radial_separation_ratio, max_volume_overlap_large=np.inf,
-                              max_volume_overlap_small=np.inf, criteria=SORT_DECREASING_MAGNITUDE, scale=6):
-    """DiscardOverlappingBlobs (feature.hpp:720-913): greedy non-max suppression, best blobs first."""
+                              max_volume_overlap_small=np.inf, criteria=SORT_DECREASING_MAGNITUDE, scale=6, ctx=None):
+    """DiscardOverlappingBlobs (feature.hpp:720-913): greedy non-max suppression, best blobs first.  ctx (a Context, or
+    None): with None the sequential host walk, otherwise Context.discard_overlapping_blobs on that context's device; the
+    lists are the same bits either way."""
+    if ctx is not None:
+        return ctx.discard_overlapping_blobs(crds, diameters, scores, min_radial_separation_ratio, max_volume_overlap_large,
+                                             max_volume_overlap_small, criteria, scale)
     L = load_library()
     c, d, s = _blob_arrays(crds, diameters, scores)
     n = _i64(len(d))
@@ -1270,6 +1289,46 @@ class Context:
         p = C.c_int(-1)
         self._chk(self._L.visfd_hip_find_spheres_last_path(self._h, C.byref(p)))
         return int(p.value)
+
+    def discard_overlapping_blobs(self, crds, diameters, scores, min_radial_separation_ratio, max_volume_overlap_large=np.inf,
+                                  max_volume_overlap_small=np.inf, criteria=SORT_DECREASING_MAGNITUDE, scale=6):
+        """DiscardOverlappingBlobs (feature.hpp:720-913) on the device, numpy in and out -> (crds, diameters, scores) of
+        the kept blobs, best first: the bits of the module-level function.  discard_overlapping_blobs_last() says what ran."""
+        c, d, s = _blob_arrays(crds, diameters, scores)
+        n = _i64(len(d))
+        self._chk(self._L.visfd_hip_discard_overlapping_blobs_ctx(
+            self._h, c.ctypes.data, d.ctypes.data, s.ctypes.data, C.byref(n), min_radial_separation_ratio,
+            max_volume_overlap_large, max_volume_overlap_small, int(criteria), int(scale)))
+        return c[:n.value], d[:n.value], s[:n.value]
+
+    def discard_overlapping_blobs_dev(self, crds, diameters, scores, min_radial_separation_ratio,
+                                      max_volume_overlap_large=np.inf, max_volume_overlap_small=np.inf,
+                                      criteria=SORT_DECREASING_MAGNITUDE, scale=6):
+        """The same on torch device tensors, IN PLACE: crds (n, 3), diameters (n,), scores (n,) float32, contiguous.
+        Returns the number of kept blobs; they are the first entries of the three tensors.  Returns with the stream idle."""
+        import torch
+        n = int(diameters.shape[0])
+        for t, m in ((crds, 3 * n), (diameters, n), (scores, n)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == m, "float32 device lists of one length"
+        k = _i64(n)
+        self._chk(self._L.visfd_hip_discard_overlapping_blobs_dev(
+            self._h, _dev(crds), _dev(diameters), _dev(scores), C.byref(k), min_radial_separation_ratio,
+            max_volume_overlap_large, max_volume_overlap_small, int(criteria), int(scale)))
+        return int(k.value)
+
+    def discard_overlapping_blobs_last(self):
+        """The last discard_overlapping_blobs[_dev] of this context: dict of path (DISCARD_OVERLAP_PATH_*), reason
+        (DISCARD_OVERLAP_REASON_*), rounds, blobs_in, blobs_kept, pairs_crit, pairs_share, table_cells."""
+        info = (_i64 * 8)()
+        self._chk(self._L.visfd_hip_discard_overlapping_blobs_last(self._h, info))
+        return dict(zip(DISCARD_OVERLAP_LAST_FIELDS, (int(x) for x in info)))
+
+    def discard_overlapping_blobs_last_times(self):
+        """Option discard_overlap_time: the last call's phases in milliseconds (reduction, ranking and records, buckets,
+        rounds, compaction), -1 where a phase did not run."""
+        ms = (C.c_float * 5)()
+        self._chk(self._L.visfd_hip_discard_overlapping_blobs_last_times(self._h, ms))
+        return dict(zip(("reduce", "rank", "buckets", "rounds", "compact"), (float(x) for x in ms)))
 
     def image_stats(self, src, mask=None):
         """Statistics of the voxels with mask != 0 (all without a mask): dict of count, n_nonfinite, min, max, the exact

@@ -57,6 +57,9 @@
 //                              ratios of the extreme score (settings.cpp:1947-1981); not under -slab
 //   The search behind the supervised flags (FindSpheres) walks the pairs on the host for small lists and runs on the GPU
 //   from FIND_SPHERES_MIN_PAIRS pairs on (VISFD_HIP_FIND_SPHERES_MIN_PAIRS overrides; 0: always the GPU).
+//   The overlap removal behind -discard-blobs and behind -find-minima / -find-maxima with -radial-separation
+//   (DiscardOverlappingBlobs) walks the list on the host below DISCARD_OVERLAP_MIN_BLOBS blobs and runs on the GPU, when
+//   there is one, from there on (VISFD_HIP_DISCARD_OVERLAP_MIN_BLOBS overrides; 0: always the GPU); same bytes either way.
 // Anything else is rejected, as the reference rejects unknown arguments (settings.cpp:3340-3365).
 //
 // MRC input/output is in mrc.hpp, the settings and the parser of the flags above in settings.hpp; both are part of
@@ -136,6 +139,30 @@ bool read_blob_file(const string& path, vector<std::array<float, 3> >& crds, vec
   return parens;
 }
 
+// Where DiscardOverlappingBlobs runs: the sequential walk on the host below this many blobs, the rounds on the device
+// (visfd_hip_discard_overlapping_blobs_ctx) from there on, when a GPU is present; the lists are the same bits either way.
+// MEASURED on an MI355X (tools/discard_overlap_time.py, second table of profiles/discard_overlap_time.txt: diameters 8 to 24
+// voxels at 10^5 blobs per 512^3, ratio 1, one staged call in a fresh process): the first context costs about 150 ms before
+// the device ranks anything, the call itself 6 to 35 ms up to 262 144 blobs; the host walk takes 52.7 ms at 65 536 blobs,
+// 177.8 ms at 131 072 (device, all told: 167.5 ms) and 553.6 ms at 262 144 (189.8 ms).  The two meet near 1.25 * 10^5
+// blobs; rounded to a power of two.  Without the start-up the device is far ahead (first table: 8.4 ms against 125 ms at
+// 10^5 blobs, 204 ms against 19.5 s at 4 * 10^6); the constant does not count on a context that happens to exist.
+const double DISCARD_OVERLAP_MIN_BLOBS = 131072.0;   // 2^17
+
+// the context to hand to DiscardOverlappingBlobs for a list of n blobs: null keeps the walk on the host.  The environment
+// variable VISFD_HIP_DISCARD_OVERLAP_MIN_BLOBS overrides the size (0: always the device) and makes the program say which ran.
+visfd_hip_ctx* overlap_context(size_t n) {
+  double min_blobs = DISCARD_OVERLAP_MIN_BLOBS;
+  const char* e = std::getenv("VISFD_HIP_DISCARD_OVERLAP_MIN_BLOBS");
+  if (e) min_blobs = std::atof(e);
+  visfd_hip_ctx* ctx = nullptr;
+  if ((double)n >= min_blobs) {
+    try { ctx = hip_detail::context(); } catch (const VisfdErr&) { ctx = nullptr; }   // no GPU: the host walk
+  }
+  if (e) cerr << "  (discard_overlap: " << (ctx ? "device" : "host") << ")" << std::endl;
+  return ctx;
+}
+
 // HandleBlobsNonmaxSuppression, bin/filter_mrc/handlers.cpp:421-596 (its supervised tail is in handle_blob_nonmax): the
 // lists of the blob files in voxels, filtered by score and size, by the mask (when one is passed) and by overlap
 void read_and_filter_blobs(const Run& r, float const* const* const* mask, vector<std::array<float, 3> >& crds,
@@ -185,8 +212,8 @@ void read_and_filter_blobs(const Run& r, float const* const* const* mask, vector
       throw VisfdErr("Error: Checking for overlapping blobs requires that you either specify the\n"
                      "       voxel width (using the \"-w\" argument).\n");
     cerr << "  discarding overlapping blobs" << std::endl;
-    DiscardOverlappingBlobs(crds, diameters, scores, s.nonmax_min_radial_separation_ratio, s.nonmax_max_overlap_large,
-                            s.nonmax_max_overlap_small, SORT_DECREASING_MAGNITUDE, &cerr);
+    DiscardOverlappingBlobs(overlap_context(crds.size()), crds, diameters, scores, s.nonmax_min_radial_separation_ratio,
+                            s.nonmax_max_overlap_large, s.nonmax_max_overlap_small, SORT_DECREASING_MAGNITUDE, &cerr);
   }
   cerr << " " << crds.size() << " blobs remaining" << std::endl;
 }
@@ -856,7 +883,7 @@ void handle_extrema(Run& r) {
     for (int side = 0; side < 2; side++) {
       vector<float> diam(crds[side].size(), s.sphere_decals_diameter * s.nonmax_min_radial_separation_ratio);
       if (!crds[side].empty() && r.mask3d()) DiscardMaskedBlobs(crds[side], diam, scores[side], r.mask3d(), r.size);
-      DiscardOverlappingBlobs(crds[side], diam, scores[side], s.nonmax_min_radial_separation_ratio,
+      DiscardOverlappingBlobs(overlap_context(crds[side].size()), crds[side], diam, scores[side], s.nonmax_min_radial_separation_ratio,
                               s.nonmax_max_overlap_large, s.nonmax_max_overlap_small,
                               side ? SORT_DECREASING : SORT_INCREASING, &cerr);
     }

@@ -125,7 +125,20 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
   if (n == 0) return VISFD_HIP_OK;
   // 1. best blobs first (feature.hpp:737-743: ascending_order = false)
   VH_TRY(visfd_hip_sort_blobs(crds, diameters, scores, n, sort_criteria, 0, nullptr));
+  vh::overlap_walk_sorted(crds, diameters, scores, n_inout, nullptr, min_radial_separation_ratio, max_volume_overlap_large,
+                          max_volume_overlap_small, scale);
+  return VISFD_HIP_OK;
+}
 
+}  // extern "C"
+
+// Steps 2 to 4 of DiscardOverlappingBlobs on a list that is sorted already.  `states` (nullable, one byte per blob) is
+// what rounds on the device have decided so far (csrc/discard_overlap.hip): a kept blob enters the grid untested, a
+// discarded one is skipped, an undecided one is tested as always.  Without states every blob is undecided.
+void vh::overlap_walk_sorted(float* crds, float* diameters, float* scores, int64_t* n_inout, const unsigned char* states,
+                             float min_radial_separation_ratio, float max_volume_overlap_large,
+                             float max_volume_overlap_small, int scale) {
+  const i64 n = *n_inout;
   // 2. integer bounds of all blobs (feature.hpp:756-768); float -> int conversions truncate
   int bmin[3] = {0, 0, 0}, bmax[3] = {-1, -1, -1};
   for (i64 i = 0; i < n; i++)
@@ -151,6 +164,8 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
     const float ix = crds[3 * i], iy = crds[3 * i + 1], iz = crds[3 * i + 2];
     const int C[3] = {(int)std::floor((ix - bmin[0]) / scale), (int)std::floor((iy - bmin[1]) / scale),
                       (int)std::floor((iz - bmin[2]) / scale)};
+    const unsigned char state = states ? states[i] : (unsigned char)vh::OVERLAP_UNDECIDED;
+    if (state == vh::OVERLAP_DISCARDED) continue;
     bool discard = false;
     auto for_cells = [&](auto&& fn) {   // the blob's cells inside the table, fn returns false to stop
       if (!has_grid) return;
@@ -169,7 +184,7 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
         }
       }
     };
-    for_cells([&](std::vector<uint32_t>& cell) {
+    if (state != vh::OVERLAP_KEPT) for_cells([&](std::vector<uint32_t>& cell) {
       for (uint32_t k : cell) {
         const float kx = crds[3 * k], ky = crds[3 * k + 1], kz = crds[3 * k + 2];
         const float rik = std::sqrt((ix - kx) * (ix - kx) + (iy - ky) * (iy - ky) + (iz - kz) * (iz - kz));
@@ -198,10 +213,7 @@ int visfd_hip_discard_overlapping_blobs(float* crds, float* diameters, float* sc
     }
   }
   *n_inout = (int64_t)keep.size();
-  return VISFD_HIP_OK;
 }
-
-}  // extern "C"
 
 // ---- the supervised score thresholds: visfd_utils.hpp:373-516, feature_implementation.hpp:48-457, feature.hpp:643-697,
 //      :988-1180.  Short sequential host logic; the one search over (training point, blob) pairs is FindSpheres

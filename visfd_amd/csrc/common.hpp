@@ -85,6 +85,10 @@ enum Slot {
   WS_CG_SEEDS,                     // ... the ranked seeds, their roots, signs and numbers (4 x int32 per seed)
   WS_CG_CLUSTER,                   // ... per cluster: size, coordinate sums, centre of mass, outward sum, final label, bound (10 x 8 bytes)
   WS_CG_COUNTERS,                  // ... the two list lengths and the reason flags
+  WS_OVL_LIST,                     // DiscardOverlappingBlobs (csrc/discard_overlap.hip): the per-blob arrays: sort keys and values, records in sorted and
+                                   // in bucket order, sorted scores, states, the two lists of undecided blobs
+  WS_OVL_CELLS,                    // ... the buckets' offsets, one word per centre cell plus one
+  WS_OVL_TEMP,                     // ... the reduction words, the counters, and the sort's and the scan's temporary storage
   WS_NSLOTS
 };
 
@@ -119,6 +123,9 @@ struct visfd_hip_options {
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
   int distance_general = 0; // 1: distance maps by the brute-force walks (csrc/distance.hip), never by the separable transform
+  int discard_overlap_host = 0;   // 1: visfd_hip_discard_overlapping_blobs_ctx / _dev run the host entry (csrc/blob_post.cpp), never the rounds on the device
+  int discard_overlap_time = 0;   // 1: those two time their phases with events on the stream (visfd_hip_discard_overlapping_blobs_last_times; tools/discard_overlap_time.py)
+  int discard_overlap_max_rounds = 256;   // rounds of csrc/discard_overlap.hip after which the host finishes the list from the states so far (a cap, not a tuning knob)
   int find_spheres_host = 0; // 1: FindSpheres walks the pairs on the host (csrc/find_spheres.hip), never launches the search kernel
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
@@ -151,6 +158,8 @@ struct visfd_hip_ctx {
   int median_last_path = -1;          // the kernel the last median call ran (VISFD_HIP_MEDIAN_PATH_*)
   int distance_last_path = -1;        // what the last distance call ran (VISFD_HIP_DISTANCE_PATH_*)
   int find_spheres_last_path = -1;    // what the last FindSpheres call ran (VISFD_HIP_FIND_SPHERES_PATH_*)
+  int64_t discard_overlap_last[8] = {-1, 0, 0, 0, 0, 0, 0, 0};   // the last visfd_hip_discard_overlapping_blobs_ctx / _dev (visfd_hip_discard_overlapping_blobs_last)
+  float discard_overlap_ms[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // option discard_overlap_time: reduction, ranking and records, buckets, rounds, compaction
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
@@ -192,6 +201,13 @@ inline int check_dims32(i64 nx, i64 ny, i64 nz) {   // for the kernels that inde
   if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
   return VISFD_HIP_OK;
 }
+
+// blob_post.cpp: steps 2 to 4 of DiscardOverlappingBlobs (bounds, the greedy walk over the occupancy grid, compaction) on a
+// list that is sorted already; `states` (nullable): what the device's rounds have decided, one OVERLAP_* byte per blob
+enum : unsigned char { OVERLAP_UNDECIDED = 0, OVERLAP_KEPT = 1, OVERLAP_DISCARDED = 2 };
+void overlap_walk_sorted(float* crds, float* diameters, float* scores, int64_t* n_inout, const unsigned char* states,
+                         float min_radial_separation_ratio, float max_volume_overlap_large, float max_volume_overlap_small,
+                         int scale);
 
 // ---- taps carried in the kernel-argument segment (scalar loads, SGPR operands) ---------------
 constexpr int MAX_HALFWIDTH = 64;

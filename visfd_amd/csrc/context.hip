@@ -59,6 +59,9 @@ const OptionDesc kOptions[] = {
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
     {"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr},
+    {"discard_overlap_host", &visfd_hip_options::discard_overlap_host, nullptr},
+    {"discard_overlap_time", &visfd_hip_options::discard_overlap_time, nullptr},
+    {"discard_overlap_max_rounds", &visfd_hip_options::discard_overlap_max_rounds, nullptr},
     {"log_pair", &visfd_hip_options::log_pair, nullptr},
     {"log_pair_chunk", &visfd_hip_options::log_pair_chunk, nullptr},
 };
