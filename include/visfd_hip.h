@@ -132,6 +132,11 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    (visfd_hip_draw_last_times); default 0
  *   connect_time     1: visfd_hip_label_connected_graph[_dev] time their stages on the host clock and wait for the stream
  *                    at each (visfd_hip_label_connected_graph_last_times); default 0
+ *   connect_settle   1: visfd_hip_label_connected_graph[_dev] keep calls with must-link constraints, voxel weights or a
+ *                    cluster whose outward sum is in doubt on the device path: the nearest labelled voxels are searched on
+ *                    the device, the merges and the flood's own long double moments are formed on the host from the
+ *                    labelled voxels alone (visfd_hip_label_connected_graph_last_settled); results are the flood's bits
+ *                    either way; default 0: such calls are handed to the flood
  *   watershed_host   1: visfd_hip_watershed[_dev] run the sequential flood on the host for calls without markers too (with
  *                    markers they always do); labels and lists are identical either way; default 0
  *   find_spheres_host 1: visfd_hip_find_spheres[_dev] walk the (query, sphere) pairs on the host (the walk of
@@ -906,6 +911,11 @@ int visfd_hip_label_connected_device_seeds_last(visfd_hip_ctx*, int* where, int6
  * before the first), and, each nullable, the reason bits, the number of valid voxels and the number of candidates the
  * host's vector test looked at (0 without directions; both -1 where the call was handed over before counting).  With a
  * null context: the calling thread's last visfd_hip_label_connected_graph_host.
+ * visfd_hip_label_connected_graph_last_settled: with the option connect_settle, MUST_LINK, WEIGHTS and OUTWARD are no reasons
+ * for visfd_hip_label_connected_graph and _graph_dev (the other reasons hand over as before, and a must-link location
+ * beyond 2^20 voxels from the origin, or 2^33 or more squared voxels from a corner of the image, is LIMITS); *settled gets
+ * the bits of those three that the context's last device-path call settled itself -- OUTWARD only if a cluster's sum
+ * was in doubt -- and 0 after a call that took the flood or ran with the option off.
  * visfd_hip_label_connected_graph_last_times: with the option connect_time, the milliseconds of the last device-path
  * call by stage: seed search, classify and compact, host vector test, edges and union-find, clusters, directions and
  * the last pass, copies to the device, copies to the host. */
@@ -957,6 +967,7 @@ int visfd_hip_label_connected_graph_host(const float* saliency, int64_t* labels,
                                          const int* must_link_directions);
 int visfd_hip_label_connected_graph_last(visfd_hip_ctx*, int* path, unsigned* reasons, int64_t* n_valid,
                                          int64_t* n_undecided);
+int visfd_hip_label_connected_graph_last_settled(visfd_hip_ctx*, unsigned* settled);
 int visfd_hip_label_connected_graph_last_times(visfd_hip_ctx*, float ms[8]);
 
 /* Principal eigenvector (eigenvector row 0 of ConvertFlatSym2Evects3 in the given order) of nvox flat tensors

@@ -269,6 +269,7 @@ _SIGS = {
     "visfd_hip_label_connected_graph_host": (C.c_int, list(_LABEL_CONNECTED_EX)),
     "visfd_hip_label_connected_graph_last": (C.c_int, [_vp, _ip, C.POINTER(C.c_uint), C.POINTER(_i64), C.POINTER(_i64)]),
     "visfd_hip_label_connected_graph_last_times": (C.c_int, [_vp, _fp]),
+    "visfd_hip_label_connected_graph_last_settled": (C.c_int, [_vp, C.POINTER(C.c_uint)]),
     "visfd_hip_principal_directions_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_tensor_saliency_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "visfd_hip_diagonalize_sym3_f32_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -1477,6 +1478,13 @@ class Context:
     def label_connected_graph_last(self):
         """(path, reasons, valid voxels, candidates of the host's vector test) of the context's last graph call."""
         return label_connected_graph_last(self)
+
+    def label_connected_graph_last_settled(self):
+        """Under the option connect_settle: the CONNECT_REASON_* bits among MUST_LINK, WEIGHTS and OUTWARD that the last
+        device-path graph call settled itself; 0 after a call that took the flood or ran with the option off."""
+        bits = C.c_uint(0)
+        self._chk(self._L.visfd_hip_label_connected_graph_last_settled(self._h, C.byref(bits)))
+        return bits.value
 
     def label_connected_graph_last_times(self):
         """Under the option connect_time: milliseconds of the last device-path graph call by stage (seed search, classify,

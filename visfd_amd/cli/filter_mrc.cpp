@@ -1078,13 +1078,22 @@ void cluster(Run& r, int order, const vector<float>& tensor) {
   } catch (const VisfdErr& e) {
     if (std::string(e.what()).find("no HIP device available") == std::string::npos) throw;
   }
-  hip_detail::check((ctx ? visfd_hip_label_connected_device_seeds : connect_on_host)(   // the same labels either way
+  // With a device: the graph entry, with must-links and doubtful outward sums settled on its device path (option
+  // connect_settle); labels and the directions of labelled voxels are the flood's bits, and nothing below reads any other
+  // direction.  The option is put back afterwards: the context is the program's one.
+  int64_t settle_before = 0;
+  if (ctx) {
+    hip_detail::check(visfd_hip_get_option(ctx, "connect_settle", &settle_before));
+    hip_detail::check(visfd_hip_set_option(ctx, "connect_settle", 1));
+  }
+  hip_detail::check((ctx ? visfd_hip_label_connected_graph : connect_on_host)(   // the same labels either way
       ctx, r.tomo_out.data(), labels.data(), mptr, r.size[0], r.size[1], r.size[2], s.connect_threshold_saliency,
       direction.data(), s.connect_threshold_vector_saliency, s.connect_threshold_vector_neighbor, 0, tensor.data(),
       s.connect_threshold_tensor_saliency, s.connect_threshold_tensor_neighbor, 1, 1, -1, 1, 1, 1, &n_clusters,
       nullptr, nullptr, nullptr, 0, nullptr, s.must_link_crds.empty() ? nullptr : s.must_link_crds.data(),
       s.must_link_group_sizes.empty() ? nullptr : s.must_link_group_sizes.data(),
       (int64_t)s.must_link_group_sizes.size(), s.must_link_directions.empty() ? nullptr : s.must_link_directions.data()));
+  if (ctx) hip_detail::check(visfd_hip_set_option(ctx, "connect_settle", settle_before));
   cerr << "Number of clusters found: " << n_clusters << "\n";
   int64_t max_label = labels[0];
   for (size_t i = 0; i < n; i++)

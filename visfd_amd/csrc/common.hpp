@@ -85,6 +85,8 @@ enum Slot {
   WS_CG_SEEDS,                     // ... the ranked seeds, their roots, signs and numbers (4 x int32 per seed)
   WS_CG_CLUSTER,                   // ... per cluster: size, coordinate sums, centre of mass, outward sum, final label, bound (10 x 8 bytes)
   WS_CG_COUNTERS,                  // ... the two list lengths and the reason flags
+  WS_CG_SETTLE,                    // ... option connect_settle: the gathered voxels (index, code, direction, weight: 6 x 4 bytes per entry)
+  WS_CG_LINKS,                     // ... option connect_settle: per must-link location its rounded position, nearest-voxel key, code and direction
   WS_OVL_LIST,                     // DiscardOverlappingBlobs (csrc/discard_overlap.hip): the per-blob arrays: sort keys and values, records in sorted and
                                    // in bucket order, sorted scores, states, the two lists of undecided blobs
   WS_OVL_CELLS,                    // ... the buckets' offsets, one word per centre cell plus one
@@ -130,6 +132,8 @@ struct visfd_hip_options {
   int watershed_host = 0;   // 1: the watershed runs the sequential host flood without markers too (csrc/watershed_host.cpp)
   int stats_blocks = 0;     // workgroups of the statistics / intensity-map kernel (csrc/intensity.hip); 0: eight per CU
   int connect_time = 0;     // 1: visfd_hip_label_connected_graph[_dev] time their stages on the host clock and wait for each (tools/connect_graph_time.py)
+  int connect_settle = 0;   // 1: visfd_hip_label_connected_graph[_dev] settle must-links, voxel weights and doubtful outward sums on the
+                            //    device path instead of handing the call to the flood (csrc/connect_graph.hip)
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int debug = 0;
 };
@@ -164,6 +168,7 @@ struct visfd_hip_ctx {
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
   int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test
+  unsigned connect_graph_settled = 0;        // option connect_settle: the reason bits the last device-path call settled itself
   float connect_graph_ms[8] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // option connect_time: its stages (csrc/connect_graph.hip: MS_*)
   std::vector<vh::BlobJob*> blob_jobs;   // the context's live blob jobs (blob_job.hip)
 };

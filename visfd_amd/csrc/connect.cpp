@@ -354,23 +354,10 @@ int vh::host_label_connected(const float* saliency, int64_t* labels, const float
             if (V) {
               const float* n_i = V + 3 * g.at(ri[0], ri[1], ri[2]);
               const float* n_j = V + 3 * g.at(rj[0], rj[1], rj[2]);
-              float r_ij[3] = {(float)(ri[0] - rj[0]), (float)(ri[1] - rj[1]), (float)(ri[2] - rj[2])};
-              {   // Normalize3 (lin3_utils.hpp:143-155)
-                const float len = std::sqrt(r_ij[0] * r_ij[0] + r_ij[1] * r_ij[1] + r_ij[2] * r_ij[2]);
-                if (len > 0) { const float inv = (float)(1.0 / (double)len); for (int d = 0; d < 3; d++) r_ij[d] *= inv; }
-                else { r_ij[0] = 1.0f; r_ij[1] = 0.0f; r_ij[2] = 0.0f; }
-              }
-              bool polarity_match;
               const int how = must_link_directions ? must_link_directions[at] : 2;   // 0 same, 1 opposite, 2 auto
-              if (how == 0) polarity_match = dot3(n_i, n_j) > 0;
-              else if (how == 1) polarity_match = dot3(n_i, n_j) < 0;
-              else {
-                const float ni_dot_rij = dot3(n_i, r_ij), nj_dot_rij = dot3(n_j, r_ij);
-                const float theta0 = (float)(M_PI / 4);
-                const float theta_i = std::asin(std::abs(ni_dot_rij)), theta_j = std::asin(std::abs(nj_dot_rij));
-                if (theta_i < theta0 && theta_j < theta0) polarity_match = dot3(n_i, n_j) > 0;
-                else polarity_match = (ni_dot_rij * nj_dot_rij <= 0);
-              }
+              float decides;
+              const int rule = vh::must_link_decider(n_i, n_j, ri, rj, how, &decides);   // connect_host.hpp
+              const bool polarity_match = vh::must_link_match(rule, decides);
               flip = polarity_match != (polarity[(size_t)basin_i] == polarity[(size_t)basin_j]);
             }
             for (size_t k = 0; k < cluster2basins[(size_t)gone].size(); k++) {
@@ -406,37 +393,21 @@ int vh::host_label_connected(const float* saliency, int64_t* labels, const float
       }
   for (i64 c = 0; c < n; c++)
     if (live(c)) labels[c] = basin2cluster[(size_t)labels[c]];
-  std::vector<long double> sizes((size_t)n_clusters, 0.0L);
   const float* W = voxel_weights;   // connect.hpp:1154-1183: the "size" of a cluster is then the sum of its voxels' weights
-  for (i64 c = 0; c < n; c++)
-    if (live(c)) sizes[(size_t)labels[c]] += W ? (long double)W[c] : 1.0L;
-  if (standardize) {   // outward orientation by the sign of sum (r - r_com).n (connect.hpp:1192-1290)
-    std::vector<std::array<long double, 3> > com((size_t)n_clusters, std::array<long double, 3>{{0.0L, 0.0L, 0.0L}});
-    for (int z = 0; z < g.nz; z++)
-      for (int y = 0; y < g.ny; y++)
-        for (int x = 0; x < g.nx; x++) {
-          const i64 c = g.at(x, y, z);
-          if (!live(c)) continue;
-          if (W) {   // connect.hpp:1211-1224: int * float products in float, summed in long double
-            com[(size_t)labels[c]][0] += x * W[c]; com[(size_t)labels[c]][1] += y * W[c]; com[(size_t)labels[c]][2] += z * W[c];
-          } else {
-            com[(size_t)labels[c]][0] += x; com[(size_t)labels[c]][1] += y; com[(size_t)labels[c]][2] += z;
-          }
-        }
-    for (i64 k = 0; k < n_clusters; k++)
-      for (int d = 0; d < 3; d++) com[(size_t)k][d] /= sizes[(size_t)k];
-    std::vector<long double> sum_dot((size_t)n_clusters, 0.0L);
-    for (int z = 0; z < g.nz; z++)
-      for (int y = 0; y < g.ny; y++)
-        for (int x = 0; x < g.nx; x++) {
-          const i64 c = g.at(x, y, z);
-          if (!live(c)) continue;
-          const i64 k = labels[c];
-          const float r[3] = {(float)(x - com[(size_t)k][0]), (float)(y - com[(size_t)k][1]), (float)(z - com[(size_t)k][2])};
-          long double delta_sum = (long double)dot3(r, V + 3 * c);
-          if (W) delta_sum *= W[c];
-          sum_dot[(size_t)k] += delta_sum;
-        }
+  // sizes, and with directions the outward orientation by the sign of sum (r - r_com).n (connect.hpp:1192-1290): the
+  // statements are in connect_host.hpp, where the settle paths of the graph entries find them too
+  std::vector<long double> sizes, sum_dot;
+  vh::cluster_moments(
+      [&](auto&& f) {
+        for (int z = 0; z < g.nz; z++)
+          for (int y = 0; y < g.ny; y++)
+            for (int x = 0; x < g.nx; x++) {
+              const i64 c = g.at(x, y, z);
+              if (live(c)) f(x, y, z, labels[c], V ? V + 3 * c : nullptr, W ? W[c] : 1.0f);
+            }
+      },
+      (size_t)n_clusters, W != nullptr, standardize, &sizes, &sum_dot);
+  if (standardize) {
     for (i64 c = 0; c < n; c++)
       if (live(c) && sum_dot[(size_t)labels[c]] < 0.0L) { V[3 * c] *= -1.0f; V[3 * c + 1] *= -1.0f; V[3 * c + 2] *= -1.0f; }
   }

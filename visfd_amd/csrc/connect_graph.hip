@@ -15,6 +15,9 @@
 // A call whose result the pop order decides (the reason bits of include/visfd_hip.h) is handed to the flood of
 // connect.cpp, from the seeds found here; the directions of unlabelled voxels are then put back, so the contract is the
 // same on every path.
+// Option connect_settle: must-links (nearest labelled voxel per location here, the merges on the host between (d) and
+// (e)), voxel weights and doubtful outward sums (the labelled voxels gathered for the host, which runs the flood's own
+// statements over them: connect_host.hpp) are then no reasons.
 #include <chrono>
 #include <limits>
 
@@ -261,7 +264,8 @@ __device__ __forceinline__ bool wave_uniform(int k, int* common) {
 }
 
 // res[k] = (provisional number << 1) | sign relative to the anchor, -1 where the listed voxel stays unlabelled; per cluster
-// the voxel count and the three coordinate sums, integers (one atomic per wave where the wave's voxels share a cluster)
+// the voxel count and the three coordinate sums, integers (one atomic per wave where the wave's voxels share a cluster;
+// sizes null: res alone)
 __global__ void __launch_bounds__(BLOCK)
 census_kernel(Params p, const int* __restrict__ list, int64_t count, unsigned* word, const int* __restrict__ aux,
               int* __restrict__ res, unsigned long long* __restrict__ sizes, unsigned long long* __restrict__ sums) {
@@ -282,6 +286,7 @@ census_kernel(Params p, const int* __restrict__ list, int64_t count, unsigned* w
       x = (unsigned)(i % p.nx); y = (unsigned)((i / p.nx) % p.ny); z = (unsigned)(i / (p.nx * p.ny));
     }
   }
+  if (!sizes) return;   // option connect_settle with voxel weights: the host forms the moments (the same for every thread)
   int common;
   if (wave_uniform(prov, &common)) {
     const unsigned long long c = wave_sum<unsigned long long>(prov >= 0 ? 1ull : 0ull);
@@ -359,6 +364,120 @@ write_kernel(const int* __restrict__ list, const int* __restrict__ res, int64_t 
   }
 }
 
+// ---- option connect_settle: must-links, voxel weights and doubtful outward sums without the flood ----------------------------
+constexpr int LINK_BATCH = 32;   // locations per pass over a workgroup's voxels
+constexpr int LINK_ITEMS = 4;    // listed voxels per thread
+constexpr unsigned long long NO_KEY = ~0ull;
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(v, o);
+    v = other < v ? other : v;
+  }
+  return v;
+}
+
+// FindNearestVoxel over the labelled voxels, for every must-link location at once: keys[l] = min of
+// (squared distance << 31) | voxel index, so among the closest the first in scan order wins, as "strictly closer wins"
+// does in the flood's scan.  want[l][3]: the location as the flood rounds it; the host has made sure that no squared
+// distance reaches 2^33.  Each thread keeps its voxels in registers and walks the locations, which are the same for the
+// whole wave; a wave's minimum goes to LDS, and a workgroup sends one atomic per location.
+__global__ void __launch_bounds__(BLOCK)
+nearest_kernel(Params p, const int* __restrict__ list, const int* __restrict__ res, int64_t count, const int* __restrict__ want,
+               int nloc, unsigned long long* __restrict__ keys) {
+  __shared__ unsigned long long best[LINK_BATCH];
+  int idx[LINK_ITEMS], x[LINK_ITEMS], y[LINK_ITEMS], z[LINK_ITEMS];
+  const int64_t base = (int64_t)blockIdx.x * (BLOCK * LINK_ITEMS) + threadIdx.x;
+  for (int j = 0; j < LINK_ITEMS; j++) {
+    const int64_t k = base + (int64_t)j * BLOCK;
+    idx[j] = -1;
+    x[j] = y[j] = z[j] = 0;
+    if (k < count && res[k] >= 0) {
+      const int i = list[k];
+      idx[j] = i;
+      x[j] = i % p.nx; y[j] = (i / p.nx) % p.ny; z[j] = i / (p.nx * p.ny);
+    }
+  }
+  for (int l0 = 0; l0 < nloc; l0 += LINK_BATCH) {
+    const int lend = nloc - l0 < LINK_BATCH ? nloc - l0 : LINK_BATCH;
+    if (threadIdx.x < LINK_BATCH) best[threadIdx.x] = NO_KEY;
+    __syncthreads();
+    for (int l = 0; l < lend; l++) {
+      const long long wx = want[3 * (l0 + l)], wy = want[3 * (l0 + l) + 1], wz = want[3 * (l0 + l) + 2];
+      unsigned long long key = NO_KEY;
+      for (int j = 0; j < LINK_ITEMS; j++) {
+        if (idx[j] < 0) continue;
+        const long long dx = wx - x[j], dy = wy - y[j], dz = wz - z[j];
+        const unsigned long long cand = ((unsigned long long)(dx * dx + dy * dy + dz * dz) << 31) | (unsigned long long)idx[j];
+        key = cand < key ? cand : key;
+      }
+      key = wave_min(key);
+      if ((threadIdx.x & 63) == 0 && key != NO_KEY) atomicMin(&best[l], key);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < lend && best[threadIdx.x] != NO_KEY) atomicMin(keys + l0 + threadIdx.x, best[threadIdx.x]);
+    __syncthreads();
+  }
+}
+
+// per location: the nearest voxel's code ((provisional number << 1) | sign to the anchor) and its direction as it came in
+__global__ void __launch_bounds__(BLOCK)
+link_fetch_kernel(int nloc, const unsigned long long* __restrict__ keys, unsigned* word, const int* __restrict__ aux,
+                  const float* __restrict__ V, int* __restrict__ code, float* __restrict__ dir) {
+  const int l = blockIdx.x * BLOCK + threadIdx.x;
+  if (l >= nloc) return;
+  int cd = -1;
+  float v[3] = {0.0f, 0.0f, 0.0f};
+  if (keys[l] != NO_KEY) {
+    const int i = (int)(keys[l] & 0x7fffffffull);
+    int sign;
+    const int a = aux[find_sign(word, i, &sign)];
+    if (a != NO_SEED) cd = a ^ sign;
+    if (V) for (int c = 0; c < 3; c++) v[c] = V[3 * (int64_t)i + c];
+  }
+  code[l] = cd;
+  for (int c = 0; c < 3; c++) dir[3 * l + c] = v[c];
+}
+
+// after the merges: map[k] = (the number cluster k's voxels carry from here on << 1) | whether they are negated
+__global__ void __launch_bounds__(BLOCK)
+remap_kernel(int64_t count, const int* __restrict__ map, int* __restrict__ res) {
+  const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (k >= count || res[k] < 0) return;
+  res[k] = map[res[k] >> 1] ^ (res[k] & 1);
+}
+
+// The labelled voxels of the clusters the host has to walk itself (wanted[k] != 0; null: all of them), compacted: voxel
+// index, cluster, the direction write_kernel would give it before the outward flip, and the weight where the weights are
+// on the device.  One atomic per wave; the order is whatever the waves make it, the host sorts by index.
+__global__ void __launch_bounds__(BLOCK)
+settle_gather_kernel(const int* __restrict__ list, const int* __restrict__ res, int64_t count,
+                     const unsigned char* __restrict__ wanted, const float* __restrict__ V, const float* __restrict__ W,
+                     unsigned long long cap, unsigned long long* __restrict__ counter, int* __restrict__ out_index,
+                     int* __restrict__ out_cluster, float* __restrict__ out_n, float* __restrict__ out_w) {
+  const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool has = k < count && res[k] >= 0 && (!wanted || wanted[res[k] >> 1]);
+  const unsigned long long holders = __ballot(has);
+  if (!holders) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((long long)holders) - 1;
+  unsigned long long first = 0;
+  if (lane == leader) first = atomicAdd(counter, (unsigned long long)__popcll(holders));
+  first = __shfl(first, leader);
+  if (!has) return;
+  const unsigned long long slot = first + (unsigned long long)__popcll(holders & ((1ull << lane) - 1ull));
+  if (slot >= cap) return;   // cannot happen: cap is the number of such voxels, or the length of the list
+  const int64_t i = list[k];
+  out_index[slot] = (int)i;
+  out_cluster[slot] = res[k] >> 1;
+  float v[3] = {0.0f, 0.0f, 0.0f};
+  if (V) {
+    for (int c = 0; c < 3; c++) v[c] = V[3 * i + c];
+    if (res[k] & 1) for (int c = 0; c < 3; c++) v[c] *= -1.0f;
+  }
+  for (int c = 0; c < 3; c++) out_n[3 * slot + c] = v[c];
+  out_w[slot] = W ? W[i] : 1.0f;
+}
+
 // ---- orchestration --------------------------------------------------------------------------------------------------------
 struct DevArrays {
   const float* S;
@@ -366,6 +485,8 @@ struct DevArrays {
   float* V;
   const float* T;
   int64_t* labels;
+  const float* W;        // voxel weights on the device (the _dev face), or
+  const float* W_host;   // on the host (the host-array face looks up the gathered voxels' weights there); both null: none
 };
 
 enum { MS_SEEDS = 0, MS_CLASSIFY, MS_VECTOR, MS_EDGES, MS_CLUSTERS, MS_DIRECTIONS, MS_COPY_IN, MS_COPY_OUT, MS_COUNT };
@@ -409,12 +530,126 @@ bool search_fits(const Call& c);
 int search_seeds(visfd_hip_ctx* ctx, const Call& c, const float* dev_saliency, const float* dev_mask, std::vector<int>* seed,
                  std::vector<float>* score);
 
+// The labelled voxels of the wanted clusters (null: all), for the host's walk.  cap: how many there can be; counter: a
+// word of the call's counters.
+int gather_for_host(visfd_hip_ctx* ctx, const DevArrays& d, const int* list, const int* res, int64_t count,
+                    const unsigned char* wanted, size_t nc, unsigned long long cap, unsigned long long* counter,
+                    std::vector<SettleVoxel>* vox) {
+  vox->clear();
+  if (nc == 0 || count == 0 || cap == 0) return VISFD_HIP_OK;
+  hipStream_t st = ctx->stream;
+  int* buf;
+  const size_t wanted_words = (nc + 3) / 4;
+  VH_TRY(ws(ctx, WS_CG_SETTLE, (size_t)(6 * cap) + wanted_words, &buf));
+  int *out_index = buf, *out_cluster = buf + cap;
+  float *out_n = reinterpret_cast<float*>(buf + 2 * cap), *out_w = reinterpret_cast<float*>(buf + 5 * cap);
+  unsigned char* dev_wanted = nullptr;
+  if (wanted) {
+    dev_wanted = reinterpret_cast<unsigned char*>(buf + 6 * cap);
+    VH_TRY(to_dev(ctx, dev_wanted, wanted, nc));
+  }
+  VH_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
+  settle_gather_kernel<<<grid_for(count, BLOCK), BLOCK, 0, st>>>(list, res, count, dev_wanted, d.V, d.W, cap, counter, out_index,
+                                                                 out_cluster, out_n, out_w);
+  VH_HIP(hipGetLastError());
+  unsigned long long m = 0;
+  VH_TRY(to_host(ctx, &m, counter, 1));
+  if (m > cap) m = cap;
+  if (m == 0) return VISFD_HIP_OK;
+  std::vector<int> hi(2 * (size_t)m);
+  std::vector<float> hn(3 * (size_t)m), hw((size_t)m);
+  VH_TRY(to_host(ctx, hi.data(), out_index, (size_t)m));
+  VH_TRY(to_host(ctx, hi.data() + m, out_cluster, (size_t)m));
+  VH_TRY(to_host(ctx, hn.data(), out_n, 3 * (size_t)m));
+  if (d.W) VH_TRY(to_host(ctx, hw.data(), out_w, (size_t)m));
+  vox->resize((size_t)m);
+  for (size_t k = 0; k < (size_t)m; k++) {
+    SettleVoxel& v = (*vox)[k];
+    v.index = hi[k];
+    v.cluster = hi[m + k];
+    for (int a = 0; a < 3; a++) v.n[a] = hn[3 * k + a];
+    v.w = d.W ? hw[k] : d.W_host ? d.W_host[v.index] : 1.0f;
+  }
+  return VISFD_HIP_OK;
+}
+
+// Must-links (option connect_settle), after the provisional clusters are numbered: the nearest labelled voxel of every
+// location on the device, the merges on the host (connect_graph_host.cpp: merge_links), then res, deepest, sizes and sums
+// speak of the merged clusters.  *reasons: ZERO_DOT where a contact cannot be decided without the flood.
+int settle_links(visfd_hip_ctx* ctx, const Call& c, const Params& p, const DevArrays& d, const int* list, int* res,
+                 int64_t count, unsigned* word, const int* aux, unsigned long long* cl, std::vector<int64_t>* deepest,
+                 std::vector<uint64_t>* sizes, std::vector<int64_t>* sums, unsigned* reasons) {
+  if (!c.must_link_group_sizes) return fail(VISFD_HIP_EINVAL, "label_connected: must-link group sizes missing");
+  std::vector<int> want;
+  link_locations(c, &want);   // its limits were looked at before any work started
+  const int nloc = (int)(want.size() / 3);
+  if (nloc == 0) return VISFD_HIP_OK;
+  const size_t nc = deepest->size();
+  if (nc == 0)   // the flood's FindNearestVoxel over an empty set (connect.cpp)
+    return fail(VISFD_HIP_EINVAL, "Error: No voxels clustered. Empty image. Your cluster criteria are too strict.\n"
+                                  "       (Attempting the find the nearest voxel from an empty set.)\n");
+  hipStream_t st = ctx->stream;
+  unsigned long long* keys;   // keys | want[3] | code | direction[3]
+  VH_TRY(ws(ctx, WS_CG_LINKS, (size_t)nloc * 5 + (nc + 1) / 2, &keys));   // 8 + 12 + 4 + 12 of 40 bytes per location; the map
+  int* dev_want = reinterpret_cast<int*>(keys + nloc);
+  int* dev_code = dev_want + 3 * nloc;
+  float* dev_dir = reinterpret_cast<float*>(dev_code + nloc);
+  int* dev_map = reinterpret_cast<int*>(keys + (size_t)nloc * 5);
+  VH_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * nloc, st));
+  VH_TRY(to_dev(ctx, dev_want, want.data(), want.size()));
+  nearest_kernel<<<grid_for(count, BLOCK * LINK_ITEMS), BLOCK, 0, st>>>(p, list, res, count, dev_want, nloc, keys);
+  link_fetch_kernel<<<grid_for(nloc, BLOCK), BLOCK, 0, st>>>(nloc, keys, word, aux, d.V, dev_code, dev_dir);
+  VH_HIP(hipGetLastError());
+  std::vector<unsigned long long> host_keys((size_t)nloc);
+  std::vector<int> host_code((size_t)nloc);
+  std::vector<float> host_dir(3 * (size_t)nloc);
+  VH_TRY(to_host(ctx, host_keys.data(), keys, (size_t)nloc));
+  VH_TRY(to_host(ctx, host_code.data(), dev_code, (size_t)nloc));
+  VH_TRY(to_host(ctx, host_dir.data(), dev_dir, 3 * (size_t)nloc));
+  std::vector<LinkContact> contact((size_t)nloc);
+  for (int l = 0; l < nloc; l++) {
+    if (host_keys[(size_t)l] == NO_KEY || host_code[(size_t)l] < 0) return fail(VISFD_HIP_EDEVICE, "label_connected_graph: a must-link location found no labelled voxel");
+    contact[(size_t)l].index = (int)(host_keys[(size_t)l] & 0x7fffffffull);
+    contact[(size_t)l].code = host_code[(size_t)l];
+    for (int a = 0; a < 3; a++) contact[(size_t)l].n[a] = host_dir[3 * (size_t)l + a];
+  }
+  std::vector<int> map;
+  *reasons |= merge_links(c, p.standardize != 0, contact, nc, &map);
+  if (*reasons) return VISFD_HIP_OK;
+  // the survivors in rank order; the sizes and sums of what they absorbed
+  std::vector<int> number(nc, -1);
+  std::vector<int64_t> kept;
+  for (size_t k = 0; k < nc; k++)
+    if ((size_t)(map[k] >> 1) == k) { number[k] = (int)kept.size(); kept.push_back((*deepest)[k]); }
+  std::vector<uint64_t> msizes(kept.size(), 0);
+  std::vector<int64_t> msums(3 * kept.size(), 0);
+  for (size_t k = 0; k < nc; k++) {
+    const int to = number[(size_t)(map[k] >> 1)];
+    msizes[(size_t)to] += (*sizes)[k];
+    for (int a = 0; a < 3; a++) msums[3 * (size_t)to + a] += (*sums)[3 * k + a];
+    map[k] = (to << 1) | (map[k] & 1);
+  }
+  VH_TRY(to_dev(ctx, dev_map, map.data(), nc));
+  remap_kernel<<<grid_for(count, BLOCK), BLOCK, 0, st>>>(count, dev_map, res);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipMemsetAsync(cl, 0, 10 * nc * sizeof(unsigned long long), st));   // stage (e) lays the merged clusters out anew
+  deepest->swap(kept);
+  sizes->swap(msizes);
+  sums->swap(msums);
+  return VISFD_HIP_OK;
+}
+
 // The device path on device arrays.  c: the call (its array pointers are not looked at); the lists go to c's host arrays.
 // *reasons != 0 on return: nothing final was written (labels hold the background fill), the caller hands over to the flood
 // with `seed` / `score`.
+// settle (option connect_settle): must-links, voxel weights and doubtful outward sums are no reasons; *settled gets the
+// bits of those that this call dealt with itself.
 int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk, std::vector<int>* seed,
-               std::vector<float>* score, Last* last, unsigned* reasons) {
+               std::vector<float>* score, Last* last, unsigned* reasons, bool settle, unsigned* settled) {
   const Params p = make_params(c);
+  *settled = 0;
+  const bool weighted = settle && (d.W || d.W_host);
+  const bool linked = settle && c.must_link_crds && c.must_link_ngroups > 0;
   const int64_t n = c.nx * c.ny * c.nz;
   hipStream_t st = ctx->stream;
   const bool minima = c.start_from_saliency_maxima == 0;
@@ -513,7 +748,7 @@ int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk
     seed_number_kernel<<<g, BLOCK, 0, st>>>(nseeds, code, seed_root, seed_sign, aux);
     VH_HIP(hipGetLastError());
   }
-  const size_t nc = deepest.size();
+  size_t nc = deepest.size();
   sizes.assign(nc, 0);
   sums.assign(3 * nc, 0);
   // per cluster: sizes | sums[3] (u64) | com[3] | sum (double) | final (int64) | B | any (unsigned)
@@ -521,18 +756,38 @@ int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk
   if (nc > 0) {
     VH_TRY(ws(ctx, WS_CG_CLUSTER, 10 * nc, &cl));
     VH_HIP(hipMemsetAsync(cl, 0, 10 * nc * sizeof(unsigned long long), st));
-    census_kernel<<<grid_for(count, BLOCK), BLOCK, 0, st>>>(p, list, count, word, aux, res, cl, cl + nc);
+    census_kernel<<<grid_for(count, BLOCK), BLOCK, 0, st>>>(p, list, count, word, aux, res, weighted ? nullptr : cl, cl + nc);
     VH_HIP(hipGetLastError());
-    std::vector<unsigned long long> host_cl(4 * nc);
-    VH_TRY(to_host(ctx, host_cl.data(), cl, 4 * nc));
-    for (size_t k = 0; k < nc; k++) sizes[k] = host_cl[k];
-    for (size_t k = 0; k < 3 * nc; k++) sums[k] = (int64_t)host_cl[nc + k];
+    if (!weighted) {
+      std::vector<unsigned long long> host_cl(4 * nc);
+      VH_TRY(to_host(ctx, host_cl.data(), cl, 4 * nc));
+      for (size_t k = 0; k < nc; k++) sizes[k] = host_cl[k];
+      for (size_t k = 0; k < 3 * nc; k++) sums[k] = (int64_t)host_cl[nc + k];
+    }
+  }
+  if (linked) {
+    VH_TRY(settle_links(ctx, c, p, d, list, res, count, word, aux, cl, &deepest, &sizes, &sums, reasons));
+    if (*reasons) return clk.mark(MS_CLUSTERS);
+    *settled |= VISFD_HIP_CONNECT_REASON_MUST_LINK;
+    nc = deepest.size();
   }
   VH_TRY(clk.mark(MS_CLUSTERS));
 
   // (e)
   std::vector<char> flip(nc, 0);
-  if (p.standardize && nc > 0) {
+  std::vector<float> weight_sizes;
+  if (weighted) {   // sizes, centres of mass and outward sums from the weights: the flood's statements over the labelled voxels
+    std::vector<long double> wsize, wsum;
+    std::vector<SettleVoxel> vox;
+    VH_TRY(gather_for_host(ctx, d, list, res, count, nullptr, nc, (unsigned long long)count, counters + 3, &vox));
+    settle_moments(c, &vox, nc, true, p.standardize != 0, &wsize, &wsum);
+    weight_sizes.resize(nc);
+    for (size_t k = 0; k < nc; k++) {
+      weight_sizes[k] = (float)wsize[k];
+      flip[k] = p.standardize && wsum[k] < 0.0L;
+    }
+    *settled |= VISFD_HIP_CONNECT_REASON_WEIGHTS;
+  } else if (p.standardize && nc > 0) {
     double* com = reinterpret_cast<double*>(cl + 4 * nc);
     double* sum = reinterpret_cast<double*>(cl + 7 * nc);
     unsigned* B = reinterpret_cast<unsigned*>(cl + 9 * nc);
@@ -545,6 +800,7 @@ int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk
     VH_HIP(hipGetLastError());
     std::vector<double> host_sum(nc);
     std::vector<unsigned> host_b(2 * nc);
+    std::vector<size_t> doubtful;
     VH_TRY(to_host(ctx, host_sum.data(), sum, nc));
     VH_TRY(to_host(ctx, host_b.data(), B, 2 * nc));
     for (size_t k = 0; k < nc; k++) {
@@ -553,12 +809,27 @@ int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk
       std::memcpy(&bk, &host_b[k], sizeof(float));
       // A device term differs from the flood's by less than 2^-21 B (r is rounded twice: one float ulp per component) and
       // the fp64 accumulation adds count * 2^-53: the sign is the flood's wherever |sum| > count * 2^-20 * B.
-      if (!(std::fabs(host_sum[k]) > (double)sizes[k] * 9.5367431640625e-07 * (double)bk)) *reasons |= VISFD_HIP_CONNECT_REASON_OUTWARD;
+      if (!(std::fabs(host_sum[k]) > (double)sizes[k] * 9.5367431640625e-07 * (double)bk)) {
+        if (settle) doubtful.push_back(k);
+        else *reasons |= VISFD_HIP_CONNECT_REASON_OUTWARD;
+      }
       flip[k] = host_sum[k] < 0.0;
     }
     if (*reasons) return clk.mark(MS_DIRECTIONS);
+    if (!doubtful.empty()) {   // the flood's own sum for these clusters, from their voxels in raster order: no guard needed
+      std::vector<unsigned char> wanted(nc, 0);
+      unsigned long long cap = 0;
+      for (size_t k : doubtful) { wanted[k] = 1; cap += sizes[k]; }
+      std::vector<long double> fsize, fsum;
+      std::vector<SettleVoxel> vox;
+      VH_TRY(gather_for_host(ctx, d, list, res, count, wanted.data(), nc, cap, counters + 3, &vox));
+      settle_moments(c, &vox, nc, false, true, &fsize, &fsum);
+      for (size_t k : doubtful) flip[k] = fsum[k] < 0.0L;
+      *settled |= VISFD_HIP_CONNECT_REASON_OUTWARD;
+    }
   }
-  const int rc = finish_lists(c, *seed, *score, deepest, sizes, &inv);
+  const int rc = weighted ? finish_lists(c, *seed, *score, deepest, weight_sizes, &inv)
+                          : finish_lists(c, *seed, *score, deepest, sizes, &inv);
   if (nc > 0) {
     int64_t* final = reinterpret_cast<int64_t*>(cl + 8 * nc);
     std::vector<int64_t> host_final(nc);
@@ -572,7 +843,8 @@ int run_device(visfd_hip_ctx* ctx, const Call& c, const DevArrays& d, Clock& clk
   return rc;
 }
 
-int record(visfd_hip_ctx* ctx, const Last& last) {
+int record(visfd_hip_ctx* ctx, const Last& last, unsigned settled = 0) {
+  ctx->connect_graph_settled = last.path == VISFD_HIP_CONNECT_GRAPH_DEVICE ? settled : 0;
   ctx->connect_graph[0] = last.path;
   ctx->connect_graph[1] = (int64_t)last.reasons;
   ctx->connect_graph[2] = last.n_valid;
@@ -586,8 +858,13 @@ bool search_fits(const Call& c) {
          c.ny <= VISFD_HIP_EXTREMA_MAX_NY_NZ && c.nz <= VISFD_HIP_EXTREMA_MAX_NY_NZ &&
          tile_count(c.nx, c.ny, c.nz) < ((i64)1 << 24);
 }
-unsigned reasons_before_work(const Call& c) {
+unsigned reasons_before_work(const Call& c, bool settle) {
   unsigned r = early_reasons(c, true);
+  if (settle) {   // option connect_settle: no reasons, but the device's nearest-voxel search has its reach
+    r &= ~(unsigned)(VISFD_HIP_CONNECT_REASON_MUST_LINK | VISFD_HIP_CONNECT_REASON_WEIGHTS);
+    std::vector<int> want;
+    r |= link_locations(c, &want);
+  }
   if (!search_fits(c)) r |= VISFD_HIP_CONNECT_REASON_LIMITS;
   return r;
 }
@@ -628,7 +905,9 @@ int visfd_hip_label_connected_graph(visfd_hip_ctx* ctx, const float* saliency, i
                   cluster_sizes, cluster_saliencies, cluster_capacity, voxel_weights, must_link_crds, must_link_group_sizes,
                   must_link_ngroups, must_link_directions};
   Last last;
-  unsigned reasons = reasons_before_work(c);
+  const bool settle = ctx->opt.connect_settle != 0;
+  unsigned settled = 0;
+  unsigned reasons = reasons_before_work(c, settle);
   VH_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)(nx * ny * nz);
   const Stage stg = {ctx, n};
@@ -658,8 +937,8 @@ int visfd_hip_label_connected_graph(visfd_hip_ctx* ctx, const float* saliency, i
   VH_TRY(stg.up(WS_H2D_3, tensor, &dt, 6));
   VH_TRY(ws(ctx, WS_H2D_4, n, &dl));
   VH_TRY(clk.mark(MS_COPY_IN));
-  const DevArrays d = {ds, dm, dv, dt, dl};
-  const int rc = run_device(ctx, c, d, clk, &seed, &score, &last, &reasons);
+  const DevArrays d = {ds, dm, dv, dt, dl, nullptr, voxel_weights};
+  const int rc = run_device(ctx, c, d, clk, &seed, &score, &last, &reasons, settle, &settled);
   if (rc != VISFD_HIP_OK && rc != VISFD_HIP_ECAPACITY) return rc;
   if (reasons) {
     const int frc = flood_keeping_unlabelled(c, &seed, &score);
@@ -675,7 +954,7 @@ int visfd_hip_label_connected_graph(visfd_hip_ctx* ctx, const float* saliency, i
   VH_HIP(hipStreamSynchronize(ctx->stream));
   VH_TRY(clk.mark(MS_COPY_OUT));
   last.path = VISFD_HIP_CONNECT_GRAPH_DEVICE;
-  record(ctx, last);
+  record(ctx, last, settled);
   return rc;
 }
 
@@ -703,19 +982,21 @@ int visfd_hip_label_connected_graph_dev(visfd_hip_ctx* ctx, const float* salienc
   Last last;
   std::vector<int> seed;
   std::vector<float> score;
-  unsigned reasons = reasons_before_work(c);
+  const bool settle = ctx->opt.connect_settle != 0;
+  unsigned settled = 0;
+  unsigned reasons = reasons_before_work(c, settle);
   int rc = VISFD_HIP_OK;
   bool have_seeds = false;
   if (reasons) {
     if ((have_seeds = search_fits(c))) VH_TRY(search_seeds(ctx, c, saliency, mask, &seed, &score));
   } else {
     have_seeds = true;
-    const DevArrays d = {saliency, mask, direction, tensor, labels};
-    rc = run_device(ctx, c, d, clk, &seed, &score, &last, &reasons);
+    const DevArrays d = {saliency, mask, direction, tensor, labels, voxel_weights, nullptr};
+    rc = run_device(ctx, c, d, clk, &seed, &score, &last, &reasons, settle, &settled);
     if (rc != VISFD_HIP_OK && rc != VISFD_HIP_ECAPACITY) return rc;
     if (!reasons) {
       last.path = VISFD_HIP_CONNECT_GRAPH_DEVICE;
-      record(ctx, last);
+      record(ctx, last, settled);
       return rc;
     }
   }
@@ -762,6 +1043,12 @@ int visfd_hip_label_connected_graph_last(visfd_hip_ctx* ctx, int* path, unsigned
   if (reasons) *reasons = last.reasons;
   if (n_valid) *n_valid = last.n_valid;
   if (n_undecided) *n_undecided = last.n_undecided;
+  return VISFD_HIP_OK;
+}
+
+int visfd_hip_label_connected_graph_last_settled(visfd_hip_ctx* ctx, unsigned* settled) {
+  VH_REQUIRE(ctx && settled, "null argument");
+  *settled = ctx->connect_graph_settled;
   return VISFD_HIP_OK;
 }
 

@@ -158,6 +158,36 @@ void number_clusters(const std::vector<int>& seed_root, std::vector<int>* prov_o
 int finish_lists(const Call& c, const std::vector<int>& seed_index, const std::vector<float>& seed_score,
                  const std::vector<int64_t>& deepest, const std::vector<uint64_t>& sizes, std::vector<int64_t>* inv);
 
+// the same from the flood's float sizes (voxel weights: the sizes are sums of weights)
+int finish_lists(const Call& c, const std::vector<int>& seed_index, const std::vector<float>& seed_score,
+                 const std::vector<int64_t>& deepest, const std::vector<float>& sizes, std::vector<int64_t>* inv);
+
+// ---- option connect_settle (device path only): what the host does from small arrays and from the labelled voxels -------------
+// The must-link locations as the flood rounds them, three ints per location in group order.  LIMITS where a location is
+// 2^20 voxels or more from the origin or could be 2^33 squared voxels or more from a voxel of the image: the device's
+// search key is (squared distance << 31) | voxel index.
+unsigned link_locations(const Call& c, std::vector<int>* want);
+
+struct LinkContact {   // the labelled voxel nearest to a location
+  int index;           // its voxel index
+  int code;            // (provisional cluster << 1) | its sign relative to the cluster's anchor
+  float n[3];          // its direction as it came in (zeros without directions)
+};
+// The flood's must-link block (connect.cpp) on cluster-level state: map[k] = (the provisional cluster that absorbed k, k
+// itself where none did) << 1 | whether k's voxels are negated on top of their sign to k's anchor.  Returns ZERO_DOT
+// where a contact's deciding quantity is a zero, which the flood reads by basin polarities the graph does not have.
+unsigned merge_links(const Call& c, bool standardize, const std::vector<LinkContact>& contact, size_t n_clusters,
+                     std::vector<int>* map);
+
+struct SettleVoxel {   // one labelled voxel gathered by the device, in no order
+  int index, cluster;
+  float n[3];          // direction with the sign to the anchor (and a must-link's negation) applied
+  float w;
+};
+// Orders the voxels by index and runs the flood's own statements over them (connect_host.hpp: cluster_moments).
+void settle_moments(const Call& c, std::vector<SettleVoxel>* voxels, size_t n_clusters, bool weighted, bool standardize,
+                    std::vector<long double>* sizes, std::vector<long double>* sum_dot);
+
 // The flood (connect.cpp) for a call whose result the pop order decides, the contract of the graph entries kept: the
 // directions of voxels that end up unlabelled or are masked are put back to their input bits.  seed_index / seed_score: the
 // ranked seeds where they are known already (both or neither).

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <unordered_map>
@@ -128,6 +129,90 @@ void number_clusters(const std::vector<int>& seed_root, std::vector<int>* prov_o
 
 int finish_lists(const Call& c, const std::vector<int>& seed, const std::vector<float>& seed_score,
                  const std::vector<int64_t>& deepest, const std::vector<uint64_t>& sizes, std::vector<int64_t>* inv) {
+  std::vector<float> as_float(sizes.size());   // an integer below 2^64 rounds to float as its long double does
+  for (size_t k = 0; k < sizes.size(); k++) as_float[k] = (float)sizes[k];
+  return finish_lists(c, seed, seed_score, deepest, as_float, inv);
+}
+
+unsigned link_locations(const Call& c, std::vector<int>* want) {
+  want->clear();
+  if (!(c.must_link_crds && c.must_link_ngroups > 0 && c.must_link_group_sizes)) return 0;
+  unsigned reasons = 0;
+  const int64_t dim[3] = {c.nx, c.ny, c.nz};
+  int64_t at = 0;
+  for (int64_t grp = 0; grp < c.must_link_ngroups; grp++)
+    for (int64_t loc = 0; loc < c.must_link_group_sizes[grp]; loc++, at++) {
+      long double reach = 0.0L;
+      for (int d = 0; d < 3; d++) {
+        const float crd = c.must_link_crds[3 * at + d];
+        if (!(std::fabs(crd) < 1048576.0f)) { reasons |= VISFD_HIP_CONNECT_REASON_LIMITS; want->push_back(0); continue; }
+        const int w = (int)std::floor(crd + 0.5);   // connect.cpp's rounding
+        want->push_back(w);
+        const long double far = (long double)std::max<int64_t>(std::llabs((long long)w), std::llabs((long long)(w - (dim[d] - 1))));
+        reach += far * far;
+      }
+      if (reach >= 8589934592.0L) reasons |= VISFD_HIP_CONNECT_REASON_LIMITS;   // 2^33
+    }
+  return reasons;
+}
+
+unsigned merge_links(const Call& c, bool standardize, const std::vector<LinkContact>& contact, size_t n_clusters,
+                     std::vector<int>* map) {
+  std::vector<int> cur(n_clusters);            // the cluster a provisional cluster belongs to by now: the smallest number in it
+  std::vector<signed char> q(n_clusters, 1);   // whether its voxels have been negated since
+  for (size_t k = 0; k < n_clusters; k++) cur[k] = (int)k;
+  unsigned reasons = 0;
+  int64_t at = 0;
+  for (int64_t grp = 0; grp < c.must_link_ngroups; grp++) {
+    const LinkContact* prev = nullptr;
+    for (int64_t loc = 0; loc < c.must_link_group_sizes[grp]; loc++, at++) {
+      const LinkContact& now = contact[(size_t)at];
+      const int pi = now.code >> 1;
+      if (prev && cur[(size_t)pi] != cur[(size_t)(prev->code >> 1)]) {
+        const int pj = prev->code >> 1;
+        const int keep = std::min(cur[(size_t)pi], cur[(size_t)pj]), gone = std::max(cur[(size_t)pi], cur[(size_t)pj]);
+        bool negate = false;
+        if (standardize) {
+          // F = the direction oriented to its provisional anchor, times q: what the flood's n * polarity is at this point.
+          // The flood decides from n = F * polarity; the polarities multiply out of every rule (negation commutes with
+          // float rounding) except at a zero, where the side the flood takes depends on them.
+          float fi[3], fj[3];
+          const bool ni = ((now.code & 1) != 0) != (q[(size_t)pi] < 0), nj = ((prev->code & 1) != 0) != (q[(size_t)pj] < 0);
+          for (int d = 0; d < 3; d++) { fi[d] = ni ? now.n[d] * -1.0f : now.n[d]; fj[d] = nj ? prev->n[d] * -1.0f : prev->n[d]; }
+          const int ri[3] = {(int)(now.index % c.nx), (int)((now.index / c.nx) % c.ny), (int)(now.index / (c.nx * c.ny))};
+          const int rj[3] = {(int)(prev->index % c.nx), (int)((prev->index / c.nx) % c.ny), (int)(prev->index / (c.nx * c.ny))};
+          float decides;
+          const int rule = must_link_decider(fi, fj, ri, rj, c.must_link_directions ? c.must_link_directions[at] : 2, &decides);
+          if (decides == 0.0f || decides != decides) reasons |= VISFD_HIP_CONNECT_REASON_ZERO_DOT;
+          negate = !must_link_match(rule, decides);
+        }
+        for (size_t k = 0; k < n_clusters; k++)
+          if (cur[k] == gone) {
+            cur[k] = keep;
+            if (negate) q[k] = (signed char)-q[k];
+          }
+      }
+      prev = &now;
+    }
+  }
+  map->resize(n_clusters);
+  for (size_t k = 0; k < n_clusters; k++) (*map)[k] = (cur[k] << 1) | (q[k] < 0 ? 1 : 0);
+  return reasons;
+}
+
+void settle_moments(const Call& c, std::vector<SettleVoxel>* voxels, size_t n_clusters, bool weighted, bool standardize,
+                    std::vector<long double>* sizes, std::vector<long double>* sum_dot) {
+  std::sort(voxels->begin(), voxels->end(), [](const SettleVoxel& a, const SettleVoxel& b) { return a.index < b.index; });
+  const int nx = (int)c.nx, ny = (int)c.ny;
+  cluster_moments(
+      [&](auto&& f) {
+        for (const SettleVoxel& v : *voxels) f(v.index % nx, (v.index / nx) % ny, v.index / (nx * ny), (int64_t)v.cluster, v.n, v.w);
+      },
+      n_clusters, weighted, standardize, sizes, sum_dot);
+}
+
+int finish_lists(const Call& c, const std::vector<int>& seed, const std::vector<float>& seed_score,
+                 const std::vector<int64_t>& deepest, const std::vector<float>& sizes, std::vector<int64_t>* inv) {
   const int64_t n_clusters = (int64_t)deepest.size();
   std::vector<int64_t> perm((size_t)n_clusters);
   inv->resize((size_t)n_clusters);

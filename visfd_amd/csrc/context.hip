@@ -56,6 +56,7 @@ const OptionDesc kOptions[] = {
     {"distance_general", &visfd_hip_options::distance_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
     {"connect_time", &visfd_hip_options::connect_time, nullptr},
+    {"connect_settle", &visfd_hip_options::connect_settle, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
     {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
     {"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr},
