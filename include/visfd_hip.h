@@ -86,7 +86,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * problem: visfd_hip_label_connected_graph[_dev|_host], _graph_last and
                                      * _graph_last_times; then DiscardOverlappingBlobs on the device:
                                      * visfd_hip_discard_overlapping_blobs_ctx, _dev, _last and
-                                     * _last_times) */
+                                     * _last_times; then the mesh voxeliser: visfd_hip_voxelize_mesh[_dev],
+                                     * visfd_hip_voxelize_last, _last_times, visfd_hip_voxelize_quantize_host and
+                                     * visfd_hip_mesh_edges_host) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -147,6 +149,10 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    (visfd_hip_discard_overlapping_blobs_last_times); default 0
  *   discard_overlap_max_rounds  rounds after which the host finishes such a list from the states reached; lists are
  *                    identical for every value; default 256
+ *   voxelize_time    1: visfd_hip_voxelize_mesh[_dev] time their three phases with events
+ *                    (visfd_hip_voxelize_last_times); default 0
+ *   voxelize_bisect  tests: the voxeliser finds the sample behind every crossing by bisection with the exact sign, never
+ *                    from its double-precision estimate; images are bit-identical either way; default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -1273,6 +1279,47 @@ int visfd_hip_blob_dog_slab(visfd_hip_slab*, const float* src_owned, int64_t nx,
                             float delta_sigma_over_sigma, float truncate_ratio, float minima_threshold, float maxima_threshold,
                             visfd_hip_blob* minima, int64_t minima_capacity, int64_t* n_minima,
                             visfd_hip_blob* maxima, int64_t maxima_capacity, int64_t* n_maxima);
+
+/* ---- voxelising a closed triangle mesh (bin/voxelize_mesh/voxelize_mesh.py) -----------------------------
+ * The reference asks vtk which grid samples lie inside the surface; here the answer is defined exactly, in integers.
+ *
+ * Quantisation (host, IEEE double, in this order): t = (double)v[d] / voxel_width; t = t - origin[d]; t = t * 1024.0;
+ * q = nearbyint(t) (ties to even) as int32: 1/1024 voxel units.  origin: the position of voxel 0, in voxels.
+ * VISFD_HIP_EINVAL for a non-finite vertex, |q| > 2^29, voxel_width zero or not finite.
+ *
+ * Inside rule.  Rays run along x; sample (ix, iy, iz) is the point 1024 * (ix, iy, iz); u = y, v = z.  For a triangle with
+ * quantised vertices A, B, C: area2 = (Bu-Au)(Cv-Av) - (Bv-Av)(Cu-Au); triangles with area2 == 0 are skipped; s =
+ * sign(area2).  For a directed edge a->b and the sample's (pu, pv): E = (bu-au)(pv-av) - (bv-av)(pu-au); sigma = sign(E) if
+ * E != 0, else -sign(bv-av) if that is not 0, else sign(bu-au) (the sample moved by (+eps, +eps^2)).  The triangle covers row
+ * (iy, iz) iff sigma of AB, BC and CA all equal s.  Its crossing is the rational x_c = Ax - (Ny (pu-Ay) + Nz (pv-Az)) / Nx
+ * with N = (B-A) x (C-A); k = floor(x_c / 1024) + 1 clamped to [0, nx].  inside(ix, iy, iz) is the parity of the
+ * crossings of row (iy, iz) with k <= ix.  dst: float32 [nz][ny][nx], 1.0 inside and 0.0 outside.
+ *
+ * vertices: float[n_vertices][3] (x, y, z) and triangles: int32[n_triangles][3] are HOST arrays on both faces; dst is a
+ * host pointer in the first form and a device pointer in the _dev form.  Both return with the stream idle.
+ * check_closed != 0: a mesh with boundary or non-manifold edges (visfd_hip_mesh_edges_host) is VISFD_HIP_EINVAL and the
+ * message names the counts.  Also VISFD_HIP_EINVAL: a triangle index out of range, images of 2^31 voxels or more,
+ * nx >= 2^19. */
+int visfd_hip_voxelize_mesh(visfd_hip_ctx*, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                            int64_t n_triangles, double voxel_width, const double origin[3], int64_t nx, int64_t ny,
+                            int64_t nz, int check_closed, float* dst);
+int visfd_hip_voxelize_mesh_dev(visfd_hip_ctx*, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                                int64_t n_triangles, double voxel_width, const double origin[3], int64_t nx, int64_t ny,
+                                int64_t nz, int check_closed, float* dst);
+/* The last voxelisation of the context: crossings (covered (triangle, row) pairs of rows inside the image), skipped
+ * triangles (area2 == 0), odd_rows (rows whose total crossing parity is odd: 0 for every closed mesh), inside voxels;
+ * -1 each before the first call. */
+int visfd_hip_voxelize_last(visfd_hip_ctx*, int64_t stats[4]);
+/* option voxelize_time: milliseconds the last voxelisation spent zeroing its toggle words, in the scatter over the
+ * triangles, and in the fill of the image */
+int visfd_hip_voxelize_last_times(visfd_hip_ctx*, float ms[3]);
+/* the quantisation above: q receives int32[n_vertices][3] */
+int visfd_hip_voxelize_quantize_host(const float* vertices, int64_t n_vertices, double voxel_width, const double origin[3],
+                                     int32_t* q);
+/* The census of undirected edges: those used by exactly one triangle (boundary) and by more than two (non-manifold).
+ * VISFD_HIP_EINVAL for an index outside [0, n_vertices). */
+int visfd_hip_mesh_edges_host(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, int64_t* boundary_edges,
+                              int64_t* nonmanifold_edges);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 //   Filter3D     lib/visfd/filter3d.hpp:37-530;  GenFilterGenGauss3D :546-638;  LocalFluctuations[ByRadius] :1698-1926
 //   CompactMultiChannelImage3D  lib/visfd/multichannel_image3d.hpp:41-204
 //   Threshold2, Threshold4, SelectIntensityRange, SelectIntensityRangeGauss  lib/threshold/threshold.hpp:52-258
+//   VoxelizeMesh  what bin/voxelize_mesh/voxelize_mesh.py computes with vtk (no C++ counterpart in the reference)
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
 #ifndef VISFD_HIP_HPP
 #define VISFD_HIP_HPP
@@ -1053,6 +1054,27 @@ void DrawSpheres(int const image_size[3], Scalar*** aaafDest, Scalar const* cons
                         "    (Did you use the \"-w\" argument?)\n"
                         "--------------------------------------------------------------------------=---\n"
                      << std::endl;
+}
+
+// ---- voxelising a closed mesh: what bin/voxelize_mesh/voxelize_mesh.py asks vtk, by the exact rule of visfd_hip.h --------
+// aaafDest[iz][iy][ix] becomes 1 where sample (ix, iy, iz) lies inside the mesh and 0 elsewhere.  vertices are in physical
+// units (divided by voxel_width), origin is the position of voxel 0 in voxels (null: 0, 0, 0); check_closed refuses a
+// surface with boundary or non-manifold edges, as the script's check_surface=True does.  A null ctx is the shim's own.
+inline void VoxelizeMesh(visfd_hip_ctx* ctx, int const image_size[3], const std::vector<std::array<float, 3> >& vertices,
+                         const std::vector<std::array<int, 3> >& triangles, float*** aaafDest, double voxel_width = 1.0,
+                         const double* origin = nullptr, bool check_closed = true) {
+  hip_detail::require_contiguous(aaafDest, image_size);
+  std::vector<float> v(3 * vertices.size());
+  std::vector<int32_t> t(3 * triangles.size());
+  for (size_t i = 0; i < vertices.size(); i++)
+    for (int d = 0; d < 3; d++) v[3 * i + d] = vertices[i][d];
+  for (size_t i = 0; i < triangles.size(); i++)
+    for (int d = 0; d < 3; d++) t[3 * i + d] = triangles[i][d];
+  const double zero[3] = {0.0, 0.0, 0.0};
+  hip_detail::check(visfd_hip_voxelize_mesh(ctx ? ctx : hip_detail::context(), v.empty() ? nullptr : v.data(),
+                                            (int64_t)vertices.size(), t.empty() ? nullptr : t.data(), (int64_t)triangles.size(),
+                                            voxel_width, origin ? origin : zero, image_size[0], image_size[1], image_size[2],
+                                            check_closed ? 1 : 0, hip_detail::flat(aaafDest)));
 }
 
 // ---- blob list post-processing: lib/visfd/visfd_utils.hpp:49-55,95-118; feature.hpp:519-616,720-969 ------

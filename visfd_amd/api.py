@@ -113,6 +113,9 @@ _LABEL_CONNECTED_EX = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_floa
                        C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                        _i64, _vp]   # visfd_hip_label_connected_ex
 
+# ctx, vertices, n_vertices, triangles, n_triangles, voxel_width, origin, nx, ny, nz, check_closed, dst
+_VOXELIZE = [_vp, _vp, _i64, _vp, _i64, C.c_double, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, _vp]
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -289,6 +292,13 @@ _SIGS = {
                                                          C.c_float, C.c_int, C.c_int]),
     "visfd_hip_discard_overlapping_blobs_last": (C.c_int, [_vp, C.POINTER(_i64)]),
     "visfd_hip_discard_overlapping_blobs_last_times": (C.c_int, [_vp, _fp]),
+    # VoxelizeMesh (csrc/voxelize.hip)
+    "visfd_hip_voxelize_mesh": (C.c_int, _VOXELIZE),
+    "visfd_hip_voxelize_mesh_dev": (C.c_int, _VOXELIZE),
+    "visfd_hip_voxelize_last": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "visfd_hip_voxelize_last_times": (C.c_int, [_vp, _fp]),
+    "visfd_hip_voxelize_quantize_host": (C.c_int, [_vp, _i64, C.c_double, C.POINTER(C.c_double), _vp]),
+    "visfd_hip_mesh_edges_host": (C.c_int, [_vp, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
     "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -864,6 +874,37 @@ def _handle(ctx):
     return None if ctx is None else ctx._h
 
 
+def _mesh(vertices, triangles):
+    """(n, 3) float32 vertices (x, y, z) and (m, 3) int32 triangles as C arrays."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    return v, t
+
+
+def _d3(v):
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
+def voxelize_quantize_host(vertices, voxel_width=1.0, origin=(0, 0, 0)):
+    """The voxeliser's quantisation (visfd_hip_voxelize_quantize_host): nearbyint((v / voxel_width - origin) * 1024) in
+    double, as int32 (n, 3); refused when a vertex is not finite or ends beyond 2^29, or the width is zero."""
+    L = load_library()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    q = np.empty(v.shape, np.int32)
+    _chk_host(L, L.visfd_hip_voxelize_quantize_host(v.ctypes.data, len(v), float(voxel_width), _d3(origin), q.ctypes.data))
+    return q
+
+
+def mesh_edges_host(triangles, n_vertices):
+    """visfd_hip_mesh_edges_host -> (boundary edges, non-manifold edges): undirected edges used by exactly one triangle, and
+    by more than two."""
+    L = load_library()
+    t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    nb, nn = _i64(), _i64()
+    _chk_host(L, L.visfd_hip_mesh_edges_host(t.ctypes.data, len(t), int(n_vertices), C.byref(nb), C.byref(nn)))
+    return int(nb.value), int(nn.value)
+
+
 def find_spheres_host(crds, sphere_crds, sphere_diameters):
     """FindSpheres (visfd_utils.hpp:271-359) by the host walk: for every point 1 + the index of the LAST sphere that holds
     it, 0 when none does -> int64 array."""
@@ -1137,6 +1178,29 @@ class Context:
                                                  p[3], n, float(background_offset), float(background_rescale),
                                                  int(background_normalize), int(foreground_normalize), C.byref(outside)))
         return (dst, bool(outside.value)) if want_outside else dst
+
+    def voxelize_mesh(self, vertices, triangles, shape, voxel_width=1.0, origin=(0, 0, 0), check_closed=True):
+        """Which samples of an image of `shape` (nz, ny, nx) lie inside the closed triangle mesh (the job of the reference's
+        voxelize_mesh.py, by the exact rule of include/visfd_hip.h): vertices (n, 3) float32 (x, y, z) in physical units,
+        triangles (m, 3) int32, origin = the position of voxel 0 in voxels.  -> float32 [nz, ny, nx] of 0 and 1."""
+        nz, ny, nx = [int(s) for s in shape]
+        v, t = _mesh(vertices, triangles)
+        dst = np.empty((nz, ny, nx), np.float32)
+        self._chk(self._L.visfd_hip_voxelize_mesh(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t), float(voxel_width),
+                                                  _d3(origin), nx, ny, nz, int(bool(check_closed)), _np(dst)))
+        return dst
+
+    def voxelize_last(self):
+        """(crossings, skipped triangles, odd rows, inside voxels) of the last voxelize_mesh[_dev]."""
+        s = (_i64 * 4)()
+        self._chk(self._L.visfd_hip_voxelize_last(self._h, s))
+        return tuple(int(x) for x in s)
+
+    def voxelize_last_times(self):
+        """(zero fill, scatter, fill) milliseconds of the last voxelize_mesh[_dev] under the option voxelize_time."""
+        ms = (C.c_float * 3)()
+        self._chk(self._L.visfd_hip_voxelize_last_times(self._h, ms))
+        return tuple(ms)
 
     def draw_regions(self, image, regions, mask=None, negative_means_subtract=False):
         """DrawRegions (draw.hpp:90-224) on a copy of `image`: regions is a list of (REGION_RECT, (xmin, xmax, ymin, ymax,
@@ -1773,6 +1837,14 @@ class Context:
                                                      int(background_normalize), int(foreground_normalize),
                                                      C.byref(outside)))
         return bool(outside.value)
+
+    def voxelize_mesh_dev(self, dst, vertices, triangles, voxel_width=1.0, origin=(0, 0, 0), check_closed=True):
+        """voxelize_mesh into a device tensor [nz, ny, nx] (the mesh lists are host arrays); returns with the stream idle."""
+        nz, ny, nx = dst.shape
+        v, t = _mesh(vertices, triangles)
+        self._chk(self._L.visfd_hip_voxelize_mesh_dev(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t),
+                                                      float(voxel_width), _d3(origin), nx, ny, nz, int(bool(check_closed)),
+                                                      _dev(dst)))
 
     def draw_last_times(self):
         """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""

@@ -91,6 +91,8 @@ enum Slot {
                                    // in bucket order, sorted scores, states, the two lists of undecided blobs
   WS_OVL_CELLS,                    // ... the buckets' offsets, one word per centre cell plus one
   WS_OVL_TEMP,                     // ... the reduction words, the counters, and the sort's and the scan's temporary storage
+  WS_VOX_TOGGLE,                   // VoxelizeMesh (csrc/voxelize.hip): the toggle volume, nx + 1 bits per row (iy, iz) in 32-bit words
+  WS_VOX_MESH,                     // ... the quantised vertices, the triangles, the tiled triangles' ids and running item counts, the counters
   WS_NSLOTS
 };
 
@@ -135,6 +137,8 @@ struct visfd_hip_options {
   int connect_settle = 0;   // 1: visfd_hip_label_connected_graph[_dev] settle must-links, voxel weights and doubtful outward sums on the
                             //    device path instead of handing the call to the flood (csrc/connect_graph.hip)
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
+  int voxelize_bisect = 0;  // tests: VoxelizeMesh finds every crossing's sample by bisection with the exact sign, never from the double estimate
+  int voxelize_time = 0;    // 1: VoxelizeMesh times its zero fill, scatter and fill with events (tools/voxelize_time.py)
   int debug = 0;
 };
 
@@ -165,6 +169,8 @@ struct visfd_hip_ctx {
   int64_t discard_overlap_last[8] = {-1, 0, 0, 0, 0, 0, 0, 0};   // the last visfd_hip_discard_overlapping_blobs_ctx / _dev (visfd_hip_discard_overlapping_blobs_last)
   float discard_overlap_ms[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};   // option discard_overlap_time: reduction, ranking and records, buckets, rounds, compaction
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
+  int64_t voxelize_stats[4] = {-1, -1, -1, -1};   // the last VoxelizeMesh: crossings, skipped triangles, odd rows, inside voxels
+  float voxelize_ms[3] = {-1.0f, -1.0f, -1.0f};   // option voxelize_time: zero fill, scatter, fill of the last VoxelizeMesh
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
   int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test

@@ -55,6 +55,8 @@ const OptionDesc kOptions[] = {
     {"median_general", &visfd_hip_options::median_general, nullptr},
     {"distance_general", &visfd_hip_options::distance_general, nullptr},
     {"draw_time", &visfd_hip_options::draw_time, nullptr},
+    {"voxelize_time", &visfd_hip_options::voxelize_time, nullptr},
+    {"voxelize_bisect", &visfd_hip_options::voxelize_bisect, nullptr},
     {"connect_time", &visfd_hip_options::connect_time, nullptr},
     {"connect_settle", &visfd_hip_options::connect_settle, nullptr},
     {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
