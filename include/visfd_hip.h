@@ -88,7 +88,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * visfd_hip_discard_overlapping_blobs_ctx, _dev, _last and
                                      * _last_times; then the mesh voxeliser: visfd_hip_voxelize_mesh[_dev],
                                      * visfd_hip_voxelize_last, _last_times, visfd_hip_voxelize_quantize_host and
-                                     * visfd_hip_mesh_edges_host) */
+                                     * visfd_hip_mesh_edges_host; then the flat ball as a threshold,
+                                     * visfd_hip_flat_ball_dsq_max) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -121,6 +122,12 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *   blob_test_cap    tests: capacity the pipelined blob scan pretends to have (exercises its overflow path)
  *   morph_general    1: morphology always walks the element entry by entry (csrc/morph.hip), never takes the flat X-run
  *                    kernel; results are bit-identical either way
+ *   morph_levels     visfd_hip_morph_sphere[_dev] with bmax == 0 on an image of at most two levels (see there) as a threshold
+ *                    on the exact distance map (csrc/morph_levels.hip), any radius: 0 never; 1 (default) when eligible and
+ *                    ceil(radius) > 10 (beyond the X-run kernel) or radius >= R0 = 5 (R0: the smallest radius timed at which
+ *                    it beats the X-run kernel in dilate, erode and open on 1024^3, profiles/morph_levels_time.txt; below
+ *                    it no census runs); 2 whenever eligible;
+ *                    results are bit-identical for every value
  *   filter3d_general 1: the general 3-D filter always walks the table entry by entry (csrc/filter3d.hip), never takes the
  *                    LDS-tiled kernel; results are bit-identical either way
  *   median_general   1: the median filter always walks the footprint in global memory (csrc/median.hip), never takes the
@@ -333,11 +340,22 @@ int visfd_hip_draw_regions_dev(visfd_hip_ctx*, float* dst, const float* mask, in
  * written (cap == 0: count only; 0 < cap < n: VISFD_HIP_ECAPACITY).  ceil(max(radius, radius_max)) must be <= 128. */
 int visfd_hip_sphere_structure(float radius, float radius_max, float bmax, int* dxyz, float* b, int64_t cap,
                                int64_t* n);
+/* The flat ball (bmax == 0) as a threshold: offset (ix, iy, iz) is in the element exactly when ix^2 + iy^2 + iz^2 <= *t,
+ * the largest integer whose double square root, rounded to float, is <= radius (the element's test is monotone in the
+ * squared length, and its cube never cuts the ball).  Host arithmetic, no table; any finite radius >= 0. */
+int visfd_hip_flat_ball_dsq_max(float radius, int64_t* t);
 /* op = VISFD_HIP_MORPH_*, with the sphere element above.  The reference library's semantics: voxels with mask == 0 are
  * not written (dst keeps its values there); neighbours with mask == 0 or outside the image are skipped; the top-hats
  * read dst.  A dst that overlaps src or mask is VISFD_HIP_EINVAL.  The temporaries live in the context's workspace.
  * Flat elements made of symmetric X-runs of half-length <= 10 (every flat ball of radius < 11) run on the X-run kernel,
- * everything else on the general element walk; both give the reference's bits. */
+ * everything else on the general element walk; both give the reference's bits.
+ * Two-level images (option morph_levels): with bmax == 0, radius finite and >= 0, radius_max finite, option morph_general
+ * 0 and nx + ny + nz <= 46340, a source whose voxels with mask != 0 hold at most two distinct bit patterns, none a NaN
+ * and the two comparing unequal (so not +0 / -0), needs no element: the flat ball is {d^2 <= visfd_hip_flat_ball_dsq_max
+ * (radius)}, a threshold on the exact squared distance to the nearest voxel of a level (csrc/distance.hip).  A census
+ * kernel decides (its few words are all the host reads back); the cost is O(voxels) at any radius, the element is neither
+ * built nor uploaded, radii beyond 128 are accepted, and the bits are the element walk's.  A call that is not eligible
+ * runs as described above, error codes included. */
 int visfd_hip_morph_sphere(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
                            int64_t nx, int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax);
 int visfd_hip_morph_sphere_dev(visfd_hip_ctx*, const float* src, float* dst, const float* mask,
@@ -351,6 +369,7 @@ int visfd_hip_morph_table_dev(visfd_hip_ctx*, const float* src, float* dst, cons
 /* the kernel the context's last morphology call ran: VISFD_HIP_MORPH_PATH_* (-1 before the first call) */
 #define VISFD_HIP_MORPH_PATH_GENERAL 0    /* morph_kernel: the element walked entry by entry */
 #define VISFD_HIP_MORPH_PATH_XRUNS 1      /* morph_runs_kernel: window maxima of X-runs, zero-sign fix-up of erosions */
+#define VISFD_HIP_MORPH_PATH_LEVELS 2     /* csrc/morph_levels.hip: every step of the call a threshold on the distance map */
 int visfd_hip_morph_last_path(visfd_hip_ctx*, int* path);
 
 /* ---- m1b: the median filter, Median / MedianSphere (lib/visfd/filter3d.hpp:1577-1674) -------------- */

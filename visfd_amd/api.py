@@ -23,7 +23,7 @@ DECREASING_EIVALS = 1
 
 # grayscale morphology ops (VISFD_HIP_MORPH_*, lib/visfd/morphology.hpp:134-597)
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_TOP_HAT_WHITE, MORPH_TOP_HAT_BLACK = range(6)
-MORPH_PATH_GENERAL, MORPH_PATH_XRUNS = 0, 1   # visfd_hip_morph_last_path
+MORPH_PATH_GENERAL, MORPH_PATH_XRUNS, MORPH_PATH_LEVELS = 0, 1, 2   # visfd_hip_morph_last_path
 MEDIAN_PATH_GENERAL, MEDIAN_PATH_TILED = 0, 1   # visfd_hip_median_last_path
 FILTER3D_PATH_GENERAL, FILTER3D_PATH_TILED = 0, 1   # visfd_hip_filter3d_last_path
 DISTANCE_PATH_GENERAL, DISTANCE_PATH_TRANSFORM = 0, 1   # visfd_hip_distance_last_path
@@ -148,6 +148,7 @@ _SIGS = {
     "visfd_hip_draw_regions_dev": (C.c_int, _DRAW_REGIONS),
     "visfd_hip_draw_last_times": (C.c_int, [_vp, _fp]),
     "visfd_hip_sphere_structure": (C.c_int, [C.c_float, C.c_float, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64)]),
+    "visfd_hip_flat_ball_dsq_max": (C.c_int, [C.c_float, C.POINTER(C.c_int64)]),
     "visfd_hip_morph_sphere": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
     "visfd_hip_morph_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
     "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
@@ -495,6 +496,15 @@ def sphere_structure(radius, radius_max=0.0, bmax=0.0):
     _chk_host(L, L.visfd_hip_sphere_structure(float(radius), float(radius_max), float(bmax), d.ctypes.data_as(_ip),
                                               b.ctypes.data_as(_fp), len(b), C.byref(n)))
     return d[:n.value].copy(), b[:n.value].copy()
+
+
+def flat_ball_dsq_max(radius):
+    """The flat ball of DilateSphere / ErodeSphere (bmax == 0) as a threshold: offset (dx, dy, dz) is in sphere_structure(radius)
+    exactly when dx^2 + dy^2 + dz^2 <= this integer.  Host arithmetic, any finite radius >= 0."""
+    L = load_library()
+    t = C.c_int64()
+    _chk_host(L, L.visfd_hip_flat_ball_dsq_max(float(radius), C.byref(t)))
+    return int(t.value)
 
 
 def median_footprint(radius):
@@ -1570,7 +1580,8 @@ class Context:
         return p.value
 
     def morph_last_path(self):
-        """The kernel the last morphology call ran: MORPH_PATH_GENERAL or MORPH_PATH_XRUNS (-1 before the first)."""
+        """What the last morphology call ran: MORPH_PATH_GENERAL, MORPH_PATH_XRUNS or MORPH_PATH_LEVELS (the distance-map path
+        of two-level images, option morph_levels); -1 before the first."""
         p = C.c_int()
         self._chk(self._L.visfd_hip_morph_last_path(self._h, C.byref(p)))
         return p.value

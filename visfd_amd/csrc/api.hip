@@ -716,6 +716,10 @@ int visfd_hip_sphere_structure(float radius, float radius_max, float bmax, int* 
 int visfd_hip_morph_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
                                int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax) {
   VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
+  // an image of at most two levels needs no element (csrc/morph_levels.hip): decided before one is built, at any radius
+  bool levels = false;
+  VH_TRY(morph_levels_try(ctx, src, dst, mask, nx, ny, nz, op, radius, radius_max, bmax, &levels));
+  if (levels) return VISFD_HIP_OK;
   int64_t n = 0;
   VH_TRY(visfd_hip_sphere_structure(radius, radius_max, bmax, nullptr, nullptr, 0, &n));
   std::vector<int> dxyz((size_t)(3 * n + 3));

@@ -124,6 +124,8 @@ struct visfd_hip_options {
   int tv_max_wg = 0;        // cap on the persistent grid (0: fill the chip); tests use it to make workgroups claim many units
   int64_t blob_test_cap = 0;   // pretend the pipelined blob scan's buffers hold this many entries (0: off)
   int morph_general = 0;    // 1: morphology always on the general element walk (csrc/morph.hip), never on the flat X-run path
+  int morph_levels = 1;     // flat balls on images of at most two levels as a threshold on the distance map (csrc/morph_levels.hip):
+                            // 0 never, 1 when eligible and ceil(radius) > 10 or radius >= 5 (R0, profiles/morph_levels_time.txt), 2 whenever eligible
   int filter3d_general = 0; // 1: the general 3-D filter always on the entry walk (csrc/filter3d.hip), never on the tiled kernel
   int median_general = 0;   // 1: the median filter always on the general footprint walk (csrc/median.hip), never on the LDS-tiled kernel
   int distance_general = 0; // 1: distance maps by the brute-force walks (csrc/distance.hip), never by the separable transform
@@ -382,6 +384,29 @@ int dev_nan_masked(visfd_hip_ctx* ctx, const float* src, const float* mask, floa
 int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, MorphElem* el);
 int morph_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
               MorphElem el);
+
+// morph_levels.hip: flat balls on images of at most two levels.  The ball of DilateSphere with bmax == 0 is {d^2 <= T}:
+// host_flat_ball_dsq_max is T, the largest integer whose double square root, rounded to float, is <= radius (radius
+// finite and >= 0).  morph_levels_try decides whether a visfd_hip_morph_sphere[_dev] call is eligible (options, radii,
+// dimensions, then the level census on the device) and, if so, runs it and sets *taken; otherwise it changes nothing.
+i64 host_flat_ball_dsq_max(float radius);
+constexpr float MORPH_LEVELS_R0 = 5.0f;   // option morph_levels = 1: the path is taken from this radius on (profiles/morph_levels_time.txt)
+int morph_levels_try(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
+                     float radius, float radius_max, float bmax, bool* taken);
+// What the last pass of the transform writes on that path instead of the squared distance, at voxels with mask != 0
+// (the others: NaN when nan_masked, else untouched): v = dsq <= t ? near : far (bit patterns), then dst = v, dst - v
+// (epi 1) or v - dst (epi 2) as morph.hip's epilogue does.
+struct LevelsEpilogue {
+  float* dst;
+  const float* mask;
+  int t;
+  unsigned near_bits, far_bits;
+  int epi, nan_masked;
+};
+// distance.hip: the row pass and the y pass of the transform into dsq with the voxels `src == level` (mask != 0) as
+// seeds, then the z pass with that epilogue; dsq is scratch afterwards.  nx + ny + nz <= 46340.
+int dev_distance_levels(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, float level,
+                        int32_t* dsq, const LevelsEpilogue& e);
 
 // median.hip: a footprint as the median kernels see it (the entries themselves are in slot WS_MEDIAN_TAB): the entry
 // count, the bounding box of the offsets and the extent W x H x D of the tiled kernel's LDS image for that box.

@@ -51,6 +51,7 @@ const OptionDesc kOptions[] = {
     {"tv_poison", &visfd_hip_options::tv_poison, nullptr}, {"tv_no_fold", &visfd_hip_options::tv_no_fold, nullptr}, {"tv_exact_tiled", &visfd_hip_options::tv_exact_tiled, nullptr}, {"tv_reserve_wg", &visfd_hip_options::tv_reserve_wg, nullptr},
     {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
     {"morph_general", &visfd_hip_options::morph_general, nullptr},
+    {"morph_levels", &visfd_hip_options::morph_levels, nullptr},
     {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
     {"median_general", &visfd_hip_options::median_general, nullptr},
     {"distance_general", &visfd_hip_options::distance_general, nullptr},

@@ -118,15 +118,37 @@ __device__ __forceinline__ i64 point_dsq(int x, int y, int z, const int* p) {
 // entries of 64 lanes: {vertex | start << 16, value at the vertex}.
 // FINAL (the z pass: u / xchunks is y, the position along the axis is z): the minimum with the first npts <= LDS_POINTS
 // listed points outside the image.
-template <bool FINAL>
-__global__ void __launch_bounds__(BLOCK)
-envelope_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step, i64 outer_stride, int nx, i64 nunits,
-                int xchunks, int cap, const int* __restrict__ pts, int npts) {
-  __shared__ int spts[3 * LDS_POINTS];
-  if (FINAL) {
-    for (int k = threadIdx.x; k < 3 * npts; k += BLOCK) spts[k] = pts[k];
-    __syncthreads();
+// What a pass does with the value d of position `off` of the column that starts at col, a place inside dsq: StoreDsq
+// writes it back.  An Out with ALWAYS visits the columns without a parabola too (d = cap everywhere).
+struct StoreDsq {
+  static constexpr bool ALWAYS = false;
+  __device__ __forceinline__ void operator()(int* __restrict__ col, const int* dsq, i64 off, int d) const { col[off] = d; }
+};
+// The last pass of two-level morphology (csrc/morph_levels.hip): the float result instead of the distance, which is
+// not stored.  The arithmetic is morph_store's (csrc/morph.hip).
+struct StoreLevels {
+  static constexpr bool ALWAYS = true;
+  LevelsEpilogue e;
+  __device__ __forceinline__ void operator()(int* __restrict__ col, const int* dsq, i64 off, int d) const {
+    const i64 i = (col - dsq) + off;
+    if (e.mask && e.mask[i] == 0.0f) {
+      if (e.nan_masked) e.dst[i] = NAN;
+      return;
+    }
+    const float cur = __uint_as_float(d <= e.t ? e.near_bits : e.far_bits);
+    float v = cur;
+    if (e.epi == 1)
+      v = e.dst[i] - cur;
+    else if (e.epi == 2)
+      v = cur - e.dst[i];
+    e.dst[i] = v;
   }
+};
+
+template <bool FINAL, class Out>
+__device__ __forceinline__ void envelope_pass(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step,
+                                              i64 outer_stride, int nx, i64 nunits, int xchunks, int cap,
+                                              const int* spts, int npts, const Out& out) {
   const int lane = threadIdx.x & (WAVE - 1);
   const i64 wave = (i64)blockIdx.x * WAVES + (threadIdx.x >> 6);
   const i64 nwaves = (i64)gridDim.x * WAVES;
@@ -176,7 +198,7 @@ envelope_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step
       }
       }
     }
-    if (q < 0 && !(FINAL && npts > 0)) continue;   // the column holds cap everywhere already
+    if (q < 0 && !(FINAL && npts > 0) && !Out::ALWAYS) continue;   // the column holds cap everywhere already
     for (int u = m - 1; u >= 0; u--) {
       int d = cap;
       if (q >= 0) {
@@ -188,7 +210,7 @@ envelope_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step
         for (int k = 0; k < npts; k++) best = min(best, point_dsq(x, (int)outer, u, spts + 3 * k));
         d = (int)best;
       }
-      col[(i64)u * step] = d;
+      out(col, dsq, (i64)u * step, d);
       if (q > 0 && u == tt) {
         q--;
         const int2 e = st[(i64)q * WAVE];
@@ -198,6 +220,25 @@ envelope_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step
       }
     }
   }
+}
+
+template <bool FINAL>
+__global__ void __launch_bounds__(BLOCK)
+envelope_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step, i64 outer_stride, int nx, i64 nunits,
+                int xchunks, int cap, const int* __restrict__ pts, int npts) {
+  __shared__ int spts[3 * LDS_POINTS];
+  if (FINAL) {
+    for (int k = threadIdx.x; k < 3 * npts; k += BLOCK) spts[k] = pts[k];
+    __syncthreads();
+  }
+  envelope_pass<FINAL>(dsq, stack, m, step, outer_stride, nx, nunits, xchunks, cap, spts, npts, StoreDsq());
+}
+
+// the z pass of dev_distance_levels: no listed points, and the epilogue instead of the store
+__global__ void __launch_bounds__(BLOCK)
+envelope_levels_kernel(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step, i64 outer_stride, int nx,
+                       i64 nunits, int xchunks, int cap, StoreLevels out) {
+  envelope_pass<false>(dsq, stack, m, step, outer_stride, nx, nunits, xchunks, cap, nullptr, 0, out);
 }
 
 // dsq = min(dsq, distance to the nearest of n listed points), a block staging LDS_POINTS of them at a time
@@ -376,6 +417,30 @@ int dev_distance_sq(visfd_hip_ctx* ctx, const float* src, const float* mask, i64
                                                            (int)ny, (int)nz);
   VH_HIP(hipGetLastError());
   ctx->distance_last_path = VISFD_HIP_DISTANCE_PATH_TRANSFORM;
+  return VISFD_HIP_OK;
+}
+
+int dev_distance_levels(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, float level,
+                        int32_t* dsq, const LevelsEpilogue& e) {
+  VH_TRY(check_common(ctx, nx, ny, nz, nullptr, 0));
+  VH_REQUIRE(src && dsq && e.dst, "null argument");
+  const i64 S = nx + ny + nz;
+  const int cap = (int)(S * S);
+  const i64 max_waves = (i64)ctx->num_cus * 16, nrows = ny * nz;
+  rows_kernel<<<(unsigned)((std::min(nrows, max_waves) + WAVES - 1) / WAVES), BLOCK, 0, ctx->stream>>>(
+      src, mask, level, level, dsq, 0, (int)nx, nrows, cap);
+  const int xchunks = (int)((nx + WAVE - 1) / WAVE);
+  const i64 units_y = nz * xchunks, units_z = ny * xchunks;
+  const i64 waves_y = std::min(units_y, max_waves), waves_z = std::min(units_z, max_waves);
+  int2* stack = nullptr;
+  VH_TRY(ws(ctx, WS_DIST_STACK, (size_t)std::max(waves_y * ny, waves_z * nz) * WAVE, &stack));
+  envelope_kernel<false><<<(unsigned)((waves_y + WAVES - 1) / WAVES), BLOCK, 0, ctx->stream>>>(
+      dsq, stack, (int)ny, nx, nx * ny, (int)nx, units_y, xchunks, cap, nullptr, 0);
+  StoreLevels out;
+  out.e = e;
+  envelope_levels_kernel<<<(unsigned)((waves_z + WAVES - 1) / WAVES), BLOCK, 0, ctx->stream>>>(
+      dsq, stack, (int)nz, nx * ny, nx, (int)nx, units_z, xchunks, cap, out);
+  VH_HIP(hipGetLastError());
   return VISFD_HIP_OK;
 }
 
