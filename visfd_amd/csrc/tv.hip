@@ -122,7 +122,7 @@ tv_dense_kernel(const float* __restrict__ sal, const float* __restrict__ dir,
 }  // namespace
 
 // The vote tables of (sigma_tv, cutoff) on the device: float4 {w, rhat_x, rhat_y, rhat_z} per offset j in z, y, x order
-// (filter3d.hpp:563-578, feature.hpp:2470-2478), in the four layouts of tv_common.hpp (TvTableLayout).  Built on the host
+// (filter3d.hpp:563-578, feature.hpp:2470-2478), in the five layouts of tv_common.hpp (TvTableLayout).  Built on the host
 // once and kept in the context: a launch with the same parameters queues no copy and never waits for the stream.
 static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int h, TvTables* out) {
   const TvTableLayout l = tv_table_layout(h);
@@ -141,6 +141,9 @@ static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int
       const size_t kb = (k / (n * n)) * nslb + 4 + ((k / n) % n + 3) * spb + (k % n);
       tab[l.box_tol + kb] = make_float4(w[k], rt2 * rh[3 * k], rt2 * rh[3 * k + 1], rt2 * rh[3 * k + 2]);
       tab[l.box_exact + kb] = tab[l.packed + k];
+      // (the square root of the float weight, rounded once; the pad entries stay exactly 0)
+      tab[l.box_tol_sq + kb] = tab[l.box_tol + kb];
+      tab[l.box_tol_sq + kb].x = (float)sqrt((double)w[k]);
     }
     float4* dtab = nullptr;
     ctx->tv_table_dev = nullptr;
@@ -153,7 +156,7 @@ static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int
     ctx->tv_table_key[1] = cutoff;
   }
   const float4* const dtab = reinterpret_cast<const float4*>(ctx->tv_table_dev);
-  *out = {dtab + l.packed, dtab + l.padded, dtab + l.box_tol, dtab + l.box_exact, h};
+  *out = {dtab + l.packed, dtab + l.padded, dtab + l.box_tol, dtab + l.box_exact, dtab + l.box_tol_sq, h};
   return VISFD_HIP_OK;
 }
 
@@ -215,7 +218,7 @@ int tv_dispatch(visfd_hip_ctx* ctx, const TvRequest& rq, float sigma_tv, float c
       case TvRoute::BoxExact: {
         const bool exact = routes[i] == TvRoute::BoxExact;
         rc = dev_tv_box(ctx, rq.sal, rq.dir, rq.out, rq.mask_src, rq.mask_dst, rq.nx, rq.ny, rq.nz, rq.z_out0, rq.z_out1, h,
-                        exact ? tab.box_exact : tab.box_tol, rq.exponent, exact);
+                        exact ? tab.box_exact : tab.box_tol, tab.box_tol_sq, rq.exponent, exact);
         break;
       }
       case TvRoute::Tiled:

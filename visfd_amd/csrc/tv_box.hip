@@ -29,8 +29,8 @@
 //     per-wave hit list in LDS, dealt alternately to the two streams.  A hit votes on ALL 32 lanes: the table slices in
 //     LDS carry 3 zero rows above and below and >= 3 zero entries between rows, so that a receiver the sender does not
 //     reach reads a zero weight (its vote adds 0) instead of being masked off.  The vote loop is branch-free:
-//     1 address subtraction + 19 vote instructions per step, its LDS reads (hit entries, sender, table) requested
-//     ahead of their use.
+//     1 address subtraction + 19 vote instructions per step (18 with folded saliencies, 17 with the square-root table:
+//     vote_fma), its LDS reads (hit entries, sender, table) requested ahead of their use.
 //   * 6 WAVES PER SIMD, 80 VGPRs: the 24 sums of a lane (2 halves x 2 sub-patches x 6) and the read-ahead
 //     registers of the vote loop stay in registers.  3 workgroups per CU, ~51 KB of LDS each at h = 12.
 //
@@ -97,14 +97,29 @@ __device__ __forceinline__ void fmacc(float& t, float a, float b) {
 // saliency's place: t' = R.n' = a t, q' = c - t'^2 = a^2 q, m' = t' R - n' = a m, so that w q'^2 m' m'^T = s w q^2 m m^T
 // without the multiplication by the saliency: 18 instructions.  (Round 3 measured no gain from this form -- that kernel was
 // bound by the latency of a vote's LDS reads; this one issues vector instructions 75 % of the time.)
+//
+// ROOT (exponent 4, folded): the table carries omega = sqrt(w) in w's place (tv_common.hpp: box_tol_sq), and the vote is the
+// outer product of ONE vector with itself: k = omega q', g = k m', T += g g^T = (omega q')^2 m' m'^T -- whatever the sign of
+// q' -- without the product (w q') q': 17 instructions.  g is of the order of s^(1/2) where b = w q'^2 m' was s^(5/6).
 template <int MODE, bool ZNEG, bool FOLD>
-__device__ __forceinline__ void vote_fma(float (&T)[6], const f4v& snd /* sal, n  or  c, n' */, const f4v& tw /* w, R */) {
+__device__ __forceinline__ void vote_fma(float (&T)[6], const f4v& snd /* sal, n  or  c, n' */, const f4v& tw /* w or omega, R */) {
   const float Rz = ZNEG ? -tw.w : tw.w;    // (a source modifier of the instructions below)
   const float t = __builtin_fmaf(Rz, snd.w, __builtin_fmaf(tw.z, snd.z, tw.y * snd.y));
   const float q = __builtin_fmaf(-t, t, FOLD ? snd.x : 2.0f);
   const float m0 = __builtin_fmaf(t, tw.y, -snd.y);
   const float m1 = __builtin_fmaf(t, tw.z, -snd.z);
   const float m2 = __builtin_fmaf(t, Rz, -snd.w);
+  if constexpr (MODE == 0 && FOLD) {
+    const float k = tw.x * q;
+    const float g0 = k * m0, g1 = k * m1, g2 = k * m2;
+    fmacc(T[0], g0, g0);
+    fmacc(T[3], g0, g1);
+    fmacc(T[5], g0, g2);
+    fmacc(T[1], g1, g1);
+    fmacc(T[4], g1, g2);
+    fmacc(T[2], g2, g2);
+    return;
+  }
   const float sw = FOLD ? tw.x : snd.x * tw.x;
   const float bse = (MODE == 0) ? (sw * q) * q : sw * q;
   const float b0 = bse * m0, b1 = bse * m1, b2 = bse * m2;
@@ -231,7 +246,7 @@ __device__ __forceinline__ bool box_reached(float dx, float dy2, float rr) { ret
 template <int MODE, bool FOLD>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6)))
 tv_box_kernel(float* __restrict__ ten, const float* __restrict__ mask_dst,
-              const float4* __restrict__ table /* [2h+1] slices of nsl entries: w, sqrt(2) rhat at j, zero padding */,
+              const float4* __restrict__ table /* [2h+1] slices of nsl entries: w (sqrt(w) for <0, true>), sqrt(2) rhat at j, zero padding */,
               BoxParams p, unsigned* __restrict__ tile_counter, unsigned ntiles,
               // the sender lists of tvl_write_kernel: for every listed plane and every 8-column tile column, the salient senders
               // of the columns the tile column can reach, in descending (y, x); rows[(zl (ny+1) + y) ntx + tx] = index of
@@ -925,12 +940,13 @@ auto box_tol_kernel(int mode, bool fold) {
 }  // namespace
 
 // Tolerance-mode tensor voting (surfaces, exponent 2 or 4).  dtab_box: the {w, sqrt(2) rhat} table on the device in this
-// kernel's slice layout (tv_common.hpp: TvTables::box_tol).
+// kernel's slice layout (tv_common.hpp: TvTables::box_tol); dtab_box_sq: the same with sqrt(w) (box_tol_sq), which
+// tv_box_kernel<0, true> reads.
 // exact: the exact form (tv_boxx_kernel) with dtab_box = the reference's {w, rhat} in the same slice layout (box_exact); it
 // declines weighted source masks (values other than 0 and 1) and non-finite saliencies (tv_tiled.hip takes them).
 int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
                const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box,
-               int exponent, bool exact) {
+               const float4* dtab_box_sq, int exponent, bool exact) {
   if (exponent != 2 && exponent != 4) return TV_DECLINED;
   if (h < 1 || h > 40) return TV_DECLINED;
   if (nx * ny >= (1LL << 29) || nx > TV_LIST_MAX_NX || ny >= (1 << 24)) return TV_DECLINED;
@@ -981,7 +997,9 @@ int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* te
   }
   const int md = exponent == 4 ? 0 : 2;
   auto kernel = exact ? box_exact_kernel(md) : box_tol_kernel(md, L.folded);
-  VH_TRY(tv_launch_lds(ctx, kernel, ngrid, NT, lds, ten, mask_dst, dtab_box, p, counter, (unsigned)nblk, L.ent, L.pos, L.rows));
+  // the table that matches the kernel: exponent 4 with folded records votes with sqrt(w) (vote_fma: ROOT)
+  const float4* const dtab = (!exact && md == 0 && L.folded) ? dtab_box_sq : dtab_box;
+  VH_TRY(tv_launch_lds(ctx, kernel, ngrid, NT, lds, ten, mask_dst, dtab, p, counter, (unsigned)nblk, L.ent, L.pos, L.rows));
   VH_HIP(hipGetLastError());
 #ifdef VH_TV_COUNT
   {

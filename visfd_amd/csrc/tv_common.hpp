@@ -32,14 +32,16 @@ inline int tv_box_row(int h) {
 }
 inline int tv_box_slice(int h) { return (2 * h + 1 + 6) * tv_box_row(h) + 8; }
 
-// The four tables of one (sigma_tv, cutoff) in ONE device buffer (tv.hip: tv_table_device), n = 2h+1, float4 entries:
+// The five tables of one (sigma_tv, cutoff) in ONE device buffer (tv.hip: tv_table_device), n = 2h+1, float4 entries:
 //   packed     n^3                   the reference's {w, rhat} (baseline kernel)
 //   padded     n^2 tv_padded_row     the same with padded rows (tiled kernel; pad entries are never read)
 //   box_tol    (n+1) tv_box_slice    {w, sqrt(2) rhat} in the slice layout above (tolerance kernel), then a slice of zeros
 //   box_exact  (n+1) tv_box_slice    {w, rhat} in that layout (exact box kernel), then a slice of zeros
+//   box_tol_sq (n+1) tv_box_slice    box_tol with (float)sqrt((double)w) in w's place (tolerance kernel, exponent 4 with folded
+//                                    saliencies: the 17-instruction vote of tv_box.hip), then a slice of zeros
 // The zero rows, row tails and slices of the box tables ARE read.
 struct TvTableLayout {
-  size_t packed, padded, box_tol, box_exact;   // first entry of each table (its size: up to the next one)
+  size_t packed, padded, box_tol, box_exact, box_tol_sq;   // first entry of each table (its size: up to the next one)
   size_t total;
 };
 inline TvTableLayout tv_table_layout(int h) {
@@ -49,11 +51,12 @@ inline TvTableLayout tv_table_layout(int h) {
   l.padded = l.packed + n * n * n;
   l.box_tol = l.padded + n * n * (size_t)tv_padded_row(h);
   l.box_exact = l.box_tol + (n + 1) * (size_t)tv_box_slice(h);
-  l.total = l.box_exact + (n + 1) * (size_t)tv_box_slice(h);
+  l.box_tol_sq = l.box_exact + (n + 1) * (size_t)tv_box_slice(h);
+  l.total = l.box_tol_sq + (n + 1) * (size_t)tv_box_slice(h);
   return l;
 }
 struct TvTables {
-  const float4 *packed, *padded, *box_tol, *box_exact;
+  const float4 *packed, *padded, *box_tol, *box_exact, *box_tol_sq;
   int h;
 };
 
@@ -112,9 +115,10 @@ inline int tv_launch_lds(visfd_hip_ctx* ctx, void (*kernel)(KArgs...), i64 ngrid
 int dev_tv_tiled(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
                  const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab, int exponent,
                  bool curves, bool weights_only);
-// tv_box.hip.  dtab_box: TvTables::box_exact if exact, else TvTables::box_tol
+// tv_box.hip.  dtab_box: TvTables::box_exact if exact, else TvTables::box_tol; dtab_box_sq: TvTables::box_tol_sq (not read if exact)
 int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src, const float* mask_dst,
-               i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box, int exponent, bool exact);
+               i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box, const float4* dtab_box_sq, int exponent,
+               bool exact);
 
 
 // tv_list.hip: the launch-wide sender lists of tv_box.hip's kernels for the receiver planes [z_out0, z_out1) -- the planes
