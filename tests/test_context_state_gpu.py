@@ -1,11 +1,14 @@
 """What a context carries BETWEEN calls: workspace slots shared by unrelated stages (freed and reallocated when a later
-call needs more), the caches that live inside slots (vote table, structuring element), visfd_hip_trim, and blob jobs that
-are begun, left pending while other calls of the same context run, and ended later.
+call needs more), the tables kept inside slots (vote table, structuring element, median footprint, filter entries),
+visfd_hip_trim, the option table, and blob jobs that are begun, left pending while other calls of the same context run, and
+ended later.
 
 A. a blob job times everything that may happen between its halves: the lists of the oracle, bit for bit;
 B. job lifetime through the C ABI: refused arguments, capacity retries, destroy / close with a live job, stale handles;
 C. no stage depends on what its slots held before: one context, every stage, oversized slots, three orders, with the
-   workspace poisoned (visfd_hip_debug_poison_workspace) before every call, trimmed before every third, or left alone.
+   workspace poisoned (visfd_hip_debug_poison_workspace) before every call, trimmed before every third, or left alone;
+   tables of equal size one after the other, and a table slot that grows;
+D. every field of the option struct answers to its name.
 
 References: the CPU oracle (and tests/morph_np.py for morphology), bit for bit, for every stage whose arithmetic is plain
 IEEE float; the suite's 1e-5 of the field's scale (conftest.assert_close_rel, per-voxel bound of test_tolerance_modes.py)
@@ -18,6 +21,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import filter3d_np
+import median_np
 import morph_np
 import volgen
 from conftest import assert_bits_equal, assert_close_rel
@@ -468,6 +473,12 @@ def _calls():
             out.append(_host(c, d))
         return out
     add("morph_dilate_soft_twice", soft, lambda o, s: [morph_np.sphere_op(api.MORPH_DILATE, _src(s), 2.0, 3.0, 50.0)] * 2)
+    # ---- the other two tables a context keeps in a slot: the median's footprint and the general filter's entries
+    add("median_sphere_masked", lambda c, s: [c.median_sphere(_src(s), 1.5, mask=_mask(s))],
+        lambda o, s: [median_np.median_sphere(_src(s), 1.5, mask=_mask(s))])
+    table = np.random.default_rng(41).standard_normal((3, 5, 3)).astype(np.float32)     # hw = (1, 2, 1)
+    add("filter3d_masked_norm", lambda c, s: [c.filter3d(_src(s), table, _mask(s), True)],
+        lambda o, s: [filter3d_np.apply(_src(s), table, None, _mask(s), True)])
     # ---- binning, fluctuations
     def binning(c, s):
         half = tuple(n // 2 for n in s)
@@ -553,3 +564,87 @@ def test_stages_do_not_depend_on_what_their_slots_held(ctx, oracle):
     assert ctx.workspace_bytes() == 0
     _check(calls[0], calls[0].run(ctx, calls[0].small), want[calls[0].name], calls[0].name + " right after trim")
     assert ctx.workspace_bytes() > 0
+
+
+# ---- the tables kept in slots: a hit is decided by content, and a slot that is reallocated forgets what it held
+TAB_SHAPE = (8, 12, 70)      # one workgroup row and a ragged edge in x
+CROSS = np.array([(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)], np.int32)
+CROSS_B = CROSS.copy()
+CROSS_B[1] = (1, 1, 0)       # as many entries, the same bounding box, one offset moved
+CROSS_HEIGHTS = np.array([0.0, -0.5, -0.25, -1.0, -0.75, -2.0, -1.5], np.float32)
+
+
+def _tab_inputs():
+    return volgen.noise_volume(TAB_SHAPE, seed=17), volgen.block_mask(TAB_SHAPE, seed=18)
+
+
+def test_a_table_of_the_same_size_is_not_taken_for_the_one_in_the_slot(ctx):
+    """A, B, A with tables of equal entry count and bounding box that differ in one offset (morphology, median) or one
+    weight (general filter): every call gets its own table's result, bit for bit against the numpy restatements."""
+    from visfd_amd import api
+    src, mask = _tab_inputs()
+    assert (CROSS.min(0) == CROSS_B.min(0)).all() and (CROSS.max(0) == CROSS_B.max(0)).all() and len(CROSS) == len(CROSS_B)
+    ta = np.random.default_rng(43).standard_normal((3, 5, 3)).astype(np.float32)     # hw = (1, 2, 1)
+    tb = ta.copy()
+    tb[2, 1, 0] += np.float32(0.5)
+    want_morph = [morph_np.dilate_erode(src, e, CROSS_HEIGHTS, True, mask) for e in (CROSS, CROSS_B)]
+    want_median = [median_np.median_table(src, e, mask=mask) for e in (CROSS, CROSS_B)]
+    want_f3d = [filter3d_np.apply(src, t, None, mask, True) for t in (ta, tb)]
+    for w in (want_morph, want_median, want_f3d):
+        assert w[0].tobytes() != w[1].tobytes(), "the two tables must give different images"
+    for pos, k in enumerate((0, 1, 0)):
+        what = "%s (call %d)" % ("AB"[k], pos)
+        assert_bits_equal(ctx.morph_table(api.MORPH_DILATE, src, (CROSS, CROSS_B)[k], CROSS_HEIGHTS, mask), want_morph[k], "morph_table " + what)
+        assert_bits_equal(ctx.median_table(src, (CROSS, CROSS_B)[k], mask), want_median[k], "median_table " + what)
+        assert_bits_equal(ctx.filter3d(src, (ta, tb)[k], mask, True), want_f3d[k], "filter3d " + what)
+
+
+def test_a_table_slot_that_had_to_grow_forgets_the_table_it_held(ctx):
+    """7 entries, then the 257 of the radius-4 ball (the slot is freed and reallocated), then the 7 again: all three right,
+    for the median's footprint and for the structuring element."""
+    from visfd_amd import api
+    src, mask = _tab_inputs()
+    ball, _ = morph_np.sphere_structure(4.0)
+    assert len(ball) == 257 and (ball == median_np.footprint(4.0)).all()
+    heights = (-0.125 * np.abs(ball).sum(axis=1)).astype(np.float32)
+    want_median = {7: median_np.median_table(src, CROSS, mask=mask), 257: median_np.median_table(src, ball, mask=mask)}
+    want_morph = {7: morph_np.dilate_erode(src, CROSS, CROSS_HEIGHTS, True, mask), 257: morph_np.dilate_erode(src, ball, heights, True, mask)}
+    for pos, n in enumerate((7, 257, 7)):
+        d, b = (CROSS, CROSS_HEIGHTS) if n == 7 else (ball, heights)
+        before = ctx.workspace_bytes()
+        assert_bits_equal(ctx.median_table(src, d, mask), want_median[n], "median_table, %d entries (call %d)" % (n, pos))
+        assert_bits_equal(ctx.morph_table(api.MORPH_DILATE, src, d, b, mask), want_morph[n], "morph_table, %d entries (call %d)" % (n, pos))
+        if pos == 1:
+            assert ctx.workspace_bytes() >= before + 2 * 4 * 4 * (257 - 7), "both table slots grew"
+        if pos == 2:
+            assert ctx.workspace_bytes() == before, "slots only grow"
+
+
+# ============================================================================================ D. options
+def test_every_option_field_is_reachable_by_name(ctx):
+    """The fields of struct visfd_hip_options, read out of common.hpp: each answers to its name with the default written
+    there (unless the environment gives another), takes a value of its own and gives it back; no other name is known."""
+    import os
+    import re
+    from conftest import ROOT
+    from visfd_amd import api
+    text = open(os.path.join(ROOT, "visfd_amd", "csrc", "common.hpp")).read()
+    body = re.search(r"struct visfd_hip_options \{(.*?)\n\};", text, re.S).group(1)
+    fields = re.findall(r"^\s*(?:int|int64_t)\s+(\w+)\s*=\s*(-?\d+)\s*;", body, re.M)
+    assert len(fields) >= 30 and len(set(n for n, _ in fields)) == len(fields)
+    assert len(fields) == len(re.findall(r"^\s*\w+\s+\w+\s*(?:=[^;]*)?;", body, re.M)), "a member line the pattern does not read"
+    for name, default in fields:
+        if "VISFD_HIP_" + name.upper() not in os.environ:
+            assert ctx.get_option(name) == int(default), name
+    for i, (name, _) in enumerate(fields):      # a value per field: two names on one field would show
+        ctx.set_option(name, 1000 + i)
+    for i, (name, _) in enumerate(fields):
+        assert ctx.get_option(name) == 1000 + i, name
+    for name, default in fields:
+        ctx.set_option(name, int(default))
+        assert ctx.get_option(name) == int(default), name
+    for call in (lambda: ctx.get_option("no_such_option"), lambda: ctx.set_option("no_such_option", 1),
+                 lambda: ctx.get_option("gauss_3pas"), lambda: ctx.get_option("")):
+        with pytest.raises(api.VisfdHipError) as e:
+            call()
+        assert e.value.code == EINVAL

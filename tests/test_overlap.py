@@ -153,7 +153,7 @@ def test_abi_header_and_binding_agree():
     assert len(api.DISCARD_OVERLAP_LAST_FIELDS) == 8
     table = open(os.path.join(ROOT, "visfd_amd", "csrc", "context.hip")).read()
     for opt in ("discard_overlap_host", "discard_overlap_max_rounds", "discard_overlap_time"):
-        assert '{"%s", &visfd_hip_options::%s, nullptr}' % (opt, opt) in table, opt
+        assert re.search(r"\bVH_OPT\(%s\)" % opt, table), opt
         assert re.search(r"^ \*   %s\b" % opt, text, flags=re.M), opt
     assert "int discard_overlap_max_rounds = 256;" in open(os.path.join(ROOT, "visfd_amd", "csrc", "common.hpp")).read()
     hpp = open(os.path.join(ROOT, "include", "visfd_hip.hpp")).read()

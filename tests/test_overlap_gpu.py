@@ -2,7 +2,7 @@
 host-array and the torch device face, bit for bit against the sequential host entry and the reference's recorded outputs
 (tests/golden/overlap.npz), with what ran asserted; the chain whose round count is its length, with and without the round
 cap; the inputs that are handed over to the host; the option that keeps the call on the host; one context across other
-stages' calls; the empty list."""
+stages' calls; the phase times of the option discard_overlap_time; the empty list."""
 import numpy as np
 import pytest
 
@@ -132,6 +132,27 @@ def test_option_discard_overlap_host(ctx, api, expected, face):
         assert same_bits(got, expected[name])
     assert same_bits(api.discard_overlapping_blobs(*CASES["post0"], ctx=ctx), expected["post0"])
     assert ctx.discard_overlapping_blobs_last()["path"] == api.DISCARD_OVERLAP_PATH_DEVICE
+
+
+def test_option_discard_overlap_time_reports_the_phases(api, expected):
+    """off on a fresh context: five times -1; on, for a list that goes through the rounds: every phase -1 (did not run) or
+    a time below a second, the reduction always timed; the list is the same either way"""
+    c = api.Context(0)
+    try:
+        for timed in (0, 1, 0):
+            with c.options(discard_overlap_time=timed):
+                got = run_ctx(c, *CASES["dense"])
+                last = c.discard_overlapping_blobs_last()
+                ms = list(c.discard_overlapping_blobs_last_times().values())
+            assert last["path"] == api.DISCARD_OVERLAP_PATH_DEVICE and last["rounds"] >= 1, last
+            assert same_bits(got, expected["dense"])
+            assert len(ms) == 5
+            if timed:
+                assert all(t == -1.0 or 0.0 <= t < 1000.0 for t in ms) and ms[0] >= 0.0, ms
+            else:
+                assert ms == [-1.0] * 5, ms
+    finally:
+        c.close()
 
 
 def test_one_context_between_other_stages(ctx, api, expected):

@@ -294,7 +294,7 @@ def test_abi_header_and_binding_agree(api):
                "DiscardBlobsByScoreSupervised"):
         assert re.search(r"inline \w+ %s\(" % fn, hpp), fn
     # the option is in the table: a context would take VISFD_HIP_FIND_SPHERES_HOST from the environment
-    assert '{"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr}' in open(
+    assert "VH_OPT(find_spheres_host)" in open(
         os.path.join(ROOT, "visfd_amd", "csrc", "context.hip")).read()
 
 

@@ -123,24 +123,13 @@ GaussOpts field_opts(const visfd_hip_ctx* ctx, float* A_out) {
   return o;
 }
 
-bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
 
-int morph_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, int op,
-                int max_op) {
+// what the morphology and median faces check first; `who` and `tag` start the messages, a face without an op passes none
+int face_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, const char* who,
+               const char* tag, int op = 0, int max_op = 0) {
   VH_REQUIRE(ctx && src && dst, "null argument");
   VH_REQUIRE(op >= 0 && op <= max_op, "unknown morphology op");
-  VH_TRY(check_dims(nx, ny, nz));
-  VH_REQUIRE(!overlaps(src, dst, nx * ny * nz), "morphology cannot run in place (dst overlaps src)");
-  VH_REQUIRE(!overlaps(mask, dst, nx * ny * nz), "morphology: dst overlaps mask");
-  VH_HIP(hipSetDevice(ctx->device));
-  return VISFD_HIP_OK;
-}
-
-int median_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz) {
-  VH_REQUIRE(ctx && src && dst, "null argument");
-  VH_TRY(check_dims(nx, ny, nz));
-  VH_REQUIRE(!overlaps(src, dst, nx * ny * nz), "the median filter cannot run in place (dst overlaps src)");
-  VH_REQUIRE(!overlaps(mask, dst, nx * ny * nz), "median: dst overlaps mask");
+  VH_TRY(check_out_of_place(ctx, src, dst, mask, nx, ny, nz, who, tag));
   VH_HIP(hipSetDevice(ctx->device));
   return VISFD_HIP_OK;
 }
@@ -715,7 +704,7 @@ int visfd_hip_sphere_structure(float radius, float radius_max, float bmax, int* 
 
 int visfd_hip_morph_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
                                int64_t ny, int64_t nz, int op, float radius, float radius_max, float bmax) {
-  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "morphology", "morphology", op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
   // an image of at most two levels needs no element (csrc/morph_levels.hip): decided before one is built, at any radius
   bool levels = false;
   VH_TRY(morph_levels_try(ctx, src, dst, mask, nx, ny, nz, op, radius, radius_max, bmax, &levels));
@@ -733,7 +722,7 @@ int visfd_hip_morph_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst,
 // the host faces: dst goes up too (masked voxels keep their values, the top-hats read it)
 int visfd_hip_morph_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
                            int64_t nz, int op, float radius, float radius_max, float bmax) {
-  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "morphology", "morphology", op, VISFD_HIP_MORPH_TOP_HAT_BLACK));
   return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
     return visfd_hip_morph_sphere_dev(ctx, ds, dd, dm, nx, ny, nz, op, radius, radius_max, bmax);
   });
@@ -741,7 +730,7 @@ int visfd_hip_morph_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, con
 
 int visfd_hip_morph_table_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
                               int64_t ny, int64_t nz, int op, const int* dxyz, const float* b, int64_t n) {
-  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_ERODE));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "morphology", "morphology", op, VISFD_HIP_MORPH_ERODE));
   MorphElem el;
   VH_TRY(morph_put_table(ctx, dxyz, b, n, &el));
   return morph_run(ctx, src, dst, mask, nx, ny, nz, op, el);
@@ -749,7 +738,7 @@ int visfd_hip_morph_table_dev(visfd_hip_ctx* ctx, const float* src, float* dst, 
 
 int visfd_hip_morph_table(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
                           int64_t nz, int op, const int* dxyz, const float* b, int64_t n) {
-  VH_TRY(morph_check(ctx, src, dst, mask, nx, ny, nz, op, VISFD_HIP_MORPH_ERODE));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "morphology", "morphology", op, VISFD_HIP_MORPH_ERODE));
   return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
     return visfd_hip_morph_table_dev(ctx, ds, dd, dm, nx, ny, nz, op, dxyz, b, n);
   });
@@ -787,7 +776,7 @@ int visfd_hip_median_footprint(float radius, int* dxyz, int64_t cap, int64_t* n)
 
 int visfd_hip_median_table_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx,
                                int64_t ny, int64_t nz, const int* dxyz, int64_t n) {
-  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "the median filter", "median"));
   MedianTab mt;
   VH_TRY(median_put_table(ctx, dxyz, n, &mt));
   return median_run(ctx, src, dst, mask, nx, ny, nz, mt);
@@ -805,7 +794,7 @@ int visfd_hip_median_sphere_dev(visfd_hip_ctx* ctx, const float* src, float* dst
 // the host faces: dst goes up too (masked voxels keep their values)
 int visfd_hip_median_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
                             int64_t nz, float radius) {
-  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "the median filter", "median"));
   int64_t n = 0;
   VH_TRY(visfd_hip_median_footprint(radius, nullptr, 0, &n));   // a bad radius is refused before anything is staged
   return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
@@ -815,7 +804,7 @@ int visfd_hip_median_sphere(visfd_hip_ctx* ctx, const float* src, float* dst, co
 
 int visfd_hip_median_table(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, int64_t nx, int64_t ny,
                            int64_t nz, const int* dxyz, int64_t n) {
-  VH_TRY(median_check(ctx, src, dst, mask, nx, ny, nz));
+  VH_TRY(face_check(ctx, src, dst, mask, nx, ny, nz, "the median filter", "median"));
   return stage_filter(ctx, src, dst, mask, nx, ny, nz, true, [&](const float* ds, float* dd, const float* dm) {
     return visfd_hip_median_table_dev(ctx, ds, dd, dm, nx, ny, nz, dxyz, n);
   });

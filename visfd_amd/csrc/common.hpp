@@ -53,7 +53,7 @@ enum Slot {
   WS_TVSCRATCH,                    // tensor voting: per-workgroup rings of compacted sender planes (exact kernel) / the launch's sender lists
   WS_TVLIST,                       // tolerance-mode tensor voting: row offsets of the sender lists
   WS_H2D_0, WS_H2D_1, WS_H2D_2, WS_H2D_3, WS_H2D_4,  // staging for the host-pointer face
-  WS_MORPH_TAB,                    // morphology: the structuring element on the device (host copy in visfd_hip_ctx::morph_tab)
+  WS_MORPH_TAB,                    // morphology: the structuring element on the device (its slot key: the same ints)
   WS_MORPH_SRC,                    // morphology: the source with masked voxels replaced by NaN
   WS_MORPH_TMP,                    // morphology: the intermediate image of open / close / the top-hats
   WS_EXT_FLAGS,                    // extrema: one byte of neighbour facts per voxel (csrc/extrema.hip)
@@ -62,7 +62,7 @@ enum Slot {
   WS_EXT_COUNTERS,                 // extrema: the two list lengths
   WS_EXT_LIST,                     // extrema: the unsorted lists (index, score, voxels)
   WS_EXT_RANKS,                    // extrema: listed roots in raster order and their sorted positions, for the label image
-  WS_F3D_TAB,                      // general 3-D filter: the table's non-zero entries on the device (what they were built from: visfd_hip_ctx::f3d_raw)
+  WS_F3D_TAB,                      // general 3-D filter: the table's non-zero entries on the device (its slot key: window, nx, ny and the raw table)
   WS_DRAW_OWNER,                   // DrawSpheres: the owner volume, one uint32 per voxel: the last sphere that holds it, plus one (csrc/draw.hip)
   WS_DRAW_TAB,                     // DrawSpheres: per-sphere values, counts, clipped boxes and running row counts; DrawRegions: its one flag
   WS_WSH_KIND,                     // watershed: one byte per voxel: ineligible / interior / chain / join, and what the merge pass adds (csrc/watershed.hip)
@@ -71,7 +71,7 @@ enum Slot {
   WS_WSH_STATE,                    // watershed: boundary state, one byte per voxel
   WS_WSH_SEEDS,                    // watershed: the seeds' root indices in list order
   WS_WSH_FLAGS,                    // watershed: the NaN flag and the per-round change flag
-  WS_MEDIAN_TAB,                   // median filter: the footprint on the device (host copy in visfd_hip_ctx::median_tab); csrc/median.hip
+  WS_MEDIAN_TAB,                   // median filter: the footprint on the device (its slot key: the same ints); csrc/median.hip
   WS_INTENSITY,                    // image statistics: the integer bins of one pass (csrc/intensity.hip), zeroed by every call that uses them
   WS_DIST_DSQ,                     // distance maps: the int32 squared distances behind the float outputs (csrc/distance.hip)
   WS_DIST_STACK,                   // distance maps: the envelope passes' stacks, per wave [entry][lane] of int2
@@ -146,25 +146,20 @@ struct visfd_hip_options {
 
 struct visfd_hip_ctx {
   visfd_hip_options opt;
-  float* tv_table_dev = nullptr;   // cached vote tables (tv_common.hpp: TvTableLayout) and what they were built for
-  float tv_table_key[2] = {0.0f, 0.0f};
-  int tv_table_h = -1;
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   void* slot_ptr[vh::WS_NSLOTS] = {};
   size_t slot_bytes[vh::WS_NSLOTS] = {};
+  std::vector<unsigned char> slot_key[vh::WS_NSLOTS];   // what a slot's contents were built from (ws_holds / ws_put); empty: nothing remembered
   int num_cus = 256;
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
-  std::vector<int> morph_tab;         // the structuring element now in slot WS_MORPH_TAB (4 ints per entry: dx, dy, dz, bits of b)
   int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
-  std::vector<float> f3d_raw;         // the filter table whose non-zero entries are now in slot WS_F3D_TAB (empty: none),
-  int64_t f3d_key[5] = {};            // its half-widths and the nx, ny its sender offsets were computed for,
-  int64_t f3d_n = 0;                  // the number of those entries, of the columns (jy, jx) that hold one
-  int64_t f3d_ncols = 0;
-  float f3d_den = 0.0f;               // and their float sum in order
+  struct {                            // of the filter table expanded into slot WS_F3D_TAB, valid only while that slot's key holds:
+    int64_t n = 0, ncols = 0;         // the number of its non-zero entries, of the columns (jy, jx) that hold one,
+    float den = 0.0f;                 // and the entries' float sum in order
+  } f3d;
   int f3d_last_path = -1;             // the kernel the last general-filter call ran (VISFD_HIP_FILTER3D_PATH_*)
-  std::vector<int> median_tab;        // the footprint now in slot WS_MEDIAN_TAB (n entries dx, dy, dz, 0, then n LDS cell offsets)
   int median_last_path = -1;          // the kernel the last median call ran (VISFD_HIP_MEDIAN_PATH_*)
   int distance_last_path = -1;        // what the last distance call ran (VISFD_HIP_DISTANCE_PATH_*)
   int find_spheres_last_path = -1;    // what the last FindSpheres call ran (VISFD_HIP_FIND_SPHERES_PATH_*)
@@ -199,6 +194,11 @@ inline int ws(visfd_hip_ctx* ctx, Slot s, size_t count, T** out) {
   *out = static_cast<T*>(p);
   return rc;
 }
+// A table a stage keeps in its slot between calls.  ws_holds: the slot's contents were built from these key bytes -- host
+// compares only, so a hit queues nothing and never waits for the stream.  ws_put: `bytes` of host memory into the slot
+// under that key.  ws_get, visfd_hip_trim and visfd_hip_debug_poison_workspace drop the key where the contents go.
+bool ws_holds(const visfd_hip_ctx* ctx, Slot s, const void* key, size_t key_bytes);
+int ws_put(visfd_hip_ctx* ctx, Slot s, const void* key, size_t key_bytes, const void* host, size_t bytes);
 
 inline int check_dims(i64 nx, i64 ny, i64 nz) {
   if (nx <= 0 || ny <= 0 || nz <= 0) return fail(VISFD_HIP_EINVAL, "image dimensions must be positive");
@@ -210,10 +210,54 @@ inline bool overlap_bytes(const void* a, size_t na, const void* b, size_t nb) {
   const char* q = static_cast<const char*>(b);
   return p && q && p < q + nb && q < p + na;
 }
+inline bool overlaps(const float* a, const float* b, i64 n) { return overlap_bytes(a, sizeof(float) * n, b, sizeof(float) * n); }
 inline int check_dims32(i64 nx, i64 ny, i64 nz) {   // for the kernels that index a volume with 32-bit coordinates
   if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
   return VISFD_HIP_OK;
 }
+// what a filter that cannot run in place says first about its arrays: `who` cannot, `tag` starts the mask's message
+inline int check_out_of_place(const visfd_hip_ctx* ctx, const float* src, const float* dst, const float* mask, i64 nx, i64 ny,
+                              i64 nz, const char* who, const char* tag) {
+  VH_REQUIRE(ctx && src && dst, "null argument");
+  VH_TRY(check_dims(nx, ny, nz));
+  VH_REQUIRE(!overlaps(src, dst, nx * ny * nz), std::string(who) + " cannot run in place (dst overlaps src)");
+  VH_REQUIRE(!overlaps(mask, dst, nx * ny * nz), std::string(tag) + ": dst overlaps mask");
+  return VISFD_HIP_OK;
+}
+
+// Events on a stream at the boundaries of a call's N phases, for the *_time options: mark(k) is the boundary before
+// phase k, mark(N) the end.  Events are created when first marked and go with the clock, whichever way the call returns.
+template <int N>
+struct PhaseClock {
+  hipStream_t st = nullptr;
+  bool on = false;
+  hipEvent_t ev[N + 1] = {};
+  bool set[N + 1] = {};
+  void start(hipStream_t s, bool enabled) {
+    st = s;
+    on = enabled;
+    mark(0);
+  }
+  void mark(int k) {   // marked again, the later one counts
+    if (!on) return;
+    if (!ev[k] && hipEventCreate(&ev[k]) != hipSuccess) { ev[k] = nullptr; return; }
+    set[k] = hipEventRecord(ev[k], st) == hipSuccess;
+  }
+  // the stream is idle; a phase that did not run has -1
+  void read(float* ms) {
+    for (int k = 0; k < N; k++) {
+      ms[k] = -1.0f;
+      if (!on || !set[k]) continue;
+      int e = k + 1;
+      while (e <= N && !set[e]) e++;
+      if (e <= N && hipEventElapsedTime(&ms[k], ev[k], ev[e]) != hipSuccess) ms[k] = -1.0f;
+    }
+  }
+  ~PhaseClock() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
 
 // blob_post.cpp: steps 2 to 4 of DiscardOverlappingBlobs (bounds, the greedy walk over the occupancy grid, compaction) on a
 // list that is sorted already; `states` (nullable): what the device's rounds have decided, one OVERLAP_* byte per blob

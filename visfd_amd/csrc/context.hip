@@ -17,6 +17,7 @@ int fail(int code, const std::string& msg) {
 int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out) {
   if (bytes == 0) bytes = 16;
   if (ctx->slot_bytes[s] < bytes) {
+    ctx->slot_key[s].clear();   // the contents go with the buffer
     // a queued blob scan that nobody has collected yet writes its survivors and counts here: fetch them first
     if (ctx->slot_ptr[s] && (s == WS_CAND || s == WS_SCANCNT)) VH_TRY(blob_jobs_drain(ctx));
     if (ctx->slot_ptr[s]) {
@@ -38,37 +39,45 @@ int ws_get(visfd_hip_ctx* ctx, Slot s, size_t bytes, void** out) {
   return VISFD_HIP_OK;
 }
 
+bool ws_holds(const visfd_hip_ctx* ctx, Slot s, const void* key, size_t key_bytes) {
+  const std::vector<unsigned char>& k = ctx->slot_key[s];
+  return key_bytes > 0 && k.size() == key_bytes && std::memcmp(k.data(), key, key_bytes) == 0;
+}
+
+int ws_put(visfd_hip_ctx* ctx, Slot s, const void* key, size_t key_bytes, const void* host, size_t bytes) {
+  ctx->slot_key[s].clear();                    // until the new contents have arrived
+  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read what the slot holds now
+  void* d = nullptr;
+  VH_TRY(ws_get(ctx, s, bytes, &d));
+  VH_HIP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));   // the copy reads host memory of this call
+  const unsigned char* k = static_cast<const unsigned char*>(key);
+  ctx->slot_key[s].assign(k, k + key_bytes);
+  return VISFD_HIP_OK;
+}
+
 namespace {
 
 // ---- options: name -> field; VISFD_HIP_<NAME> in the environment gives the value a new context starts with ----------
-struct OptionDesc { const char* name; int visfd_hip_options::*i; int64_t visfd_hip_options::*l; };
-const OptionDesc kOptions[] = {
-    {"gauss_3pass", &visfd_hip_options::gauss_3pass, nullptr},   {"gauss_cfg", &visfd_hip_options::gauss_cfg, nullptr},
-    {"gauss_wg_per_cu", &visfd_hip_options::gauss_wg_per_cu, nullptr}, {"tv_dense", &visfd_hip_options::tv_dense, nullptr},
-    {"tv_zrun", &visfd_hip_options::tv_zrun, nullptr}, {"tv_fma", &visfd_hip_options::tv_fma, nullptr},
-    {"gauss_fma", &visfd_hip_options::gauss_fma, nullptr}, {"eig_f32", &visfd_hip_options::eig_f32, nullptr},
-    {"tv_no_replay", &visfd_hip_options::tv_no_replay, nullptr}, {"tv_max_wg", &visfd_hip_options::tv_max_wg, nullptr},
-    {"tv_poison", &visfd_hip_options::tv_poison, nullptr}, {"tv_no_fold", &visfd_hip_options::tv_no_fold, nullptr}, {"tv_exact_tiled", &visfd_hip_options::tv_exact_tiled, nullptr}, {"tv_reserve_wg", &visfd_hip_options::tv_reserve_wg, nullptr},
-    {"blob_test_cap", nullptr, &visfd_hip_options::blob_test_cap}, {"debug", &visfd_hip_options::debug, nullptr},
-    {"morph_general", &visfd_hip_options::morph_general, nullptr},
-    {"morph_levels", &visfd_hip_options::morph_levels, nullptr},
-    {"filter3d_general", &visfd_hip_options::filter3d_general, nullptr},
-    {"median_general", &visfd_hip_options::median_general, nullptr},
-    {"distance_general", &visfd_hip_options::distance_general, nullptr},
-    {"draw_time", &visfd_hip_options::draw_time, nullptr},
-    {"voxelize_time", &visfd_hip_options::voxelize_time, nullptr},
-    {"voxelize_bisect", &visfd_hip_options::voxelize_bisect, nullptr},
-    {"connect_time", &visfd_hip_options::connect_time, nullptr},
-    {"connect_settle", &visfd_hip_options::connect_settle, nullptr},
-    {"stats_blocks", &visfd_hip_options::stats_blocks, nullptr},
-    {"watershed_host", &visfd_hip_options::watershed_host, nullptr},
-    {"find_spheres_host", &visfd_hip_options::find_spheres_host, nullptr},
-    {"discard_overlap_host", &visfd_hip_options::discard_overlap_host, nullptr},
-    {"discard_overlap_time", &visfd_hip_options::discard_overlap_time, nullptr},
-    {"discard_overlap_max_rounds", &visfd_hip_options::discard_overlap_max_rounds, nullptr},
-    {"log_pair", &visfd_hip_options::log_pair, nullptr},
-    {"log_pair_chunk", &visfd_hip_options::log_pair_chunk, nullptr},
+struct OptionDesc {
+  const char* name;
+  int visfd_hip_options::*i = nullptr;
+  int64_t visfd_hip_options::*l = nullptr;
+  OptionDesc(const char* n, int visfd_hip_options::*f) : name(n), i(f) {}
+  OptionDesc(const char* n, int64_t visfd_hip_options::*f) : name(n), l(f) {}
 };
+#define VH_OPT(field) {#field, &visfd_hip_options::field}
+const OptionDesc kOptions[] = {   // every field of visfd_hip_options (common.hpp documents them), in its order
+    VH_OPT(gauss_3pass), VH_OPT(gauss_cfg), VH_OPT(gauss_wg_per_cu), VH_OPT(log_pair), VH_OPT(log_pair_chunk),
+    VH_OPT(tv_dense), VH_OPT(tv_fma), VH_OPT(gauss_fma), VH_OPT(eig_f32), VH_OPT(tv_zrun), VH_OPT(tv_no_replay),
+    VH_OPT(tv_exact_tiled), VH_OPT(tv_no_fold), VH_OPT(tv_poison), VH_OPT(tv_reserve_wg), VH_OPT(tv_max_wg),
+    VH_OPT(blob_test_cap), VH_OPT(morph_general), VH_OPT(morph_levels), VH_OPT(filter3d_general), VH_OPT(median_general),
+    VH_OPT(distance_general), VH_OPT(discard_overlap_host), VH_OPT(discard_overlap_time),
+    VH_OPT(discard_overlap_max_rounds), VH_OPT(find_spheres_host), VH_OPT(watershed_host), VH_OPT(stats_blocks),
+    VH_OPT(connect_time), VH_OPT(connect_settle), VH_OPT(draw_time), VH_OPT(voxelize_bisect), VH_OPT(voxelize_time),
+    VH_OPT(debug),
+};
+#undef VH_OPT
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {
   for (const OptionDesc& d : kOptions) {
     if (std::strcmp(d.name, name) != 0) continue;
@@ -91,15 +100,6 @@ void options_from_environment(visfd_hip_options* o) {
     for (const char* c = d.name; *c; c++) env += (char)std::toupper((unsigned char)*c);
     if (const char* e = std::getenv(env.c_str())) set_option(o, d.name, (int64_t)std::atoll(e));
   }
-}
-
-// what the context remembers about the CONTENTS of its slots (trim frees them, the poison call overwrites them)
-void forget_slot_caches(visfd_hip_ctx* ctx) {
-  ctx->tv_table_dev = nullptr;   // lives in a workspace slot
-  ctx->tv_table_h = -1;
-  ctx->morph_tab.clear();        // so does the structuring element
-  ctx->f3d_raw.clear();          // and the general filter's table
-  ctx->median_tab.clear();       // and the median's footprint
 }
 
 }  // namespace
@@ -166,8 +166,8 @@ int visfd_hip_trim(visfd_hip_ctx* ctx) {
   VH_HIP(hipSetDevice(ctx->device));
   VH_TRY(blob_jobs_drain(ctx));   // live blob jobs keep their lists on the host from here on
   VH_HIP(hipStreamSynchronize(ctx->stream));
-  forget_slot_caches(ctx);
   for (int s = 0; s < WS_NSLOTS; s++) {
+    ctx->slot_key[s].clear();
     if (ctx->slot_ptr[s]) VH_HIP(hipFree(ctx->slot_ptr[s]));
     ctx->slot_ptr[s] = nullptr;
     ctx->slot_bytes[s] = 0;
@@ -180,9 +180,10 @@ int visfd_hip_debug_poison_workspace(visfd_hip_ctx* ctx) {
   VH_HIP(hipSetDevice(ctx->device));
   VH_TRY(blob_jobs_drain(ctx));
   VH_HIP(hipStreamSynchronize(ctx->stream));
-  forget_slot_caches(ctx);
-  for (int s = 0; s < WS_NSLOTS; s++)
+  for (int s = 0; s < WS_NSLOTS; s++) {
+    ctx->slot_key[s].clear();   // overwritten below
     if (ctx->slot_ptr[s]) VH_HIP(hipMemsetAsync(ctx->slot_ptr[s], 0xFF, ctx->slot_bytes[s], ctx->stream));
+  }
   VH_HIP(hipStreamSynchronize(ctx->stream));
   return VISFD_HIP_OK;
 }

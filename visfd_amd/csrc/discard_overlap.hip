@@ -376,39 +376,9 @@ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 // option discard_overlap_time: events on the stream at the phase boundaries (reduction | ranking and records | buckets |
 // rounds | compaction), read after the call's last wait
 enum { PH_REDUCE = 0, PH_RANK, PH_BUCKETS, PH_ROUNDS, PH_COMPACT, PH_COUNT };
-struct PhaseClock {
-  hipStream_t st = nullptr;
-  bool on = false;
-  hipEvent_t ev[PH_COUNT + 1] = {};
-  bool set[PH_COUNT + 1] = {};
-  void start(hipStream_t s, bool enabled) {
-    st = s;
-    on = enabled;
-    mark(0);
-  }
-  void mark(int k) {   // the boundary before phase k (PH_COUNT: the end)
-    if (!on) return;
-    if (!ev[k] && hipEventCreate(&ev[k]) != hipSuccess) { ev[k] = nullptr; return; }
-    set[k] = hipEventRecord(ev[k], st) == hipSuccess;
-  }
-  // the stream is idle; a phase that did not run has -1
-  void read(float* ms) {
-    for (int k = 0; k < PH_COUNT; k++) {
-      ms[k] = -1.0f;
-      if (!on || !set[k]) continue;
-      int e = k + 1;
-      while (e <= PH_COUNT && !set[e]) e++;
-      if (e <= PH_COUNT && hipEventElapsedTime(&ms[k], ev[k], ev[e]) != hipSuccess) ms[k] = -1.0f;
-    }
-  }
-  ~PhaseClock() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
 
 struct Plan {   // what the core found out and did
-  PhaseClock clock;
+  PhaseClock<PH_COUNT> clock;
   int reason = VISFD_HIP_DISCARD_OVERLAP_REASON_NONE;
   i64 rounds = 0, kept = 0, pairs_crit = 0, pairs_share = 0, cells = 0;
   bool on_host = false;           // the round cap was reached: hc, hd, hs hold the finished list

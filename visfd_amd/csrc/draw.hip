@@ -177,7 +177,6 @@ struct SpheresArgs {
 };
 
 bool fits_int(float c) { return std::isfinite(c) && c >= -2147483648.0f && c < 2147483648.0f; }
-bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
 
 // Everything that can be refused is refused here, before the device is touched; fills the records of the spheres whose
 // clipped box is not empty and the running row count.
@@ -271,17 +270,14 @@ int draw_spheres(visfd_hip_ctx* ctx, const SpheresArgs& a) {
     b.rms = rms;
   }
 
-  // option draw_time: events around the three phases (the call then waits for the last one)
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const bool timed = ctx->opt.draw_time != 0;
-  if (timed)
-    for (int k = 0; k < 4; k++) VH_HIP(hipEventCreate(&ev[k]));
-  auto mark = [&](int k) { return timed ? hipEventRecord(ev[k], ctx->stream) : hipSuccess; };
+  // option draw_time: events around the three phases (the call then waits for the last one); without spheres the
+  // first two boundaries stay here, with spheres they are marked again below
+  PhaseClock<3> clock;
+  clock.start(ctx->stream, ctx->opt.draw_time != 0);
+  clock.mark(1);
 
   unsigned* owner = nullptr;
   float* value = nullptr;
-  VH_HIP(mark(0));
-  VH_HIP(mark(1));
   const unsigned gvox = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 64);
   if (!recs.empty()) {
     // one slot: values [n] | counts [n] (foreground_normalize) | records | running row counts
@@ -305,9 +301,9 @@ int draw_spheres(visfd_hip_ctx* ctx, const SpheresArgs& a) {
     VH_HIP(hipMemcpyAsync(value, fg, sizeof(float) * (size_t)a.n, hipMemcpyHostToDevice, ctx->stream));
     VH_HIP(hipMemcpyAsync(drec, recs.data(), sizeof(SphereRec) * nrec, hipMemcpyHostToDevice, ctx->stream));
     VH_HIP(hipMemcpyAsync(drow, row_end.data(), sizeof(i64) * nrec, hipMemcpyHostToDevice, ctx->stream));
-    VH_HIP(mark(0));
+    clock.mark(0);
     VH_HIP(hipMemsetAsync(owner, 0, sizeof(unsigned) * (size_t)nvox, ctx->stream));
-    VH_HIP(mark(1));
+    clock.mark(1);
     const i64 nrows = row_end.back();
     const unsigned grows = grid_for(nrows, BLOCK / WAVE, (i64)ctx->num_cus * 64);
     scatter_kernel<false><<<dim3(grows), dim3(BLOCK), 0, ctx->stream>>>(drec, drow, (int)nrec, nrows, owner, nullptr, nullptr,
@@ -322,14 +318,13 @@ int draw_spheres(visfd_hip_ctx* ctx, const SpheresArgs& a) {
       VH_HIP(hipGetLastError());
     }
   }
-  VH_HIP(mark(2));
+  clock.mark(2);
   resolve_kernel<<<dim3(gvox), dim3(BLOCK), 0, ctx->stream>>>(a.dst, a.background, a.mask, owner, value, b, nvox);
   VH_HIP(hipGetLastError());
-  VH_HIP(mark(3));
-  if (timed) {
-    VH_HIP(hipEventSynchronize(ev[3]));
-    for (int k = 0; k < 3; k++) VH_HIP(hipEventElapsedTime(&ctx->draw_ms[k], ev[k], ev[k + 1]));
-    for (int k = 0; k < 4; k++) VH_HIP(hipEventDestroy(ev[k]));
+  clock.mark(3);
+  if (clock.on) {
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    clock.read(ctx->draw_ms);
   }
   if (a.any_center_outside) *a.any_center_outside = outside ? 1 : 0;
   return VISFD_HIP_OK;

@@ -204,7 +204,6 @@ bool tiled_accepts(const int hw[3]) {
   return (i64)(FX + 2 * hw[0]) * (FY + 2 * hw[1]) * 2 * (i64)sizeof(float) <= 48 * 1024;
 }
 
-bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
 
 int check_halfwidths(const int hw[3]) {
   VH_REQUIRE(hw, "null argument");
@@ -221,28 +220,27 @@ i64 table_size(const int hw[3]) { return (2 * (i64)hw[0] + 1) * (2 * (i64)hw[1] 
 // everything that can be said about a filter call without a device
 int filter3d_check(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
                    const float* den_out) {
-  VH_REQUIRE(ctx && src && dst, "null argument");
-  VH_TRY(check_dims(nx, ny, nz));
+  VH_TRY(check_out_of_place(ctx, src, dst, mask, nx, ny, nz, "the 3-D filter", "the 3-D filter"));
   const i64 n = nx * ny * nz;
-  VH_REQUIRE(!overlaps(src, dst, n), "the 3-D filter cannot run in place (dst overlaps src)");
-  VH_REQUIRE(!overlaps(mask, dst, n), "the 3-D filter: dst overlaps mask");
   VH_REQUIRE(!overlaps(den_out, dst, n) && !overlaps(den_out, src, n) && !overlaps(den_out, mask, n),
              "the 3-D filter: the denominator overlaps another array");
   return VISFD_HIP_OK;
 }
 
 // The table's non-zero entries into slot WS_F3D_TAB in the two forms filter3d_kernel reads (jz outermost, then jy, then
-// jx, each ascending).  The context keeps the raw table, the window and the image's row and plane lengths it expanded
-// last: a call with the same ones compares the raw bytes and sends nothing.  *den_inside = the float sum of the entries
+// jx, each ascending).  The slot's key is the window, the image's row and plane lengths and the raw table it expanded
+// last: a call with the same ones compares the bytes and sends nothing.  *den_inside = the float sum of the entries
 // in order: the denominator of every voxel whose window lies inside an unmasked image.
 int filter3d_put_table(visfd_hip_ctx* ctx, const float* table, const int hw[3], i64 nx, i64 ny, i64* n_out,
                        float* den_inside) {
   const size_t size = (size_t)table_size(hw);
-  const int64_t key[5] = {hw[0], hw[1], hw[2], nx, ny};
-  if (ctx->f3d_raw.size() == size && std::memcmp(ctx->f3d_key, key, sizeof key) == 0 &&
-      std::memcmp(ctx->f3d_raw.data(), table, sizeof(float) * size) == 0) {
-    *n_out = ctx->f3d_n;
-    *den_inside = ctx->f3d_den;
+  const int64_t head[5] = {hw[0], hw[1], hw[2], nx, ny};
+  std::vector<unsigned char> key(sizeof head + sizeof(float) * size);
+  std::memcpy(key.data(), head, sizeof head);
+  std::memcpy(key.data() + sizeof head, table, sizeof(float) * size);
+  if (ws_holds(ctx, WS_F3D_TAB, key.data(), key.size())) {
+    *n_out = ctx->f3d.n;
+    *den_inside = ctx->f3d.den;
     return VISFD_HIP_OK;
   }
   std::vector<int> near, far;   // the tested form, the offset form
@@ -282,17 +280,8 @@ int filter3d_put_table(visfd_hip_ctx* ctx, const float* table, const int hw[3], 
         for (int jz = 0; jz <= 2 * hw[2]; jz++) std::memcpy(&near[at + 1 + (FK - 1) + jz], &col[jz * slab], 4);
         ncols++;
       }
-  ctx->f3d_raw.clear();                           // until the new one has arrived
-  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read the table now in the slot
-  int* d = nullptr;
-  VH_TRY(ws(ctx, WS_F3D_TAB, near.size(), &d));
-  VH_HIP(hipMemcpyAsync(d, near.data(), sizeof(int) * near.size(), hipMemcpyHostToDevice, ctx->stream));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->f3d_raw.assign(table, table + size);
-  std::memcpy(ctx->f3d_key, key, sizeof key);
-  ctx->f3d_n = *n_out;
-  ctx->f3d_ncols = ncols;
-  ctx->f3d_den = total;
+  VH_TRY(ws_put(ctx, WS_F3D_TAB, key.data(), key.size(), near.data(), sizeof(int) * near.size()));
+  ctx->f3d = {*n_out, ncols, total};
   return VISFD_HIP_OK;
 }
 
@@ -320,7 +309,7 @@ int dev_filter3d(visfd_hip_ctx* ctx, const float* src, float* dst, const float* 
     const size_t patch = (size_t)(FX + 2 * hw[0]) * (FY + 2 * hw[1]) * sizeof(float);
     const size_t lds = (mask || normalize || den_out) ? 2 * patch : patch;
     filter3d_tiled_kernel<<<dim3(gx, gy, (unsigned)((nz + FK - 1) / FK)), block, lds, ctx->stream>>>(
-        src, dst, mask, den_out, cols, (int)ctx->f3d_ncols, (int)nx, (int)ny, (int)nz, hw[0], hw[1], hw[2],
+        src, dst, mask, den_out, cols, (int)ctx->f3d.ncols, (int)nx, (int)ny, (int)nz, hw[0], hw[1], hw[2],
         normalize ? 1 : 0, den_inside);
     VH_HIP(hipGetLastError());
     return VISFD_HIP_OK;

@@ -324,8 +324,6 @@ void host_tally(StatsBins* b, float v) {
   b->orr[e] |= m;
 }
 
-bool overlaps(const float* a, const float* b, i64 n) { return a && b && a < b + n && b < a + n; }
-
 int check_map(const float* in, const float* out, const float* mask, i64 nx, i64 ny, i64 nz, const visfd_hip_intensity* p) {
   VH_REQUIRE(out && p, "null argument");
   VH_TRY(check_dims(nx, ny, nz));

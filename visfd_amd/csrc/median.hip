@@ -301,20 +301,15 @@ int median_put_table(visfd_hip_ctx* ctx, const int* dxyz, i64 n, MedianTab* mt) 
     t[4 * k + 3] = 0;
     t[4 * n + k] = (e[0] - mt->lo[0]) + mt->W * ((e[1] - mt->lo[1]) + mt->H * (e[2] - mt->lo[2]));
   }
-  if (t == ctx->median_tab) return VISFD_HIP_OK;
-  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read the footprint now in the slot
-  int* d = nullptr;
-  VH_TRY(ws(ctx, WS_MEDIAN_TAB, t.size(), &d));
-  VH_HIP(hipMemcpyAsync(d, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice, ctx->stream));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->median_tab.swap(t);
-  return VISFD_HIP_OK;
+  const size_t bytes = sizeof(int) * t.size();
+  if (ws_holds(ctx, WS_MEDIAN_TAB, t.data(), bytes)) return VISFD_HIP_OK;
+  return ws_put(ctx, WS_MEDIAN_TAB, t.data(), bytes, t.data(), bytes);
 }
 
 int median_run(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz,
                const MedianTab& mt) {
   VH_REQUIRE(nx < (1 << 30) && ny < (1 << 30) && nz < (1 << 30), "median: image dimensions must be below 2^30");
-  VH_REQUIRE(ctx->slot_ptr[WS_MEDIAN_TAB] && !ctx->median_tab.empty(), "median: no footprint on the device");
+  VH_REQUIRE(ctx->slot_ptr[WS_MEDIAN_TAB] && !ctx->slot_key[WS_MEDIAN_TAB].empty(), "median: no footprint on the device");
   const uint32_t* s = reinterpret_cast<const uint32_t*>(src);   // bit patterns throughout: a median has no arithmetic
   uint32_t* d = reinterpret_cast<uint32_t*>(dst);
   MedianRoute routes[2];

@@ -298,14 +298,9 @@ int morph_put_table(visfd_hip_ctx* ctx, const int* dxyz, const float* b, i64 n, 
     el->runs = ok;
     el->R = R;
   }
-  if (n == 0 || t == ctx->morph_tab) return VISFD_HIP_OK;
-  VH_HIP(hipStreamSynchronize(ctx->stream));   // queued kernels may still read the element now in the slot
-  int* d = nullptr;
-  VH_TRY(ws(ctx, WS_MORPH_TAB, t.size(), &d));
-  VH_HIP(hipMemcpyAsync(d, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice, ctx->stream));
-  VH_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->morph_tab.swap(t);
-  return VISFD_HIP_OK;
+  const size_t bytes = sizeof(int) * t.size();
+  if (n == 0 || ws_holds(ctx, WS_MORPH_TAB, t.data(), bytes)) return VISFD_HIP_OK;
+  return ws_put(ctx, WS_MORPH_TAB, t.data(), bytes, t.data(), bytes);
 }
 
 // one op with the element in WS_MORPH_TAB.  Open = erode then dilate, close = dilate then erode (morphology.hpp:431-510),

@@ -123,12 +123,12 @@ tv_dense_kernel(const float* __restrict__ sal, const float* __restrict__ dir,
 
 // The vote tables of (sigma_tv, cutoff) on the device: float4 {w, rhat_x, rhat_y, rhat_z} per offset j in z, y, x order
 // (filter3d.hpp:563-578, feature.hpp:2470-2478), in the five layouts of tv_common.hpp (TvTableLayout).  Built on the host
-// once and kept in the context: a launch with the same parameters queues no copy and never waits for the stream.
+// once and kept in slot WS_TVTAB under the key (h, sigma_tv, cutoff): a launch with the same parameters queues no copy and
+// never waits for the stream.
 static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int h, TvTables* out) {
   const TvTableLayout l = tv_table_layout(h);
-  if (!(ctx->tv_table_dev && ctx->tv_table_h == h && ctx->tv_table_key[0] == sigma_tv && ctx->tv_table_key[1] == cutoff)) {
-    // kernels of an earlier call may still read the old table, and the copy below reads host memory of this call
-    VH_HIP(hipStreamSynchronize(ctx->stream));
+  const struct { int h; float sigma_tv, cutoff; } key = {h, sigma_tv, cutoff};
+  if (!ws_holds(ctx, WS_TVTAB, &key, sizeof key)) {
     const size_t n = 2 * (size_t)h + 1, m = n * n * n;
     std::vector<float> w(m), rh(3 * m);
     host_tv_tables(sigma_tv, h, w.data(), rh.data());
@@ -145,17 +145,9 @@ static int tv_table_device(visfd_hip_ctx* ctx, float sigma_tv, float cutoff, int
       tab[l.box_tol_sq + kb] = tab[l.box_tol + kb];
       tab[l.box_tol_sq + kb].x = (float)sqrt((double)w[k]);
     }
-    float4* dtab = nullptr;
-    ctx->tv_table_dev = nullptr;
-    VH_TRY(ws(ctx, WS_TVTAB, l.total, &dtab));
-    VH_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(float4) * l.total, hipMemcpyHostToDevice, ctx->stream));
-    VH_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->tv_table_dev = reinterpret_cast<float*>(dtab);
-    ctx->tv_table_h = h;
-    ctx->tv_table_key[0] = sigma_tv;
-    ctx->tv_table_key[1] = cutoff;
+    VH_TRY(ws_put(ctx, WS_TVTAB, &key, sizeof key, tab.data(), sizeof(float4) * l.total));
   }
-  const float4* const dtab = reinterpret_cast<const float4*>(ctx->tv_table_dev);
+  const float4* const dtab = static_cast<const float4*>(ctx->slot_ptr[WS_TVTAB]);
   *out = {dtab + l.packed, dtab + l.padded, dtab + l.box_tol, dtab + l.box_exact, dtab + l.box_tol_sq, h};
   return VISFD_HIP_OK;
 }

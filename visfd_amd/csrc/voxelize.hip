@@ -385,12 +385,7 @@ int voxelize(visfd_hip_ctx* ctx, const MeshArgs& a, const std::vector<int32_t>& 
   i64* dend = reinterpret_cast<i64*>(tab + off_end);
   unsigned long long* counters = reinterpret_cast<unsigned long long*>(tab + off_cnt);
 
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const bool timed = ctx->opt.voxelize_time != 0;
-  if (timed)
-    for (int k = 0; k < 4; k++) VH_HIP(hipEventCreate(&ev[k]));
-  auto mark = [&](int k) { return timed ? hipEventRecord(ev[k], ctx->stream) : hipSuccess; };
-
+  PhaseClock<3> clock;   // option voxelize_time
   if (a.m > 0) {
     VH_HIP(hipMemcpyAsync(dq, q.data(), sizeof(int) * q.size(), hipMemcpyHostToDevice, ctx->stream));
     VH_HIP(hipMemcpyAsync(dtri, a.triangles, sizeof(int) * 3 * (size_t)a.m, hipMemcpyHostToDevice, ctx->stream));
@@ -400,9 +395,9 @@ int voxelize(visfd_hip_ctx* ctx, const MeshArgs& a, const std::vector<int32_t>& 
     VH_HIP(hipMemcpyAsync(dend, item_end.data(), sizeof(i64) * ntiled, hipMemcpyHostToDevice, ctx->stream));
   }
   VH_HIP(hipMemsetAsync(counters, 0, 3 * sizeof(unsigned long long), ctx->stream));
-  VH_HIP(mark(0));
+  clock.start(ctx->stream, ctx->opt.voxelize_time != 0);
   VH_HIP(hipMemsetAsync(toggle, 0, sizeof(unsigned) * (size_t)nrows * W, ctx->stream));
-  VH_HIP(mark(1));
+  clock.mark(1);
   const i64 cap = (i64)ctx->num_cus * 64;
   const bool bisect = ctx->opt.voxelize_bisect != 0;   // tests: k never from the estimate
   if (a.m > 0) {
@@ -415,21 +410,18 @@ int voxelize(visfd_hip_ctx* ctx, const MeshArgs& a, const std::vector<int32_t>& 
         dq, dtri, did, dend, (int)ntiled, nitems, nx, ny, nz, W, bisect, toggle, counters);
     VH_HIP(hipGetLastError());
   }
-  VH_HIP(mark(2));
+  clock.mark(2);
   const unsigned grows = grid_for(nrows, BLOCK / WAVE, cap);
   if (nx % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0)
     fill_kernel<true><<<dim3(grows), dim3(BLOCK), 0, ctx->stream>>>(toggle, dst, nx, nrows, W, counters);
   else
     fill_kernel<false><<<dim3(grows), dim3(BLOCK), 0, ctx->stream>>>(toggle, dst, nx, nrows, W, counters);
   VH_HIP(hipGetLastError());
-  VH_HIP(mark(3));
+  clock.mark(3);
   unsigned long long c[3] = {0, 0, 0};
   VH_HIP(hipMemcpyAsync(c, counters, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
   VH_HIP(hipStreamSynchronize(ctx->stream));
-  if (timed) {
-    for (int k = 0; k < 3; k++) VH_HIP(hipEventElapsedTime(&ctx->voxelize_ms[k], ev[k], ev[k + 1]));
-    for (int k = 0; k < 4; k++) VH_HIP(hipEventDestroy(ev[k]));
-  }
+  if (clock.on) clock.read(ctx->voxelize_ms);
   ctx->voxelize_stats[0] = (int64_t)c[0];
   ctx->voxelize_stats[1] = skipped;
   ctx->voxelize_stats[2] = (int64_t)c[1];
