@@ -1027,6 +1027,42 @@ int visfd_hip_surface_points(const float* saliency, const float* voxel2cluster, 
                              const float voxel_width[3], float curve_ds, int find_ridge,
                              float max_distance_to_feature, float* crds, float* norms, int64_t capacity,
                              int64_t* n_points);
+/* The same points from a context's device: the selection and its raster-order list, the walks along the normals and the
+ * gather of the ridge snap's Hessians and gradients run as kernels (csrc/surface_points.hip); the 3x3 eigen solve of the
+ * snap, its rejections and the voxel_width scaling run on the host over the compacted points.  Points, normals, count and
+ * order are those of visfd_hip_surface_points bit for bit, provided every direction a walk meets has a finite, non-zero
+ * length (where one has not, the host's own conversion of a NaN to an index is undefined: the device ends that walk as if
+ * it had left the image, reads nothing out of range, and still returns VISFD_HIP_OK).
+ *   _ctx  host arrays, direction [nz][ny][nx][3]; crds / norms host [capacity][3].
+ *   _dev  device arrays, direction channel-planar [3][nz][ny][nx]; crds / norms [capacity][3] in device or host memory.
+ * One call counts and fills: with crds == norms == NULL it only counts; otherwise, when the points do not fit,
+ * *n_points holds the needed count, crds / norms are left unwritten and the call returns VISFD_HIP_ECAPACITY.  Every
+ * dimension must be at least 3 and below 2^24 (positions are floats); the voxel count is not limited to 2^31.
+ * A walk takes at most `surface_steps_cap` steps per direction on the device (option, default 256).  A call in which a
+ * walk needs more, or in which a walked point rounds to a voxel outside the image, is handed over to
+ * visfd_hip_surface_points (the _dev entry brings the volumes to the host for it); visfd_hip_surface_points_last says so. */
+int visfd_hip_surface_points_ctx(visfd_hip_ctx*, const float* saliency, const float* voxel2cluster, const float* direction,
+                                 const float* mask, int64_t nx, int64_t ny, int64_t nz, int select_cluster,
+                                 const float voxel_width[3], float curve_ds, int find_ridge,
+                                 float max_distance_to_feature, float* crds, float* norms, int64_t capacity,
+                                 int64_t* n_points);
+int visfd_hip_surface_points_dev(visfd_hip_ctx*, const float* saliency, const float* voxel2cluster, const float* direction,
+                                 const float* mask, int64_t nx, int64_t ny, int64_t nz, int select_cluster,
+                                 const float voxel_width[3], float curve_ds, int find_ridge,
+                                 float max_distance_to_feature, float* crds, float* norms, int64_t capacity,
+                                 int64_t* n_points);
+#define VISFD_HIP_SURFACE_POINTS_PATH_DEVICE 0
+#define VISFD_HIP_SURFACE_POINTS_PATH_HANDED_OVER 1
+#define VISFD_HIP_SURFACE_POINTS_REASON_STEPS 1u    /* a walk reached surface_steps_cap */
+#define VISFD_HIP_SURFACE_POINTS_REASON_BOUNDS 2u   /* a walked point rounds to a voxel outside the image */
+/* The context's last _ctx / _dev call: out[0] the path, out[1] the reason bits of a hand-over, out[2] the selected voxels,
+ * out[3] the points, out[4] the longest walk in steps (one direction; on the device path), out[5] the steps all walks of
+ * the device path took together (the last, failing step of each direction and the second walk to the two positions
+ * around the average included).  -1, 0, -1, -1, -1, -1 before the first call. */
+int visfd_hip_surface_points_last(visfd_hip_ctx*, int64_t out[6]);
+/* Under the option surface_points_time: milliseconds of the last device-path call: select and compact, walk, ridge
+ * gather (events on the stream), host finish with the copies out (host clock); -1 for a stage that did not run. */
+int visfd_hip_surface_points_last_times(visfd_hip_ctx*, float ms[4]);
 
 /* ---- f4: BinArray3D / UnbinArray3D, lib/visfd/resample.hpp:53-166 -------------------------------------
  * Sizes are {nx, ny, nz}.  bin[d] = floor(size_big[d] / size_small[d]); `offset` (nullable) shifts the

@@ -281,6 +281,13 @@ _SIGS = {
     "visfd_hip_convert_flat_sym2_evects3_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "visfd_hip_surface_points": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int, C.c_float,
                                            _vp, _vp, _i64, C.POINTER(_i64)]),
+    # the same behind a context (csrc/surface_points.hip)
+    "visfd_hip_surface_points_ctx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int,
+                                               C.c_float, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "visfd_hip_surface_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int,
+                                               C.c_float, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "visfd_hip_surface_points_last": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "visfd_hip_surface_points_last_times": (C.c_int, [_vp, _fp]),
     "visfd_hip_sphere_overlap": (C.c_float, [C.c_float, C.c_float, C.c_float]),
     "visfd_hip_sort_blobs": (C.c_int, [_fp, _fp, _fp, _i64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "visfd_hip_discard_masked_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), _vp, _i64, _i64, _i64]),
@@ -805,6 +812,43 @@ DO_NOT_SORT, SORT_DECREASING, SORT_INCREASING, SORT_DECREASING_MAGNITUDE, SORT_I
 def _chk_host(L, rc):
     if rc:
         raise VisfdHipError(rc, L.visfd_hip_last_error().decode())
+
+
+# visfd_hip_surface_points_last (VISFD_HIP_SURFACE_POINTS_PATH_*, _REASON_*)
+SURFACE_POINTS_PATH_DEVICE, SURFACE_POINTS_PATH_HANDED_OVER = 0, 1
+SURFACE_POINTS_REASON_STEPS, SURFACE_POINTS_REASON_BOUNDS = 1, 2
+
+
+def _surface_points(call, L, shape, select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity):
+    """One surface-points entry behind call(select, width, ds, ridge, maxd, crds, norms, capacity, n) -> (crds, norms) as
+    numpy (n, 3).  capacity None: room for 65536 points, and once more with the reported count where that is too little; a
+    given capacity is passed as it is, and VISFD_HIP_ECAPACITY raises with the needed count in the error's `needed`."""
+    cap = 65536 if capacity is None else int(capacity)
+    for attempt in range(2):
+        crds, norms = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.float32)
+        n = _i64(0)
+        rc = call(int(select_cluster), _f3(voxel_width), float(curve_ds), int(bool(find_ridge)),
+                  float(max_distance_to_feature), crds.ctypes.data, norms.ctypes.data, cap, C.byref(n))
+        if rc == 4 and capacity is None and attempt == 0:   # VISFD_HIP_ECAPACITY: the count came back
+            cap = int(n.value)
+            continue
+        if rc:
+            err = VisfdHipError(rc, L.visfd_hip_last_error().decode())
+            err.needed = int(n.value)
+            raise err
+        return crds[:n.value], norms[:n.value]
+
+
+def surface_points_host(saliency, direction, voxel2cluster=None, mask=None, select_cluster=1, voxel_width=(1, 1, 1),
+                        curve_ds=0.2, find_ridge=True, max_distance_to_feature=1.3, capacity=None):
+    """visfd_hip_surface_points (the -normals-file tail of HandleTV, handlers.cpp:2039-2309) on the host: saliency, mask and
+    voxel2cluster (the labels as floats; None: every unmasked voxel as it is) float32 [nz, ny, nx], direction [nz, ny, nx, 3]
+    -> (crds, norms), numpy (n, 3) each."""
+    L = load_library()
+    nz, ny, nx = saliency.shape
+    return _surface_points(lambda *t: L.visfd_hip_surface_points(_np(saliency), _np(voxel2cluster), _np(direction), _np(mask),
+                                                                 nx, ny, nz, *t),
+                           L, saliency.shape, select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity)
 
 
 # visfd_hip_discard_overlapping_blobs_last (VISFD_HIP_DISCARD_OVERLAP_PATH_*, _REASON_*)
@@ -1565,6 +1609,53 @@ class Context:
         host vector test, edges, clusters, directions, copies in, copies out)."""
         ms = (C.c_float * 8)()
         self._chk(self._L.visfd_hip_label_connected_graph_last_times(self._h, ms))
+        return tuple(ms)
+
+    def surface_points(self, saliency, direction, voxel2cluster=None, mask=None, select_cluster=1, voxel_width=(1, 1, 1),
+                       curve_ds=0.2, find_ridge=True, max_distance_to_feature=1.3, capacity=None):
+        """api.surface_points_host on this context's device (visfd_hip_surface_points_ctx; numpy arrays, direction
+        [nz, ny, nx, 3]): the same points, bit for bit."""
+        nz, ny, nx = saliency.shape
+        return _surface_points(lambda *t: self._L.visfd_hip_surface_points_ctx(
+            self._h, _np(saliency), _np(voxel2cluster), _np(direction), _np(mask), nx, ny, nz, *t),
+            self._L, saliency.shape, select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity)
+
+    def surface_points_dev(self, saliency, direction, voxel2cluster=None, mask=None, select_cluster=1, voxel_width=(1, 1, 1),
+                           curve_ds=0.2, find_ridge=True, max_distance_to_feature=1.3, capacity=None, crds=None, norms=None):
+        """surface_points on device tensors (visfd_hip_surface_points_dev): saliency, voxel2cluster, mask float32
+        [nz, ny, nx], direction channel-planar [3, nz, ny, nx].  -> (crds, norms) as numpy (n, 3); or, with crds and norms
+        given as contiguous cuda float32 [capacity, 3], the points go there and the count is returned.  Returns with the
+        stream idle."""
+        nz, ny, nx = saliency.shape
+        assert tuple(direction.shape) == (3, nz, ny, nx), "direction: channel-planar [3, nz, ny, nx]"
+        args = (self._h, _dev(saliency), _dev(voxel2cluster), _dev(direction), _dev(mask), nx, ny, nz)
+        if crds is None:
+            return _surface_points(lambda *t: self._L.visfd_hip_surface_points_dev(*(args + t)), self._L, saliency.shape,
+                                   select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity)
+        assert tuple(crds.shape) == tuple(norms.shape) and crds.shape[1] == 3, "crds, norms: [capacity, 3]"
+        n = _i64(0)
+        rc = self._L.visfd_hip_surface_points_dev(*(args + (int(select_cluster), _f3(voxel_width), float(curve_ds),
+                                                            int(bool(find_ridge)), float(max_distance_to_feature), _dev(crds),
+                                                            _dev(norms), int(crds.shape[0]), C.byref(n))))
+        if rc:
+            err = VisfdHipError(rc, self._L.visfd_hip_last_error().decode())
+            err.needed = int(n.value)
+            raise err
+        return int(n.value)
+
+    def surface_points_last(self):
+        """(path, reasons, selected voxels, points, longest walk in steps, steps of all walks) of the context's last
+        surface_points[_dev]: path
+        SURFACE_POINTS_PATH_DEVICE or _HANDED_OVER (the host entry finished the call) with the SURFACE_POINTS_REASON_* bits."""
+        out = (_i64 * 6)()
+        self._chk(self._L.visfd_hip_surface_points_last(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def surface_points_last_times(self):
+        """Under the option surface_points_time: (select and compact, walk, ridge gather, host finish and copies out)
+        milliseconds of the last device-path surface_points[_dev]."""
+        ms = (C.c_float * 4)()
+        self._chk(self._L.visfd_hip_surface_points_last_times(self._h, ms))
         return tuple(ms)
 
     def watershed_last_stats(self):

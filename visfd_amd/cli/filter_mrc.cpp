@@ -1022,7 +1022,9 @@ void save_tensors(Run& r, const vector<float>& tensor) {
 }
 
 // -normals-file (handlers.cpp:2039-2309): the points of the selected cluster's surface and their normals, as a PLY file
-void write_normals_file(Run& r, const vector<float>& saliency, const vector<float>& direction) {
+// With a context (`ctx` non-null) the points come from the device in one call (visfd_hip_surface_points_ctx: the same points
+// bit for bit, profiles/surface_points_time.txt); without a device the host entry counts, then fills.
+void write_normals_file(Run& r, visfd_hip_ctx* ctx, const vector<float>& saliency, const vector<float>& direction) {
   const Settings& s = r.s;
   const float* mptr = r.mask_flat();
   const float* o = r.tomo_out.data();
@@ -1030,13 +1032,29 @@ void write_normals_file(Run& r, const vector<float>& saliency, const vector<floa
   if (maxd < 0.0f) maxd /= -r.vw[0];
   else maxd /= (float)r.bin;
   int64_t np = 0;
-  hip_detail::check(visfd_hip_surface_points(saliency.data(), o, direction.data(), mptr, r.size[0], r.size[1], r.size[2],
-                                             s.select_cluster, r.vw, s.surface_normal_curve_ds, s.surface_find_ridge ? 1 : 0,
-                                             maxd, nullptr, nullptr, 0, &np));
-  vector<float> crds(3 * (size_t)np + 3), norms(3 * (size_t)np + 3);
-  hip_detail::check(visfd_hip_surface_points(saliency.data(), o, direction.data(), mptr, r.size[0], r.size[1], r.size[2],
-                                             s.select_cluster, r.vw, s.surface_normal_curve_ds, s.surface_find_ridge ? 1 : 0,
-                                             maxd, crds.data(), norms.data(), np, &np));
+  vector<float> crds, norms;
+  if (ctx) {
+    int64_t cap = 1 << 16;
+    for (int attempt = 0; attempt < 2; attempt++) {   // too small a guess: the count comes back, once more with room for it
+      crds.assign(3 * (size_t)cap + 3, 0.0f);
+      norms.assign(3 * (size_t)cap + 3, 0.0f);
+      const int rc = visfd_hip_surface_points_ctx(ctx, saliency.data(), o, direction.data(), mptr, r.size[0], r.size[1], r.size[2],
+                                                  s.select_cluster, r.vw, s.surface_normal_curve_ds,
+                                                  s.surface_find_ridge ? 1 : 0, maxd, crds.data(), norms.data(), cap, &np);
+      if (rc == VISFD_HIP_ECAPACITY && attempt == 0) { cap = np; continue; }
+      hip_detail::check(rc);
+      break;
+    }
+  } else {
+    hip_detail::check(visfd_hip_surface_points(saliency.data(), o, direction.data(), mptr, r.size[0], r.size[1], r.size[2],
+                                               s.select_cluster, r.vw, s.surface_normal_curve_ds, s.surface_find_ridge ? 1 : 0,
+                                               maxd, nullptr, nullptr, 0, &np));
+    crds.assign(3 * (size_t)np + 3, 0.0f);
+    norms.assign(3 * (size_t)np + 3, 0.0f);
+    hip_detail::check(visfd_hip_surface_points(saliency.data(), o, direction.data(), mptr, r.size[0], r.size[1], r.size[2],
+                                               s.select_cluster, r.vw, s.surface_normal_curve_ds, s.surface_find_ridge ? 1 : 0,
+                                               maxd, crds.data(), norms.data(), np, &np));
+  }
   std::ofstream ply(s.out_normals_file.c_str());              // file_io.hpp:501-527
   if (!ply) throw VisfdErr("Error: unable to open \"" + s.out_normals_file + "\" for writing.\n");
   ply << "ply\nformat ascii 1.0\ncomment  created by visfd\nelement vertex " << np
@@ -1101,7 +1119,7 @@ void cluster(Run& r, int order, const vector<float>& tensor) {
   vector<float> saliency;
   if (!s.out_normals_file.empty()) saliency.assign(r.tomo_out.data(), r.tomo_out.data() + n);   // handlers.cpp:1929-1934
   labels_to_image(s, labels.data(), max_label, r.tomo_out.data(), n);
-  if (!s.out_normals_file.empty()) write_normals_file(r, saliency, direction);
+  if (!s.out_normals_file.empty()) write_normals_file(r, ctx, saliency, direction);
 }
 
 bool handle_membrane(Run& r) {

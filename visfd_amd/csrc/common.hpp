@@ -93,6 +93,11 @@ enum Slot {
   WS_OVL_TEMP,                     // ... the reduction words, the counters, and the sort's and the scan's temporary storage
   WS_VOX_TOGGLE,                   // VoxelizeMesh (csrc/voxelize.hip): the toggle volume, nx + 1 bits per row (iy, iz) in 32-bit words
   WS_VOX_MESH,                     // ... the quantised vertices, the triangles, the tiled triangles' ids and running item counts, the counters
+  WS_SP_BITS,                      // surface points (csrc/surface_points.hip): one selection bit per voxel, a byte per 8 voxels
+  WS_SP_CHUNKS,                    // ... per workgroup chunk its count (uint32) and its list offset (uint64); the counters; the table of arc lengths
+  WS_SP_LIST,                      // ... the selected voxels' linear indices in raster order (int64)
+  WS_SP_OUT,                       // ... per listed voxel its position and its normal (2 x 3 floats), then the ridge records (9 floats)
+  WS_SP_SCRATCH,                   // ... the backward weights of one batch of walks, [step][lane]
   WS_NSLOTS
 };
 
@@ -141,6 +146,10 @@ struct visfd_hip_options {
   int draw_time = 0;        // 1: DrawSpheres times its zero fill, scatter and resolve with events and waits for them (tools/draw_time.py)
   int voxelize_bisect = 0;  // tests: VoxelizeMesh finds every crossing's sample by bisection with the exact sign, never from the double estimate
   int voxelize_time = 0;    // 1: VoxelizeMesh times its zero fill, scatter and fill with events (tools/voxelize_time.py)
+  int surface_steps_cap = 256;   // visfd_hip_surface_points_ctx / _dev: steps a walk may take per direction on the device; a call in which
+                            //    a walk needs more is finished by the host entry.  One float of scratch per step and lane of a batch:
+                            //    256 steps x 262144 lanes = 256 MiB (csrc/surface_points.hip).  Clamped to 1..65536
+  int surface_points_time = 0;   // 1: those two time their stages (visfd_hip_surface_points_last_times; tools/surface_points_time.py)
   int debug = 0;
 };
 
@@ -168,6 +177,8 @@ struct visfd_hip_ctx {
   float draw_ms[3] = {-1.0f, -1.0f, -1.0f};   // option draw_time: zero fill, scatter (with count and values), resolve of the last DrawSpheres
   int64_t voxelize_stats[4] = {-1, -1, -1, -1};   // the last VoxelizeMesh: crossings, skipped triangles, odd rows, inside voxels
   float voxelize_ms[3] = {-1.0f, -1.0f, -1.0f};   // option voxelize_time: zero fill, scatter, fill of the last VoxelizeMesh
+  int64_t surface_points_last[6] = {-1, 0, -1, -1, -1, -1};   // the last visfd_hip_surface_points_ctx / _dev: path, reasons, selected voxels, points, longest walk, steps taken
+  float surface_points_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f};   // option surface_points_time: select and compact, walk, ridge gather, host finish and copies
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
   int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test

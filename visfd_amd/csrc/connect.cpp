@@ -684,7 +684,51 @@ void diagonalize_sym3(const R mat[3][3], R eivals[3], R eivects[3][3], int order
 
 inline float length3f(const float* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }   // visfd_utils.hpp:41-43
 
+// The tail of find_ridge (handlers.cpp:2262-2296): from the Hessian and the gradient of the saliency at the voxel
+// (ix0, iy0, iz0), the point moved onto the ridge along the principal Hessian direction, in physical units.  False: the
+// point is dropped.  One text for visfd_hip_surface_points and for the device path's host finish (surface_points.hip).
+inline bool ridge_snap(float H[3][3], const float grad[3], int ix0, int iy0, int iz0, const int size[3],
+                       const float voxel_width[3], float max_distance_to_feature, float xyz[3]) {
+  float ev[3], E[3][3];
+  diagonalize_sym3<float>(H, ev, E, EIG_DECREASING_ABS);
+  float g1 = dot3(grad, E[0]);
+  if (g1 < 0.0f) { g1 = -g1; for (int d = 0; d < 3; d++) E[0][d] = -E[0][d]; }
+  else if (g1 == 0.0f) return false;
+  const float dist = (ev[0] != 0) ? g1 / ev[0] : std::numeric_limits<float>::infinity();
+  if (max_distance_to_feature > 0.0f && std::abs(dist) > max_distance_to_feature) return false;
+  xyz[0] = ix0 - dist * E[0][0];
+  xyz[1] = iy0 - dist * E[0][1];
+  xyz[2] = iz0 - dist * E[0][2];
+  if (xyz[0] < 0.0f || size[0] < xyz[0] || xyz[1] < 0.0f || size[1] < xyz[1] || xyz[2] < 0.0f || size[2] < xyz[2]) return false;
+  for (int d = 0; d < 3; d++) xyz[d] *= voxel_width[d];
+  return true;
+}
+
 }  // namespace
+
+// The host finish of the device path (surface_points.hip): per walked point k, rec[9k..] = the Hessian (xx, yy, zz, xy, yz,
+// xz) and the gradient of the saliency at round(xyz[3k..]), as the device gathered them.  Snaps in place and compacts
+// xyz / nrm, order kept; returns the number of points that stay.
+int64_t vh::host_surface_ridge_finish(float* xyz, float* nrm, const float* rec, int64_t n, const int size[3],
+                                      const float voxel_width[3], float max_distance_to_feature) {
+  std::vector<unsigned char> keep((size_t)n);
+  vh::parallel_voxels(n, [&](int64_t lo, int64_t hi) {   // the points are independent: the snaps across the host's cores
+    for (int64_t k = lo; k < hi; k++) {
+      float* p = xyz + 3 * k;
+      const int ix0 = (int)std::round(p[0]), iy0 = (int)std::round(p[1]), iz0 = (int)std::round(p[2]);
+      const float* r = rec + 9 * k;
+      float H[3][3] = {{r[0], r[3], r[5]}, {r[3], r[1], r[4]}, {r[5], r[4], r[2]}};
+      keep[(size_t)k] = ridge_snap(H, r + 6, ix0, iy0, iz0, size, voxel_width, max_distance_to_feature, p) ? 1 : 0;
+    }
+  });
+  int64_t count = 0;
+  for (int64_t k = 0; k < n; k++) {   // the compaction in order
+    if (!keep[(size_t)k]) continue;
+    for (int d = 0; d < 3; d++) { xyz[3 * count + d] = xyz[3 * k + d]; nrm[3 * count + d] = nrm[3 * k + d]; }
+    count++;
+  }
+  return count;
+}
 
 // DiagonalizeSym3<float> (eigen3_simple.hpp:137-266): m9 = 3x3 row-major, eivects9 = eigenvectors as rows;
 // order 0..3 = INCREASING, DECREASING, INCREASING_ABS, DECREASING_ABS eigenvalues.
@@ -801,18 +845,7 @@ extern "C" int visfd_hip_surface_points(const float* saliency, const float* voxe
             grad[1] = (float)(0.5 * (S[g.at(gx, gy + 1, gz)] - S[g.at(gx, gy - 1, gz)]));
             grad[2] = (float)(0.5 * (S[g.at(gx, gy, gz + 1)] - S[g.at(gx, gy, gz - 1)]));
           }
-          float ev[3], E[3][3];
-          diagonalize_sym3<float>(H, ev, E, EIG_DECREASING_ABS);
-          float g1 = dot3(grad, E[0]);
-          if (g1 < 0.0f) { g1 = -g1; for (int d = 0; d < 3; d++) E[0][d] = -E[0][d]; }
-          else if (g1 == 0.0f) continue;
-          const float dist = (ev[0] != 0) ? g1 / ev[0] : std::numeric_limits<float>::infinity();
-          if (max_distance_to_feature > 0.0f && std::abs(dist) > max_distance_to_feature) continue;
-          xyz[0] = ix0 - dist * E[0][0];
-          xyz[1] = iy0 - dist * E[0][1];
-          xyz[2] = iz0 - dist * E[0][2];
-          if (xyz[0] < 0.0f || size[0] < xyz[0] || xyz[1] < 0.0f || size[1] < xyz[1] || xyz[2] < 0.0f || size[2] < xyz[2]) continue;
-          for (int d = 0; d < 3; d++) xyz[d] *= voxel_width[d];
+          if (!ridge_snap(H, grad, ix0, iy0, iz0, size, voxel_width, max_distance_to_feature, xyz)) continue;
         }
         emit(xyz, normal);
       }

@@ -31,6 +31,13 @@ int host_label_connected(const float* saliency, int64_t* labels, const float* ma
 void host_find_seeds(const float* saliency, const float* mask, int64_t nx, int64_t ny, int64_t nz, bool seek_minima,
                      float threshold, int connectivity, std::vector<int>* index, std::vector<float>* score);
 
+// connect.cpp: the host finish of the device path of the surface points (surface_points.hip).  Per walked point k,
+// rec[9k..] holds the Hessian (xx, yy, zz, xy, yz, xz) and the gradient of the saliency at round(xyz[3k..]).  Runs the
+// ridge snap of visfd_hip_surface_points (the same text) on each, compacts xyz / nrm in place with the order kept, and
+// returns the number of points that stay.
+int64_t host_surface_ridge_finish(float* xyz, float* nrm, const float* rec, int64_t n, const int size[3],
+                                  const float voxel_width[3], float max_distance_to_feature);
+
 // ---- text that the flood (connect.cpp) and the settle paths of the graph entries (connect_graph_host.cpp) both run, so
 // that the two cannot drift apart: every statement below is the flood's, operand order and types kept.
 
