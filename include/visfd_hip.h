@@ -89,7 +89,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * _last_times; then the mesh voxeliser: visfd_hip_voxelize_mesh[_dev],
                                      * visfd_hip_voxelize_last, _last_times, visfd_hip_voxelize_quantize_host and
                                      * visfd_hip_mesh_edges_host; then the flat ball as a threshold,
-                                     * visfd_hip_flat_ball_dsq_max) */
+                                     * visfd_hip_flat_ball_dsq_max; then the closing of an oriented point cloud into a
+                                     * mask: visfd_hip_close_surface[_dev], visfd_hip_close_surface_splat[_dev|_host],
+                                     * visfd_hip_close_surface_last and _last_times) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -160,6 +162,13 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    (visfd_hip_voxelize_last_times); default 0
  *   voxelize_bisect  tests: the voxeliser finds the sample behind every crossing by bisection with the exact sign, never
  *                    from its double-precision estimate; images are bit-identical either way; default 0
+ *   close_surface_rtol_exp   k: visfd_hip_close_surface[_dev] stop their multigrid cycles when the residual's 2-norm is at
+ *                    most 10^-k of the right-hand side's; default 5 (profiles/close_surface_time.txt)
+ *   close_surface_max_cycles  ... or after this many cycles (the mask is still returned and
+ *                    visfd_hip_close_surface_last reports the stop); default 20, twice the
+ *                    most cycles the test cases take at the default rtol
+ *   close_surface_time  1: those two entries time their three phases with events (visfd_hip_close_surface_last_times);
+ *                    default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
 int visfd_hip_get_option(visfd_hip_ctx* ctx, const char* name, int64_t* value_out);
@@ -1375,6 +1384,66 @@ int visfd_hip_voxelize_quantize_host(const float* vertices, int64_t n_vertices, 
  * VISFD_HIP_EINVAL for an index outside [0, n_vertices). */
 int visfd_hip_mesh_edges_host(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, int64_t* boundary_edges,
                               int64_t* nonmanifold_edges);
+
+/* ---- closing an oriented point cloud into a mask ----------------------------------------------------------
+ * No counterpart in the reference: its Example 3 writes the cloud with -normals-file, closes it with an external surface
+ * reconstruction program, and voxelises the mesh for the next run's -mask.  Here the mask is computed on the voxel grid, as
+ * the grid form of Poisson surface reconstruction.  The result is defined as follows.
+ *
+ * Inputs.  n points p_i (float[n][3], x y z, in voxel coordinates: voxel (ix, iy, iz) is the node at that coordinate), their
+ * normals n_i (float[n][3]), the image size nx, ny, nz >= 3, pad >= 0 (the equation is solved on the box that is the image
+ * grown by pad nodes on every face: Nd = nd + 2 pad nodes per axis, each at most 65535), and the orientation
+ * (VISFD_HIP_CLOSE_OUTWARD: the normals point out of the solid, _INWARD, or _AUTO).
+ *
+ * 1. Splat (exact, independent of order).  A point is USED when its six floats are finite, no |n_d| exceeds 2^30 (so that
+ *    no contribution leaves int64), and its cell floor(p) .. floor(p) + 1 lies inside the box; the others are counted as
+ *    skipped.  In double: f_d = (double)p_d - floor((double)p_d); a corner's weight is (wx * wy) * wz with w = f or 1 - f;
+ *    its contribution to channel d is llrint((weight * (double)n_d) * 2^24), ties to even.  Contributions are added as
+ *    64-bit integers into three int64 volumes acc[d][Nz][Ny][Nx].  V_d = (float)((double)acc_d * 2^-24).
+ * 2. Right-hand side, in float: b = ((0.5 (Vx[x+1] - Vx[x-1]) + 0.5 (Vy[y+1] - Vy[y-1])) + 0.5 (Vz[z+1] - Vz[z-1])), V = 0
+ *    outside the box.
+ * 3. chi solves Laplace(chi) = b with the 7-point Laplacian at unit spacing, chi = 0 outside the box: float32 multigrid
+ *    V-cycles on the device, stopped when |b - Laplace(chi)|_2 <= rtol |b|_2 (rtol = 10^-close_surface_rtol_exp), the norm
+ *    being that of the iterate the call returns, or after close_surface_max_cycles cycles.  Every reduction has a fixed
+ *    order: a call gives the same bits on every run.  The float64 solve of tests/close_surface_np.py is the yardstick.
+ * 4. Level: iso = (the sum over the used points, in double and in a fixed order, of chi interpolated trilinearly at p_i with
+ *    the weights of step 1) / n_used.
+ * 5. Mask over the image (the pad is dropped), float32 [nz][ny][nx] of 0 and 1 like visfd_hip_voxelize_mesh's:
+ *    outward: 1 where (double)chi < iso; inward: 1 where (double)chi > iso; auto: whichever of the two sets holds fewer
+ *    nodes on the six faces of the padded box, outward on a tie.
+ * chi_out (nullable): float32 [nz][ny][nx], chi over the image.
+ *
+ * A call in which no point is used (n == 0 included) succeeds with a mask of zeros.  VISFD_HIP_EINVAL, before anything is
+ * allocated: a null context or mask, a dimension below 3, a negative pad or n, n > 0 with a null array, an unknown
+ * orientation, a padded dimension above 65535.  points, normals, mask and chi_out are host arrays in the first form and
+ * device arrays in the _dev form, where an output that overlaps a list or the other output is VISFD_HIP_EINVAL too.  Both return with the stream idle. */
+#define VISFD_HIP_CLOSE_OUTWARD 0
+#define VISFD_HIP_CLOSE_INWARD 1
+#define VISFD_HIP_CLOSE_AUTO 2
+#define VISFD_HIP_CLOSE_STOP_RTOL 0   /* the residual test was met */
+#define VISFD_HIP_CLOSE_STOP_CAP 1    /* close_surface_max_cycles cycles were run first */
+#define VISFD_HIP_CLOSE_STOP_NONE 2   /* nothing to solve: no used point, or a right-hand side of zeros */
+int visfd_hip_close_surface(visfd_hip_ctx*, const float* points, const float* normals, int64_t n, int64_t nx, int64_t ny,
+                            int64_t nz, int64_t pad, int orientation, float* mask, float* chi_out);
+int visfd_hip_close_surface_dev(visfd_hip_ctx*, const float* points, const float* normals, int64_t n, int64_t nx, int64_t ny,
+                                int64_t nz, int64_t pad, int orientation, float* mask, float* chi_out);
+/* Step 1 alone: acc receives int64[3][Nz][Ny][Nx] (a host array, in the _dev form a device array like the lists), counts
+ * (nullable, host) the used and the skipped points.  Refusals as above (acc in the place of mask). */
+int visfd_hip_close_surface_splat(visfd_hip_ctx*, const float* points, const float* normals, int64_t n, int64_t nx, int64_t ny,
+                                  int64_t nz, int64_t pad, int64_t* acc, int64_t counts[2]);
+int visfd_hip_close_surface_splat_dev(visfd_hip_ctx*, const float* points, const float* normals, int64_t n, int64_t nx,
+                                      int64_t ny, int64_t nz, int64_t pad, int64_t* acc, int64_t counts[2]);
+/* The same integers by a serial walk on the host: no context, no device. */
+int visfd_hip_close_surface_splat_host(const float* points, const float* normals, int64_t n, int64_t nx, int64_t ny, int64_t nz,
+                                       int64_t pad, int64_t* acc, int64_t counts[2]);
+/* The last visfd_hip_close_surface[_dev] of the context.  stats: used points, skipped points, cycles run, the stop
+ * (VISFD_HIP_CLOSE_STOP_*), the orientation taken (VISFD_HIP_CLOSE_OUTWARD or _INWARD), 1 when the mask holds a voxel on a
+ * face of the image (a surface cut by the border: pad), else 0; -1 each before the first call.
+ * values: the final |b - Laplace(chi)| / |b|, and iso. */
+int visfd_hip_close_surface_last(visfd_hip_ctx*, int64_t stats[6], double values[2]);
+/* option close_surface_time: milliseconds of the last call's splat with the right-hand side, its solve, and its level
+ * and cut */
+int visfd_hip_close_surface_last_times(visfd_hip_ctx*, float ms[3]);
 
 #ifdef __cplusplus
 }

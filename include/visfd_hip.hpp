@@ -22,6 +22,8 @@
 //   CompactMultiChannelImage3D  lib/visfd/multichannel_image3d.hpp:41-204
 //   Threshold2, Threshold4, SelectIntensityRange, SelectIntensityRangeGauss  lib/threshold/threshold.hpp:52-258
 //   VoxelizeMesh  what bin/voxelize_mesh/voxelize_mesh.py computes with vtk (no C++ counterpart in the reference)
+//   CloseSurface  an oriented point cloud closed into a mask on the grid (no counterpart in the reference, whose workflow
+//                 leaves this step to an external surface reconstruction program; visfd_hip.h states the definition)
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
 #ifndef VISFD_HIP_HPP
 #define VISFD_HIP_HPP
@@ -1075,6 +1077,29 @@ inline void VoxelizeMesh(visfd_hip_ctx* ctx, int const image_size[3], const std:
                                             (int64_t)vertices.size(), t.empty() ? nullptr : t.data(), (int64_t)triangles.size(),
                                             voxel_width, origin ? origin : zero, image_size[0], image_size[1], image_size[2],
                                             check_closed ? 1 : 0, hip_detail::flat(aaafDest)));
+}
+
+// ---- closing an oriented point cloud into a mask (visfd_hip.h states the definition) ---------------------
+// aaafDest[iz][iy][ix] becomes 1 inside the solid the cloud bounds and 0 elsewhere.  points are in voxel coordinates (the
+// cloud of -normals-file divided by the voxel width), orientation is VISFD_HIP_CLOSE_OUTWARD, _INWARD or _AUTO, pad the
+// number of nodes the solve's box extends beyond the image on every face.  aaafChi (nullable) receives the field that was
+// cut.  A null ctx is the shim's own.
+inline void CloseSurface(visfd_hip_ctx* ctx, int const image_size[3], const std::vector<std::array<float, 3> >& points,
+                         const std::vector<std::array<float, 3> >& normals, float*** aaafDest, int pad = 0,
+                         int orientation = VISFD_HIP_CLOSE_OUTWARD, float*** aaafChi = nullptr) {
+  hip_detail::require_contiguous(aaafDest, image_size);
+  if (aaafChi) hip_detail::require_contiguous(aaafChi, image_size);
+  if (points.size() != normals.size()) throw VisfdErr("Error: CloseSurface needs as many normals as points.\n");
+  std::vector<float> p(3 * points.size()), m(3 * points.size());
+  for (size_t i = 0; i < points.size(); i++)
+    for (int d = 0; d < 3; d++) {
+      p[3 * i + d] = points[i][d];
+      m[3 * i + d] = normals[i][d];
+    }
+  hip_detail::check(visfd_hip_close_surface(ctx ? ctx : hip_detail::context(), p.empty() ? nullptr : p.data(),
+                                            m.empty() ? nullptr : m.data(), (int64_t)points.size(), image_size[0], image_size[1],
+                                            image_size[2], pad, orientation, hip_detail::flat(aaafDest),
+                                            aaafChi ? hip_detail::flat(aaafChi) : nullptr));
 }
 
 // ---- blob list post-processing: lib/visfd/visfd_utils.hpp:49-55,95-118; feature.hpp:519-616,720-969 ------

@@ -116,6 +116,11 @@ _LABEL_CONNECTED_EX = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_floa
 # ctx, vertices, n_vertices, triangles, n_triangles, voxel_width, origin, nx, ny, nz, check_closed, dst
 _VOXELIZE = [_vp, _vp, _i64, _vp, _i64, C.c_double, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, _vp]
 
+# ctx, points, normals, n, nx, ny, nz, pad, orientation, mask, chi_out
+_CLOSE = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp]
+# ctx, points, normals, n, nx, ny, nz, pad, acc, counts
+_CLOSE_SPLAT = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, C.POINTER(_i64)]
+
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
     "visfd_hip_destroy": (C.c_int, [_vp]),
@@ -307,6 +312,14 @@ _SIGS = {
     "visfd_hip_voxelize_last_times": (C.c_int, [_vp, _fp]),
     "visfd_hip_voxelize_quantize_host": (C.c_int, [_vp, _i64, C.c_double, C.POINTER(C.c_double), _vp]),
     "visfd_hip_mesh_edges_host": (C.c_int, [_vp, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    # close_surface (csrc/close_surface.hip)
+    "visfd_hip_close_surface": (C.c_int, _CLOSE),
+    "visfd_hip_close_surface_dev": (C.c_int, _CLOSE),
+    "visfd_hip_close_surface_splat": (C.c_int, _CLOSE_SPLAT),
+    "visfd_hip_close_surface_splat_dev": (C.c_int, _CLOSE_SPLAT),
+    "visfd_hip_close_surface_splat_host": (C.c_int, _CLOSE_SPLAT[1:]),
+    "visfd_hip_close_surface_last": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "visfd_hip_close_surface_last_times": (C.c_int, [_vp, _fp]),
     # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
     "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -959,6 +972,43 @@ def mesh_edges_host(triangles, n_vertices):
     return int(nb.value), int(nn.value)
 
 
+CLOSE_OUTWARD, CLOSE_INWARD, CLOSE_AUTO = 0, 1, 2   # VISFD_HIP_CLOSE_*
+CLOSE_STOP_RTOL, CLOSE_STOP_CAP, CLOSE_STOP_NONE = 0, 1, 2   # VISFD_HIP_CLOSE_STOP_*
+_CLOSE_NAMES = {"outward": CLOSE_OUTWARD, "inward": CLOSE_INWARD, "auto": CLOSE_AUTO}
+
+
+def _orientation(o):
+    if isinstance(o, str):
+        if o not in _CLOSE_NAMES:
+            raise ValueError("orientation must be outward, inward or auto")
+        return _CLOSE_NAMES[o]
+    return int(o)
+
+
+def _cloud(points, normals):
+    """(n, 3) float32 points and normals (x, y, z) as C arrays; None: an empty list"""
+    p = np.zeros((0, 3), np.float32) if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    m = np.zeros((0, 3), np.float32) if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(p) != len(m):
+        raise ValueError("as many normals as points")
+    return p, m
+
+
+def close_surface_splat_host(points, normals, shape, pad=0):
+    """Step 1 of close_surface (include/visfd_hip.h) by a serial walk on the host: -> (acc int64 [3, Nz, Ny, Nx] over the
+    padded box, used points, skipped points).  No context, no device."""
+    L = load_library()
+    nz, ny, nx = [int(s) for s in shape]
+    p, m = _cloud(points, normals)
+    if nz < 3 or ny < 3 or nx < 3 or pad < 0:
+        raise VisfdHipError(1, "close_surface: every image dimension must be at least 3 and pad at least 0")
+    acc = np.empty((3, nz + 2 * pad, ny + 2 * pad, nx + 2 * pad), np.int64)
+    counts = (_i64 * 2)()
+    _chk_host(L, L.visfd_hip_close_surface_splat_host(p.ctypes.data if len(p) else None, m.ctypes.data if len(p) else None,
+                                                      len(p), nx, ny, nz, int(pad), acc.ctypes.data, counts))
+    return acc, int(counts[0]), int(counts[1])
+
+
 def find_spheres_host(crds, sphere_crds, sphere_diameters):
     """FindSpheres (visfd_utils.hpp:271-359) by the host walk: for every point 1 + the index of the LAST sphere that holds
     it, 0 when none does -> int64 array."""
@@ -1243,6 +1293,45 @@ class Context:
         self._chk(self._L.visfd_hip_voxelize_mesh(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t), float(voxel_width),
                                                   _d3(origin), nx, ny, nz, int(bool(check_closed)), _np(dst)))
         return dst
+
+    def close_surface(self, points, normals, shape, pad=0, orientation="outward", want_chi=False):
+        """An oriented point cloud closed into a mask (include/visfd_hip.h): points and normals (n, 3) float32
+        (x, y, z) in voxel coordinates, shape (nz, ny, nx), orientation "outward", "inward" or "auto".
+        -> float32 [nz, ny, nx] of 0 and 1, or (mask, chi) with want_chi."""
+        nz, ny, nx = [int(s) for s in shape]
+        p, m = _cloud(points, normals)
+        mask = np.empty((nz, ny, nx), np.float32)
+        chi = np.empty((nz, ny, nx), np.float32) if want_chi else None
+        self._chk(self._L.visfd_hip_close_surface(self._h, p.ctypes.data if len(p) else None, m.ctypes.data if len(p) else None,
+                                                  len(p), nx, ny, nz, int(pad), _orientation(orientation), _np(mask), _np(chi)))
+        return (mask, chi) if want_chi else mask
+
+    def close_surface_splat(self, points, normals, shape, pad=0):
+        """Step 1 of close_surface on the device -> (acc int64 [3, Nz, Ny, Nx], used points, skipped points)."""
+        nz, ny, nx = [int(s) for s in shape]
+        p, m = _cloud(points, normals)
+        acc = np.empty((3, max(nz + 2 * pad, 0), max(ny + 2 * pad, 0), max(nx + 2 * pad, 0)), np.int64)
+        counts = (_i64 * 2)()
+        self._chk(self._L.visfd_hip_close_surface_splat(self._h, p.ctypes.data if len(p) else None,
+                                                        m.ctypes.data if len(p) else None, len(p), nx, ny, nz, int(pad),
+                                                        acc.ctypes.data, counts))
+        return acc, int(counts[0]), int(counts[1])
+
+    def close_surface_last(self):
+        """The last close_surface[_dev]: dict with n_used, n_skipped, cycles, stop (CLOSE_STOP_*), orientation
+        ("outward" or "inward"), touches_face, ratio (the final residual ratio) and iso."""
+        s, v = (_i64 * 6)(), (C.c_double * 2)()
+        self._chk(self._L.visfd_hip_close_surface_last(self._h, s, v))
+        return {"n_used": int(s[0]), "n_skipped": int(s[1]), "cycles": int(s[2]), "stop": int(s[3]),
+                "orientation": "inward" if s[4] == CLOSE_INWARD else "outward", "touches_face": int(s[5]),
+                "ratio": float(v[0]), "iso": float(v[1])}
+
+    def close_surface_last_times(self):
+        """(splat and right-hand side, solve, level and cut) milliseconds of the last close_surface[_dev] under the option
+        close_surface_time."""
+        ms = (C.c_float * 3)()
+        self._chk(self._L.visfd_hip_close_surface_last_times(self._h, ms))
+        return tuple(ms)
 
     def voxelize_last(self):
         """(crossings, skipped triangles, odd rows, inside voxels) of the last voxelize_mesh[_dev]."""
@@ -1947,6 +2036,26 @@ class Context:
         self._chk(self._L.visfd_hip_voxelize_mesh_dev(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t),
                                                       float(voxel_width), _d3(origin), nx, ny, nz, int(bool(check_closed)),
                                                       _dev(dst)))
+
+    def close_surface_dev(self, mask, points, normals, pad=0, orientation="outward", chi=None):
+        """close_surface on device tensors: mask (and chi, optional) [nz, ny, nx], points and normals (n, 3) float32; returns
+        with the stream idle."""
+        nz, ny, nx = mask.shape
+        n = int(points.shape[0])
+        assert tuple(points.shape) == (n, 3) and tuple(normals.shape) == (n, 3), "points and normals are (n, 3)"
+        self._chk(self._L.visfd_hip_close_surface_dev(self._h, _dev(points) if n else None, _dev(normals) if n else None, n,
+                                                      nx, ny, nz, int(pad), _orientation(orientation), _dev(mask), _dev(chi)))
+
+    def close_surface_splat_dev(self, acc, points, normals, shape, pad=0):
+        """close_surface_splat on device tensors: acc int64 [3, Nz, Ny, Nx] -> (used points, skipped points)."""
+        nz, ny, nx = [int(s) for s in shape]
+        n = int(points.shape[0])
+        assert acc.is_cuda and acc.is_contiguous() and str(acc.dtype) == "torch.int64", "need contiguous cuda int64"
+        assert tuple(acc.shape) == (3, nz + 2 * pad, ny + 2 * pad, nx + 2 * pad), "acc is [3, Nz, Ny, Nx]"
+        counts = (_i64 * 2)()
+        self._chk(self._L.visfd_hip_close_surface_splat_dev(self._h, _dev(points) if n else None, _dev(normals) if n else None,
+                                                            n, nx, ny, nz, int(pad), acc.data_ptr(), counts))
+        return int(counts[0]), int(counts[1])
 
     def draw_last_times(self):
         """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""

@@ -98,6 +98,9 @@ enum Slot {
   WS_SP_LIST,                      // ... the selected voxels' linear indices in raster order (int64)
   WS_SP_OUT,                       // ... per listed voxel its position and its normal (2 x 3 floats), then the ridge records (9 floats)
   WS_SP_SCRATCH,                   // ... the backward weights of one batch of walks, [step][lane]
+  WS_CS_ACC,                       // close_surface (csrc/close_surface.hip): the three int64 volumes of the splat over the padded box
+  WS_CS_GRID,                      // ... per multigrid level the two iterates and the right-hand side (rows padded to a multiple of 4 floats)
+  WS_CS_AUX,                       // ... the workgroups' partial sums (double), the three totals, the counters
   WS_NSLOTS
 };
 
@@ -150,6 +153,9 @@ struct visfd_hip_options {
                             //    a walk needs more is finished by the host entry.  One float of scratch per step and lane of a batch:
                             //    256 steps x 262144 lanes = 256 MiB (csrc/surface_points.hip).  Clamped to 1..65536
   int surface_points_time = 0;   // 1: those two time their stages (visfd_hip_surface_points_last_times; tools/surface_points_time.py)
+  int close_surface_rtol_exp = 5;   // close_surface stops its cycles when |b - Laplace(chi)| <= 10^-k |b| (profiles/close_surface_time.txt)
+  int close_surface_max_cycles = 20;   // ... or after this many cycles: the mask is still returned, visfd_hip_close_surface_last says which
+  int close_surface_time = 0;   // 1: close_surface times its splat, solve and cut with events (visfd_hip_close_surface_last_times; tools/close_surface_time.py)
   int debug = 0;
 };
 
@@ -179,6 +185,9 @@ struct visfd_hip_ctx {
   float voxelize_ms[3] = {-1.0f, -1.0f, -1.0f};   // option voxelize_time: zero fill, scatter, fill of the last VoxelizeMesh
   int64_t surface_points_last[6] = {-1, 0, -1, -1, -1, -1};   // the last visfd_hip_surface_points_ctx / _dev: path, reasons, selected voxels, points, longest walk, steps taken
   float surface_points_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f};   // option surface_points_time: select and compact, walk, ridge gather, host finish and copies
+  int64_t close_surface_last[6] = {-1, -1, -1, -1, -1, -1};   // the last close_surface: used and skipped points, cycles, stop reason, orientation taken, mask on a face
+  double close_surface_values[2] = {0.0, 0.0};   // ... its final residual ratio and its level iso
+  float close_surface_ms[3] = {-1.0f, -1.0f, -1.0f};   // option close_surface_time: splat and right-hand side, solve, level and cut
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
   int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test

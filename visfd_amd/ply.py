@@ -135,6 +135,74 @@ def read_ply(path):
     return verts.astype(np.float32), _fans(polys).astype(np.int32)
 
 
+_NORMALS = ("nx", "ny", "nz")
+
+
+def read_ply_points(path):
+    """An oriented point cloud, such as filter_mrc -normals-file writes (ascii, vertex properties x y z nx ny nz): ->
+    (xyz float32 (n, 3), normals float32 (n, 3)).  All three formats; other vertex properties and other elements are read
+    past; a file whose vertices lack nx, ny or nz (a plain mesh) is refused with PlyError."""
+    with open(path, "rb") as f:
+        fmt, elements = _header(f)
+        vertex = [e for e in elements if e[0] == "vertex"]
+        if not vertex:
+            raise PlyError("PLY file without a vertex element")
+        names = {p[0] for p in vertex[0][2] if p[1] is None}
+        if not {"x", "y", "z"} <= names:
+            raise PlyError("PLY vertex element without x, y, z")
+        if not set(_NORMALS) <= names:
+            raise PlyError("PLY vertex element without the normals nx, ny, nz: not an oriented point cloud")
+        cols = ("x", "y", "z") + _NORMALS
+        if fmt == "ascii":
+            tok = f.read().split()
+            pos, out = 0, None
+            for name, count, props in elements:
+                if name == "vertex":
+                    if any(p[1] is not None for p in props):
+                        raise PlyError("PLY vertex element with a list property")
+                    w = len(props)
+                    if len(tok) < pos + w * count:
+                        raise PlyError("PLY file ends inside element vertex")
+                    try:
+                        a = np.array([float(t) for t in tok[pos:pos + w * count]], np.float64).reshape(count, w)
+                    except ValueError:
+                        raise PlyError("PLY vertex element with a field that is not a number")
+                    idx = [[p[0] for p in props].index(c) for c in cols]
+                    out = a[:, idx]
+                    break
+                for _ in range(count):          # an element before the vertices: read past it
+                    for pname, ctype, _t in props:
+                        pos += 1 if ctype is None else 1 + int(tok[pos])
+        else:
+            order = "<" if fmt == "binary_little_endian" else ">"
+            out = None
+            for name, count, props in elements:
+                if any(p[1] is not None for p in props):
+                    if name == "vertex":
+                        raise PlyError("PLY vertex element with a list property")
+                    for _ in range(count):
+                        for pname, ctype, itype in props:
+                            if ctype is None:
+                                f.read(np.dtype(itype).itemsize)
+                            else:
+                                cd = np.dtype(order + ctype)
+                                raw = f.read(cd.itemsize)
+                                if len(raw) != cd.itemsize:
+                                    raise PlyError("PLY file ends inside element " + name)
+                                f.read(np.dtype(itype).itemsize * int(np.frombuffer(raw, cd)[0]))
+                    continue
+                dt = np.dtype([(p[0], order + p[2]) for p in props])
+                raw = f.read(dt.itemsize * count)
+                if len(raw) != dt.itemsize * count:
+                    raise PlyError("PLY file ends inside element " + name)
+                if name == "vertex":
+                    a = np.frombuffer(raw, dt)
+                    out = np.stack([a[c] for c in cols], 1).astype(np.float64) if count else np.zeros((0, 6))
+                    break
+    out = out.reshape(-1, 6).astype(np.float32)
+    return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3:])
+
+
 def write_ply(path, vertices, faces, fmt="binary_little_endian", extra=(), index_name="vertex_indices", count_type="uchar",
               index_type="int"):
     """A minimal writer.  faces: a list of polygons (index lists).  extra: [(name, type, values per vertex)] written after
