@@ -91,7 +91,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * visfd_hip_mesh_edges_host; then the flat ball as a threshold,
                                      * visfd_hip_flat_ball_dsq_max; then the closing of an oriented point cloud into a
                                      * mask: visfd_hip_close_surface[_dev], visfd_hip_close_surface_splat[_dev|_host],
-                                     * visfd_hip_close_surface_last and _last_times) */
+                                     * visfd_hip_close_surface_last and _last_times; then the membrane stage on the
+                                     * caller's arrays, visfd_hip_membrane_stage_dev, with the option membrane_queue and
+                                     * the test aids visfd_hip_debug_ridge_directions_thr_dev and _debug_tv_lists_dev) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -101,6 +103,10 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    it applies; results are bit-identical either way
  *   log_pair_chunk   march length of those two launches along z and y (0, the default: 256 and 512); results are
  *                    bit-identical for every value
+ *   membrane_queue   the membrane stage (visfd_hip_membrane_detect*_dev, visfd_hip_membrane_stage_dev, and the select of
+ *                    visfd_hip_threshold_fraction*) queued without host steps: 1 (default) the select's digits are picked on
+ *                    the device, the stage makes no threshold pass and waits once; 0: a host walk after every select round,
+ *                    the threshold pass, a wait for the sender lists' length.  Results are bit-identical either way
  *   tv_dense         1: tensor voting by the baseline kernel
  *   tv_fma           1: TOLERANCE MODE of tensor voting (surfaces, angular exponent 2 or 4): the vote chain with fused
  *                    multiply-adds.  Tensors are then within 1e-5 of the field's scale of the reference's instead of
@@ -1241,6 +1247,26 @@ int visfd_hip_membrane_detect_bg_dev(visfd_hip_ctx*, const float* src, const flo
                                      float sigma_tv, int tv_exponent, float tv_cutoff_ratio, float sigma_background,
                                      int normalize_background, float* saliency_out, float* tensor_out, float* direction_out,
                                      float* threshold_out);
+/* The same stage (fraction cut, sigma_tv > 0) with every volume the caller's, all device memory: `scratch` receives the
+ * smoothed image, `background` (NULL unless sigma_background > 0) the background of the peak-height factor, saliency,
+ * direction (3 planes) and tensor (6 planes) the results.  Voxels of `direction_out` whose score did not survive the cut
+ * keep what they held. */
+int visfd_hip_membrane_stage_dev(visfd_hip_ctx*, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                 float sigma, float truncate_ratio, int eival_order, float best_fraction, float sigma_tv,
+                                 int tv_exponent, float tv_cutoff_ratio, float sigma_background, int normalize_background,
+                                 float* background, float* scratch, float* saliency_out, float* direction_out,
+                                 float* tensor_out, float* threshold_out);
+/* Test aids: the two consumers of a saliency volume that has NOT been cut.  thr_dev: one float in device memory (a voxel
+ * counts if !(s < *thr_dev) && s != 0), or NULL for a volume that has been cut.  The lists of the whole volume for vote
+ * windows of half-width h (mode 0, 2: saliencies times 1/4, 1/2; 1: as they are; fold: the folded records) come back in
+ * HOST arrays: rows (nz (ny + 1) ceil(nx / 16) words: list (z, tx) is [rows[(z (ny + 1) + ny) ntx + tx], rows[z (ny + 1) ntx + tx])),
+ * entries (4 floats each) and positions.  *nrows and *total are set in any case; an array that is too small stays as it was. */
+int visfd_hip_debug_ridge_directions_thr_dev(visfd_hip_ctx*, const float* smoothed, int64_t nx, int64_t ny, int64_t nz,
+                                             float sigma, int eival_order, const float* saliency, const float* thr_dev,
+                                             float* direction_out);
+int visfd_hip_debug_tv_lists_dev(visfd_hip_ctx*, const float* saliency, const float* direction, const float* thr_dev, int64_t nx,
+                                 int64_t ny, int64_t nz, int h, int mode, int fold, uint32_t* rows, int64_t rows_cap, float* entries,
+                                 uint32_t* positions, int64_t entries_cap, int64_t* nrows, int64_t* total, uint32_t* flags);
 
 /* ---- Z-slab helpers for the separable filter (multi-GPU) -------------------------- */
 /* Same as apply_gauss_dev on a slab: arrays hold planes [z_lo, z_lo+nz_local) of a volume of height

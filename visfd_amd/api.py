@@ -251,6 +251,12 @@ _SIGS = {
     "visfd_hip_membrane_detect_bg_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int,
                                                    C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int,
                                                    _vp, _vp, _vp, _fp]),
+    # the stage on the caller's arrays (pipeline.membrane_detect) and the test aids of its consumers
+    "visfd_hip_membrane_stage_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float,
+                                               C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _vp, _vp, _fp]),
+    "visfd_hip_debug_ridge_directions_thr_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, _vp, _vp, _vp]),
+    "visfd_hip_debug_tv_lists_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
+                                               _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint32)]),
     "visfd_hip_membrane_detect_slab_bg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int,
                                                         C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _fp]),
     "visfd_hip_membrane_detect_slab_bg": (C.c_int, [_vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
@@ -2181,6 +2187,45 @@ class Context:
         nz, ny, nx = smoothed.shape
         self._chk(self._L.visfd_hip_ridge_directions_dev(self._h, _dev(smoothed), nx, ny, nz, float(sigma), int(order),
                                                          _dev(sal), _dev(dirs)))
+
+    def membrane_stage_dev(self, src, sal, dirs, tensor, scratch, sigma, ratio, order, best_fraction, sigma_tv, exponent=4,
+                           cutoff=2.0 ** 0.5, mask=None, sigma_background=0.0, background=None, normalize_background=True):
+        """visfd_hip_membrane_stage_dev: scores, fraction cut, directions of the survivors, vote and post-vote score on the
+        caller's tensors, queued in one go under the option membrane_queue (one wait, no threshold pass).  `scratch`
+        receives the smoothed image, `background` the background when sigma_background > 0.  Returns the threshold."""
+        nz, ny, nx = src.shape
+        thr = C.c_float()
+        self._chk(self._L.visfd_hip_membrane_stage_dev(
+            self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma), float(ratio), int(order), float(best_fraction),
+            float(sigma_tv), int(exponent), float(cutoff), float(sigma_background), int(bool(normalize_background)),
+            _dev(background), _dev(scratch), _dev(sal), _dev(dirs), _dev(tensor), C.byref(thr)))
+        return thr.value
+
+    def debug_ridge_directions_thr_dev(self, smoothed, sal, dirs, sigma, order, thr_dev=None):
+        """Test aid: ridge_directions_dev on a volume that has not been cut; thr_dev: a one-element device tensor."""
+        nz, ny, nx = smoothed.shape
+        self._chk(self._L.visfd_hip_debug_ridge_directions_thr_dev(self._h, _dev(smoothed), nx, ny, nz, float(sigma), int(order),
+                                                                   _dev(sal), _dev(thr_dev), _dev(dirs)))
+
+    def debug_tv_lists_dev(self, sal, dirs, h, mode=0, fold=False, thr_dev=None):
+        """Test aid: the sender lists of tensor voting for the whole volume -> (rows uint32 [nz, ny + 1, ntx], entries float32
+        [total, 4], positions uint32 [total], flags).  List (z, tx) is entries[rows[z, ny, tx]:rows[z, 0, tx]]; where the
+        lists lie in the arrays differs from run to run."""
+        nz, ny, nx = sal.shape
+        ntx = (nx + 15) // 16
+        nrows, total, flags = _i64(), _i64(), C.c_uint32()
+        rows = np.empty((nz, ny + 1, ntx), np.uint32)
+        ent, pos = np.empty((0, 4), np.float32), np.empty(0, np.uint32)
+        for _ in range(2):   # the second call has arrays for the total the first one reported
+            self._chk(self._L.visfd_hip_debug_tv_lists_dev(
+                self._h, _dev(sal), _dev(dirs), _dev(thr_dev), nx, ny, nz, int(h), int(mode), int(bool(fold)),
+                rows.ctypes.data, rows.size, ent.ctypes.data, pos.ctypes.data, pos.size, C.byref(nrows), C.byref(total),
+                C.byref(flags)))
+            assert nrows.value == rows.size
+            if total.value <= pos.size:
+                break
+            ent, pos = np.empty((total.value, 4), np.float32), np.empty(total.value, np.uint32)
+        return rows, ent[:total.value], pos[:total.value], int(flags.value)
 
     def threshold_fraction_dev(self, sal, fraction, mask=None):
         thr = C.c_float()

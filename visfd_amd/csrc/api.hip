@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "tv_common.hpp"
 
 namespace vh {
 
@@ -427,6 +428,54 @@ int visfd_hip_ridge_directions_dev(visfd_hip_ctx* ctx, const float* smoothed, in
   return dev_ridge_directions(ctx, smoothed, sal, nx, ny, nz, sigma, order, dir);
 }
 
+// Test aids: the two consumers of an uncut saliency volume on their own (tests/test_membrane_consumers_gpu.py).
+// thr_dev: one float in device memory, or null for the kernels as they run on a cut volume.
+int visfd_hip_debug_ridge_directions_thr_dev(visfd_hip_ctx* ctx, const float* smoothed, int64_t nx, int64_t ny, int64_t nz,
+                                             float sigma, int order, const float* sal, const float* thr_dev, float* dir) {
+  VH_REQUIRE(ctx && smoothed && sal && dir, "null argument");
+  VH_REQUIRE(order == 0 || order == 1, "unsupported eigenvalue order");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(check_dims(nx, ny, nz));
+  return dev_ridge_directions(ctx, smoothed, sal, nx, ny, nz, sigma, order, dir, thr_dev);
+}
+// The sender lists of the whole volume (tv_list.hip) for windows of half-width h, copied to HOST arrays: rows
+// (nz (ny + 1) ceil(nx / 16) words), entries (4 floats each) and positions; *nrows and *total say how many there are, and
+// nothing is copied into an array that is too small.
+int visfd_hip_debug_tv_lists_dev(visfd_hip_ctx* ctx, const float* sal, const float* dir, const float* thr_dev, int64_t nx,
+                                 int64_t ny, int64_t nz, int h, int mode, int fold, uint32_t* rows, int64_t rows_cap, float* ent,
+                                 uint32_t* pos, int64_t ent_cap, int64_t* nrows, int64_t* total, uint32_t* flags) {
+  VH_REQUIRE(ctx && sal && dir && nrows && total && flags, "null argument");
+  VH_REQUIRE(h >= 1 && h <= 40 && mode >= 0 && mode <= 2, "bad list parameters");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(check_dims(nx, ny, nz));
+  VH_TRY(check_dims32(nx, ny, nz));
+  VH_REQUIRE(nx <= TV_LIST_MAX_NX && ny < (1 << 24), "volume too wide for the lists");
+  unsigned* counter = nullptr;
+  VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));
+  TvListPlan plan;
+  int rc = tv_list_count(ctx, sal, thr_dev, nullptr, nx, ny, nz, 0, nz, h, mode, counter,
+                         reinterpret_cast<unsigned long long*>(counter + 4), counter + 6, &plan);
+  VH_REQUIRE(rc != TV_DECLINED, "the lists declined the volume");
+  VH_TRY(rc);
+  unsigned long long tot2[2] = {0, 0};
+  VH_HIP(hipMemcpyAsync(tot2, counter + 4, sizeof(tot2), hipMemcpyDeviceToHost, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  TvSenderLists L;
+  rc = tv_list_write(ctx, plan, sal, dir, nullptr, tot2[0], (unsigned)tot2[1], 0u, fold != 0, &L);
+  VH_REQUIRE(rc != TV_DECLINED, "the lists declined the volume");
+  VH_TRY(rc);
+  *nrows = (int64_t)plan.g.nzl * (int64_t)(ny + 1) * (int64_t)plan.g.ntx;
+  *total = (int64_t)L.total;
+  *flags = L.flags;
+  if (rows && rows_cap >= *nrows) VH_HIP(hipMemcpyAsync(rows, L.rows, sizeof(uint32_t) * (size_t)*nrows, hipMemcpyDeviceToHost, ctx->stream));
+  if (ent && pos && ent_cap >= *total && *total > 0) {
+    VH_HIP(hipMemcpyAsync(ent, L.ent, sizeof(float) * 4 * (size_t)*total, hipMemcpyDeviceToHost, ctx->stream));
+    VH_HIP(hipMemcpyAsync(pos, L.pos, sizeof(uint32_t) * (size_t)*total, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  return VISFD_HIP_OK;
+}
+
 // ---- a12 (threshold) -------------------------------------------------------------------------
 int visfd_hip_threshold_fraction_dev(visfd_hip_ctx* ctx, float* sal, const float* mask, int64_t nvox,
                                      float fraction, float* thr_out) {
@@ -576,6 +625,77 @@ int visfd_hip_tv_weight_sum(visfd_hip_ctx* ctx, const float* sal, float* den, co
 }
 
 // ---- HandleTV compute section ------------------------------------------------------------------
+// The stage behind the scores, queued in one go (option membrane_queue): the select's three
+// histogram / pick pairs, the sender lists' count and scan, ONE copy of {threshold, flag, list total, list flags} to pinned
+// memory with an event behind it, and the direction kernel, which needs only the threshold on the device -- then the one
+// wait, with those directions still queued.  No threshold pass: directions and lists cut sal for themselves.
+// Unmasked fraction cuts only (n is known, so a fraction that selects no voxel is refused before anything is queued).
+// TV_DECLINED: the vote's first route is not a kernel of tv_box.hip that takes the request; at most a select has run.
+static int membrane_queued(visfd_hip_ctx* ctx, i64 nx, i64 ny, i64 nz, float sigma, int order, float best_fraction, float sigma_tv,
+                           int exponent, float cutoff, const float* smoothed, float* sal, float* ten, float* dir, bool zero_dir,
+                           const float* peak_img, const float* peak_bg, float* thr_out) {
+  hipStream_t st = ctx->stream;
+  const i64 n = nx * ny * nz;
+  VH_TRY(select_rank_check((uint64_t)n, best_fraction));
+  if (!ctx->stage_pinned) VH_HIP(hipHostMalloc(&ctx->stage_pinned, sizeof(StageReadback)));
+  if (!ctx->stage_event) VH_HIP(hipEventCreateWithFlags(&ctx->stage_event, hipEventDisableTiming));
+  StageReadback* block = nullptr;
+  VH_TRY(ws(ctx, WS_SELECT, 1, &block));
+  VH_HIP(hipMemsetAsync(block, 0, sizeof(*block), st));
+  VH_TRY(dev_select_queue(ctx, sal, nullptr, n, best_fraction, &block->sel));
+  const float* const thr_dev = &block->sel.thr;
+  TvStagePlan plan;
+  VH_TRY(dev_tv_stage_count(ctx, sal, thr_dev, nullptr, nx, ny, nz, sigma_tv, exponent, cutoff, &block->list_total,
+                            &block->list_flags, &plan));
+  const StageReadback* const got = static_cast<const StageReadback*>(ctx->stage_pinned);
+  VH_HIP(hipMemcpyAsync(ctx->stage_pinned, block, sizeof(*block), hipMemcpyDeviceToHost, st));
+  VH_HIP(hipEventRecord(ctx->stage_event, st));
+  if (zero_dir) VH_HIP(hipMemsetAsync(dir, 0, sizeof(float) * 3 * (size_t)n, st));
+  VH_TRY(dev_ridge_directions(ctx, smoothed, sal, nx, ny, nz, sigma, order, dir, thr_dev));
+  VH_HIP(hipEventSynchronize(ctx->stage_event));   // the stage's one wait: the directions are still queued behind it
+  float thr = 0.0f;
+  VH_TRY(select_result(got->sel, &thr));
+  if (thr_out) *thr_out = thr;
+  int rc = dev_tv_stage_vote(ctx, plan, got->list_total, got->list_flags, sal, dir, ten, nullptr, nx, ny, nz, exponent);
+  if (rc == TV_DECLINED) {   // (what the lists' count saw is not for this kernel: the other routes read a cut sal)
+    VH_TRY(dev_apply_threshold(ctx, sal, n, thr));
+    rc = dev_tv_dense_stick(ctx, sal, dir, ten, nullptr, nullptr, nx, ny, nz, 0, nz, sigma_tv, exponent, cutoff, false);
+  }
+  VH_TRY(rc);
+  return dev_tensor_saliency(ctx, ten, nullptr, n, order, sal, peak_img, peak_bg);
+}
+
+// HandleTV's compute section on the caller's device arrays.  bg: a volume for the background (read only if
+// sigma_background > 0); zero_dir: `dir` receives zeros where the score did not survive, else those voxels keep what it held.
+static int membrane_stage(visfd_hip_ctx* ctx, const float* src, const float* mask, i64 nx, i64 ny, i64 nz, float sigma, float ratio,
+                          int order, float best_fraction, float threshold_abs, float sigma_tv, int exponent, float cutoff,
+                          float sigma_background, int normalize_background, float* bg, float* smoothed, float* sal, float* ten,
+                          float* dir, bool zero_dir, float* thr_out) {
+  const i64 n = nx * ny * nz;
+  // optional peak-height factor (`-membrane-background`): scores and post-vote scores are multiplied by image - background
+  if (sigma_background > 0.0f)
+    VH_TRY(visfd_hip_peak_background_dev(ctx, src, mask, nx, ny, nz, sigma_background, ratio, normalize_background, bg));
+  else bg = nullptr;
+  VH_TRY(visfd_hip_ridge_scores_bg_dev(ctx, src, mask, nx, ny, nz, sigma, ratio, order, bg, sal, smoothed));
+  if (ctx->opt.membrane_queue && sigma_tv > 0.0f && best_fraction >= 0.0f && !mask) {
+    const int rc = membrane_queued(ctx, nx, ny, nz, sigma, order, best_fraction, sigma_tv, exponent, cutoff, smoothed, sal, ten, dir,
+                                   zero_dir, bg ? src : nullptr, bg, thr_out);
+    if (rc != TV_DECLINED) return rc;
+  }
+  float thr = threshold_abs;
+  if (best_fraction >= 0.0f) VH_TRY(dev_threshold_fraction(ctx, sal, mask, n, best_fraction, &thr));
+  else VH_TRY(dev_apply_threshold(ctx, sal, n, thr));
+  if (thr_out) *thr_out = thr;
+  // directions only where the score survived: nothing else is read downstream
+  if (zero_dir) VH_HIP(hipMemsetAsync(dir, 0, sizeof(float) * 3 * (size_t)n, ctx->stream));
+  VH_TRY(dev_ridge_directions(ctx, smoothed, sal, nx, ny, nz, sigma, order, dir));
+  if (sigma_tv > 0.0f) {
+    VH_TRY(dev_tv_dense_stick(ctx, sal, dir, ten, mask, mask, nx, ny, nz, 0, nz, sigma_tv, exponent, cutoff, false));
+    VH_TRY(dev_tensor_saliency(ctx, ten, mask, n, order, sal, bg ? src : nullptr, bg));
+  }
+  return VISFD_HIP_OK;
+}
+
 int visfd_hip_membrane_detect_bg_dev(visfd_hip_ctx* ctx, const float* src, const float* mask, int64_t nx,
                                      int64_t ny, int64_t nz, float sigma, float ratio, int order,
                                      float best_fraction, float threshold_abs, float sigma_tv, int exponent,
@@ -589,30 +709,29 @@ int visfd_hip_membrane_detect_bg_dev(visfd_hip_ctx* ctx, const float* src, const
   const i64 n = nx * ny * nz;
   float* d = dir;
   if (!d) VH_TRY(ws(ctx, WS_TVAUX, (size_t)(3 * n), &d));
-  float* smoothed = nullptr;
+  float *smoothed = nullptr, *bg = nullptr, *t = ten;
   VH_TRY(ws(ctx, WS_D, (size_t)n, &smoothed));
-  // optional peak-height factor (`-membrane-background`): scores and post-vote scores are multiplied by image - background
-  float* bg = nullptr;
-  if (sigma_background > 0.0f) {
-    VH_TRY(ws(ctx, WS_C, (size_t)n, &bg));
-    VH_TRY(visfd_hip_peak_background_dev(ctx, src, mask, nx, ny, nz, sigma_background, ratio, normalize_background, bg));
-  }
-  VH_TRY(visfd_hip_ridge_scores_bg_dev(ctx, src, mask, nx, ny, nz, sigma, ratio, order, bg, sal, smoothed));
-  float thr = threshold_abs;
-  if (best_fraction >= 0.0f) VH_TRY(dev_threshold_fraction(ctx, sal, mask, n, best_fraction, &thr));
-  else VH_TRY(dev_apply_threshold(ctx, sal, n, thr));
-  if (thr_out) *thr_out = thr;
-  // directions only where the score survived: nothing else is read downstream (a caller-supplied `dir`
-  // receives zeros elsewhere)
-  if (dir) VH_HIP(hipMemsetAsync(dir, 0, sizeof(float) * 3 * (size_t)n, ctx->stream));
-  VH_TRY(dev_ridge_directions(ctx, smoothed, sal, nx, ny, nz, sigma, order, d));
-  if (sigma_tv > 0.0f) {
-    float* t = ten;
-    if (!t) VH_TRY(ws(ctx, WS_B, (size_t)(6 * n), &t));
-    VH_TRY(dev_tv_dense_stick(ctx, sal, d, t, mask, mask, nx, ny, nz, 0, nz, sigma_tv, exponent, cutoff, false));
-    VH_TRY(dev_tensor_saliency(ctx, t, mask, n, order, sal, bg ? src : nullptr, bg));
-  }
-  return VISFD_HIP_OK;
+  if (sigma_background > 0.0f) VH_TRY(ws(ctx, WS_C, (size_t)n, &bg));
+  if (!t && sigma_tv > 0.0f) VH_TRY(ws(ctx, WS_B, (size_t)(6 * n), &t));
+  // (a caller-supplied `dir` receives zeros where the score did not survive)
+  return membrane_stage(ctx, src, mask, nx, ny, nz, sigma, ratio, order, best_fraction, threshold_abs, sigma_tv, exponent, cutoff,
+                        sigma_background, normalize_background, bg, smoothed, sal, t, d, dir != nullptr, thr_out);
+}
+// The same stage with every volume the caller's: `scratch` receives the smoothed image, `background` (nullable unless
+// sigma_background > 0) the background, and voxels of `dir` whose score did not survive keep what they held.
+int visfd_hip_membrane_stage_dev(visfd_hip_ctx* ctx, const float* src, const float* mask, int64_t nx, int64_t ny, int64_t nz,
+                                 float sigma, float ratio, int order, float best_fraction, float sigma_tv, int exponent,
+                                 float cutoff, float sigma_background, int normalize_background, float* background,
+                                 float* scratch, float* sal, float* dir, float* ten, float* thr_out) {
+  VH_REQUIRE(ctx && src && scratch && sal && dir && ten, "null argument");
+  VH_REQUIRE(order == 0 || order == 1, "unsupported eigenvalue order");
+  VH_REQUIRE(best_fraction >= 0.0f && best_fraction <= 1.0f, "fraction must be in [0,1]");
+  VH_REQUIRE(sigma_tv > 0.0f, "the voting width must be positive");
+  VH_REQUIRE(!(sigma_background > 0.0f) || background, "the background needs a volume");
+  VH_HIP(hipSetDevice(ctx->device));
+  VH_TRY(check_dims(nx, ny, nz));
+  return membrane_stage(ctx, src, mask, nx, ny, nz, sigma, ratio, order, best_fraction, 0.0f, sigma_tv, exponent, cutoff,
+                        sigma_background, normalize_background, background, scratch, sal, ten, dir, false, thr_out);
 }
 int visfd_hip_membrane_detect_dev(visfd_hip_ctx* ctx, const float* src, const float* mask, int64_t nx,
                                   int64_t ny, int64_t nz, float sigma, float ratio, int order,

@@ -101,6 +101,8 @@ enum Slot {
   WS_CS_ACC,                       // close_surface (csrc/close_surface.hip): the three int64 volumes of the splat over the padded box
   WS_CS_GRID,                      // ... per multigrid level the two iterates and the right-hand side (rows padded to a multiple of 4 floats)
   WS_CS_AUX,                       // ... the workgroups' partial sums (double), the three totals, the counters
+  WS_SELECT,                       // radix select with the digit picked on the device: its state block (SelectState), and behind it the words
+                                   // the queued membrane stage reads back with it (StageReadback) -- theirs alone, no pending scan owns any
   WS_NSLOTS
 };
 
@@ -117,6 +119,9 @@ struct visfd_hip_options {
   int log_pair = 1;         // both Gaussians of an unmasked DoG/LoG scale in two shared launches (csrc/gauss_pair.hip): 0 never,
                             // 1 for the half-widths its table lists, 2 wherever it applies
   int log_pair_chunk = 0;   // march length of those launches along z and y (0: default); tests put chunk seams into small volumes
+  int membrane_queue = 1;   // the membrane stage queued in one go (csrc/api.hip: membrane_stage): the select's digits picked on the device, no
+                            // threshold pass, one wait per stage with the direction kernel queued behind it; 0: a host walk after every
+                            // select round, the threshold pass, a wait for the lists' total.  The bits are the same either way
   int tv_dense = 0;         // 1: tensor voting by the baseline kernel (csrc/tv.hip)
   int tv_fma = 0;           // 1: TOLERANCE MODE of tensor voting: fused multiply-adds, results within 1e-5 of the field's scale
                             //    instead of bit-identical (surfaces, exponent 2 or 4; everything else stays exact)
@@ -169,6 +174,8 @@ struct visfd_hip_ctx {
   std::vector<unsigned char> slot_key[vh::WS_NSLOTS];   // what a slot's contents were built from (ws_holds / ws_put); empty: nothing remembered
   int num_cus = 256;
   hipStream_t aux_stream = nullptr;   // host copies that must not queue behind the main stream's kernels
+  void* stage_pinned = nullptr;       // the queued membrane stage's one readback (StageReadback, pinned host memory) and the event
+  hipEvent_t stage_event = nullptr;   // behind its copy; both made by the first such stage, gone with the context
   int morph_last_path = -1;           // the kernel the last morphology call ran (VISFD_HIP_MORPH_PATH_*)
   struct {                            // of the filter table expanded into slot WS_F3D_TAB, valid only while that slot's key holds:
     int64_t n = 0, ncols = 0;         // the number of its non-zero entries, of the columns (jy, jx) that hold one,
@@ -399,8 +406,10 @@ int dev_ridge_saliency_fused(visfd_hip_ctx* ctx, const float* smoothed, const fl
 // (bin/filter_mrc/handlers.cpp:1698-1702 and :1883-1887, `-membrane-background`)
 int dev_ridge_score(visfd_hip_ctx* ctx, const float* smoothed, const float* mask, i64 nx, i64 ny, i64 nz,
                     float sigma, int order, float* saliency, const float* peak_img = nullptr, const float* peak_bg = nullptr);
+// thr_dev (nullable, device memory): the saliency volume has not been cut; a voxel survives if !(s < *thr_dev) && s != 0 --
+// the voxels dev_apply_threshold followed by s != 0 keeps
 int dev_ridge_directions(visfd_hip_ctx* ctx, const float* smoothed, const float* saliency, i64 nx, i64 ny, i64 nz,
-                         float sigma, int order, float* dir_planar);
+                         float sigma, int order, float* dir_planar, const float* thr_dev = nullptr);
 int dev_diagonalize(visfd_hip_ctx* ctx, const float* m6_planar, float* out6_planar, i64 n, int order);
 int dev_tensor_saliency(visfd_hip_ctx* ctx, const float* tensor_planar, const float* mask, i64 nvox,
                         int order, float* saliency, const float* peak_img = nullptr, const float* peak_bg = nullptr);
@@ -409,6 +418,25 @@ int dev_select_histogram(visfd_hip_ctx* ctx, const float* sal, const float* mask
                          uint32_t prefix, uint64_t* hist_host, uint64_t* n_unmasked_host);
 int dev_select_histogram_todev(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, int pass, uint32_t prefix,
                                uint64_t* hist_dev);
+// The select with no host step between its rounds (select.hip: pick_kernel): what the device keeps of it.
+enum : uint32_t { SELECT_NO_VOXEL = 1u, SELECT_INCONSISTENT = 2u };
+struct SelectState {
+  uint32_t prefix;   // the digits picked so far, right-aligned; after round 2 the order key of the threshold
+  uint32_t flag;     // 0, or why there is no threshold (SELECT_*)
+  uint64_t k;        // the rank left inside the picked bins
+  uint64_t n;        // round 0's total: the unmasked voxels
+  float thr;         // after round 2: the threshold (+inf with a flag)
+  uint32_t pad;
+};
+// What the queued membrane stage reads back in its one copy (slot WS_SELECT holds the same layout on the device)
+struct StageReadback {
+  SelectState sel;
+  unsigned long long list_total;   // tv_list.hip: the sender lists' length
+  unsigned list_flags, pad;        // ... and what their count pass saw (TVL_*)
+};
+int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state_dev);
+int select_result(const SelectState& s, float* thr_out);   // the state read back: the threshold, or the select's error
+int select_rank_check(uint64_t n, float fraction);         // the select's VISFD_HIP_EINVAL, from n alone (no mask: n is known before round 0)
 int dev_apply_threshold(visfd_hip_ctx* ctx, float* sal, i64 nvox, float thr);
 int dev_threshold_fraction(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction,
                            float* thr_out);

@@ -69,6 +69,7 @@ struct OptionDesc {
 #define VH_OPT(field) {#field, &visfd_hip_options::field}
 const OptionDesc kOptions[] = {   // every field of visfd_hip_options (common.hpp documents them), in its order
     VH_OPT(gauss_3pass), VH_OPT(gauss_cfg), VH_OPT(gauss_wg_per_cu), VH_OPT(log_pair), VH_OPT(log_pair_chunk),
+    VH_OPT(membrane_queue),
     VH_OPT(tv_dense), VH_OPT(tv_fma), VH_OPT(gauss_fma), VH_OPT(eig_f32), VH_OPT(tv_zrun), VH_OPT(tv_no_replay),
     VH_OPT(tv_exact_tiled), VH_OPT(tv_no_fold), VH_OPT(tv_poison), VH_OPT(tv_reserve_wg), VH_OPT(tv_max_wg),
     VH_OPT(blob_test_cap), VH_OPT(morph_general), VH_OPT(morph_levels), VH_OPT(filter3d_general), VH_OPT(median_general),
@@ -197,6 +198,8 @@ int visfd_hip_destroy(visfd_hip_ctx* ctx) {
   blob_jobs_abort(ctx);
   int rc = visfd_hip_trim(ctx);
   if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
+  if (ctx->stage_event) (void)hipEventDestroy(ctx->stage_event);
+  if (ctx->stage_pinned) (void)hipHostFree(ctx->stage_pinned);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return rc;

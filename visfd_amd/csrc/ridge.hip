@@ -167,7 +167,10 @@ constexpr int DIR_CHUNK = DIR_PER * BLOCK;  // eigenvector loop then keeps 3-4 o
 template <bool F32>
 __global__ void __launch_bounds__(BLOCK)
 ridge_directions_kernel(const float* __restrict__ S, const float* __restrict__ sal, int nx, int ny, int nz,
-                        float sigma, int order, float* __restrict__ dir) {
+                        float sigma, int order, float* __restrict__ dir,
+                        // nullable: sal is uncut and the cut is made here -- !(s < thr) && s != 0, the voxels
+                        // apply_threshold_kernel (select.hip) followed by s != 0 keeps: -0, NaN and +inf pass it, zeros do not
+                        const float* __restrict__ thr_dev) {
   __shared__ unsigned short list[DIR_CHUNK];
   __shared__ int wave_tot[BLOCK / 64];
   const i64 nvox = (i64)nx * ny * nz;
@@ -175,10 +178,13 @@ ridge_directions_kernel(const float* __restrict__ S, const float* __restrict__ s
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned keep = 0u;   // bit k: voxel base + k * BLOCK + tid survives
   int cnt = 0;
+  const bool cut = thr_dev != nullptr;
+  const float thr = cut ? *thr_dev : 0.0f;
 #pragma unroll
   for (int k = 0; k < DIR_PER; k++) {
     const i64 v = base + k * BLOCK + tid;
-    const bool kp = v < nvox && sal[v] != 0.0f;
+    const float sv = v < nvox ? sal[v] : 0.0f;
+    const bool kp = sv != 0.0f && !(cut && sv < thr);
     keep |= (kp ? 1u : 0u) << k;
     cnt += kp ? 1 : 0;
   }
@@ -342,13 +348,13 @@ int dev_ridge_score(visfd_hip_ctx* ctx, const float* S, const float* mask, i64 n
 }
 
 int dev_ridge_directions(visfd_hip_ctx* ctx, const float* S, const float* sal, i64 nx, i64 ny, i64 nz, float sigma,
-                         int order, float* dir) {
+                         int order, float* dir, const float* thr_dev) {
   if (nx < 3 || ny < 3 || nz < 3)
     return fail(VISFD_HIP_EINVAL, "ridge detection requires an image at least 3 voxels wide in x,y,z");
   if (nx >= (1LL << 31) || ny >= (1LL << 31) || nz >= (1LL << 31)) return fail(VISFD_HIP_EINVAL, "dimension too large");
   const i64 nb = (nx * ny * nz + DIR_CHUNK - 1) / DIR_CHUNK;
   if (nb > 0x7fffffffLL) return fail(VISFD_HIP_EINVAL, "volume too large for one launch");
-  VH_EIG_LAUNCH(ridge_directions_kernel, dim3((unsigned)nb), S, sal, (int)nx, (int)ny, (int)nz, sigma, order, dir);
+  VH_EIG_LAUNCH(ridge_directions_kernel, dim3((unsigned)nb), S, sal, (int)nx, (int)ny, (int)nz, sigma, order, dir, thr_dev);
   VH_HIP(hipGetLastError());
   return VISFD_HIP_OK;
 }

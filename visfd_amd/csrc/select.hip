@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "select_pick.hpp"
 
 namespace vh {
 
@@ -23,19 +24,22 @@ __device__ __forceinline__ uint32_t order_key(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-inline float key_to_float(uint32_t k) {
+__host__ __device__ inline float key_to_float(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
   float f;
-  std::memcpy(&f, &u, 4);
+  __builtin_memcpy(&f, &u, 4);
   return f;
 }
 
 // digit layout of the 32-bit key: round 0 = bits 31..21, round 1 = bits 20..10, round 2 = bits 9..0.
-// `prefix` holds the already-selected higher digits (right-aligned); only keys matching it count.
+// `prefix` holds the already-selected higher digits (right-aligned); only keys matching it count.  DEVPREFIX: the digits
+// come from the select's state block on the device, where pick_kernel left them (no host step between the rounds).
+template <bool DEVPREFIX>
 __global__ void __launch_bounds__(BLOCK)
 histogram_kernel(const float* __restrict__ sal, const float* __restrict__ mask, i64 n, int round,
-                 uint32_t prefix, unsigned long long* __restrict__ hist) {
+                 uint32_t prefix_arg, const SelectState* __restrict__ state, unsigned long long* __restrict__ hist) {
   __shared__ unsigned int lh[NBINS];
+  const uint32_t prefix = DEVPREFIX ? state->prefix : prefix_arg;
   for (int i = threadIdx.x; i < NBINS; i += BLOCK) lh[i] = 0;
   __syncthreads();
   const int shift = (round == 0) ? 21 : (round == 1) ? 10 : 0;
@@ -72,6 +76,57 @@ histogram_kernel(const float* __restrict__ sal, const float* __restrict__ mask, 
   }
 }
 
+// The host's step between two rounds, on the device: ONE workgroup reads the round's histogram (and zeroes it for the next
+// round), thread 0 walks it from the top -- first the 256 sums of 8 neighbouring bins, then the 8 bins of the chunk that walk
+// stops in: the same bin and the same remainder as one walk over all 2048, by the same function -- and leaves {digits so
+// far, rank left} in the state block; after round 2 the threshold itself.  Round 0 also turns its total into the rank.
+__global__ void __launch_bounds__(BLOCK)
+pick_kernel(unsigned long long* __restrict__ hist, int round, float fraction, SelectState* __restrict__ state) {
+  constexpr int PER = NBINS / BLOCK;
+  __shared__ uint64_t lh[NBINS];
+  __shared__ uint64_t chunk[BLOCK];
+  const int t = threadIdx.x;
+  uint64_t sum = 0;
+#pragma unroll
+  for (int i = 0; i < PER; i++) {
+    const uint64_t c = hist[t * PER + i];
+    hist[t * PER + i] = 0;
+    lh[t * PER + i] = c;
+    sum += c;
+  }
+  chunk[t] = sum;
+  __syncthreads();
+  if (t != 0) return;
+  uint64_t k = 0;
+  uint32_t prefix = 0;
+  if (round == 0) {
+    uint64_t n = 0;
+    for (int i = 0; i < BLOCK; i++) n += chunk[i];
+    state->n = n;
+    state->flag = 0;
+    if (!select_rank(n, fraction, &k)) {
+      state->flag = SELECT_NO_VOXEL;
+      state->thr = __builtin_inff();   // (consumers queued behind a failed select keep nothing finite)
+      return;
+    }
+  } else {
+    if (state->flag) return;
+    k = state->k;
+    prefix = state->prefix;
+  }
+  const int c = select_pick_bin(chunk, BLOCK, &k);
+  const int d = c < 0 ? -1 : select_pick_bin(lh + c * PER, PER, &k);
+  if (d < 0) {
+    state->flag = SELECT_INCONSISTENT;
+    state->thr = __builtin_inff();
+    return;
+  }
+  prefix = (prefix << (round == 2 ? 10 : 11)) | (uint32_t)(c * PER + d);
+  state->prefix = prefix;
+  state->k = k;
+  if (round == 2) state->thr = key_to_float(prefix);
+}
+
 __global__ void __launch_bounds__(BLOCK)
 apply_threshold_kernel(float* __restrict__ sal, i64 n, float thr) {
   i64 i = (i64)blockIdx.x * BLOCK + threadIdx.x;
@@ -92,7 +147,7 @@ int dev_select_histogram(visfd_hip_ctx* ctx, const float* sal, const float* mask
   hipStream_t st = ctx->stream;
   VH_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned long long) * NBINS, st));
   const unsigned g = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 32);
-  histogram_kernel<<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, hist);
+  histogram_kernel<false><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, nullptr, hist);
   VH_HIP(hipGetLastError());
   VH_HIP(hipMemcpyAsync(hist_host, hist, sizeof(uint64_t) * NBINS, hipMemcpyDeviceToHost, st));
   VH_HIP(hipStreamSynchronize(st));
@@ -111,7 +166,7 @@ int dev_select_histogram_todev(visfd_hip_ctx* ctx, const float* sal, const float
   hipStream_t st = ctx->stream;
   VH_HIP(hipMemsetAsync(hist_dev, 0, sizeof(unsigned long long) * NBINS, st));
   const unsigned g = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 32);
-  histogram_kernel<<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, reinterpret_cast<unsigned long long*>(hist_dev));
+  histogram_kernel<false><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, nullptr, reinterpret_cast<unsigned long long*>(hist_dev));
   VH_HIP(hipGetLastError());
   return VISFD_HIP_OK;
 }
@@ -123,42 +178,68 @@ int dev_apply_threshold(visfd_hip_ctx* ctx, float* sal, i64 nvox, float thr) {
   return VISFD_HIP_OK;
 }
 
-// Walk a histogram from the largest key down; returns the bin holding the k-th largest
-// (0-based) element and rewrites k to the rank inside that bin.
-static int pick_bin_descending(const std::vector<uint64_t>& h, uint64_t* k) {
-  uint64_t seen = 0;
-  for (int b = NBINS - 1; b >= 0; b--) {
-    if (seen + h[b] > *k) { *k -= seen; return b; }
-    seen += h[b];
+// The whole select queued with no host step: the three histogram / pick pairs.  *state (device memory) then holds the
+// threshold, or a flag that select_result turns into the error.  A masked select takes its n from round 0's total.
+int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state) {
+  unsigned long long* hist = nullptr;
+  VH_TRY(ws(ctx, WS_HIST, (size_t)NBINS, &hist));
+  hipStream_t st = ctx->stream;
+  VH_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned long long) * NBINS, st));   // (every pick leaves it zeroed for the next round)
+  const unsigned g = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 32);
+  for (int round = 0; round < 3; round++) {
+    histogram_kernel<true><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, round, 0u, state, hist);
+    pick_kernel<<<dim3(1), dim3(BLOCK), 0, st>>>(hist, round, fraction, state);
   }
-  return -1;
+  VH_HIP(hipGetLastError());
+  return VISFD_HIP_OK;
+}
+
+static const char* const kNoVoxel = "threshold fraction selects no voxel (the reference would read past its array)";
+static const char* const kInconsistent = "radix select: inconsistent histogram";
+
+int select_result(const SelectState& s, float* thr_out) {
+  if (s.flag & SELECT_NO_VOXEL) return fail(VISFD_HIP_EINVAL, kNoVoxel);
+  if (s.flag) return fail(VISFD_HIP_EDEVICE, kInconsistent);
+  if (thr_out) *thr_out = s.thr;
+  return VISFD_HIP_OK;
+}
+int select_rank_check(uint64_t n, float fraction) {
+  uint64_t k = 0;
+  if (!select_rank(n, fraction, &k)) return fail(VISFD_HIP_EINVAL, kNoVoxel);
+  return VISFD_HIP_OK;
 }
 
 // the host steps of one radix round on an (all-reduced) histogram, for the multi-rank select of slab.hip
-int select_pick_digit(const uint64_t* hist, uint64_t* k) {
-  return pick_bin_descending(std::vector<uint64_t>(hist, hist + NBINS), k);
-}
+int select_pick_digit(const uint64_t* hist, uint64_t* k) { return select_pick_bin(hist, NBINS, k); }
 float select_key_to_float(uint32_t key) { return key_to_float(key); }
 
+// Option membrane_queue: the rounds queued back to back with the digit picked on the device and ONE wait for the state
+// block; 0: a wait and a host walk after every round.  Either way sal is cut only once the threshold is known to exist.
 int dev_threshold_fraction(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction,
                            float* thr_out) {
-  std::vector<uint64_t> h(NBINS);
-  uint64_t n_unmasked = 0;
-  VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 0, 0, h.data(), &n_unmasked));
-  // i = floor(n_voxels * fraction): size_t -> float product (handlers.cpp:1781)
-  const float prod = (float)n_unmasked * fraction;
-  uint64_t k = (uint64_t)std::floor(prod);
-  if (n_unmasked == 0 || k >= n_unmasked)
-    return fail(VISFD_HIP_EINVAL, "threshold fraction selects no voxel (the reference would read past its array)");
-  const int d0 = pick_bin_descending(h, &k);
-  if (d0 < 0) return fail(VISFD_HIP_EDEVICE, "radix select: inconsistent histogram");
-  VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 1, (uint32_t)d0, h.data(), nullptr));
-  const int d1 = pick_bin_descending(h, &k);
-  if (d1 < 0) return fail(VISFD_HIP_EDEVICE, "radix select: inconsistent histogram");
-  VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 2, ((uint32_t)d0 << 11) | (uint32_t)d1, h.data(), nullptr));
-  const int d2 = pick_bin_descending(h, &k);
-  if (d2 < 0) return fail(VISFD_HIP_EDEVICE, "radix select: inconsistent histogram");
-  const float thr = key_to_float(((uint32_t)d0 << 21) | ((uint32_t)d1 << 10) | (uint32_t)d2);
+  float thr = 0.0f;
+  if (ctx->opt.membrane_queue) {
+    StageReadback* block = nullptr;   // (the slot's one layout; only the select's part is used here)
+    VH_TRY(ws(ctx, WS_SELECT, 1, &block));
+    VH_TRY(dev_select_queue(ctx, sal, mask, nvox, fraction, &block->sel));
+    SelectState got;
+    VH_HIP(hipMemcpyAsync(&got, &block->sel, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+    VH_HIP(hipStreamSynchronize(ctx->stream));
+    VH_TRY(select_result(got, &thr));
+  } else {
+    std::vector<uint64_t> h(NBINS);
+    uint64_t n_unmasked = 0, k = 0;
+    VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 0, 0, h.data(), &n_unmasked));
+    if (!select_rank(n_unmasked, fraction, &k)) return fail(VISFD_HIP_EINVAL, kNoVoxel);
+    uint32_t key = 0;
+    for (int round = 0; round < 3; round++) {
+      if (round > 0) VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, round, key, h.data(), nullptr));
+      const int d = select_pick_bin(h.data(), NBINS, &k);
+      if (d < 0) return fail(VISFD_HIP_EDEVICE, kInconsistent);
+      key = (key << (round == 2 ? 10 : 11)) | (uint32_t)d;
+    }
+    thr = key_to_float(key);
+  }
   if (thr_out) *thr_out = thr;
   return dev_apply_threshold(ctx, sal, nvox, thr);
 }

@@ -238,6 +238,30 @@ int dev_tv_dense_stick(visfd_hip_ctx* ctx, const float* sal, const float* dir, f
                      cutoff);
 }
 
+// (tv_common.hpp: TvStagePlan)  The surface vote of a whole volume in two halves around the caller's one read.
+int dev_tv_stage_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask, i64 nx, i64 ny, i64 nz,
+                       float sigma_tv, int exponent, float cutoff, unsigned long long* total_dev, unsigned* flags_dev,
+                       TvStagePlan* plan) {
+  VH_TRY(check_dims(nx, ny, nz));
+  VH_TRY(check_dims32(nx, ny, nz));
+  const int h = host_tv_halfwidth(sigma_tv, cutoff);
+  VH_REQUIRE(h >= 0 && h <= 255, "tensor-voting window halfwidth out of range");
+  TvRoute routes[4];
+  tv_routes(ctx->opt, {sal, nullptr, nullptr, mask, mask, nx, ny, nz, 0, nz, exponent, false, false}, routes);
+  if (routes[0] != TvRoute::BoxTol && routes[0] != TvRoute::BoxExact) return TV_DECLINED;
+  TvTables tab;
+  VH_TRY(tv_table_device(ctx, sigma_tv, cutoff, h, &tab));
+  const bool exact = routes[0] == TvRoute::BoxExact;
+  *plan = {h, exact, exact ? tab.box_exact : tab.box_tol, tab.box_tol_sq, {}};
+  return dev_tv_box_count(ctx, sal, thr_dev, mask, nx, ny, nz, 0, nz, h, exponent, exact, total_dev, flags_dev, &plan->lists);
+}
+
+int dev_tv_stage_vote(visfd_hip_ctx* ctx, const TvStagePlan& plan, unsigned long long total, unsigned flags, const float* sal,
+                      const float* dir, float* ten, const float* mask, i64 nx, i64 ny, i64 nz, int exponent) {
+  return dev_tv_box_vote(ctx, plan.lists, total, flags, sal, dir, ten, mask, mask, nx, ny, nz, 0, nz, plan.h, plan.dtab_box,
+                         plan.dtab_box_sq, exponent, plan.exact);
+}
+
 // The sum of the weights of the votes every receiver takes (one plane-sized volume): the "denominator" TVDenseStick
 // accumulates for its normalisation (feature.hpp:1761-1822, 2376-2382) -- w(j) * mask_src(sender) over the in-bounds
 // senders with non-zero saliency, source mask and weight, added in vote order.

@@ -937,21 +937,17 @@ auto box_tol_kernel(int mode, bool fold) {
   return fold ? tv_box_kernel<2, true> : tv_box_kernel<2, false>;
 }
 
-}  // namespace
-
-// Tolerance-mode tensor voting (surfaces, exponent 2 or 4).  dtab_box: the {w, sqrt(2) rhat} table on the device in this
-// kernel's slice layout (tv_common.hpp: TvTables::box_tol); dtab_box_sq: the same with sqrt(w) (box_tol_sq), which
-// tv_box_kernel<0, true> reads.
-// exact: the exact form (tv_boxx_kernel) with dtab_box = the reference's {w, rhat} in the same slice layout (box_exact); it
-// declines weighted source masks (values other than 0 and 1) and non-finite saliencies (tv_tiled.hip takes them).
-int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
-               const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box,
-               const float4* dtab_box_sq, int exponent, bool exact) {
+// What both halves of a launch work out from the request alone.  TV_DECLINED: the kernels of this file do not take it.
+struct BoxPlan {
+  BoxParams p;
+  size_t lds, lds_static;
+  i64 nblk;   // units of work; 0: nothing to do
+};
+int box_plan(visfd_hip_ctx* ctx, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, int exponent, bool exact, BoxPlan* b) {
   if (exponent != 2 && exponent != 4) return TV_DECLINED;
   if (h < 1 || h > 40) return TV_DECLINED;
   if (nx * ny >= (1LL << 29) || nx > TV_LIST_MAX_NX || ny >= (1 << 24)) return TV_DECLINED;
-  hipStream_t st = ctx->stream;
-  BoxParams p;
+  BoxParams& p = b->p;
   p.nx = (int)nx; p.ny = (int)ny; p.nz = (int)nz;
   p.z_out0 = (int)z_out0; p.z_out1 = (int)z_out1;
   p.h = h;
@@ -965,26 +961,51 @@ int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* te
   p.tiles_y = (int)((ny + TY - 1) / TY);
   // (sweep at 1024^3, tools/tv_sweep.py: 2..8 planes 280-281 ms, 16: 283, 32: 290, 64: 296, 128: 306 -- short runs keep the
   //  workgroups of the chip on neighbouring planes, whose lists and slices they then share in L2)
-  i64 nblk = 0;
-  VH_TRY(tv_plan_units(ctx, 8, p.tiles_x, p.tiles_y, z_out0, z_out1, &p.zrun, &nblk));
-  if (nblk == 0) return VISFD_HIP_OK;
+  b->nblk = 0;
+  VH_TRY(tv_plan_units(ctx, 8, p.tiles_x, p.tiles_y, z_out0, z_out1, &p.zrun, &b->nblk));
   // two slices + the per-pass table of row stretches ([2h + 4 planes][pairs][waves] words)
-  const size_t lds = 2 * slice_bytes + sizeof(unsigned) * (size_t)(2 * h + 4) * NW * (exact ? NPAIR : 1);
-  const size_t lds_static = sizeof(float4) * (LSLOTS + 1) + sizeof(uint2) * LSLOTS + sizeof(uint2) * NW * NSUB * 2 * HCAP + 1536;
+  b->lds = 2 * slice_bytes + sizeof(unsigned) * (size_t)(2 * h + 4) * NW * (exact ? NPAIR : 1);
+  b->lds_static = sizeof(float4) * (LSLOTS + 1) + sizeof(uint2) * LSLOTS + sizeof(uint2) * NW * NSUB * 2 * HCAP + 1536;
   static_assert(2 * HCAP == HX, "the two kernels' hit lists take the same LDS");
-  if (lds + lds_static > 150 * 1024) return TV_DECLINED;   // window too wide
+  if (b->nblk > 0 && b->lds + b->lds_static > 150 * 1024) return TV_DECLINED;   // window too wide
+  return VISFD_HIP_OK;
+}
+inline int list_mode(int exponent, bool exact) { return exact ? 1 : (exponent == 4 ? 0 : 2); }
 
-  // The sender lists.  What their count pass reports decides two things here:
-  //  * the exact form declines a non-finite saliency (the zero-padded slices would spread it) and a weighted source mask
-  //    (fv = w * mask value, feature.hpp:2262-2275; a mask of zeros and ones only multiplies the kept senders' weights by
-  //    1.0 -- exactly nothing -- so it takes that);
-  //  * the tolerance form folds the saliencies into the normals (the 18-instruction vote) if every one is positive
-  //    (option tv_no_fold, tests: the general form on positive saliencies too).
+}  // namespace
+
+int dev_tv_box_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask_src, i64 nx, i64 ny, i64 nz,
+                     i64 z_out0, i64 z_out1, int h, int exponent, bool exact, unsigned long long* total_dev, unsigned* flags_dev,
+                     TvListPlan* plan) {
+  BoxPlan b;
+  VH_TRY(box_plan(ctx, nx, ny, nz, z_out0, z_out1, h, exponent, exact, &b));
+  if (b.nblk == 0) return TV_DECLINED;
   unsigned* counter = nullptr;
   VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));   // word 0: the kernel's unit counter (zeroed with the lists' words); 8: poison sink
+  return tv_list_count(ctx, sal, thr_dev, mask_src, nx, ny, nz, z_out0, z_out1, h, list_mode(exponent, exact), counter, total_dev,
+                       flags_dev, plan);
+}
+
+// The sender lists.  What their count pass reports decides two things here:
+//  * the exact form declines a non-finite saliency (the zero-padded slices would spread it) and a weighted source mask
+//    (fv = w * mask value, feature.hpp:2262-2275; a mask of zeros and ones only multiplies the kept senders' weights by
+//    1.0 -- exactly nothing -- so it takes that);
+//  * the tolerance form folds the saliencies into the normals (the 18-instruction vote) if every one is positive
+//    (option tv_no_fold, tests: the general form on positive saliencies too).
+int dev_tv_box_vote(visfd_hip_ctx* ctx, const TvListPlan& plan, unsigned long long total, unsigned flags, const float* sal,
+                    const float* dir, float* ten, const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0,
+                    i64 z_out1, int h, const float4* dtab_box, const float4* dtab_box_sq, int exponent, bool exact) {
+  hipStream_t st = ctx->stream;
+  BoxPlan b;
+  VH_TRY(box_plan(ctx, nx, ny, nz, z_out0, z_out1, h, exponent, exact, &b));
+  BoxParams& p = b.p;
+  const size_t lds = b.lds, lds_static = b.lds_static;
+  const i64 nblk = b.nblk;
+  unsigned* counter = nullptr;
+  VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));   // (the words the count zeroed)
   TvSenderLists L;
-  VH_TRY(tv_sender_lists(ctx, sal, dir, mask_src, nx, ny, nz, z_out0, z_out1, h, exact ? 1 : (exponent == 4 ? 0 : 2),
-                         exact ? (TVL_NON_FINITE | TVL_WEIGHTED_MASK) : 0u, !exact && !ctx->opt.tv_no_fold, counter, &L));
+  VH_TRY(tv_list_write(ctx, plan, sal, dir, mask_src, total, flags, exact ? (TVL_NON_FINITE | TVL_WEIGHTED_MASK) : 0u,
+                       !exact && !ctx->opt.tv_no_fold, &L));
   p.zl0 = L.zl0; p.nzl = L.nzl;
 
   size_t wg_per_cu = (160 * 1024) / (lds + lds_static);
@@ -1025,6 +1046,31 @@ int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* te
   }
 #endif
   return VISFD_HIP_OK;
+}
+
+// Tolerance-mode tensor voting (surfaces, exponent 2 or 4).  dtab_box: the {w, sqrt(2) rhat} table on the device in this
+// kernel's slice layout (tv_common.hpp: TvTables::box_tol); dtab_box_sq: the same with sqrt(w) (box_tol_sq), which
+// tv_box_kernel<0, true> reads.
+// exact: the exact form (tv_boxx_kernel) with dtab_box = the reference's {w, rhat} in the same slice layout (box_exact); it
+// declines weighted source masks (values other than 0 and 1) and non-finite saliencies (tv_tiled.hip takes them).
+int dev_tv_box(visfd_hip_ctx* ctx, const float* sal, const float* dir, float* ten, const float* mask_src,
+               const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0, i64 z_out1, int h, const float4* dtab_box,
+               const float4* dtab_box_sq, int exponent, bool exact) {
+  BoxPlan b;
+  VH_TRY(box_plan(ctx, nx, ny, nz, z_out0, z_out1, h, exponent, exact, &b));
+  if (b.nblk == 0) return VISFD_HIP_OK;
+  unsigned* counter = nullptr;
+  VH_TRY(ws(ctx, WS_COUNTER, 16, &counter));
+  // the lists' total length and flags: counter words 4..7, the one place this launch waits for the device
+  unsigned long long* const total_dev = reinterpret_cast<unsigned long long*>(counter + 4);
+  TvListPlan plan;
+  VH_TRY(tv_list_count(ctx, sal, nullptr, mask_src, nx, ny, nz, z_out0, z_out1, h, list_mode(exponent, exact), counter, total_dev,
+                       counter + 6, &plan));
+  unsigned long long tot2[2] = {0, 0};
+  VH_HIP(hipMemcpyAsync(tot2, total_dev, sizeof(tot2), hipMemcpyDeviceToHost, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  return dev_tv_box_vote(ctx, plan, tot2[0], (unsigned)tot2[1], sal, dir, ten, mask_src, mask_dst, nx, ny, nz, z_out0, z_out1, h,
+                         dtab_box, dtab_box_sq, exponent, exact);
 }
 
 }  // namespace vh

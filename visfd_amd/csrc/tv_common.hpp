@@ -140,8 +140,50 @@ struct TvSenderLists {
 // mode: the saliency's scaling -- 0: 1/4 (tolerance vote, exponent 4), 2: 1/2 (exponent 2), 1: none (exact vote).
 // decline_on: flags with which the caller has no use for the lists (TV_DECLINED before they are written).
 // may_fold: records are folded if every listed saliency is positive.
-int tv_sender_lists(visfd_hip_ctx* ctx, const float* sal, const float* dir, const float* mask_src, i64 nx, i64 ny, i64 nz,
-                    i64 z_out0, i64 z_out1, int h, int mode, unsigned decline_on, bool may_fold, unsigned* counter,
-                    TvSenderLists* out);
+// Two halves around the caller's read of {total, flags} (dev_tv_box waits for it at once; api.hip's membrane_stage reads it
+// together with other words and with more work queued behind them): tv_list_count queues the count pass and the scan,
+// which leave the two in *total_dev and *flags_dev (device words zeroed by the caller, or among the 16 of `counter`, which
+// are zeroed here); tv_list_write is everything after the read.
+// thr_dev (nullable, device memory): sal is uncut, and only voxels with !(s < *thr_dev) are salient.
+struct TvListGeo {
+  int nx, ny, nz;
+  int zl0, nzl;   // listed planes [zl0, zl0 + nzl)
+  int ntx, h;
+};
+struct TvListPlan {
+  TvListGeo g;
+  unsigned* rows;
+  unsigned row_blocks;
+  int mode;
+  const float* thr_dev;
+};
+int tv_list_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask_src, i64 nx, i64 ny, i64 nz,
+                  i64 z_out0, i64 z_out1, int h, int mode, unsigned* counter, unsigned long long* total_dev, unsigned* flags_dev,
+                  TvListPlan* plan);
+int tv_list_write(visfd_hip_ctx* ctx, const TvListPlan& plan, const float* sal, const float* dir, const float* mask_src,
+                  unsigned long long total, unsigned flags, unsigned decline_on, bool may_fold, TvSenderLists* out);
+
+// tv_box.hip in the same two halves: dev_tv_box_count checks the request as dev_tv_box does (TV_DECLINED before anything is
+// queued) and queues the lists' count; dev_tv_box_vote writes the lists and votes.  dev_tv_box is the two around one read.
+int dev_tv_box_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask_src, i64 nx, i64 ny, i64 nz,
+                     i64 z_out0, i64 z_out1, int h, int exponent, bool exact, unsigned long long* total_dev, unsigned* flags_dev,
+                     TvListPlan* plan);
+int dev_tv_box_vote(visfd_hip_ctx* ctx, const TvListPlan& plan, unsigned long long total, unsigned flags, const float* sal,
+                    const float* dir, float* ten, const float* mask_src, const float* mask_dst, i64 nx, i64 ny, i64 nz, i64 z_out0,
+                    i64 z_out1, int h, const float4* dtab_box, const float4* dtab_box_sq, int exponent, bool exact);
+
+// tv.hip, for the queued membrane stage: the vote of the whole volume by the request's FIRST route, in those halves.
+// dev_tv_stage_count returns TV_DECLINED (nothing queued) unless that route is a form of tv_box.hip that takes the request.
+struct TvStagePlan {
+  int h;
+  bool exact;
+  const float4 *dtab_box, *dtab_box_sq;
+  TvListPlan lists;
+};
+int dev_tv_stage_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask, i64 nx, i64 ny, i64 nz,
+                       float sigma_tv, int exponent, float cutoff, unsigned long long* total_dev, unsigned* flags_dev,
+                       TvStagePlan* plan);
+int dev_tv_stage_vote(visfd_hip_ctx* ctx, const TvStagePlan& plan, unsigned long long total, unsigned flags, const float* sal,
+                      const float* dir, float* ten, const float* mask, i64 nx, i64 ny, i64 nz, int exponent);
 
 }  // namespace vh

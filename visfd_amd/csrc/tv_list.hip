@@ -19,11 +19,7 @@ using namespace box_tile;
 
 namespace {
 
-struct ListGeo {
-  int nx, ny, nz;
-  int zl0, nzl;   // listed planes [zl0, zl0 + nzl)
-  int ntx, h;
-};
+using ListGeo = TvListGeo;
 constexpr int LNT = 256;
 constexpr int LWORDS_MAX = TV_LIST_MAX_NX / 32;
 
@@ -43,7 +39,9 @@ __global__ void __launch_bounds__(LNT)
 tvl_row_kernel(const float* __restrict__ sal, const float* __restrict__ dir, const float* __restrict__ mask_src, ListGeo g,
                unsigned* __restrict__ rows, float4* __restrict__ ent, unsigned* __restrict__ pos,
                unsigned* __restrict__ neg_flag /* count pass: set if a listed saliency (times its mask value) is not positive */,
-               int fold /* write pass: records {c, a n} instead of {s, n} (vote_fma) */) {
+               int fold /* write pass: records {c, a n} instead of {s, n} (vote_fma) */,
+               const float* __restrict__ thr_dev /* nullable: sal is uncut, and a voxel below *thr_dev is not salient (ridge.hip:
+                                                    ridge_directions_kernel has the same predicate) */) {
   // ONE WAVE PER IMAGE ROW (no workgroup barrier: a wave's bit mask is its own): its salient flags as a bit mask in LDS,
   // 64 voxels per ballot.  A wave is a chain of memory round trips, so every phase requests LB chunks' worth of loads before
   // it uses the first (the loops are otherwise one round trip per 64 voxels: 8 ms for the write pass at 1024^3)
@@ -66,6 +64,8 @@ tvl_row_kernel(const float* __restrict__ sal, const float* __restrict__ dir, con
   }
   unsigned any = 0, total = 0;
   unsigned* const cum = cum_all[WRITE ? wave : 0];
+  const bool cut = thr_dev != nullptr;
+  const float thr = cut ? *thr_dev : 0.0f;
   for (int c0 = 0; c0 < nchunks; c0 += LB) {   // uniform
     float v[LB], m[LB];
 #pragma unroll
@@ -77,7 +77,7 @@ tvl_row_kernel(const float* __restrict__ sal, const float* __restrict__ dir, con
 #pragma unroll
     for (int k = 0; k < LB; k++) {
       if (c0 + k >= nchunks) break;   // uniform
-      const bool f = v[k] != 0.0f && m[k] != 0.0f;
+      const bool f = v[k] != 0.0f && m[k] != 0.0f && !(cut && v[k] < thr);
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(f);
       if (lane == 0) {
         bits[2 * (c0 + k)] = (unsigned)bal;
@@ -173,11 +173,17 @@ tvl_scan_kernel(ListGeo g, unsigned* __restrict__ rows, unsigned long long* __re
 
 }  // namespace
 
-// (tv_common.hpp: TvSenderLists)  The count pass, the scan, the one host read of {total, flags} -- the one place a launch waits
-// for the device -- and the write pass.  counter: the 16 words of WS_COUNTER; all are zeroed, words 4..7 are used here.
-int tv_sender_lists(visfd_hip_ctx* ctx, const float* sal, const float* dir, const float* mask_src, i64 nx, i64 ny, i64 nz,
-                    i64 z_out0, i64 z_out1, int h, int mode, unsigned decline_on, bool may_fold, unsigned* counter,
-                    TvSenderLists* out) {
+namespace {
+auto row_kernel(bool write, int mode) {   // (one signature)
+  if (write) return mode == 1 ? tvl_row_kernel<true, 1> : mode == 0 ? tvl_row_kernel<true, 0> : tvl_row_kernel<true, 2>;
+  return mode == 1 ? tvl_row_kernel<false, 1> : mode == 0 ? tvl_row_kernel<false, 0> : tvl_row_kernel<false, 2>;
+}
+}  // namespace
+
+// (tv_common.hpp: TvListPlan)  The count pass and the scan, queued.  counter: the 16 words of WS_COUNTER, all zeroed here.
+int tv_list_count(visfd_hip_ctx* ctx, const float* sal, const float* thr_dev, const float* mask_src, i64 nx, i64 ny, i64 nz,
+                  i64 z_out0, i64 z_out1, int h, int mode, unsigned* counter, unsigned long long* total_dev, unsigned* flags_dev,
+                  TvListPlan* plan) {
   hipStream_t st = ctx->stream;
   ListGeo g;
   g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz; g.h = h; g.ntx = (int)((nx + TX - 1) / TX);
@@ -187,21 +193,20 @@ int tv_sender_lists(visfd_hip_ctx* ctx, const float* sal, const float* dir, cons
   if ((i64)g.nzl * ny > 0x7fffffffLL) return TV_DECLINED;
   unsigned* rows = nullptr;
   if (ws(ctx, WS_TVLIST, nrows, &rows) != VISFD_HIP_OK) { set_error(""); (void)hipGetLastError(); return TV_DECLINED; }
-  unsigned long long* total_dev = reinterpret_cast<unsigned long long*>(counter + 4);
   VH_HIP(hipMemsetAsync(counter, 0, 16 * sizeof(unsigned), st));
   const unsigned row_blocks = (unsigned)(((i64)g.nzl * ny + LNT / 64 - 1) / (LNT / 64));
-  const auto row_pass = [&](auto kernel, float4* ent, unsigned* pos, int fold) {
-    kernel<<<dim3(row_blocks), dim3(LNT), 0, st>>>(sal, dir, mask_src, g, rows, ent, pos, counter + 6, fold);
-  };
-  row_pass(mode == 1 ? tvl_row_kernel<false, 1> : mode == 0 ? tvl_row_kernel<false, 0> : tvl_row_kernel<false, 2>, nullptr, nullptr, 0);
+  row_kernel(false, mode)<<<dim3(row_blocks), dim3(LNT), 0, st>>>(sal, nullptr, mask_src, g, rows, nullptr, nullptr, flags_dev, 0, thr_dev);
   tvl_scan_kernel<<<dim3((unsigned)(((size_t)g.nzl * g.ntx + LNT - 1) / LNT)), dim3(LNT), 0, st>>>(g, rows, total_dev);
   VH_HIP(hipGetLastError());
-  // the lists' total length decides the size of the entry arrays
-  unsigned long long tot2[2] = {0, 0};   // {total, (flags, -)}: counter words 4..7
-  VH_HIP(hipMemcpyAsync(tot2, total_dev, sizeof(tot2), hipMemcpyDeviceToHost, st));
-  VH_HIP(hipStreamSynchronize(st));
-  const unsigned long long total = tot2[0];
-  const unsigned flags = (unsigned)tot2[1];
+  *plan = {g, rows, row_blocks, mode, thr_dev};
+  return VISFD_HIP_OK;
+}
+
+// The write pass, once the host has {total, flags} of the plan's count pass: total sizes the entry arrays, the flags decide
+// whether the caller has a use for the lists and whether their records are folded.
+int tv_list_write(visfd_hip_ctx* ctx, const TvListPlan& plan, const float* sal, const float* dir, const float* mask_src,
+                  unsigned long long total, unsigned flags, unsigned decline_on, bool may_fold, TvSenderLists* out) {
+  hipStream_t st = ctx->stream;
   if (flags & decline_on) return TV_DECLINED;
   if (total >= (1ull << 32) - 2048) return TV_DECLINED;   // 32-bit entry indices
   const int fold = (may_fold && !(flags & TVL_NOT_POSITIVE)) ? 1 : 0;
@@ -210,9 +215,10 @@ int tv_sender_lists(visfd_hip_ctx* ctx, const float* sal, const float* dir, cons
   float4* const ent = reinterpret_cast<float4*>(lists);
   unsigned* const pos = reinterpret_cast<unsigned*>(lists + (size_t)(total + 16) * 16);
   if (ctx->opt.tv_poison) VH_HIP(hipMemsetAsync(lists, 0xff, (size_t)(total + 16) * 20, st));
-  row_pass(mode == 1 ? tvl_row_kernel<true, 1> : mode == 0 ? tvl_row_kernel<true, 0> : tvl_row_kernel<true, 2>, ent, pos, fold);
+  row_kernel(true, plan.mode)<<<dim3(plan.row_blocks), dim3(LNT), 0, st>>>(sal, dir, mask_src, plan.g, plan.rows, ent, pos, nullptr, fold,
+                                                                           plan.thr_dev);
   VH_HIP(hipGetLastError());
-  *out = {ent, pos, rows, total, flags, fold != 0, g.zl0, g.nzl};
+  *out = {ent, pos, plan.rows, total, flags, fold != 0, plan.g.zl0, plan.g.nzl};
   return VISFD_HIP_OK;
 }
 

@@ -108,13 +108,19 @@ def membrane_detect(ctx, src, sal, dirs, tensor, sigma, tv_sigma_ratio, tv_expon
     bg = None
     if sigma_background > 0:   # -membrane-background: both scores times (src - background), handlers.cpp:1577-1605,1698-1702
         bg = background if background is not None else src.new_empty(src.shape)
-        ctx.peak_background_dev(src, bg, sigma_background, ratio, mask)
-    ctx.ridge_scores_dev(src, sal, smoothed, sigma, ratio, order, mask, bg)
-    thr = ctx.threshold_fraction_dev(sal, best_fraction, mask)
-    ctx.ridge_directions_dev(smoothed, sal, dirs, sigma, order)
     sigma_tv = float(np.float32(tv_sigma_ratio) * np.float32(sigma))  # settings.cpp:3535-3540
-    ctx.tv_dense_stick_dev(sal, dirs, tensor, sigma_tv, tv_exponent, tv_truncate_ratio, mask, mask)
-    ctx.tensor_saliency_dev(tensor, sal, order, mask, src if bg is not None else None, bg)
+    if sigma_tv > 0:
+        # the whole stage in one call of the library, which queues it in one go (option membrane_queue, csrc/api.hip)
+        thr = ctx.membrane_stage_dev(src, sal, dirs, tensor, smoothed, sigma, ratio, order, best_fraction, sigma_tv, tv_exponent,
+                                     tv_truncate_ratio, mask, sigma_background if bg is not None else 0.0, bg)
+    else:   # a vote of width 0 (the baseline kernel's self votes): stage by stage
+        if bg is not None:
+            ctx.peak_background_dev(src, bg, sigma_background, ratio, mask)
+        ctx.ridge_scores_dev(src, sal, smoothed, sigma, ratio, order, mask, bg)
+        thr = ctx.threshold_fraction_dev(sal, best_fraction, mask)
+        ctx.ridge_directions_dev(smoothed, sal, dirs, sigma, order)
+        ctx.tv_dense_stick_dev(sal, dirs, tensor, sigma_tv, tv_exponent, tv_truncate_ratio, mask, mask)
+        ctx.tensor_saliency_dev(tensor, sal, order, mask, src if bg is not None else None, bg)
     if tail is not None:
         if tail.get("map", api.MAP_NONE) not in (api.MAP_NONE, api.MAP_RESCALE):
             raise ValueError("membrane_detect: the threshold maps read the input image; only MAP_RESCALE acts on the saliency")
