@@ -28,7 +28,7 @@ TV_VARIANT = [("tv_tiled.hip", "tv_tiled", ["-fno-slp-vectorize"]), ("tv_box.hip
 PAIR_FLAGS = ["-fno-slp-vectorize"]
 VARIANTS = TV_VARIANT + [("gauss_pair.hip", "gauss_pair", PAIR_FLAGS)] + [("gauss_fused.hip", "gauss_fused_h%d" % h, ["-DVH_FUSED_H=%d" % h, "-fno-slp-vectorize"])
                          for h in range(1, 9)]
-HEADERS = ["common.hpp", "exact_div.hpp", "tv_common.hpp", "select_pick.hpp", "eigen3.hpp", "union_find.hpp", "tile.hpp", "watershed_host.hpp", "intensity.hpp", "connect_host.hpp", "connect_graph.hpp", os.path.join("..", "..", "include", "visfd_hip.h")]
+HEADERS = ["common.hpp", "exact_div.hpp", "tv_common.hpp", "select_pick.hpp", "eigen3.hpp", "union_find.hpp", "tile.hpp", "watershed_host.hpp", "intensity.hpp", "connect_host.hpp", "connect_graph.hpp", "wave.hpp", os.path.join("..", "..", "include", "visfd_hip.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

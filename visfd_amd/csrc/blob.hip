@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -188,7 +189,7 @@ blob_candidates_kernel(const float* __restrict__ mid, const float* __restrict__ 
           if (cand && mask && mask[v] == 0.0f) cand = false;
           const unsigned long long bal = __ballot(cand);
           if (bal != 0ull) {   // uniform
-            if (cand) wbuf[cnt + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = (unsigned long long)v;
+            if (cand) wbuf[cnt + (unsigned)wave_rank(bal, lane)] = (unsigned long long)v;
             cnt += (unsigned)__popcll(bal);
           }
         }

@@ -24,13 +24,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
 constexpr int ROWS = BLOCK / WAVE;       // the sweeps: one wave per row, four rows per workgroup
 constexpr int CTX = 32, CTY = 8;         // resid_restrict_kernel: the coarse tile of a workgroup
 constexpr int POST_SWEEPS = 3;
@@ -88,11 +88,6 @@ __host__ __device__ inline void splat_point(const PointCell& c, const float* nrm
   }
 }
 
-__device__ inline void add_count(unsigned long long mine, unsigned long long* counter) {
-  for (int d = WAVE / 2; d > 0; d >>= 1) mine += __shfl_down(mine, d, WAVE);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(counter, mine);
-}
-
 // counters[0] += used points, counters[1] += skipped points
 __global__ void __launch_bounds__(BLOCK)
 splat_kernel(const float* __restrict__ points, const float* __restrict__ normals, i64 n, Box B, long long* __restrict__ acc,
@@ -112,8 +107,8 @@ splat_kernel(const float* __restrict__ points, const float* __restrict__ normals
       if (v) atomicAdd(reinterpret_cast<unsigned long long*>(acc + d * nodes + node), (unsigned long long)v);
     });
   }
-  add_count(used, counters);
-  add_count(skipped, counters + 1);
+  wave_count(used, counters);   // behind the grid-stride loop every lane is back
+  wave_count(skipped, counters + 1);
 }
 
 // ---- fixed-order sums ---------------------------------------------------------------------------------------------------
@@ -468,8 +463,8 @@ face_kernel(Box B, int P, const float* __restrict__ chi, double iso, unsigned lo
     lo += c < iso ? 1 : 0;
     hi += c > iso ? 1 : 0;
   }
-  add_count(lo, counters + 2);
-  add_count(hi, counters + 3);
+  wave_count(lo, counters + 2);   // behind the grid-stride loop every lane is back
+  wave_count(hi, counters + 3);
 }
 
 // mask = 1 where chi < iso (inward: chi > iso) over the image, chi_out (nullable) = chi there;
@@ -488,7 +483,7 @@ cut_kernel(Box B, int P, const float* __restrict__ chi, double iso, int inward, 
     if (chi_out) chi_out[i] = c;
     if (in && (x == 0 || y == 0 || z == 0 || x == B.nx - 1 || y == B.ny - 1 || z == B.nz - 1)) touch++;
   }
-  add_count(touch, counters + 4);
+  wave_count(touch, counters + 4);   // behind the grid-stride loop every lane is back
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------

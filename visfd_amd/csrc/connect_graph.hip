@@ -25,6 +25,7 @@
 #include "connect_graph.hpp"
 #include "connect_host.hpp"
 #include "tile.hpp"
+#include "wave.hpp"
 
 namespace vh {
 namespace cg {
@@ -249,20 +250,6 @@ seed_number_kernel(int64_t nseeds, const int* __restrict__ prov, const int* __re
   if (prov[k] >= 0) aux[seed_root[k]] = (prov[k] << 1) | seed_sign[k];
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// all lanes of the wave call this with k < 0 where they hold nothing: true when the lanes that hold something agree on k
-__device__ __forceinline__ bool wave_uniform(int k, int* common) {
-  const unsigned long long holds = __ballot(k >= 0);
-  if (!holds) { *common = -1; return true; }
-  const int first = __shfl(k, __ffsll((long long)holds) - 1);
-  *common = first;
-  return __ballot(k >= 0 && k != first) == 0;
-}
-
 // res[k] = (provisional number << 1) | sign relative to the anchor, -1 where the listed voxel stays unlabelled; per cluster
 // the voxel count and the three coordinate sums, integers (one atomic per wave where the wave's voxels share a cluster;
 // sizes null: res alone)
@@ -287,11 +274,12 @@ census_kernel(Params p, const int* __restrict__ list, int64_t count, unsigned* w
     }
   }
   if (!sizes) return;   // option connect_settle with voxel weights: the host forms the moments (the same for every thread)
+  // no lane has left: a lane past the list holds nothing (prov < 0) and adds zeros
   int common;
-  if (wave_uniform(prov, &common)) {
+  if (wave_agree(prov, &common)) {
     const unsigned long long c = wave_sum<unsigned long long>(prov >= 0 ? 1ull : 0ull);
     x = wave_sum(x); y = wave_sum(y); z = wave_sum(z);
-    if ((threadIdx.x & 63) == 0 && common >= 0) {
+    if (wave_lane() == 0 && common >= 0) {
       atomicAdd(sizes + common, c);
       atomicAdd(sums + 3 * common, x); atomicAdd(sums + 3 * common + 1, y); atomicAdd(sums + 3 * common + 2, z);
     }
@@ -327,15 +315,15 @@ outward_kernel(Params p, const float* __restrict__ V, const int* __restrict__ li
   }
   // one atomic of each kind per wave where the wave's voxels share a cluster (a lane that holds nothing adds 0, 0, false)
   int common;
-  if (wave_uniform(prov, &common)) {
-    term = wave_sum(term);
+  if (wave_agree(prov, &common)) {
+    term = wave_sum(term);   // fp64: the butterfly's order fixes the bits
     unsigned bits = __float_as_uint(bound);
     for (int o = 32; o > 0; o >>= 1) {
       const unsigned other = __shfl_xor(bits, o);
       bits = other > bits ? other : bits;
     }
     const bool some = __ballot(nonzero) != 0;
-    if ((threadIdx.x & 63) == 0 && common >= 0) {
+    if (wave_lane() == 0 && common >= 0) {
       atomicAdd(sum + common, term);
       atomicMax(B + common, bits);
       if (some) atomicOr(any + common, 1u);
@@ -368,14 +356,6 @@ write_kernel(const int* __restrict__ list, const int* __restrict__ res, int64_t 
 constexpr int LINK_BATCH = 32;   // locations per pass over a workgroup's voxels
 constexpr int LINK_ITEMS = 4;    // listed voxels per thread
 constexpr unsigned long long NO_KEY = ~0ull;
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(v, o);
-    v = other < v ? other : v;
-  }
-  return v;
-}
 
 // FindNearestVoxel over the labelled voxels, for every must-link location at once: keys[l] = min of
 // (squared distance << 31) | voxel index, so among the closest the first in scan order wins, as "strictly closer wins"
@@ -411,8 +391,8 @@ nearest_kernel(Params p, const int* __restrict__ list, const int* __restrict__ r
         const unsigned long long cand = ((unsigned long long)(dx * dx + dy * dy + dz * dz) << 31) | (unsigned long long)idx[j];
         key = cand < key ? cand : key;
       }
-      key = wave_min(key);
-      if ((threadIdx.x & 63) == 0 && key != NO_KEY) atomicMin(&best[l], key);
+      key = wave_min(key);   // the loops over l0 and l are the same for every thread; a lane without voxels holds NO_KEY
+      if (wave_lane() == 0 && key != NO_KEY) atomicMin(&best[l], key);
     }
     __syncthreads();
     if ((int)threadIdx.x < lend && best[threadIdx.x] != NO_KEY) atomicMin(keys + l0 + threadIdx.x, best[threadIdx.x]);
@@ -459,12 +439,12 @@ settle_gather_kernel(const int* __restrict__ list, const int* __restrict__ res, 
   const bool has = k < count && res[k] >= 0 && (!wanted || wanted[res[k] >> 1]);
   const unsigned long long holders = __ballot(has);
   if (!holders) return;
-  const int lane = threadIdx.x & 63, leader = __ffsll((long long)holders) - 1;
+  const int lane = wave_lane(), leader = wave_leader(holders);
   unsigned long long first = 0;
   if (lane == leader) first = atomicAdd(counter, (unsigned long long)__popcll(holders));
   first = __shfl(first, leader);
   if (!has) return;
-  const unsigned long long slot = first + (unsigned long long)__popcll(holders & ((1ull << lane) - 1ull));
+  const unsigned long long slot = first + (unsigned long long)wave_rank(holders, lane);
   if (slot >= cap) return;   // cannot happen: cap is the number of such voxels, or the length of the list
   const int64_t i = list[k];
   out_index[slot] = (int)i;

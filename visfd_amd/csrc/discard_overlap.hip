@@ -39,12 +39,12 @@
 #include <limits>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 namespace {
 
 constexpr int OV_BLOCK = 256;
-constexpr int OV_WAVE = 64;
 constexpr i64 OV_MAX_CELLS = (i64)1 << 27;   // table cells, and cells of the bucket range, beyond which the host takes the list
 constexpr unsigned OV_FLAG_NONFINITE = 1u, OV_FLAG_NEGATIVE = 2u;
 
@@ -139,23 +139,6 @@ __device__ inline bool share_dev(int ix, int iy, int iz, int Ri, int kx, int ky,
 }
 
 // ---- preparation ----------------------------------------------------------------------------------------------------------
-__device__ inline unsigned wave_min(unsigned v) {
-#pragma unroll
-  for (int d = OV_WAVE / 2; d >= 1; d >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, d, OV_WAVE);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ inline unsigned wave_max(unsigned v) {
-#pragma unroll
-  for (int d = OV_WAVE / 2; d >= 1; d >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, d, OV_WAVE);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // red: OV_RED_WORDS words, the minima preset to all ones and the rest to zero
 __global__ __launch_bounds__(OV_BLOCK) void reduce_kernel(const float* __restrict__ crds, const float* __restrict__ diam,
                                                           const float* __restrict__ score, i64 n, unsigned* __restrict__ red) {
@@ -177,7 +160,8 @@ __global__ __launch_bounds__(OV_BLOCK) void reduce_kernel(const float* __restric
       chi[a] = max(chi[a], mono_bits(c));
     }
   }
-  const bool lead = (threadIdx.x % OV_WAVE) == 0;
+  // behind the grid-stride loop every lane is back; one without a blob holds the neutral words
+  const bool lead = wave_lane() == 0;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
     const unsigned v0 = wave_min(lo[a]), v1 = wave_max(hi[a]), v2 = wave_min(clo[a]), v3 = wave_max(chi[a]);
@@ -260,8 +244,8 @@ __global__ __launch_bounds__(OV_BLOCK) void round_kernel(const float4* __restric
                                                          unsigned* state, const unsigned* __restrict__ und, unsigned n_und,
                                                          unsigned* __restrict__ und_next, unsigned long long* __restrict__ counters,
                                                          OvParams p) {
-  const i64 wave = ((i64)blockIdx.x * OV_BLOCK + threadIdx.x) / OV_WAVE;
-  const int lane = threadIdx.x % OV_WAVE;
+  const i64 wave = ((i64)blockIdx.x * OV_BLOCK + threadIdx.x) / WAVE;
+  const int lane = wave_lane();
   if (wave >= n_und) return;   // the whole wave
   const unsigned i = und[wave];
   const float4 me = rec[i];
@@ -276,7 +260,7 @@ __global__ __launch_bounds__(OV_BLOCK) void round_kernel(const float4* __restric
   const int ny = y1 - y0 + 1, nrows = (x1 < x0 || y1 < y0 || z1 < z0) ? 0 : ny * (z1 - z0 + 1);
   bool found = false, pending = false;
   unsigned n_crit = 0u, n_share = 0u;
-  for (int rbase = 0; rbase < nrows; rbase += OV_WAVE) {
+  for (int rbase = 0; rbase < nrows; rbase += WAVE) {
     const int r = rbase + lane;
     unsigned start = 0u, cnt = 0u;
     if (r < nrows) {
@@ -286,23 +270,23 @@ __global__ __launch_bounds__(OV_BLOCK) void round_kernel(const float4* __restric
     }
     unsigned incl = cnt;   // candidates of rows rbase .. r
 #pragma unroll
-    for (int d = 1; d < OV_WAVE; d <<= 1) {
-      const unsigned t = (unsigned)__shfl_up((int)incl, d, OV_WAVE);
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const unsigned t = (unsigned)__shfl_up((int)incl, d, WAVE);
       if (lane >= d) incl += t;
     }
-    const unsigned total = (unsigned)__shfl((int)incl, OV_WAVE - 1, OV_WAVE);
+    const unsigned total = (unsigned)__shfl((int)incl, WAVE - 1, WAVE);
     const unsigned excl = incl - cnt;
-    for (unsigned tb = 0u; tb < total; tb += OV_WAVE) {
+    for (unsigned tb = 0u; tb < total; tb += WAVE) {
       const unsigned t = tb + (unsigned)lane;
-      int lo = 0, hi = OV_WAVE - 1;   // the first row whose inclusive count exceeds t
+      int lo = 0, hi = WAVE - 1;   // the first row whose inclusive count exceeds t
 #pragma unroll
       for (int s = 0; s < 6; s++) {
         const int mid = (lo + hi) >> 1;
-        const unsigned v = (unsigned)__shfl((int)incl, mid, OV_WAVE);
+        const unsigned v = (unsigned)__shfl((int)incl, mid, WAVE);
         if (v > t) hi = mid; else lo = mid + 1;
       }
-      lo = min(lo, OV_WAVE - 1);
-      const unsigned s0 = (unsigned)__shfl((int)start, lo, OV_WAVE), e0 = (unsigned)__shfl((int)excl, lo, OV_WAVE);
+      lo = min(lo, WAVE - 1);
+      const unsigned s0 = (unsigned)__shfl((int)start, lo, WAVE), e0 = (unsigned)__shfl((int)excl, lo, WAVE);
       if (t < total) {
         const unsigned j = s0 + (t - e0);
         const unsigned k = bpos[j];
@@ -332,9 +316,9 @@ __global__ __launch_bounds__(OV_BLOCK) void round_kernel(const float4* __restric
   }
   const bool any_found = __any(found), any_pending = __any(pending);
 #pragma unroll
-  for (int d = OV_WAVE / 2; d >= 1; d >>= 1) {
-    n_crit += (unsigned)__shfl_xor((int)n_crit, d, OV_WAVE);
-    n_share += (unsigned)__shfl_xor((int)n_share, d, OV_WAVE);
+  for (int d = WAVE / 2; d >= 1; d >>= 1) {
+    n_crit += (unsigned)__shfl_xor((int)n_crit, d, WAVE);
+    n_share += (unsigned)__shfl_xor((int)n_share, d, WAVE);
   }
   if (lane == 0) {
     if (any_found) state[i] = (p.round << 2) | (unsigned)OVERLAP_DISCARDED;
@@ -518,7 +502,7 @@ int discard_dev(visfd_hip_ctx* ctx, float* crds, float* diam, float* score, i64 
       plan->rounds++;
       p.round = (unsigned)plan->rounds;
       VH_HIP(hipMemsetAsync(counters, 0, sizeof(unsigned long long), st));
-      const i64 waves_per_block = OV_BLOCK / OV_WAVE;
+      const i64 waves_per_block = OV_BLOCK / WAVE;
       round_kernel<<<(unsigned)((n_und + waves_per_block - 1) / waves_per_block), OV_BLOCK, 0, st>>>(
           rec, brec, bpos, offsets, state, cur, (unsigned)n_und, next, counters, p);
       VH_HIP(hipGetLastError());

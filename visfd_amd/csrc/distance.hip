@@ -35,12 +35,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
 namespace {
 
-constexpr int BLOCK = 256, WAVE = 64, WAVES = BLOCK / WAVE;
+constexpr int BLOCK = 256, WAVES = BLOCK / WAVE;
 constexpr int LDS_POINTS = 256;     // listed points a block stages at a time
 constexpr int REDUCE_POINTS = 16;   // query points of one reduction pass
 constexpr int PREFETCH = 8;         // envelope passes: loads of g in flight per column
@@ -71,7 +72,7 @@ __global__ void __launch_bounds__(BLOCK) scatter_kernel(int* __restrict__ dsq, c
 __global__ void __launch_bounds__(BLOCK)
 rows_kernel(const float* __restrict__ src, const float* __restrict__ mask, float lo, float hi, int* __restrict__ dsq,
             int flags, int nx, i64 nrows, int cap) {
-  const int lane = threadIdx.x & (WAVE - 1);
+  const int lane = wave_lane();
   const i64 nwaves = (i64)gridDim.x * WAVES;
   const int last = ((nx - 1) / WAVE) * WAVE;
   for (i64 row = (i64)blockIdx.x * WAVES + (threadIdx.x >> 6); row < nrows; row += nwaves) {
@@ -97,11 +98,11 @@ rows_kernel(const float* __restrict__ src, const float* __restrict__ mask, float
       const int dl = x < nx ? line[x] : NONE;
       const unsigned long long b = __ballot(dl == 0);
       const unsigned long long mine = b & (~0ull << lane);           // seeds at or right of this lane
-      const int right = mine ? c0 + __ffsll((long long)mine) - 1 : carry;
+      const int right = mine ? c0 + wave_leader(mine) : carry;
       int d = dl;
       if (right >= 0) d = min(d, right - x);
       if (x < nx) line[x] = d == NONE ? cap : d * d;                 // d < 2^16
-      if (b) carry = c0 + __ffsll((long long)b) - 1;
+      if (b) carry = c0 + wave_leader(b);
     }
   }
 }
@@ -149,7 +150,7 @@ template <bool FINAL, class Out>
 __device__ __forceinline__ void envelope_pass(int* __restrict__ dsq, int2* __restrict__ stack, int m, i64 step,
                                               i64 outer_stride, int nx, i64 nunits, int xchunks, int cap,
                                               const int* spts, int npts, const Out& out) {
-  const int lane = threadIdx.x & (WAVE - 1);
+  const int lane = wave_lane();
   const i64 wave = (i64)blockIdx.x * WAVES + (threadIdx.x >> 6);
   const i64 nwaves = (i64)gridDim.x * WAVES;
   int2* st = stack + wave * m * WAVE + lane;   // entry q of this column: st[q * WAVE]
@@ -311,7 +312,7 @@ reduce_points_kernel(const float* __restrict__ src, const float* __restrict__ ma
   for (int k = 0; k < REDUCE_POINTS; k++) {
     int v = (int)best[k];   // at most cap
     for (int off = WAVE / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, WAVE));
-    if (k < cnt && (threadIdx.x & (WAVE - 1)) == 0 && v < cap) atomicMin(&res[q[4 * k + 3]], v);
+    if (k < cnt && wave_lane() == 0 && v < cap) atomicMin(&res[q[4 * k + 3]], v);
   }
 }
 

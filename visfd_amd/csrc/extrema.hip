@@ -31,6 +31,7 @@
 #include "common.hpp"
 #include "tile.hpp"
 #include "union_find.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -148,11 +149,11 @@ __global__ void __launch_bounds__(256) reduce_kernel(unsigned char* flags, const
     // one add per wave where all of a wave's members share their root (the inside of a large plateau)
     const unsigned long long m = __ballot(member);
     if (m == 0) continue;
-    const int first = __ffsll((long long)m) - 1;
+    const int first = wave_leader(m);
     const int r0 = __shfl(r, first);
     const bool uniform = __ballot(member && r != r0) == 0;
     if (uniform) {
-      if ((int)(threadIdx.x & 63) == first) atomicAdd(count + r0, __popcll(m));
+      if (wave_lane() == first) atomicAdd(count + r0, __popcll(m));
     } else if (member) {
       atomicAdd(count + r, 1);
     }
@@ -165,18 +166,6 @@ __global__ void __launch_bounds__(256) reduce_kernel(unsigned char* flags, const
 __device__ __forceinline__ unsigned plateau_kind(unsigned f, int allow_borders) {   // bit 0: minimum, bit 1: maximum
   if (!allow_borders && (f & F_MISSING)) return 0u;
   return ((f & F_LOWER) ? 0u : 1u) | ((f & F_HIGHER) ? 0u : 2u);
-}
-
-// position of a hit in the list behind `counter`: one atomic per wave
-__device__ __forceinline__ unsigned long long wave_append(bool hit, unsigned long long* counter) {
-  const unsigned long long m = __ballot(hit);
-  if (m == 0) return 0;
-  const int lane = threadIdx.x & 63;
-  const int first = __ffsll((long long)m) - 1;
-  unsigned long long base = 0;
-  if (lane == first) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-  base = __shfl(base, first);
-  return base + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 // counters[0], [1]: listed minima and maxima.  out_min / out_max null: count only.

@@ -27,13 +27,13 @@
 #include <limits>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 namespace {
 
 constexpr int FS_BLOCK = 256;                    // threads of a search workgroup (four waves)
-constexpr int FS_WAVE = 64;
-constexpr int FS_WAVES = FS_BLOCK / FS_WAVE;
+constexpr int FS_WAVES = FS_BLOCK / WAVE;
 constexpr int FS_UNROLL = 8;                     // records per lane
 constexpr int FS_PASS = FS_BLOCK * FS_UNROLL;    // spheres per workgroup pass
 constexpr int FS_QB = 16;                        // queries per batch
@@ -168,14 +168,14 @@ __global__ __launch_bounds__(FS_BLOCK) void search_kernel(const int4* __restrict
   unsigned any = 0u;
 #pragma unroll
   for (int j = 0; j < FS_QB; j++) any |= best[j];
-  const int lane = threadIdx.x % FS_WAVE, wave = threadIdx.x / FS_WAVE;
-  if (__ballot(any != 0u) != 0ull) {   // the usual wave found nothing: it skips the shuffles
+  const int lane = wave_lane(), wave = threadIdx.x / WAVE;
+  if (__ballot(any != 0u) != 0ull) {   // the usual wave found nothing: it skips the shuffles (the whole wave does)
 #pragma unroll
     for (int j = 0; j < FS_QB; j++) {
       unsigned v = best[j];
 #pragma unroll
-      for (int d = FS_WAVE / 2; d >= 1; d >>= 1) {
-        const unsigned o = (unsigned)__shfl_xor((int)v, d, FS_WAVE);
+      for (int d = WAVE / 2; d >= 1; d >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)v, d, WAVE);
         v = v > o ? v : o;
       }
       if (lane == 0) s_best[wave][j] = v;

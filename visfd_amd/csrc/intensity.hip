@@ -19,6 +19,7 @@
 
 #include "common.hpp"
 #include "intensity.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -37,17 +38,6 @@ struct StatsBins {
 
 __host__ __device__ inline uint32_t key_of(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __host__ __device__ inline uint32_t bits_of(uint32_t k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v |= __shfl_xor(v, o);
-  return v;
-}
 
 // what a thread carries between values
 struct Tally {
@@ -73,11 +63,11 @@ __device__ __forceinline__ void tally(StatsBins* lds, Tally& t, float v, bool ta
   const bool pending = fin && m != 0u;
   unsigned long long todo = __ballot(pending);
   while (todo) {   // the same for every lane
-    const int leader = __ffsll((long long)todo) - 1;
+    const int leader = wave_leader(todo);
     const uint32_t e0 = __shfl(e, leader);
     const bool mine = pending && e == e0;
-    const uint32_t p = wave_add(mine && !(u >> 31) ? m : 0u);   // 64 * 2^24 fits
-    const uint32_t q = wave_add(mine && (u >> 31) ? m : 0u);
+    const uint32_t p = wave_sum(mine && !(u >> 31) ? m : 0u);   // 64 * 2^24 fits
+    const uint32_t q = wave_sum(mine && (u >> 31) ? m : 0u);
     const uint32_t o = wave_or(mine ? m : 0u);
     if (lane == 0) {
       if (p) atomicAdd(&lds->pos[e0], (unsigned long long)p);
@@ -111,7 +101,7 @@ __device__ __forceinline__ float one_voxel(const KernelArgs& a, float vin, float
 template <bool MAP, bool STATS>
 __global__ void __launch_bounds__(BLOCK) intensity_kernel(KernelArgs a, StatsBins* bins) {
   __shared__ StatsBins lds;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x, lane = wave_lane();
   if (STATS) {
     for (int b = tid; b < NBINS; b += BLOCK) {
       lds.pos[b] = 0;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -110,7 +111,8 @@ median_tiled_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst
       keys[c] = k;
     }
     const unsigned long long b = __ballot(valid);
-    if ((tid & 63) == 0 && c < cells) {   // c is a multiple of 64 here; the bit array is padded to whole pairs of words
+    // base is the same for every thread, so whole waves take every trip; TX is WAVE, so wave_lane() is the lane
+    if (wave_lane() == 0 && c < cells) {   // c is a multiple of 64 here; the bit array is padded to whole pairs of words
       vbits[c >> 5] = (uint32_t)b;
       vbits[(c >> 5) + 1] = (uint32_t)(b >> 32);
     }

@@ -25,12 +25,13 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
 namespace {
 
-constexpr int BLOCK = 256, WAVE = 64;
+constexpr int BLOCK = 256;
 constexpr int TILE_VECS = 4;   // float4 loads in flight per lane and array
 
 // slot: 0 = empty, else 2^32 | the pattern
@@ -60,7 +61,7 @@ __device__ __forceinline__ void census_fold(WaveLevels& L, unsigned bits, bool v
       L.bad = true;
       return;
     }
-    const unsigned p = (unsigned)__shfl((int)bits, __ffsll((long long)pend) - 1, WAVE);
+    const unsigned p = (unsigned)__shfl((int)bits, wave_leader(pend), WAVE);
     if (L.n == 0) L.w0 = p; else L.w1 = p;
     L.n++;
     pend = __ballot(valid && bits != L.w0 && !(L.n > 1 && bits == L.w1));
@@ -86,14 +87,14 @@ __device__ __forceinline__ void census_merge(CensusRecord* rec, unsigned bits) {
 template <bool VEC>
 __global__ void __launch_bounds__(BLOCK)
 census_kernel(const float* __restrict__ src, const float* __restrict__ mask, i64 n, CensusRecord* __restrict__ rec) {
-  const int lane = threadIdx.x & (WAVE - 1);
+  const int lane = wave_lane();
   const i64 wave = (i64)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6);
   const i64 nwaves = (i64)gridDim.x * (BLOCK / WAVE);
   WaveLevels L;
   const i64 items = VEC ? n / 4 : n;                                  // float4 or float
   const i64 ntiles = (items + WAVE * TILE_VECS - 1) / (WAVE * TILE_VECS);
   for (i64 t = wave; t < ntiles && !L.bad; t += nwaves) {
-    if (census_flagged(rec)) return;   // somebody else has seen enough
+    if (census_flagged(rec)) return;   // somebody else has seen enough (one load of one word: the whole wave leaves, or none of it)
     const i64 i0 = t * (WAVE * TILE_VECS) + lane;
     if (VEC) {
       const float4* s4 = reinterpret_cast<const float4*>(src);

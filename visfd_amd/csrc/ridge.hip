@@ -5,6 +5,7 @@
 // Device layout: multi-channel fields are channel-planar, field[c*nvox + v].
 #include "common.hpp"
 #include "eigen3.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -188,12 +189,7 @@ ridge_directions_kernel(const float* __restrict__ S, const float* __restrict__ s
     keep |= (kp ? 1u : 0u) << k;
     cnt += kp ? 1 : 0;
   }
-  int incl = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
+  const int incl = wave_scan(cnt, lane);
   if (lane == 63) wave_tot[wave] = incl;
   __syncthreads();
   int off = incl - cnt, total = 0;

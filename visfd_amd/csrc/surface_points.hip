@@ -26,29 +26,16 @@
 #include "common.hpp"
 #include "connect_graph.hpp"
 #include "connect_host.hpp"
+#include "wave.hpp"
 
 namespace vh {
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
 constexpr int PER_LANE = 8;                     // voxels per lane of the select sweep: two 16-byte loads per image
 constexpr int SCAN_BLOCK = 1024;
 constexpr i64 WALK_BATCH = 262144;              // lanes per walk launch: what the scratch is sized by
 constexpr i64 MAX_DIM = (i64)1 << 24;           // positions are floats
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-// inclusive prefix sum over the lanes of a wave
-__device__ __forceinline__ unsigned wave_scan(unsigned v, int lane) {
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const unsigned u = __shfl_up(v, o, WAVE);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
 
 __device__ __forceinline__ void load8(const float* __restrict__ p, i64 base, float v[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p + base);
@@ -82,7 +69,7 @@ select_kernel(const float* __restrict__ C, const float* __restrict__ M, i64 n, f
   }
   bits[g] = (unsigned char)b;   // the array has a byte for every launched lane
   const unsigned s = wave_sum((unsigned)__popc(b));
-  if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = s;
+  if (wave_lane() == 0) wsum[threadIdx.x / WAVE] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned t = 0;
@@ -96,7 +83,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK)
 scan_kernel(const unsigned* __restrict__ chunk_count, i64 nchunks, unsigned long long* __restrict__ chunk_off,
             unsigned long long* __restrict__ total) {
   __shared__ unsigned wtot[SCAN_BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const int lane = wave_lane(), wave = threadIdx.x / WAVE;
   unsigned long long carry = 0;
   for (i64 t0 = 0; t0 < nchunks; t0 += SCAN_BLOCK) {
     const i64 b = t0 + threadIdx.x;
@@ -121,7 +108,7 @@ __global__ void __launch_bounds__(BLOCK)
 list_kernel(const unsigned char* __restrict__ bits, const unsigned long long* __restrict__ chunk_off, i64 count,
             i64* __restrict__ list) {
   __shared__ unsigned wtot[BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const int lane = wave_lane(), wave = threadIdx.x / WAVE;
   const i64 g = (i64)blockIdx.x * BLOCK + threadIdx.x;
   unsigned b = bits[g];
   const unsigned v = (unsigned)__popc(b);
@@ -315,13 +302,14 @@ walk_kernel(Volumes v, const i64* __restrict__ list, i64 first, i64 count, float
       nrm[3 * k + d] = normal[d];
     }
   }
+  // the walks sit inside `if (lane_id < count)`: every lane arrives here, one without a walk with zeros
   for (int o = WAVE / 2; o > 0; o >>= 1) {
     const unsigned u = __shfl_xor(longest, o, WAVE);
     longest = u > longest ? u : longest;
   }
   taken = wave_sum(taken);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && longest > 0) atomicMax(&stats[1], longest);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && taken > 0) atomicAdd(steps, (unsigned long long)taken);
+  if (wave_lane() == 0 && longest > 0) atomicMax(&stats[1], longest);
+  if (wave_lane() == 0 && taken > 0) atomicAdd(steps, (unsigned long long)taken);
 }
 
 // rec[9k..]: the Hessian (xx, yy, zz, xy, yz, xz; visfd_utils.hpp:528-616) and the gradient (:631-669) of the saliency at

@@ -23,13 +23,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
 constexpr int QBITS = 10;             // 1024 units per voxel
 constexpr int QMAX = 1 << 29;         // |q| <= 2^29
 constexpr int TILE = 8;               // a tile is TILE x TILE rows: one lane each
@@ -131,6 +131,7 @@ __device__ inline bool scatter_row(const Tri& T, int iy, int iz, int nx, int ny,
   return true;
 }
 
+// the scatter kernels' count: __shfl_down measured a microsecond faster there than wave_count (profiles/wave_refactor_time.txt)
 __device__ inline void add_count(unsigned long long mine, unsigned long long* counter) {
   for (int d = WAVE / 2; d > 0; d >>= 1) mine += __shfl_down(mine, d, WAVE);
   if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(counter, mine);
@@ -151,7 +152,7 @@ scatter_small_kernel(const int* __restrict__ q, const int* __restrict__ tri, i64
     for (int iz = r.z0; iz <= r.z1; iz++)
       for (int iy = r.y0; iy <= r.y1; iy++) mine += scatter_row(T, iy, iz, nx, ny, W, bisect, toggle) ? 1 : 0;
   }
-  add_count(mine, crossings);
+  add_count(mine, crossings);   // behind the grid-stride loop every lane is back
 }
 
 // the tiled triangle that owns item i: the first k with item_end[k] > i
@@ -197,7 +198,7 @@ scatter_tiled_kernel(const int* __restrict__ q, const int* __restrict__ tri, con
       if (iy <= r.y1 && iz <= r.z1) mine += scatter_row(T, iy, iz, nx, ny, W, bisect, toggle) ? 1 : 0;
     }
   }
-  add_count(mine, crossings);
+  add_count(mine, crossings);   // a wave without items skips the `if` above and arrives with zeros
 }
 
 // One wave per row.  VEC: nx is a multiple of 4 and dst is 16-byte aligned, so a lane stores four voxels at once.
@@ -206,7 +207,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(BLOCK)
 fill_kernel(const unsigned* __restrict__ toggle, float* __restrict__ dst, int nx, i64 nrows, int W,
             unsigned long long* __restrict__ counters) {
-  const int lane = threadIdx.x & (WAVE - 1);
+  const int lane = wave_lane();
   const i64 wave = ((i64)blockIdx.x * BLOCK + threadIdx.x) / WAVE;
   const i64 nwaves = (i64)gridDim.x * (BLOCK / WAVE);
   unsigned long long inside = 0, odd = 0;
@@ -223,11 +224,8 @@ fill_kernel(const unsigned* __restrict__ toggle, float* __restrict__ dst, int nx
       x ^= x << 8;
       x ^= x << 16;
       const unsigned own = x >> 31;   // the parity of this lane's word
-      unsigned scan = own;            // becomes the parity of the words of lanes 0..lane
-      for (int d = 1; d < WAVE; d <<= 1) {
-        const unsigned o = __shfl_up(scan, d, WAVE);
-        if (lane >= d) scan ^= o;
-      }
+      // the parity of the words of lanes 0..lane
+      const unsigned scan = wave_scan(own, lane, [](unsigned a, unsigned b) { return a ^ b; });
       x ^= ((scan ^ own) ? ~0u : 0u) ^ carry;
       carry ^= __shfl(scan, WAVE - 1, WAVE) ? ~0u : 0u;
       // x: bit b says whether sample 32 wi + b is inside
@@ -260,8 +258,8 @@ fill_kernel(const unsigned* __restrict__ toggle, float* __restrict__ dst, int nx
       }
     }
   }
-  add_count(odd, counters + 1);
-  add_count(inside, counters + 2);
+  wave_count(odd, counters + 1);   // rows and word chunks are the wave's: every lane has left the loops
+  wave_count(inside, counters + 2);
 }
 
 // ---- host: quantisation, the edge census, the plan -------------------------------------------------------------------

@@ -43,6 +43,7 @@
 #include "tile.hpp"
 #include "union_find.hpp"
 #include "watershed_host.hpp"
+#include "wave.hpp"
 
 namespace vh {
 
@@ -91,7 +92,7 @@ __device__ __forceinline__ float s_of(const float* src, i64 i, unsigned flip) { 
 // one store per wave in which `hit` holds anywhere
 __device__ __forceinline__ void raise(bool hit, unsigned* flag) {
   const unsigned long long m = __ballot(hit);
-  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicOr(flag, 1u);
+  if (m && wave_lane() == wave_leader(m)) atomicOr(flag, 1u);
 }
 
 template <int C>
