@@ -93,7 +93,9 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
                                      * mask: visfd_hip_close_surface[_dev], visfd_hip_close_surface_splat[_dev|_host],
                                      * visfd_hip_close_surface_last and _last_times; then the membrane stage on the
                                      * caller's arrays, visfd_hip_membrane_stage_dev, with the option membrane_queue and
-                                     * the test aids visfd_hip_debug_ridge_directions_thr_dev and _debug_tv_lists_dev) */
+                                     * the test aids visfd_hip_debug_ridge_directions_thr_dev and _debug_tv_lists_dev;
+                                     * then the isosurface mesh: visfd_hip_isosurface[_dev|_host], visfd_hip_isosurface_last
+                                     * and _last_times) */
 /* Tuning and test switches of a context (integers; unknown names are VISFD_HIP_EINVAL).  A new context starts from the
  * environment (VISFD_HIP_<NAME>, read once in visfd_hip_create); nothing reads the environment afterwards.
  *   gauss_3pass      1: the separable filter always takes its three single-axis passes
@@ -174,6 +176,8 @@ int visfd_hip_abi_version(void);   /* 10: entry points only get added between ve
  *                    visfd_hip_close_surface_last reports the stop); default 20, twice the
  *                    most cycles the test cases take at the default rtol
  *   close_surface_time  1: those two entries time their three phases with events (visfd_hip_close_surface_last_times);
+ *                    default 0
+ *   isosurface_time  1: visfd_hip_isosurface[_dev] time their four phases with events (visfd_hip_isosurface_last_times);
  *                    default 0
  *   gauss_cfg, debug development aids */
 int visfd_hip_set_option(visfd_hip_ctx* ctx, const char* name, int64_t value);
@@ -1470,6 +1474,60 @@ int visfd_hip_close_surface_last(visfd_hip_ctx*, int64_t stats[6], double values
 /* option close_surface_time: milliseconds of the last call's splat with the right-hand side, its solve, and its level
  * and cut */
 int visfd_hip_close_surface_last_times(visfd_hip_ctx*, float ms[3]);
+
+/* ---- the closed triangle mesh of a level set -------------------------------------------------------------
+ * No counterpart in the reference, whose Example 3 takes its mesh from an external reconstruction program.  The mesh is
+ * defined to the bit, by marching tetrahedra on the Kuhn split of every grid cell.
+ *
+ * Inputs.  vol: float32 [nz][ny][nx], every dimension >= 1; iso: a double; side: VISFD_HIP_ISO_BELOW (a node is inside iff
+ * (double)v < iso) or VISFD_HIP_ISO_ABOVE (inside iff (double)v > iso).  A NaN node is never inside.
+ *
+ * Grid.  The image nodes are surrounded by one layer of border nodes (coordinates -1 and n_d), which are always outside:
+ * that caps every solid the image border cuts.  Cells have lower corners from -1 to n_d - 1 on each axis.  A cell is split
+ * into the 6 tetrahedra 0, e_a, e_a + e_b, e_a + e_b + e_c for the permutations (a, b, c) of the axes in lexicographic
+ * order xyz, xzy, yxz, yzx, zxy, zyx: that order is the tet index 0..5 and the corner order within a tet.  Every tet edge
+ * runs from a node to the node at + dir; the 7 directions, in this order the edge class 0..6, are (1,0,0) (0,1,0) (0,0,1)
+ * (1,1,0) (0,1,1) (1,0,1) (1,1,1).
+ *
+ * Vertices.  One per edge whose two ends differ in insideness.  a: the lower end, b = a + dir.  With both ends image nodes,
+ * in double: t = (iso - (double)v_a) / ((double)v_b - (double)v_a); a non-finite t becomes 0.5; t is clamped to
+ * [1/64, 63/64].  With a border node at one end t = 0.5.  Coordinate d is (float)((double)a_d + t) where dir_d = 1 and
+ * (float)a_d elsewhere; no fused multiply-add changes these.  The clamp keeps a vertex quantised to 1/1024 voxel (the
+ * voxeliser above) off the nodes.  Vertices are in voxel coordinates, listed in ascending order of key(a) * 7 + class,
+ * key(a) = ((a_z + 1)(ny + 1) + (a_y + 1))(nx + 1) + (a_x + 1).
+ *
+ * Triangles.  Per tet, I and O: its inside and outside corners in tet corner order; e(i, o): the vertex on that edge.
+ * |I| = 1: the polygon [e(I0, o) for o in O]; |I| = 3: [e(i, O0) for i in I]; |I| = 2: [e(I0,O0), e(I0,O1), e(I1,O1),
+ * e(I1,O0)].  With the vertices at the edge midpoints, if (P1 - P0) x (P2 - P0) points from the mean of the outside corners
+ * towards the mean of the inside corners, the whole list is reversed: normals point out of the solid.  (P0, P1, P2) is
+ * emitted, and for a quad (P0, P2, P3) too.  Triangles are listed in order of (cell key, tet index, first / second);
+ * indices are int32.  The mesh is closed and edge-manifold by construction.
+ *
+ * Outputs: vertices float[vertices_cap][3] (x, y, z), triangles int32[triangles_cap][3]; *n_vertices and *n_triangles are
+ * always set.  A null array is not written (both null: the count query).  An array whose capacity is below its count is left
+ * exactly as it was and the call returns VISFD_HIP_ECAPACITY; the other array is still written.
+ * VISFD_HIP_EINVAL, nothing written: a null context, volume or count pointer, a dimension < 1 (or >= 2^31 - 2), an unknown
+ * side, a non-finite iso, a negative capacity, more than 2^31 - 1 vertices; on the device face outputs that overlap the
+ * volume or each other.  vol and the arrays are host memory in the first form, device memory in the _dev form; both return
+ * with the stream idle.  Two calls write the same bytes. */
+#define VISFD_HIP_ISO_BELOW 0
+#define VISFD_HIP_ISO_ABOVE 1
+int visfd_hip_isosurface(visfd_hip_ctx*, const float* vol, int64_t nx, int64_t ny, int64_t nz, double iso, int side,
+                         float* vertices, int64_t vertices_cap, int32_t* triangles, int64_t triangles_cap, int64_t* n_vertices,
+                         int64_t* n_triangles);
+int visfd_hip_isosurface_dev(visfd_hip_ctx*, const float* vol, int64_t nx, int64_t ny, int64_t nz, double iso, int side,
+                             float* vertices, int64_t vertices_cap, int32_t* triangles, int64_t triangles_cap,
+                             int64_t* n_vertices, int64_t* n_triangles);
+/* The same mesh by a serial walk on the host: no context, no device. */
+int visfd_hip_isosurface_host(const float* vol, int64_t nx, int64_t ny, int64_t nz, double iso, int side, float* vertices,
+                              int64_t vertices_cap, int32_t* triangles, int64_t triangles_cap, int64_t* n_vertices,
+                              int64_t* n_triangles);
+/* The last visfd_hip_isosurface[_dev] of the context: vertices, triangles, inside nodes, 1 if an inside node lies on a face
+ * of the image (the border layer capped the solid there) else 0; -1 each before the first call. */
+int visfd_hip_isosurface_last(visfd_hip_ctx*, int64_t stats[4]);
+/* option isosurface_time: milliseconds of the last call's classification, its scan with the host's read of the totals, its
+ * vertex pass and its triangle pass (-1: the phase did not run) */
+int visfd_hip_isosurface_last_times(visfd_hip_ctx*, float ms[4]);
 
 #ifdef __cplusplus
 }

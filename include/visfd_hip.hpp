@@ -24,6 +24,8 @@
 //   VoxelizeMesh  what bin/voxelize_mesh/voxelize_mesh.py computes with vtk (no C++ counterpart in the reference)
 //   CloseSurface  an oriented point cloud closed into a mask on the grid (no counterpart in the reference, whose workflow
 //                 leaves this step to an external surface reconstruction program; visfd_hip.h states the definition)
+//   IsoSurface    the closed triangle mesh of a level set by marching tetrahedra (no counterpart in the reference, whose
+//                 workflow takes its mesh from that external program; visfd_hip.h states the definition)
 // Only Scalar = float is provided (the hot path and the CLI use float throughout).
 #ifndef VISFD_HIP_HPP
 #define VISFD_HIP_HPP
@@ -1100,6 +1102,31 @@ inline void CloseSurface(visfd_hip_ctx* ctx, int const image_size[3], const std:
                                             m.empty() ? nullptr : m.data(), (int64_t)points.size(), image_size[0], image_size[1],
                                             image_size[2], pad, orientation, hip_detail::flat(aaafDest),
                                             aaafChi ? hip_detail::flat(aaafChi) : nullptr));
+}
+
+// ---- the closed triangle mesh of a level set (visfd_hip.h states the definition) -------------------------
+// The surface of {aaafSource < iso} (side VISFD_HIP_ISO_BELOW) or {aaafSource > iso} (_ABOVE) as vertices (x, y, z in voxel
+// coordinates) and triangles with outward normals; closed also where the image border cuts the solid.  A null ctx is the
+// shim's own.  Returns the number of triangles.
+inline size_t IsoSurface(visfd_hip_ctx* ctx, int const image_size[3], float const* const* const* aaafSource, double iso, int side,
+                         std::vector<std::array<float, 3> >& vertices, std::vector<std::array<int, 3> >& triangles) {
+  hip_detail::require_contiguous(aaafSource, image_size);
+  visfd_hip_ctx* c = ctx ? ctx : hip_detail::context();
+  const float* src = hip_detail::flat(aaafSource);
+  int64_t nv = 0, nt = 0;
+  hip_detail::check(visfd_hip_isosurface(c, src, image_size[0], image_size[1], image_size[2], iso, side, nullptr, 0, nullptr, 0,
+                                         &nv, &nt));
+  std::vector<float> v(3 * (size_t)nv + 3);
+  std::vector<int32_t> t(3 * (size_t)nt + 3);
+  hip_detail::check(visfd_hip_isosurface(c, src, image_size[0], image_size[1], image_size[2], iso, side, v.data(), nv, t.data(),
+                                         nt, &nv, &nt));
+  vertices.resize((size_t)nv);
+  triangles.resize((size_t)nt);
+  for (size_t i = 0; i < (size_t)nv; i++)
+    for (int d = 0; d < 3; d++) vertices[i][d] = v[3 * i + d];
+  for (size_t i = 0; i < (size_t)nt; i++)
+    for (int d = 0; d < 3; d++) triangles[i][d] = (int)t[3 * i + d];
+  return (size_t)nt;
 }
 
 // ---- blob list post-processing: lib/visfd/visfd_utils.hpp:49-55,95-118; feature.hpp:519-616,720-969 ------

@@ -120,6 +120,8 @@ _VOXELIZE = [_vp, _vp, _i64, _vp, _i64, C.c_double, C.POINTER(C.c_double), _i64,
 _CLOSE = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp]
 # ctx, points, normals, n, nx, ny, nz, pad, acc, counts
 _CLOSE_SPLAT = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, C.POINTER(_i64)]
+# (after the context:) vol, nx, ny, nz, iso, side, vertices, vertices_cap, triangles, triangles_cap, n_vertices, n_triangles
+_ISOSURFACE = [_vp, _i64, _i64, _i64, C.c_double, C.c_int, _vp, _i64, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]
 
 _SIGS = {
     "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
@@ -326,6 +328,12 @@ _SIGS = {
     "visfd_hip_close_surface_splat_host": (C.c_int, _CLOSE_SPLAT[1:]),
     "visfd_hip_close_surface_last": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "visfd_hip_close_surface_last_times": (C.c_int, [_vp, _fp]),
+    # the isosurface mesh (csrc/isosurface.hip)
+    "visfd_hip_isosurface": (C.c_int, [_vp] + _ISOSURFACE),
+    "visfd_hip_isosurface_dev": (C.c_int, [_vp] + _ISOSURFACE),
+    "visfd_hip_isosurface_host": (C.c_int, _ISOSURFACE),
+    "visfd_hip_isosurface_last": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "visfd_hip_isosurface_last_times": (C.c_int, [_vp, _fp]),
     # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
     "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -1015,6 +1023,70 @@ def close_surface_splat_host(points, normals, shape, pad=0):
     return acc, int(counts[0]), int(counts[1])
 
 
+ISO_BELOW, ISO_ABOVE = 0, 1   # VISFD_HIP_ISO_*
+_ISO_NAMES = {"below": ISO_BELOW, "above": ISO_ABOVE}
+
+
+def _iso_side(side):
+    if isinstance(side, str):
+        if side not in _ISO_NAMES:
+            raise ValueError("side must be below or above")
+        return _ISO_NAMES[side]
+    return int(side)
+
+
+def _isosurface(call, L, iso, side, alloc, vertices, triangles, count_only=False):
+    """One isosurface entry behind call(iso, side, vertices pointer, cap, triangles pointer, cap, nv, nt).  Without arrays:
+    the count query, then a call into arrays from alloc(rows, kind) -> (array, pointer), -> (vertices, triangles).  With
+    vertices and / or triangles ((array, pointer, rows), or None): one call into them -> (n_vertices, n_triangles); an error
+    carries the counts as `counts` when the call got as far as setting them.  count_only: the count query alone."""
+    nv, nt = _i64(-1), _i64(-1)
+    iso, side = float(iso), _iso_side(side)
+
+    def once(v, t):
+        rc = call(iso, side, v[1] if v else None, v[2] if v else 0, t[1] if t else None, t[2] if t else 0, C.byref(nv),
+                  C.byref(nt))
+        if rc:
+            err = VisfdHipError(rc, L.visfd_hip_last_error().decode())
+            err.counts = (int(nv.value), int(nt.value)) if nv.value >= 0 else None
+            raise err
+        return int(nv.value), int(nt.value)
+
+    if count_only or vertices is not None or triangles is not None:
+        return once(vertices, triangles)
+    n, m = once(None, None)
+    v, vp = alloc(n, "vertices")
+    t, tp = alloc(m, "triangles")
+    once((v, vp, n), (t, tp, m))
+    return v, t
+
+
+def _iso_host_array(a, dtype, what):
+    assert isinstance(a, np.ndarray) and a.dtype == dtype and a.flags["C_CONTIGUOUS"] and a.ndim == 2 and a.shape[1] == 3, \
+        what + " must be a C-contiguous (n, 3) array of " + np.dtype(dtype).name
+    return a, a.ctypes.data, len(a)
+
+
+def _iso_host_alloc(rows, kind):
+    a = np.empty((rows, 3), np.float32 if kind == "vertices" else np.int32)
+    return a, a.ctypes.data
+
+
+def isosurface_host(vol, iso, side="below", vertices=None, triangles=None, count_only=False):
+    """The closed triangle mesh of {vol < iso} (side "below") or {vol > iso} ("above") by marching tetrahedra, as
+    include/visfd_hip.h defines it to the bit, by a serial walk on the host: no context, no device.  vol float32
+    [nz, ny, nx] -> (vertices float32 (n, 3) x y z in voxel coordinates, triangles int32 (m, 3)).  With `vertices` and / or
+    `triangles` (arrays to write into): one call -> (n_vertices, n_triangles); an array that is too small stays as it was
+    and the call raises VisfdHipError 4, whose `counts` holds the two numbers.  count_only: -> (n_vertices, n_triangles)
+    without writing anything."""
+    L = load_library()
+    vol = np.ascontiguousarray(vol, np.float32)
+    nz, ny, nx = vol.shape if vol.ndim == 3 else (0, 0, 0)
+    return _isosurface(lambda *tail: L.visfd_hip_isosurface_host(vol.ctypes.data, nx, ny, nz, *tail), L, iso, side,
+                       _iso_host_alloc, None if vertices is None else _iso_host_array(vertices, np.float32, "vertices"),
+                       None if triangles is None else _iso_host_array(triangles, np.int32, "triangles"), count_only)
+
+
 def find_spheres_host(crds, sphere_crds, sphere_diameters):
     """FindSpheres (visfd_utils.hpp:271-359) by the host walk: for every point 1 + the index of the LAST sphere that holds
     it, 0 when none does -> int64 array."""
@@ -1337,6 +1409,31 @@ class Context:
         close_surface_time."""
         ms = (C.c_float * 3)()
         self._chk(self._L.visfd_hip_close_surface_last_times(self._h, ms))
+        return tuple(ms)
+
+    def isosurface(self, vol, iso, side="below", vertices=None, triangles=None, count_only=False):
+        """isosurface_host's mesh, bit for bit, by the kernels of csrc/isosurface.hip: vol float32 [nz, ny, nx] on the host
+        -> (vertices float32 (n, 3), triangles int32 (m, 3)); with arrays to write into -> (n_vertices, n_triangles), as
+        isosurface_host."""
+        vol = np.ascontiguousarray(vol, np.float32)
+        nz, ny, nx = vol.shape if vol.ndim == 3 else (0, 0, 0)
+        return _isosurface(lambda *tail: self._L.visfd_hip_isosurface(self._h, vol.ctypes.data, nx, ny, nz, *tail), self._L,
+                           iso, side, _iso_host_alloc,
+                           None if vertices is None else _iso_host_array(vertices, np.float32, "vertices"),
+                           None if triangles is None else _iso_host_array(triangles, np.int32, "triangles"), count_only)
+
+    def isosurface_last(self):
+        """The last isosurface[_dev]: dict with n_vertices, n_triangles, n_inside (inside nodes) and capped (1 when the
+        image border cut the solid and the border layer closed it there)."""
+        s = (_i64 * 4)()
+        self._chk(self._L.visfd_hip_isosurface_last(self._h, s))
+        return {"n_vertices": int(s[0]), "n_triangles": int(s[1]), "n_inside": int(s[2]), "capped": int(s[3])}
+
+    def isosurface_last_times(self):
+        """(classify, scan and the host's read of the totals, vertices, triangles) milliseconds of the last isosurface[_dev]
+        under the option isosurface_time; -1 for a phase that did not run."""
+        ms = (C.c_float * 4)()
+        self._chk(self._L.visfd_hip_isosurface_last_times(self._h, ms))
         return tuple(ms)
 
     def voxelize_last(self):
@@ -2062,6 +2159,26 @@ class Context:
         self._chk(self._L.visfd_hip_close_surface_splat_dev(self._h, _dev(points) if n else None, _dev(normals) if n else None,
                                                             n, nx, ny, nz, int(pad), acc.data_ptr(), counts))
         return int(counts[0]), int(counts[1])
+
+    def isosurface_dev(self, vol, iso, side="below", vertices=None, triangles=None, count_only=False):
+        """isosurface on device tensors: vol float32 [nz, ny, nx] -> (vertices float32 (n, 3), triangles int32 (m, 3)) as new
+        tensors on vol's device; with tensors to write into -> (n_vertices, n_triangles), as isosurface_host.  Returns with
+        the stream idle."""
+        import torch
+        nz, ny, nx = vol.shape
+
+        def given(t, dtype, what):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3, \
+                what + " must be a contiguous cuda (n, 3) tensor of " + str(dtype)
+            return t, t.data_ptr(), int(t.shape[0])
+
+        def alloc(rows, kind):
+            t = torch.empty((rows, 3), dtype=torch.float32 if kind == "vertices" else torch.int32, device=vol.device)
+            return t, t.data_ptr()
+
+        return _isosurface(lambda *tail: self._L.visfd_hip_isosurface_dev(self._h, _dev(vol), nx, ny, nz, *tail), self._L,
+                           iso, side, alloc, None if vertices is None else given(vertices, torch.float32, "vertices"),
+                           None if triangles is None else given(triangles, torch.int32, "triangles"), count_only)
 
     def draw_last_times(self):
         """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""

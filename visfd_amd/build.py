@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(ROOT, "build", "visfd_hip")
 LIB = os.path.join(HERE, "libvisfd_hip.so")
 
-SOURCES = ["host_math.cpp", "blob_post.cpp", "connect.cpp", "watershed_host.cpp", "context.hip", "api.hip", "blob_job.hip", "gauss.hip", "blob.hip", "select.hip", "tv.hip", "resample.hip", "slab.hip", "morph.hip", "morph_levels.hip", "extrema.hip", "filter3d.hip", "draw.hip", "watershed.hip", "median.hip", "intensity.hip", "distance.hip", "find_spheres.hip", "discard_overlap.hip", "connect_seeds.hip", "connect_graph_host.cpp", "connect_graph.hip", "voxelize.hip", "surface_points.hip", "close_surface.hip"]
+SOURCES = ["host_math.cpp", "blob_post.cpp", "connect.cpp", "watershed_host.cpp", "context.hip", "api.hip", "blob_job.hip", "gauss.hip", "blob.hip", "select.hip", "tv.hip", "resample.hip", "slab.hip", "morph.hip", "morph_levels.hip", "extrema.hip", "filter3d.hip", "draw.hip", "watershed.hip", "median.hip", "intensity.hip", "distance.hip", "find_spheres.hip", "discard_overlap.hip", "connect_seeds.hip", "connect_graph_host.cpp", "connect_graph.hip", "voxelize.hip", "surface_points.hip", "close_surface.hip", "isosurface.hip"]
 # (source, object stem, extra flags): the fused Gaussian is compiled once per window half-width
 # the vote loop is faster without the SLP vectoriser's packed-f32 shuffles (profiles/r01 notes)
 TV_VARIANT = [("tv_tiled.hip", "tv_tiled", ["-fno-slp-vectorize"]), ("tv_box.hip", "tv_box", ["-fno-slp-vectorize"]),

@@ -101,6 +101,11 @@ enum Slot {
   WS_CS_ACC,                       // close_surface (csrc/close_surface.hip): the three int64 volumes of the splat over the padded box
   WS_CS_GRID,                      // ... per multigrid level the two iterates and the right-hand side (rows padded to a multiple of 4 floats)
   WS_CS_AUX,                       // ... the workgroups' partial sums (double), the three totals, the counters
+  WS_ISO_TAB,                      // isosurface (csrc/isosurface.hip): the polygon tables of the 6 tets (their slot key: a version string)
+  WS_ISO_CODE,                     // ... one byte per lower node: the insideness of its cell's 8 corners
+  WS_ISO_CHUNKS,                   // ... per workgroup chunk its offsets (2 x uint64) and its counts (4 x uint32), then the 4 totals
+  WS_ISO_FIRST,                    // ... every lower node's first vertex id (int32)
+  WS_ISO_OUT,                      // ... the host-pointer face's vertices and triangles
   WS_SELECT,                       // radix select with the digit picked on the device: its state block (SelectState), and behind it the words
                                    // the queued membrane stage reads back with it (StageReadback) -- theirs alone, no pending scan owns any
   WS_NSLOTS
@@ -161,6 +166,7 @@ struct visfd_hip_options {
   int close_surface_rtol_exp = 5;   // close_surface stops its cycles when |b - Laplace(chi)| <= 10^-k |b| (profiles/close_surface_time.txt)
   int close_surface_max_cycles = 20;   // ... or after this many cycles: the mask is still returned, visfd_hip_close_surface_last says which
   int close_surface_time = 0;   // 1: close_surface times its splat, solve and cut with events (visfd_hip_close_surface_last_times; tools/close_surface_time.py)
+  int isosurface_time = 0;   // 1: visfd_hip_isosurface[_dev] time their four phases with events (visfd_hip_isosurface_last_times; tools/isosurface_time.py)
   int debug = 0;
 };
 
@@ -195,6 +201,8 @@ struct visfd_hip_ctx {
   int64_t close_surface_last[6] = {-1, -1, -1, -1, -1, -1};   // the last close_surface: used and skipped points, cycles, stop reason, orientation taken, mask on a face
   double close_surface_values[2] = {0.0, 0.0};   // ... its final residual ratio and its level iso
   float close_surface_ms[3] = {-1.0f, -1.0f, -1.0f};   // option close_surface_time: splat and right-hand side, solve, level and cut
+  int64_t isosurface_last[4] = {-1, -1, -1, -1};   // the last visfd_hip_isosurface[_dev]: vertices, triangles, inside nodes, 1 if the image border cut the solid
+  float isosurface_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f};   // option isosurface_time: classify, scan and the host's read of the totals, vertices, triangles
   int64_t wsh_stats[4] = {-1, -1, -1, -1};   // the last watershed call: path, label rounds, boundary rounds, basins
   int64_t connect_seeds[2] = {-1, -1};       // the last visfd_hip_label_connected_device_seeds: where the seeds were searched, how many (csrc/connect_seeds.hip)
   int64_t connect_graph[4] = {-1, 0, -1, -1};   // the last visfd_hip_label_connected_graph[_dev]: path, reasons, valid voxels, candidates of the host's vector test

@@ -77,7 +77,7 @@ const OptionDesc kOptions[] = {   // every field of visfd_hip_options (common.hp
     VH_OPT(discard_overlap_max_rounds), VH_OPT(find_spheres_host), VH_OPT(watershed_host), VH_OPT(stats_blocks),
     VH_OPT(connect_time), VH_OPT(connect_settle), VH_OPT(draw_time), VH_OPT(voxelize_bisect), VH_OPT(voxelize_time),
     VH_OPT(surface_steps_cap), VH_OPT(surface_points_time), VH_OPT(close_surface_rtol_exp),
-    VH_OPT(close_surface_max_cycles), VH_OPT(close_surface_time), VH_OPT(debug),
+    VH_OPT(close_surface_max_cycles), VH_OPT(close_surface_time), VH_OPT(isosurface_time), VH_OPT(debug),
 };
 #undef VH_OPT
 bool set_option(visfd_hip_options* o, const char* name, int64_t value) {

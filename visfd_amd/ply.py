@@ -230,5 +230,10 @@ def write_ply(path, vertices, faces, fmt="binary_little_endian", extra=(), index
             rec[n] = np.asarray(a)
         f.write(rec.tobytes())
         cd, idt = np.dtype(order + _TYPES[count_type]), np.dtype(order + _TYPES[index_type])
+        if isinstance(faces, np.ndarray) and faces.ndim == 2:   # an (m, k) array: the same bytes in one piece
+            rows = np.zeros(len(faces), np.dtype([("n", cd), ("i", idt, (faces.shape[1],))]))
+            rows["n"], rows["i"] = faces.shape[1], faces
+            f.write(rows.tobytes())
+            return
         for p in faces:
             f.write(np.asarray([len(p)], cd).tobytes() + np.asarray(p, idt).tobytes())
