@@ -1295,7 +1295,8 @@ typedef struct visfd_hip_slab visfd_hip_slab;
 /* A transport other than RCCL (tests; MPI hosts).  Pointers are DEVICE pointers; work must be ordered on `stream`
  * (a hipStream_t) or complete on return.  Every callback returns 0 on success. */
 typedef struct visfd_hip_transport {
-  /* send `bytes` from sendbuf to rank `peer` and receive as many from it into recvbuf (a paired exchange) */
+  /* send `bytes` from sendbuf to rank `peer` and receive as many from it into recvbuf (a paired exchange); `peer` is a
+   * Z-neighbour, or the rank itself when visfd_hip_slab_selftest calls */
   int (*sendrecv)(void* user, int peer, const void* sendbuf, void* recvbuf, size_t bytes, void* stream);
   /* sum `count` uint64 counters over all ranks, in place */
   int (*allreduce_sum_u64)(void* user, uint64_t* buf, size_t count, void* stream);

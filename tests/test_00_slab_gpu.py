@@ -52,7 +52,11 @@ def test_slab_case_matrix_on_gpu(world):
                   visfd_hip_blob_dog_slab;
       plateau     a constant block across ranks with the fraction's cut inside its run of equal scores;
       tolerance   bench.py's tolerance options: threshold bit-equal, tensors within 1e-5 of the field scale;
-      refusals    windows deeper than the ghost zone refused on every rank, then the same handle runs a valid stage."""
+      refusals    windows deeper than the ghost zone refused on every rank, then the same handle runs a valid stage;
+      no-voxel    best_fraction 1.0 refused on every rank (code 1, "selects no voxel") after the select's three summed rounds,
+                  then the same handle runs a valid stage.
+    The first handle also runs the transport's self-test on every rank (the halos' exchange routine with the rank as its own
+    peer, the sum of the select's counters)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tools", "slab_check.py"), "--matrix"]

@@ -4,7 +4,8 @@ Launch with one process per rank:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
         --master-port 29533 tools/slab_check.py [--matrix]
 --matrix runs the case list of matrix() instead (uneven splits, tight and wide ghosts, thin slabs, the peak-height
-background, the host-memory faces, a plateau at the threshold, tolerance mode, refusals) and prints "SLAB-OK world=N
+background, the host-memory faces, a plateau at the threshold, tolerance mode, refusals, a fraction that selects no
+voxel; the transport's self-test on the first handle) and prints "SLAB-OK world=N
 cases=..." when every case passed.
 With at least as many GPUs as ranks every rank takes its own GPU and halos travel over RCCL
 ("nccl"); on a one-GPU box the ranks share cuda:0 and halos are staged through gloo.  Every rank
@@ -158,7 +159,7 @@ def _cases(world):
     """(name, nz, ghost, options): every case gets a fresh slab handle; ghosts start as NaN."""
     uneven = {2: 47, 3: 50, 4: 47}[world]
     return [
-        ("uneven", dict(nz=uneven, ghost=9)),
+        ("uneven", dict(nz=uneven, ghost=9, selftest=True)),
         ("tight", dict(nz=12 * world + 1, ghost=5, blobs=BLOB_SEAM, seam_blob=True)),       # ghost = blob depth 5
         ("tight-wide", dict(nz=12 * world + 1, ghost=11, blobs=BLOB_SEAM, seam_blob=True)),
         ("tight-tv", dict(nz=8 * world + 3, ghost=6, tv_ratio=3.6)),                         # ghost = h_tv = blob depth 6
@@ -169,6 +170,7 @@ def _cases(world):
         ("plateau", dict(nz=12 * world + 1, ghost=6, plateau=True)),
         ("tolerance", dict(nz=uneven, ghost=9, opts=TOLERANCE, blobs=None)),
         ("refusals", dict(nz=10 * world + 1, ghost=4, refusals=True, blobs=None)),
+        ("no-voxel", dict(nz=10 * world + 1, ghost=4, no_voxel=True, blobs=None)),
     ]
 
 
@@ -205,6 +207,13 @@ def _run_case(ctx, dev, rank, world, name, c, O):
     L = slab.make_slab(ctx, rank, world, nz, ghost)
     out = dict(z0=L.z0, z1=L.z1, fraction=fraction, seam_z=seam_z)
     lshape = (L.nz_local, 36, 44)
+    if c.get("selftest"):
+        # the exchange routine of the halos with this rank as its own peer, and the select's sum over the ranks
+        try:
+            L.selftest(1 << 12)
+            out["selftest_bad"] = None
+        except api.VisfdHipError as e:
+            out["selftest_bad"] = str(e)
 
     def fresh():
         t = torch.full(lshape, float("nan"), device=dev)
@@ -233,6 +242,18 @@ def _run_case(ctx, dev, rank, world, name, c, O):
             out["refusal_bad"] = flags
             ctx.synchronize()
             # ... and the same handle then runs a stage that fits (the membrane stage needs 4 planes)
+        if c.get("no_voxel"):
+            # best_fraction 1.0 of far fewer than 2^24 voxels: the float product is n itself, the rank one past the last voxel.
+            # Round 0's pick finds that out on every rank from the same summed counters; the error comes once all three
+            # rounds and their sums have been queued, so the ranks' collectives stay matched and the handle stays usable
+            try:
+                L.membrane_detect(fresh(), torch.zeros(lshape, device=dev), torch.zeros((3,) + lshape, device=dev),
+                                  torch.zeros((6,) + lshape, device=dev), torch.zeros(lshape, device=dev), sigma, ratio,
+                                  api.DECREASING_EIVALS, 1.0, sigma_tv, 4, math.sqrt(2.0))
+                out["refusal_bad"] = ["fraction 1.0: accepted"]
+            except api.VisfdHipError as e:
+                out["refusal_bad"] = [] if e.code == 1 and "selects no voxel" in str(e) else ["fraction 1.0: " + str(e)]
+            ctx.synchronize()
         src, sal = fresh(), torch.zeros(lshape, device=dev)
         dirs, ten = torch.zeros((3,) + lshape, device=dev), torch.zeros((6,) + lshape, device=dev)
         bg = torch.full(lshape, float("nan"), device=dev) if sigma_bg > 0 else None
@@ -298,6 +319,8 @@ def _single_volume(ctx, dev, name, c, full, parts, O):
     for p in parts:
         z0, z1 = p["z0"], p["z1"]
         where = "planes %d..%d" % (z0, z1)
+        if p.get("selftest_bad"):
+            bad.append("self-test on %s: %s" % (where, p["selftest_bad"]))
         if p.get("refusal_bad"):
             bad.append("refusals on %s: %s" % (where, "; ".join(p["refusal_bad"])))
         if p["thr"] != fthr:

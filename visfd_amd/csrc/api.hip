@@ -91,11 +91,11 @@ void halfwidths_from_ratio(const float sigma[3], float ratio, int hw[3]) {   // 
   }
 }
 
-// The isotropic Gaussian of half-width floor(sigma * ratio) -- feature.hpp:1223: no lower bound of 1 here -- into dst, or
-// into slot WS_D where dst is null (taken once the half-width has passed); *out tells where it went.
+// The isotropic Gaussian of half-width host_iso_halfwidth -- floor(sigma * ratio), feature.hpp:1223: no lower bound of 1
+// here -- into dst, or into slot WS_D where dst is null (taken once the half-width has passed); *out tells where it went.
 int gauss_iso_dev(visfd_hip_ctx* ctx, const float* src, float* dst, const float* mask, i64 nx, i64 ny, i64 nz, float sigma,
                   float ratio, bool normalize, const char* what, float** out = nullptr) {
-  const int hwv = (int)std::floor(sigma * ratio);
+  const int hwv = host_iso_halfwidth(sigma, ratio);
   VH_REQUIRE(hwv >= 0 && hwv <= MAX_HALFWIDTH, std::string(what) + " must be in [0, 64]");
   if (!dst) VH_TRY(ws(ctx, WS_D, (size_t)(nx * ny * nz), &dst));
   if (out) *out = dst;
@@ -507,11 +507,11 @@ int visfd_hip_select_histogram_dev(visfd_hip_ctx* ctx, const float* sal, const f
 }
 
 int visfd_hip_select_histogram_todev(visfd_hip_ctx* ctx, const float* sal, const float* mask, int64_t nvox, int pass,
-                                     uint32_t prefix, uint64_t* hist_dev) {
-  VH_REQUIRE(ctx && sal && hist_dev && nvox > 0, "bad argument");
+                                     uint32_t prefix, uint64_t* hist) {
+  VH_REQUIRE(ctx && sal && hist && nvox > 0, "bad argument");
   VH_REQUIRE(pass >= 0 && pass <= 2, "round must be 0, 1 or 2");
   VH_HIP(hipSetDevice(ctx->device));
-  return dev_select_histogram_todev(ctx, sal, mask, nvox, pass, prefix, hist_dev);
+  return dev_select_histogram_todev(ctx, sal, mask, nvox, pass, prefix, hist);
 }
 
 int visfd_hip_apply_threshold_dev(visfd_hip_ctx* ctx, float* sal, int64_t nvox, float thr) {

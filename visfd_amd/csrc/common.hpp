@@ -126,7 +126,8 @@ struct visfd_hip_options {
   int log_pair_chunk = 0;   // march length of those launches along z and y (0: default); tests put chunk seams into small volumes
   int membrane_queue = 1;   // the membrane stage queued in one go (csrc/api.hip: membrane_stage): the select's digits picked on the device, no
                             // threshold pass, one wait per stage with the direction kernel queued behind it; 0: a host walk after every
-                            // select round, the threshold pass, a wait for the lists' total.  The bits are the same either way
+                            // select round, the threshold pass, a wait for the lists' total.  The bits are the same either way.
+                            // (The slab stage's select is always the queued one: a host walk would have to fetch the ranks' sums)
   int tv_dense = 0;         // 1: tensor voting by the baseline kernel (csrc/tv.hip)
   int tv_fma = 0;           // 1: TOLERANCE MODE of tensor voting: fused multiply-adds, results within 1e-5 of the field's scale
                             //    instead of bit-identical (surfaces, exponent 2 or 4; everything else stays exact)
@@ -311,6 +312,7 @@ struct Taps {
 // host-side arithmetic (taps.cpp)
 void host_gauss_taps(float sigma, int h, float* t);
 void host_conv_ones(i64 n, const float* t, int h, float* out);  // filter applied to a line of ones
+int host_iso_halfwidth(float sigma, float ratio);   // the isotropic Gaussian's: what gauss_iso_dev runs and the slab stage sizes halos by
 int host_tv_halfwidth(float sigma, float cutoff);
 void host_tv_tables(float sigma, int h, float* w, float* rhat);
 float host_gengauss3d_peak(const float width[3], float m_exp, float ratio);
@@ -425,7 +427,7 @@ int dev_tensor_saliency(visfd_hip_ctx* ctx, const float* tensor_planar, const fl
 int dev_select_histogram(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, int pass,
                          uint32_t prefix, uint64_t* hist_host, uint64_t* n_unmasked_host);
 int dev_select_histogram_todev(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, int pass, uint32_t prefix,
-                               uint64_t* hist_dev);
+                               uint64_t* hist);
 // The select with no host step between its rounds (select.hip: pick_kernel): what the device keeps of it.
 enum : uint32_t { SELECT_NO_VOXEL = 1u, SELECT_INCONSISTENT = 2u };
 struct SelectState {
@@ -442,10 +444,21 @@ struct StageReadback {
   unsigned long long list_total;   // tv_list.hip: the sender lists' length
   unsigned list_flags, pad;        // ... and what their count pass saw (TVL_*)
 };
-int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state_dev);
+// A select over the ranks of a slab run: called after each round's histogram_kernel and before its pick_kernel, it sums
+// the `count` counters over the ranks, in place, ordered on `stream` (the context's); returns a VISFD_HIP_* code.  Every
+// rank then picks from the same sums, so every rank picks the same digit, and round 0's total is the global n.
+struct SelectReduce {
+  int (*sum)(void* user, uint64_t* hist, size_t count, hipStream_t stream);
+  void* user;
+};
+int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state_dev,
+                     const SelectReduce* reduce = nullptr);
 int select_result(const SelectState& s, float* thr_out);   // the state read back: the threshold, or the select's error
 int select_rank_check(uint64_t n, float fraction);         // the select's VISFD_HIP_EINVAL, from n alone (no mask: n is known before round 0)
 int dev_apply_threshold(visfd_hip_ctx* ctx, float* sal, i64 nvox, float thr);
+// the queued form whatever the option says (the slab stage); dev_threshold_fraction takes it under membrane_queue
+int dev_threshold_queued(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction, float* thr_out,
+                         const SelectReduce* reduce = nullptr);
 int dev_threshold_fraction(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction,
                            float* thr_out);
 

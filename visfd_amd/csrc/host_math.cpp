@@ -51,6 +51,10 @@ void host_conv_ones(i64 n, const float* t, int h, float* out) {
   }
 }
 
+// Half-width of the isotropic Gaussian of the ridge and background stages: reference lib/visfd/feature.hpp:1223, the floor
+// of the float product with no lower bound of 1.
+int host_iso_halfwidth(float sigma, float ratio) { return (int)std::floor(sigma * ratio); }
+
 // Tensor-voting window: reference lib/visfd/feature.hpp:1669-1675.
 int host_tv_halfwidth(float sigma, float cutoff) { return (int)std::floor(sigma * cutoff); }
 

@@ -5,8 +5,9 @@
 // floor(n*fraction).  Here the same order statistic is found exactly with a three-digit radix
 // select (11 + 11 + 10 bits) over the order-preserving 32-bit key of the float: each round is one
 // 4 B/voxel sweep that builds a 2048-bin histogram in LDS per workgroup and merges it with a few
-// global atomics.  Rounds also shard across GPUs: per-rank histograms are summed by the caller
-// (SURVEY.md §8e).
+// global atomics.  Rounds also shard across GPUs: per-rank histograms are summed between a round's
+// histogram and its pick (SelectReduce: the slab stage of slab.hip), or by a caller that walks with
+// the public histogram entry points.
 #include <cmath>
 #include <vector>
 
@@ -162,11 +163,11 @@ int dev_select_histogram(visfd_hip_ctx* ctx, const float* sal, const float* mask
 // The same histogram left on the device (2048 counters, zeroed here first), asynchronous: multi-GPU callers all-reduce it
 // there and fetch the sum once.
 int dev_select_histogram_todev(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, int pass, uint32_t prefix,
-                               uint64_t* hist_dev) {
+                               uint64_t* hist) {
   hipStream_t st = ctx->stream;
-  VH_HIP(hipMemsetAsync(hist_dev, 0, sizeof(unsigned long long) * NBINS, st));
+  VH_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned long long) * NBINS, st));
   const unsigned g = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 32);
-  histogram_kernel<false><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, nullptr, reinterpret_cast<unsigned long long*>(hist_dev));
+  histogram_kernel<false><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, pass, prefix, nullptr, reinterpret_cast<unsigned long long*>(hist));
   VH_HIP(hipGetLastError());
   return VISFD_HIP_OK;
 }
@@ -180,7 +181,12 @@ int dev_apply_threshold(visfd_hip_ctx* ctx, float* sal, i64 nvox, float thr) {
 
 // The whole select queued with no host step: the three histogram / pick pairs.  *state (device memory) then holds the
 // threshold, or a flag that select_result turns into the error.  A masked select takes its n from round 0's total.
-int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state) {
+// reduce (nullable): the ranks of a slab run sum their counters between a round's histogram and its pick (SelectReduce),
+// so pick_kernel applies select_rank to the GLOBAL n and walks the global histogram -- the single volume's select on the
+// single volume's counts.  A fraction that selects no voxel is flagged by round 0's pick; rounds 1 and 2 are queued all the
+// same (their picks return at once), so every rank makes the same three reductions whatever the outcome.
+int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i64 nvox, float fraction, SelectState* state,
+                     const SelectReduce* reduce) {
   unsigned long long* hist = nullptr;
   VH_TRY(ws(ctx, WS_HIST, (size_t)NBINS, &hist));
   hipStream_t st = ctx->stream;
@@ -188,6 +194,7 @@ int dev_select_queue(visfd_hip_ctx* ctx, const float* sal, const float* mask, i6
   const unsigned g = grid_for(nvox, BLOCK, (i64)ctx->num_cus * 32);
   for (int round = 0; round < 3; round++) {
     histogram_kernel<true><<<dim3(g), dim3(BLOCK), 0, st>>>(sal, mask, nvox, round, 0u, state, hist);
+    if (reduce) VH_TRY(reduce->sum(reduce->user, reinterpret_cast<uint64_t*>(hist), (size_t)NBINS, st));
     pick_kernel<<<dim3(1), dim3(BLOCK), 0, st>>>(hist, round, fraction, state);
   }
   VH_HIP(hipGetLastError());
@@ -209,37 +216,38 @@ int select_rank_check(uint64_t n, float fraction) {
   return VISFD_HIP_OK;
 }
 
-// the host steps of one radix round on an (all-reduced) histogram, for the multi-rank select of slab.hip
-int select_pick_digit(const uint64_t* hist, uint64_t* k) { return select_pick_bin(hist, NBINS, k); }
-float select_key_to_float(uint32_t key) { return key_to_float(key); }
+// The rounds queued back to back with the digit picked on the device and ONE wait for the state block; sal is cut only once
+// the threshold is known to exist.  With `reduce` it is the slab stage's select over all ranks' owned voxels.
+int dev_threshold_queued(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction, float* thr_out,
+                         const SelectReduce* reduce) {
+  StageReadback* block = nullptr;   // (the slot's one layout; only the select's part is used here)
+  VH_TRY(ws(ctx, WS_SELECT, 1, &block));
+  VH_TRY(dev_select_queue(ctx, sal, mask, nvox, fraction, &block->sel, reduce));
+  SelectState got;
+  VH_HIP(hipMemcpyAsync(&got, &block->sel, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+  VH_HIP(hipStreamSynchronize(ctx->stream));
+  float thr = 0.0f;
+  VH_TRY(select_result(got, &thr));
+  if (thr_out) *thr_out = thr;
+  return dev_apply_threshold(ctx, sal, nvox, thr);
+}
 
-// Option membrane_queue: the rounds queued back to back with the digit picked on the device and ONE wait for the state
-// block; 0: a wait and a host walk after every round.  Either way sal is cut only once the threshold is known to exist.
+// Option membrane_queue: the queued form above; 0: a wait and a host walk after every round.  The same bits either way.
 int dev_threshold_fraction(visfd_hip_ctx* ctx, float* sal, const float* mask, i64 nvox, float fraction,
                            float* thr_out) {
-  float thr = 0.0f;
-  if (ctx->opt.membrane_queue) {
-    StageReadback* block = nullptr;   // (the slot's one layout; only the select's part is used here)
-    VH_TRY(ws(ctx, WS_SELECT, 1, &block));
-    VH_TRY(dev_select_queue(ctx, sal, mask, nvox, fraction, &block->sel));
-    SelectState got;
-    VH_HIP(hipMemcpyAsync(&got, &block->sel, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-    VH_HIP(hipStreamSynchronize(ctx->stream));
-    VH_TRY(select_result(got, &thr));
-  } else {
-    std::vector<uint64_t> h(NBINS);
-    uint64_t n_unmasked = 0, k = 0;
-    VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 0, 0, h.data(), &n_unmasked));
-    if (!select_rank(n_unmasked, fraction, &k)) return fail(VISFD_HIP_EINVAL, kNoVoxel);
-    uint32_t key = 0;
-    for (int round = 0; round < 3; round++) {
-      if (round > 0) VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, round, key, h.data(), nullptr));
-      const int d = select_pick_bin(h.data(), NBINS, &k);
-      if (d < 0) return fail(VISFD_HIP_EDEVICE, kInconsistent);
-      key = (key << (round == 2 ? 10 : 11)) | (uint32_t)d;
-    }
-    thr = key_to_float(key);
+  if (ctx->opt.membrane_queue) return dev_threshold_queued(ctx, sal, mask, nvox, fraction, thr_out);
+  std::vector<uint64_t> h(NBINS);
+  uint64_t n_unmasked = 0, k = 0;
+  VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, 0, 0, h.data(), &n_unmasked));
+  if (!select_rank(n_unmasked, fraction, &k)) return fail(VISFD_HIP_EINVAL, kNoVoxel);
+  uint32_t key = 0;
+  for (int round = 0; round < 3; round++) {
+    if (round > 0) VH_TRY(dev_select_histogram(ctx, sal, mask, nvox, round, key, h.data(), nullptr));
+    const int d = select_pick_bin(h.data(), NBINS, &k);
+    if (d < 0) return fail(VISFD_HIP_EDEVICE, kInconsistent);
+    key = (key << (round == 2 ? 10 : 11)) | (uint32_t)d;
   }
+  const float thr = key_to_float(key);
   if (thr_out) *thr_out = thr;
   return dev_apply_threshold(ctx, sal, nvox, thr);
 }

@@ -1,6 +1,8 @@
 // select_pick.hpp -- the two host/device steps of the radix select (select.hip): the rank the reference reads, and the walk
 // that picks one digit from a histogram.  Plain C++ (tests/select_pick_check.cpp compiles it with g++), __host__ __device__
-// under hipcc: the host select, the multi-rank select of slab.hip and the pick kernel all run THIS code.
+// under hipcc: pick_kernel and the host walk of dev_threshold_fraction run THIS code and nothing else does (select_rank_check
+// is select_rank's verdict before anything is queued).  The slab stage has no select of its own: it is pick_kernel on the
+// ranks' summed counters.
 #pragma once
 
 #include <cmath>

@@ -3,12 +3,16 @@
 // volumes larger than one GPU's HBM run across the GPUs of a node).
 //
 // One process per GPU.  A rank stores its owned planes [z0, z1) plus `ghost` planes on each INTERIOR face; every
-// "outside the image" rule of the reference fires at the true faces of the volume only.  The transport is
-//   * RCCL (loaded at run time from librccl.so: the library has no link-time dependency on it): grouped ncclSend/ncclRecv
-//     with the two Z-neighbours -- one xGMI link each -- on a transfer stream of its own, and three all-reduces of a
-//     2048-counter histogram for the exact global top-fraction threshold (handlers.cpp:1751-1797); or
-//   * caller-provided callbacks (visfd_hip_transport): what the world-2 tests drive the same code with, and what an MPI
-//     host would plug in.
+// "outside the image" rule of the reference fires at the true faces of the volume only.  Everything behind creation sees
+// ONE transport, a visfd_hip_transport of callbacks: paired exchanges with the two Z-neighbours, grouped per halo, on a
+// transfer stream of the slab's own, and an in-place sum of 2048 counters over the ranks on the context's stream.  It is
+//   * the caller's (visfd_hip_slab_create_custom): what the multi-rank tests drive the code with, and what an MPI host
+//     would plug in; or
+//   * RCCL behind the same four callbacks (visfd_hip_slab_create_rccl; loaded at run time from librccl.so, so the library
+//     has no link-time dependency on it): ncclSend + ncclRecv with one peer -- one xGMI link each -- inside
+//     ncclGroupStart/End, and ncclAllReduce(uint64, sum).
+// The exact global top-fraction threshold (handlers.cpp:1751-1797) is the single-volume select of select.hip with that sum
+// between each round's histogram and its pick: three reductions, one host wait.
 // OVERLAP.  The (saliency, direction) halo of the voting stage travels on the transfer stream while the main stream votes
 // the interior receiver planes (those whose windows touch owned sender planes only); the two bands next to the interior
 // faces follow once the halo has landed.  The voting kernels are persistent grids sized to fill every wave slot of the
@@ -17,16 +21,10 @@
 // slots (default 64 = 16 CUs' worth) free for the transport's kernels.
 #include <dlfcn.h>
 
-#include <cmath>
 #include <mutex>
 #include <vector>
 
 #include "common.hpp"
-
-namespace vh {
-int select_pick_digit(const uint64_t* hist, uint64_t* k);   // select.hip
-float select_key_to_float(uint32_t key);
-}  // namespace vh
 
 using namespace vh;
 
@@ -79,24 +77,40 @@ struct visfd_hip_slab {
   int rank = 0, world = 1, ghost = 0;
   i64 nz_global = 0, z0 = 0, z1 = 0, lo = 0, hi = 0;   // owned [z0, z1), stored [lo, hi) (global plane indices)
   i64 own0 = 0, own1 = 0, nz_local = 0;                // the owned planes inside the local array
-  Rccl* rccl = nullptr;
+  visfd_hip_transport tr = {};                         // the caller's, or the rccl_* adapters below; none (sendrecv null) at
+                                                       // world 1 created without an id, where nothing is exchanged or summed
+  Rccl* rccl = nullptr;                                // behind the adapters only
   ncclComm_p comm = nullptr;
-  visfd_hip_transport custom = {};
-  bool use_custom = false;
   hipStream_t xfer = nullptr;                          // transfers run here, ordered against ctx->stream by events
   hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-  uint64_t* hist_dev = nullptr;
   int reserve_wg = 64;
   bool in_flight = false;
 };
 
 namespace {
 
-#define VH_NCCL(s, expr)                                                                         \
-  do {                                                                                           \
-    int _r = (expr);                                                                             \
-    if (_r != 0) return fail(VISFD_HIP_EDEVICE, std::string(#expr) + ": " + (s)->rccl->GetErrorString(_r)); \
-  } while (0)
+// ---- RCCL as a visfd_hip_transport (user: the slab).  They return RCCL's own result, which transport_rc turns into the
+// error text ----------------------------------------------------------------------------------------------------------
+int rccl_sendrecv(void* user, int peer, const void* sendbuf, void* recvbuf, size_t bytes, void* stream) {
+  const visfd_hip_slab* s = static_cast<const visfd_hip_slab*>(user);
+  const int r = s->rccl->Send(sendbuf, bytes / sizeof(float), kNcclFloat, peer, s->comm, static_cast<hipStream_t>(stream));
+  return r != 0 ? r : s->rccl->Recv(recvbuf, bytes / sizeof(float), kNcclFloat, peer, s->comm, static_cast<hipStream_t>(stream));
+}
+int rccl_allreduce_sum_u64(void* user, uint64_t* buf, size_t count, void* stream) {
+  const visfd_hip_slab* s = static_cast<const visfd_hip_slab*>(user);
+  return s->rccl->AllReduce(buf, buf, count, kNcclUint64, kNcclSum, s->comm, static_cast<hipStream_t>(stream));
+}
+int rccl_group_start(void* user) { return static_cast<const visfd_hip_slab*>(user)->rccl->GroupStart(); }
+int rccl_group_end(void* user) { return static_cast<const visfd_hip_slab*>(user)->rccl->GroupEnd(); }
+const char* rccl_error(const visfd_hip_slab* s, int r) { return s->rccl->GetErrorString(r); }
+
+// What a transport callback returned, as the error: RCCL's own string for the adapters, "transport: ... failed" for a
+// caller's callback, with `code` (a stage has always said VISFD_HIP_EINVAL there, the self-test VISFD_HIP_EDEVICE).
+int transport_rc(const visfd_hip_slab* s, int r, const char* what, int code) {
+  if (r == 0) return VISFD_HIP_OK;
+  if (s->comm) return fail(VISFD_HIP_EDEVICE, std::string("RCCL ") + what + ": " + rccl_error(s, r));
+  return fail(code, std::string("transport: ") + what + " failed");
+}
 
 int slab_common(visfd_hip_ctx* ctx, int rank, int world, i64 nz_global, int ghost, visfd_hip_slab** out) {
   VH_REQUIRE(ctx && out, "null argument");
@@ -122,56 +136,52 @@ int slab_common(visfd_hip_ctx* ctx, int rank, int world, i64 nz_global, int ghos
   VH_HIP(hipStreamCreateWithFlags(&s->xfer, hipStreamNonBlocking));
   VH_HIP(hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming));
   VH_HIP(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
-  VH_HIP(hipMalloc(reinterpret_cast<void**>(&s->hist_dev), sizeof(uint64_t) * 2048));
   *out = s;
   return VISFD_HIP_OK;
 }
 
+// `n` paired exchanges of `cnt` floats each as ONE group on the transfer stream: queued behind everything the main stream
+// has done so far (ev_ready), ev_done behind them; the main stream is NOT made to wait here.
+struct Exchange {
+  int peer;
+  const float* send;
+  float* recv;
+};
+int exchange_group(visfd_hip_slab* s, const Exchange* x, int n, size_t cnt, int code) {
+  const visfd_hip_transport& tr = s->tr;
+  VH_HIP(hipEventRecord(s->ev_ready, s->ctx->stream));
+  VH_HIP(hipStreamWaitEvent(s->xfer, s->ev_ready, 0));
+  if (tr.group_start) VH_TRY(transport_rc(s, tr.group_start(tr.user), "group_start", code));
+  for (int i = 0; i < n; i++)
+    VH_TRY(transport_rc(s, tr.sendrecv(tr.user, x[i].peer, x[i].send, x[i].recv, cnt * sizeof(float), (void*)s->xfer), "sendrecv", code));
+  if (tr.group_end) VH_TRY(transport_rc(s, tr.group_end(tr.user), "group_end", code));
+  VH_HIP(hipEventRecord(s->ev_done, s->xfer));
+  return VISFD_HIP_OK;
+}
+
+// The select's step between a round's histogram and its pick (SelectReduce; user: the slab)
+int sum_over_ranks(void* user, uint64_t* hist, size_t count, hipStream_t stream) {
+  const visfd_hip_slab* s = static_cast<const visfd_hip_slab*>(user);
+  return transport_rc(s, s->tr.allreduce_sum_u64(s->tr.user, hist, count, (void*)stream), "allreduce", VISFD_HIP_EINVAL);
+}
+
 // The ghost planes of `nvol` volumes within `depth` planes of the owned range, from the Z-neighbours' owned planes, as
-// ONE group on the transfer stream: queued behind everything the main stream has done so far (ev_ready); the main stream
-// is NOT made to wait here -- halo_wait() does that.
+// one group; halo_wait() makes the main stream wait for it.
 int halo_start(visfd_hip_slab* s, float* const* vols, int nvol, i64 nx, i64 ny, int depth) {
   if (s->world == 1 || depth == 0) return VISFD_HIP_OK;
   VH_REQUIRE(depth <= s->ghost, "halo deeper than the ghost zone");
   VH_REQUIRE(!s->in_flight, "a halo exchange is already in flight");
-  const size_t plane = (size_t)nx * ny, cnt = plane * (size_t)depth;
-  const int up = s->rank + 1, down = s->rank - 1;
-  VH_HIP(hipEventRecord(s->ev_ready, s->ctx->stream));
-  VH_HIP(hipStreamWaitEvent(s->xfer, s->ev_ready, 0));
-  if (s->use_custom) {
-    if (s->custom.group_start) VH_REQUIRE(s->custom.group_start(s->custom.user) == 0, "transport: group_start failed");
-  } else {
-    VH_NCCL(s, s->rccl->GroupStart());
-  }
-  for (int v = 0; v < nvol; v++) {
-    float* t = vols[v];
-    if (down >= 0) {
-      const float* send = t + (size_t)s->own0 * plane;
-      float* recv = t + (size_t)(s->own0 - depth) * plane;
-      if (s->use_custom) {
-        VH_REQUIRE(s->custom.sendrecv(s->custom.user, down, send, recv, cnt * sizeof(float), (void*)s->xfer) == 0, "transport: sendrecv failed");
-      } else {
-        VH_NCCL(s, s->rccl->Send(send, cnt, kNcclFloat, down, s->comm, s->xfer));
-        VH_NCCL(s, s->rccl->Recv(recv, cnt, kNcclFloat, down, s->comm, s->xfer));
-      }
+  const size_t plane = (size_t)nx * ny;
+  std::vector<Exchange> x;
+  for (int v = 0; v < nvol; v++)
+    for (int up = 0; up < 2; up++) {   // per volume the neighbour below, then the one above
+      const int peer = s->rank + (up ? 1 : -1);
+      if (peer < 0 || peer >= s->world) continue;
+      // the `depth` owned planes next to that face go out, the ghost planes beyond it come in
+      const i64 z_send = up ? s->own1 - depth : s->own0, z_recv = up ? s->own1 : s->own0 - depth;
+      x.push_back({peer, vols[v] + (size_t)z_send * plane, vols[v] + (size_t)z_recv * plane});
     }
-    if (up < s->world) {
-      const float* send = t + (size_t)(s->own1 - depth) * plane;
-      float* recv = t + (size_t)s->own1 * plane;
-      if (s->use_custom) {
-        VH_REQUIRE(s->custom.sendrecv(s->custom.user, up, send, recv, cnt * sizeof(float), (void*)s->xfer) == 0, "transport: sendrecv failed");
-      } else {
-        VH_NCCL(s, s->rccl->Send(send, cnt, kNcclFloat, up, s->comm, s->xfer));
-        VH_NCCL(s, s->rccl->Recv(recv, cnt, kNcclFloat, up, s->comm, s->xfer));
-      }
-    }
-  }
-  if (s->use_custom) {
-    if (s->custom.group_end) VH_REQUIRE(s->custom.group_end(s->custom.user) == 0, "transport: group_end failed");
-  } else {
-    VH_NCCL(s, s->rccl->GroupEnd());
-  }
-  VH_HIP(hipEventRecord(s->ev_done, s->xfer));
+  VH_TRY(exchange_group(s, x.data(), (int)x.size(), plane * (size_t)depth, VISFD_HIP_EINVAL));
   s->in_flight = true;
   return VISFD_HIP_OK;
 }
@@ -194,42 +204,6 @@ struct HaloGuard {
     }
   }
 };
-
-// Exact global k-th largest saliency over all ranks' owned voxels (three radix rounds, each all-reducing 2048 counters
-// on the device), then every owned voxel below it is zeroed (handlers.cpp:1751-1797).
-int global_threshold(visfd_hip_slab* s, float* sal_owned, i64 nvox, float fraction, float* thr_out) {
-  visfd_hip_ctx* ctx = s->ctx;
-  std::vector<uint64_t> h(2048);
-  uint32_t prefix = 0, key = 0;
-  uint64_t k = 0;
-  const int shifts[3] = {21, 10, 0};
-  for (int rnd = 0; rnd < 3; rnd++) {
-    VH_TRY(dev_select_histogram_todev(ctx, sal_owned, nullptr, nvox, rnd, prefix, s->hist_dev));
-    if (s->world > 1) {
-      if (s->use_custom) {
-        VH_REQUIRE(s->custom.allreduce_sum_u64(s->custom.user, s->hist_dev, 2048, (void*)ctx->stream) == 0, "transport: allreduce failed");
-      } else {
-        VH_NCCL(s, s->rccl->AllReduce(s->hist_dev, s->hist_dev, 2048, kNcclUint64, kNcclSum, s->comm, ctx->stream));
-      }
-    }
-    VH_HIP(hipMemcpyAsync(h.data(), s->hist_dev, sizeof(uint64_t) * 2048, hipMemcpyDeviceToHost, ctx->stream));
-    VH_HIP(hipStreamSynchronize(ctx->stream));
-    if (rnd == 0) {
-      uint64_t n = 0;
-      for (uint64_t c : h) n += c;
-      const float prod = (float)n * fraction;   // size_t -> float product (handlers.cpp:1781)
-      k = (uint64_t)std::floor(prod);
-      if (n == 0 || k >= n) return fail(VISFD_HIP_EINVAL, "threshold fraction selects no voxel");
-    }
-    const int digit = select_pick_digit(h.data(), &k);
-    if (digit < 0) return fail(VISFD_HIP_EDEVICE, "radix select: inconsistent histogram");
-    key |= (uint32_t)digit << shifts[rnd];
-    if (rnd < 2) prefix = (prefix << 11) | (uint32_t)digit;
-  }
-  const float thr = select_key_to_float(key);
-  if (thr_out) *thr_out = thr;
-  return dev_apply_threshold(ctx, sal_owned, nvox, thr);
-}
 
 }  // namespace
 
@@ -269,6 +243,7 @@ int visfd_hip_slab_create_rccl(visfd_hip_ctx* ctx, const void* unique_id, int ra
       visfd_hip_slab_destroy(s);
       return fail(VISFD_HIP_EDEVICE, msg);
     }
+    s->tr = {rccl_sendrecv, rccl_allreduce_sum_u64, rccl_group_start, rccl_group_end, s};
   }
   *out = s;
   return VISFD_HIP_OK;
@@ -279,8 +254,7 @@ int visfd_hip_slab_create_custom(visfd_hip_ctx* ctx, const visfd_hip_transport* 
   VH_REQUIRE(tr && tr->sendrecv && tr->allreduce_sum_u64, "the transport needs sendrecv and allreduce_sum_u64");
   visfd_hip_slab* s = nullptr;
   VH_TRY(slab_common(ctx, rank, world, nz_global, ghost, &s));
-  s->custom = *tr;
-  s->use_custom = true;
+  s->tr = *tr;
   *out = s;
   return VISFD_HIP_OK;
 }
@@ -290,7 +264,6 @@ int visfd_hip_slab_destroy(visfd_hip_slab* s) {
   (void)hipSetDevice(s->ctx->device);
   if (s->xfer) (void)hipStreamSynchronize(s->xfer);
   if (s->comm && s->rccl) (void)s->rccl->CommDestroy(s->comm);
-  if (s->hist_dev) (void)hipFree(s->hist_dev);
   if (s->ev_ready) (void)hipEventDestroy(s->ev_ready);
   if (s->ev_done) (void)hipEventDestroy(s->ev_done);
   if (s->xfer) (void)hipStreamDestroy(s->xfer);
@@ -304,16 +277,19 @@ int visfd_hip_slab_layout(visfd_hip_slab* s, int64_t out[7]) {
   return VISFD_HIP_OK;
 }
 
-// The transport's own smoke test: a grouped send/receive of `count` floats from this rank to ITSELF on the transfer stream
-// (RCCL allows self send/recv inside a group) and an all-reduce of 2048 counters on the context's stream, both verified.
+// The transport's own smoke test: a grouped send/receive of `count` floats from this rank to ITSELF on the transfer stream,
+// through the exchange routine the halos take (RCCL allows self send/recv inside a group), and a sum of 2048 counters over
+// the ranks on the context's stream, in the select's histogram slot, both verified.
 // With one rank per GPU it checks the wiring of every rank; with a one-rank communicator (world == 1 created with an id) it
 // is what a one-GPU box can run of the RCCL path: the run-time loading of librccl.so, the call signatures and enums, the
 // stream/event ordering.
 int visfd_hip_slab_selftest(visfd_hip_slab* s, int64_t count) {
   VH_REQUIRE(s && count > 0, "bad argument");
-  VH_REQUIRE(s->use_custom || s->comm, "the slab has no communicator (world == 1 created without an id)");
+  VH_REQUIRE(s->tr.sendrecv, "the slab has no communicator (world == 1 created without an id)");
   visfd_hip_ctx* ctx = s->ctx;
   VH_HIP(hipSetDevice(ctx->device));
+  uint64_t* hist = nullptr;
+  VH_TRY(ws(ctx, WS_HIST, (size_t)2048, &hist));
   float *a = nullptr, *b = nullptr;
   VH_HIP(hipMalloc(reinterpret_cast<void**>(&a), sizeof(float) * (size_t)count));
   VH_HIP(hipMalloc(reinterpret_cast<void**>(&b), sizeof(float) * (size_t)count));
@@ -323,39 +299,16 @@ int visfd_hip_slab_selftest(visfd_hip_slab* s, int64_t count) {
   auto check = [&](hipError_t e) { if (e != hipSuccess && rc == VISFD_HIP_OK) rc = fail(VISFD_HIP_EDEVICE, hipGetErrorString(e)); };
   check(hipMemcpyAsync(a, h.data(), sizeof(float) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
   check(hipMemsetAsync(b, 0, sizeof(float) * (size_t)count, ctx->stream));
-  check(hipEventRecord(s->ev_ready, ctx->stream));
-  check(hipStreamWaitEvent(s->xfer, s->ev_ready, 0));
-  if (rc == VISFD_HIP_OK) {
-    if (s->use_custom) {
-      if (s->custom.group_start && s->custom.group_start(s->custom.user) != 0) rc = fail(VISFD_HIP_EDEVICE, "transport: group_start failed");
-      if (rc == VISFD_HIP_OK && s->custom.sendrecv(s->custom.user, s->rank, a, b, sizeof(float) * (size_t)count, (void*)s->xfer) != 0)
-        rc = fail(VISFD_HIP_EDEVICE, "transport: sendrecv failed");
-      if (rc == VISFD_HIP_OK && s->custom.group_end && s->custom.group_end(s->custom.user) != 0) rc = fail(VISFD_HIP_EDEVICE, "transport: group_end failed");
-    } else {
-      int r = s->rccl->GroupStart();
-      if (r == 0) r = s->rccl->Send(a, (size_t)count, kNcclFloat, s->rank, s->comm, s->xfer);
-      if (r == 0) r = s->rccl->Recv(b, (size_t)count, kNcclFloat, s->rank, s->comm, s->xfer);
-      const int r2 = s->rccl->GroupEnd();
-      if (r == 0) r = r2;
-      if (r != 0) rc = fail(VISFD_HIP_EDEVICE, std::string("RCCL self send/recv: ") + s->rccl->GetErrorString(r));
-    }
-  }
-  check(hipEventRecord(s->ev_done, s->xfer));
+  const Exchange self = {s->rank, a, b};
+  if (rc == VISFD_HIP_OK) rc = exchange_group(s, &self, 1, (size_t)count, VISFD_HIP_EDEVICE);
   check(hipStreamWaitEvent(ctx->stream, s->ev_done, 0));
   check(hipMemcpyAsync(back.data(), b, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
-  // all-reduce: every rank contributes i + 1 in counter i
+  // the sum: every rank contributes i + 1 in counter i
   std::vector<uint64_t> hh(2048), hs(2048);
   for (int i = 0; i < 2048; i++) hh[(size_t)i] = (uint64_t)i + 1;
-  check(hipMemcpyAsync(s->hist_dev, hh.data(), sizeof(uint64_t) * 2048, hipMemcpyHostToDevice, ctx->stream));
-  if (rc == VISFD_HIP_OK) {
-    if (s->use_custom) {
-      if (s->custom.allreduce_sum_u64(s->custom.user, s->hist_dev, 2048, (void*)ctx->stream) != 0) rc = fail(VISFD_HIP_EDEVICE, "transport: allreduce failed");
-    } else {
-      const int r = s->rccl->AllReduce(s->hist_dev, s->hist_dev, 2048, kNcclUint64, kNcclSum, s->comm, ctx->stream);
-      if (r != 0) rc = fail(VISFD_HIP_EDEVICE, std::string("ncclAllReduce: ") + s->rccl->GetErrorString(r));
-    }
-  }
-  check(hipMemcpyAsync(hs.data(), s->hist_dev, sizeof(uint64_t) * 2048, hipMemcpyDeviceToHost, ctx->stream));
+  check(hipMemcpyAsync(hist, hh.data(), sizeof(uint64_t) * 2048, hipMemcpyHostToDevice, ctx->stream));
+  if (rc == VISFD_HIP_OK) rc = transport_rc(s, s->tr.allreduce_sum_u64(s->tr.user, hist, 2048, (void*)ctx->stream), "allreduce", VISFD_HIP_EDEVICE);
+  check(hipMemcpyAsync(hs.data(), hist, sizeof(uint64_t) * 2048, hipMemcpyDeviceToHost, ctx->stream));
   check(hipStreamSynchronize(ctx->stream));
   (void)hipFree(a);
   (void)hipFree(b);
@@ -395,9 +348,9 @@ int visfd_hip_membrane_detect_slab_bg_dev(visfd_hip_slab* s, float* src, float* 
   VH_HIP(hipSetDevice(ctx->device));
   const i64 nzl = s->nz_local, plane = nx * ny, nvl = plane * nzl;
   VH_TRY(check_dims(nx, ny, nzl));
-  const int h_gauss = (int)std::floor(sigma * ratio);
+  const int h_gauss = host_iso_halfwidth(sigma, ratio);
   const int h_tv = host_tv_halfwidth(sigma_tv, cutoff);
-  const int h_bg = sigma_background > 0.0f ? (int)std::floor(sigma_background * ratio) : 0;
+  const int h_bg = sigma_background > 0.0f ? host_iso_halfwidth(sigma_background, ratio) : 0;
   VH_REQUIRE(s->world == 1 || (h_gauss + 1 <= s->ghost && h_tv <= s->ghost && h_bg <= s->ghost), "ghost depth too small for this window");
   // 1. source halo deep enough for smoothing + the finite-difference stencil (and for the background filter)
   if (!src_halo_ready) {
@@ -413,10 +366,12 @@ int visfd_hip_membrane_detect_slab_bg_dev(visfd_hip_slab* s, float* src, float* 
   }
   // 2. scores on every stored plane (planes closer than h_gauss + 1 to an interior array end are garbage; owned planes exact)
   VH_TRY(visfd_hip_ridge_scores_bg_dev(ctx, src, nullptr, nx, ny, nzl, sigma, ratio, order, bg, sal, scratch));
-  // 3. global top-fraction threshold over the owned voxels
-  float thr = 0.0f;
-  VH_TRY(global_threshold(s, sal + s->own0 * plane, (s->own1 - s->own0) * plane, best_fraction, &thr));
-  if (thr_out) *thr_out = thr;
+  // 3. global top-fraction threshold over the owned voxels: the single volume's queued select, the ranks' counters summed
+  // before each pick.  A fraction that selects no voxel is refused (VISFD_HIP_EINVAL, on every rank alike) once all three
+  // rounds and their sums have been queued, with the scores uncut
+  const SelectReduce sum = {sum_over_ranks, s};
+  VH_TRY(dev_threshold_queued(ctx, sal + s->own0 * plane, nullptr, (s->own1 - s->own0) * plane, best_fraction, thr_out,
+                              s->world > 1 ? &sum : nullptr));
   VH_TRY(dev_ridge_directions(ctx, scratch, sal, nx, ny, nzl, sigma, order, dirs));
   // 4. stored planes beyond the voting halo must not vote; then the four channels of the halo as ONE group
   if (s->own0 - h_tv > 0) VH_HIP(hipMemsetAsync(sal, 0, sizeof(float) * (size_t)((s->own0 - h_tv) * plane), ctx->stream));
