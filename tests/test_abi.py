@@ -37,6 +37,54 @@ def test_library_exports_every_declared_symbol(lib):
     assert L.visfd_hip_abi_version() == 10
 
 
+def test_binding_types_come_from_the_header(lib):
+    """The argument and return types of the binding are parsed from include/visfd_hip.h.  One prototype, typed by hand
+    here, for every spelling the header uses: double, const double[3], int64_t[6], float* const*, uint32_t, uint64_t*,
+    int32_t, a struct pointer, visfd_hip_ctx**, an unnamed pointer, const char* as a parameter; and for every return
+    type: int, void, void*, int64_t, float, const char*."""
+    c_int, i64, f32, f64, vp, u32, i32 = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.c_int32)
+    want = {
+        "visfd_hip_create": (c_int, [c_int, vp, vp]),
+        "visfd_hip_get_stream": (vp, [vp]),
+        "visfd_hip_last_error": (ctypes.c_char_p, []),
+        "visfd_hip_set_option": (c_int, [vp, ctypes.c_char_p, i64]),
+        "visfd_hip_workspace_bytes": (i64, [vp]),
+        "visfd_hip_ratio_from_threshold": (f32, [f32]),
+        "visfd_hip_blob_dog_abort": (None, [vp]),
+        "visfd_hip_image_stats_host": (c_int, [vp, vp, i64, vp]),
+        "visfd_hip_select_histogram_dev": (c_int, [vp, vp, vp, i64, c_int, u32, vp, vp]),
+        "visfd_hip_slab_exchange_dev": (c_int, [vp, vp, c_int, i64, i64, c_int]),
+        "visfd_hip_voxelize_quantize_host": (c_int, [vp, i64, f64, vp, vp]),
+        "visfd_hip_close_surface_last": (c_int, [vp, vp, vp]),
+        "visfd_hip_sort_blobs": (c_int, [vp, vp, vp, i64, c_int, c_int, vp]),
+        "visfd_hip_watershed": (c_int, [vp, vp, vp, vp, i64, i64, i64, f32, c_int, c_int, c_int, i32, i32, vp, vp, vp, i64, vp]),
+        "visfd_hip_isosurface_host": (c_int, [vp, i64, i64, i64, f64, c_int, vp, i64, vp, i64, vp, vp]),
+    }
+    for name, sig in want.items():
+        assert lib._SIGS[name] == sig, name
+    L = lib.load_library()
+    for name, (res, args) in want.items():
+        fn = getattr(L, name)
+        assert fn.restype == res and list(fn.argtypes) == args, name
+
+
+def test_header_parser_refuses_what_it_does_not_know(lib):
+    ok = "/* a comment with visfd_hip_ghost(int); in it */\nint visfd_hip_fine(const float* src, int64_t n,\n    double w[3]);\n"
+    assert lib._parse_header(ok) == {"visfd_hip_fine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])}
+    with pytest.raises(ImportError, match="visfd_hip_odd.*long double x"):
+        lib._parse_header("int visfd_hip_fine(void);\nint visfd_hip_odd(float a, long double x);\n")
+    with pytest.raises(ImportError, match="visfd_hip_odd"):
+        lib._parse_header("int visfd_hip_fine(void);\nsize_t visfd_hip_odd(float a);\n")
+    for unnamed in ("unsigned long", "unsigned char", "unsigned int"):   # the last word is no parameter name
+        with pytest.raises(ImportError, match="visfd_hip_odd.*" + unnamed):
+            lib._parse_header("int visfd_hip_odd(float a, %s);\n" % unnamed)
+    assert lib._parse_header("int visfd_hip_fine(unsigned, const float scale, int64_t);\n") == {
+        "visfd_hip_fine": (ctypes.c_int, [ctypes.c_uint, ctypes.c_float, ctypes.c_int64])}
+    with pytest.raises(ImportError, match="visfd_hip_callback"):   # a parenthesised parameter is not skipped silently
+        lib._parse_header("int visfd_hip_fine(void);\nint visfd_hip_callback(int (*fn)(void* user), void* user);\n")
+
+
 def test_host_arithmetic_matches_oracle(lib, oracle):
     for s, h in volgen.TAP_CASES:
         assert_bits_equal(lib.gauss_taps(s, h), oracle.gauss_taps(s, h), "taps")

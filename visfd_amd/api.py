@@ -7,10 +7,13 @@ Two faces, like the C ABI:
                                       dir (3,nz,ny,nx), tensor (6,nz,ny,nx))
 
 There is NO CPU fallback: loading fails loudly when the HIP library is missing, and creating a
-context fails when no GPU is present.
+context fails when no GPU is present.  The argument types of the entry points are read from include/visfd_hip.h when this
+module is imported (so that `_SIGS` is whole for every reader): without that header next to the package the import fails
+with an ImportError that names the path.
 """
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -92,282 +95,64 @@ def intensity(map=MAP_NONE, t=(), out_a=0.0, out_b=1.0, invert_ave=None, masked_
     p.stats_mask = int(bool(stats_mask))
     return p
 
-# dst, mask, background, sizes, centers, diameters, thicknesses, foreground, n, offset, rescale, two flags, any_center_outside
-_DRAW_SPHERES = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, _fp, _fp, _fp, _i64, C.c_float, C.c_float, C.c_int, C.c_int, _ip]
-_DRAW_REGIONS = [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(Region), _i64, C.c_int]
 
-_VOL = [_vp, _vp, _vp, _i64, _i64, _i64]  # src, dst, mask, nx, ny, nz  (pointers as void*)
+# ---- the signatures of the entry points, read from the header the library is compiled against
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "visfd_hip.h")
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+            "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_RETURNS = dict(_SCALARS, **{"void": None, "void*": _vp, "const char*": C.c_char_p})
+_PROTOTYPE = re.compile(r"^[ \t]*(\w[\w \t*]*?)[ \t]*\b(visfd_hip_\w+)[ \t]*\(([^()]*)\)\s*;", re.M)
+_TYPE_WORDS = {"int", "long", "short", "char", "unsigned", "signed", "float", "double"}   # never a parameter's name
 
-# find_minima, find_maxima, both thresholds, connectivity, allow_borders, then (index, score, nvoxels, cap, n) per kind, labels
-_EXTREMA_TAIL = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int] + 2 * [_vp, _vp, _vp, _i64, C.POINTER(_i64)] + [_vp]
 
-# src, mask, markers, nx, ny, nz, halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary,
-# label_undefined, labels, basin_index, basin_score, basin_cap, n_basins
-_WATERSHED = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
-              C.POINTER(_i64)]
+def _scalar(p):
+    """The ctypes type of a scalar parameter `[const] type [name]`, or None: the whole spelling is tried as a type first, so
+    that the last word of an unnamed `unsigned long` is not taken for a name"""
+    words = [w for w in p.split() if w != "const"]
+    if " ".join(words) in _SCALARS:
+        return _SCALARS[" ".join(words)]
+    if len(words) > 1 and words[-1] not in _TYPE_WORDS:
+        return _SCALARS.get(" ".join(words[:-1]))
+    return None
 
-# ctx, src, mask, nx, ny, nz, lo, hi, points (host int32 triples), npoints, dsq
-_DIST_SQ = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, _vp, _i64, _vp]
 
-_LABEL_CONNECTED_EX = [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float, C.c_float, C.c_int, _vp, C.c_float, C.c_float,
-                       C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                       _i64, _vp]   # visfd_hip_label_connected_ex
+def _parse_header(text):
+    """The prototypes `ret visfd_hip_name(args);` of a C header -> {name: (restype, [argtypes])} for ctypes.  Scalars by
+    their spelling, `const char*` as c_char_p, every other pointer or array as c_void_p (which takes byref(), ctypes arrays
+    and pointers, integers and None).  A spelling that is not in the tables raises and names the prototype, and so does a
+    visfd_hip_ name followed by `(` that is no such prototype (a parenthesised parameter, say): nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        proto = "%s %s(%s)" % (ret, name, " ".join(params.split()))
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise ImportError("cannot bind `%s`: return type %r is not one the binding knows" % (proto, ret))
+        args = []
+        for p in [" ".join(p.split()) for p in params.split(",") if params.strip() not in ("", "void")]:
+            if re.fullmatch(r"const char ?\*(?: ?\w+)?", p):
+                args.append(C.c_char_p)
+            elif "*" in p or "[" in p:
+                args.append(_vp)
+            elif _scalar(p) is not None:
+                args.append(_scalar(p))
+            else:
+                raise ImportError("cannot bind `%s`: parameter %r is not of a type the binding knows" % (proto, p))
+        sigs[name] = (_RETURNS[ret], args)
+    unread = set(re.findall(r"\b(visfd_hip_\w+)\s*\(", text)) - set(sigs)
+    if unread:
+        raise ImportError("cannot bind %s: not of the form `ret name(args);`" % ", ".join(sorted(unread)))
+    return sigs
 
-# ctx, vertices, n_vertices, triangles, n_triangles, voxel_width, origin, nx, ny, nz, check_closed, dst
-_VOXELIZE = [_vp, _vp, _i64, _vp, _i64, C.c_double, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, _vp]
 
-# ctx, points, normals, n, nx, ny, nz, pad, orientation, mask, chi_out
-_CLOSE = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp]
-# ctx, points, normals, n, nx, ny, nz, pad, acc, counts
-_CLOSE_SPLAT = [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, C.POINTER(_i64)]
-# (after the context:) vol, nx, ny, nz, iso, side, vertices, vertices_cap, triangles, triangles_cap, n_vertices, n_triangles
-_ISOSURFACE = [_vp, _i64, _i64, _i64, C.c_double, C.c_int, _vp, _i64, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError("%s is missing: the binding reads the entry points' signatures from it" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return _parse_header(f.read())
 
-_SIGS = {
-    "visfd_hip_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
-    "visfd_hip_destroy": (C.c_int, [_vp]),
-    "visfd_hip_synchronize": (C.c_int, [_vp]),
-    "visfd_hip_trim": (C.c_int, [_vp]),
-    "visfd_hip_last_error": (C.c_char_p, []),
-    "visfd_hip_abi_version": (C.c_int, []),
-    "visfd_hip_workspace_bytes": (_i64, [_vp]),
-    "visfd_hip_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
-    "visfd_hip_get_option": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_int64)]),
-    "visfd_hip_gauss_taps": (C.c_int, [C.c_float, C.c_int, _fp]),
-    "visfd_hip_ratio_from_threshold": (C.c_float, [C.c_float]),
-    "visfd_hip_local_fluctuations": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
-    "visfd_hip_local_fluctuations_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_float, C.c_float, C.c_int]),
-    "visfd_hip_gengauss3d_halfwidths": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _ip]),
-    "visfd_hip_gengauss3d_table": (C.c_int, [_fp, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64), _fp]),
-    "visfd_hip_dogg3d_table": (C.c_int, [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _ip, _fp, _i64,
-                                         C.POINTER(C.c_int64), _fp, _fp]),
-    "visfd_hip_filter3d": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _vp]),
-    "visfd_hip_filter3d_dev": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _vp]),
-    "visfd_hip_apply_ggauss": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, _ip, C.c_int, _fp]),
-    "visfd_hip_apply_ggauss_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, _ip, C.c_int, _fp]),
-    "visfd_hip_apply_dogg": (C.c_int, [_vp] + _VOL + [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp]),
-    "visfd_hip_apply_dogg_dev": (C.c_int, [_vp] + _VOL + [_fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp]),
-    "visfd_hip_local_fluctuations_gen": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
-    "visfd_hip_local_fluctuations_gen_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, C.c_int]),
-    "visfd_hip_draw_spheres": (C.c_int, _DRAW_SPHERES),
-    "visfd_hip_draw_spheres_dev": (C.c_int, _DRAW_SPHERES),
-    "visfd_hip_draw_regions": (C.c_int, _DRAW_REGIONS),
-    "visfd_hip_draw_regions_dev": (C.c_int, _DRAW_REGIONS),
-    "visfd_hip_draw_last_times": (C.c_int, [_vp, _fp]),
-    "visfd_hip_sphere_structure": (C.c_int, [C.c_float, C.c_float, C.c_float, _ip, _fp, _i64, C.POINTER(C.c_int64)]),
-    "visfd_hip_flat_ball_dsq_max": (C.c_int, [C.c_float, C.POINTER(C.c_int64)]),
-    "visfd_hip_morph_sphere": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
-    "visfd_hip_morph_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_int, C.c_float, C.c_float, C.c_float]),
-    "visfd_hip_morph_table": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
-    "visfd_hip_morph_table_dev": (C.c_int, [_vp] + _VOL + [C.c_int, _ip, _fp, _i64]),
-    "visfd_hip_morph_last_path": (C.c_int, [_vp, _ip]),
-    "visfd_hip_median_footprint": (C.c_int, [C.c_float, _ip, _i64, C.POINTER(C.c_int64)]),
-    "visfd_hip_median_sphere": (C.c_int, [_vp] + _VOL + [C.c_float]),
-    "visfd_hip_median_sphere_dev": (C.c_int, [_vp] + _VOL + [C.c_float]),
-    "visfd_hip_median_table": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
-    "visfd_hip_median_table_dev": (C.c_int, [_vp] + _VOL + [_ip, _i64]),
-    "visfd_hip_median_last_path": (C.c_int, [_vp, _ip]),
-    "visfd_hip_distance_sq": (C.c_int, _DIST_SQ),
-    "visfd_hip_distance_sq_dev": (C.c_int, _DIST_SQ),
-    "visfd_hip_distance_to_points": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_float]),
-    "visfd_hip_distance_to_points_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_float]),
-    "visfd_hip_distance_from_points": (C.c_int, _DIST_SQ[:-1] + [C.c_float, _vp]),
-    "visfd_hip_distance_from_points_dev": (C.c_int, _DIST_SQ[:-1] + [C.c_float, _vp]),
-    "visfd_hip_distance_last_path": (C.c_int, [_vp, _ip]),
-    "visfd_hip_image_stats": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
-    "visfd_hip_image_stats_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(Stats)]),
-    "visfd_hip_image_stats_host": (C.c_int, [_vp, _vp, _i64, C.POINTER(Stats)]),
-    "visfd_hip_intensity_map": (C.c_int, [_vp] + _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
-    "visfd_hip_intensity_map_dev": (C.c_int, [_vp] + _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
-    "visfd_hip_intensity_map_host": (C.c_int, _VOL + [C.POINTER(Intensity), C.POINTER(Stats)]),
-    "visfd_hip_filter3d_last_path": (C.c_int, [_vp, _ip]),
-    "visfd_hip_find_extrema": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
-    "visfd_hip_find_extrema_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64] + _EXTREMA_TAIL),
-    "visfd_hip_watershed_host": (C.c_int, _WATERSHED),
-    "visfd_hip_watershed": (C.c_int, [_vp] + _WATERSHED),
-    "visfd_hip_watershed_dev": (C.c_int, [_vp] + _WATERSHED),
-    "visfd_hip_watershed_last_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_fluctuation_sigmas": (C.c_int, [_fp, C.c_float, C.c_float, C.c_float, _fp, C.POINTER(C.c_float)]),
-    "visfd_hip_gauss_halfwidths": (C.c_int, [_fp, C.c_float, _ip]),
-    "visfd_hip_separable3d": (C.c_int, [_vp] + _VOL + [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
-    "visfd_hip_separable3d_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
-    "visfd_hip_apply_gauss": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _fp]),
-    "visfd_hip_apply_gauss_dev": (C.c_int, [_vp] + _VOL + [_fp, _ip, C.c_int, _fp]),
-    "visfd_hip_apply_gauss_slab_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _fp, _ip, C.c_int, _fp]),
-    "visfd_hip_apply_dog": (C.c_int, [_vp] + _VOL + [_fp, _fp, _ip, _fp, _fp]),
-    "visfd_hip_apply_dog_dev": (C.c_int, [_vp] + _VOL + [_fp, _fp, _ip, _fp, _fp]),
-    "visfd_hip_apply_log": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, _fp, _fp]),
-    "visfd_hip_apply_log_dev": (C.c_int, [_vp] + _VOL + [_fp, C.c_float, C.c_float, _fp, _fp]),
-    "visfd_hip_blob_dog": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_int, _fp, C.c_float, C.c_float,
-                                     C.c_float, C.c_float, C.c_int, C.POINTER(Blob), _i64, C.POINTER(_i64),
-                                     C.POINTER(Blob), _i64, C.POINTER(_i64)]),
-    "visfd_hip_blob_dog_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_int, _fp, C.c_float, C.c_float,
-                                         C.c_float, C.c_float, C.c_int, C.POINTER(Blob), _i64, C.POINTER(_i64),
-                                         C.POINTER(Blob), _i64, C.POINTER(_i64)]),
-    "visfd_hip_blob_dog_begin_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _fp, C.c_int, _fp, C.c_float, C.c_float,
-                                               C.c_float, C.c_float, C.c_int, C.POINTER(_vp)]),
-    "visfd_hip_blob_dog_end": (C.c_int, [_vp, C.POINTER(Blob), _i64, C.POINTER(_i64), C.POINTER(Blob), _i64, C.POINTER(_i64)]),
-    "visfd_hip_blob_dog_abort": (None, [_vp]),
-    "visfd_hip_blob_jobs_pending": (C.c_int, [_vp]),
-    "visfd_hip_debug_poison_workspace": (C.c_int, [_vp]),
-    "visfd_hip_blob_diameters_to_sigmas": (C.c_int, [_fp, C.c_int, _fp]),
-    "visfd_hip_blob_sigmas_to_diameters": (C.c_int, [_fp, C.c_int, _fp]),
-    "visfd_hip_calc_hessian": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float]),
-    "visfd_hip_calc_hessian_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float]),
-    "visfd_hip_diagonalize_flat_sym3": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int]),
-    "visfd_hip_diagonalize_flat_sym3_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int]),
-    "visfd_hip_hessian_saliency": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
-    "visfd_hip_hessian_saliency_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
-    "visfd_hip_ridge_saliency_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int,
-                                               _vp, _vp]),
-    "visfd_hip_ridge_scores_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, _vp, _vp]),
-    "visfd_hip_ridge_directions_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, _vp, _vp]),
-    "visfd_hip_threshold_fraction": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _fp]),
-    "visfd_hip_threshold_fraction_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _fp]),
-    "visfd_hip_select_histogram_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_uint32,
-                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    "visfd_hip_select_histogram_todev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, C.c_uint32, _vp]),
-    "visfd_hip_get_stream": (_vp, [_vp]),
-    "visfd_hip_apply_threshold_dev": (C.c_int, [_vp, _vp, _i64, C.c_float]),
-    "visfd_hip_tv_dense_stick": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int,
-                                           C.c_float, C.c_int]),
-    "visfd_hip_tv_dense_stick_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int,
-                                               C.c_float, C.c_int]),
-    "visfd_hip_tv_dense_stick_slab_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                                    C.c_float, C.c_int, C.c_float, C.c_int]),
-    "visfd_hip_tv_tables": (C.c_int, [C.c_float, C.c_float, _ip, _fp, _fp]),
-    "visfd_hip_tv_weight_sum": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float]),
-    "visfd_hip_membrane_detect": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float,
-                                            C.c_float, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp, _fp]),
-    "visfd_hip_membrane_detect_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int,
-                                                C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, _vp, _vp, _vp,
-                                                _fp]),
-    "visfd_hip_tensor_saliency": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
-    "visfd_hip_tensor_saliency_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
-    # the peak-height factor (`-membrane-background`)
-    "visfd_hip_peak_background_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, _vp]),
-    "visfd_hip_ridge_scores_bg_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
-    "visfd_hip_tensor_saliency_bg_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
-    "visfd_hip_membrane_detect_bg": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float,
-                                               C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _fp]),
-    "visfd_hip_membrane_detect_bg_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int,
-                                                   C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int,
-                                                   _vp, _vp, _vp, _fp]),
-    # the stage on the caller's arrays (pipeline.membrane_detect) and the test aids of its consumers
-    "visfd_hip_membrane_stage_dev": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float,
-                                               C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _vp, _vp, _fp]),
-    "visfd_hip_debug_ridge_directions_thr_dev": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_float, C.c_int, _vp, _vp, _vp]),
-    "visfd_hip_debug_tv_lists_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp,
-                                               _vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint32)]),
-    "visfd_hip_membrane_detect_slab_bg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int,
-                                                        C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _fp]),
-    "visfd_hip_membrane_detect_slab_bg": (C.c_int, [_vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
-                                                    C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, _fp]),
-    "visfd_hip_bin_array3d": (C.c_int, [_vp, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _ip]),
-    "visfd_hip_bin_array3d_dev": (C.c_int, [_vp, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _ip]),
-    "visfd_hip_unbin_array3d": (C.c_int, [_vp, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _ip]),
-    "visfd_hip_unbin_array3d_dev": (C.c_int, [_vp, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _ip]),
-    "visfd_hip_label_connected": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float, C.c_float, C.c_int,
-                                            _vp, C.c_float, C.c_float, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int,
-                                            C.POINTER(_i64), _vp, _vp, _vp, _i64]),
-    "visfd_hip_label_connected_ex": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float, C.c_float, C.c_int,
-                                               _vp, C.c_float, C.c_float, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_int,
-                                               C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    # LabelConnected with its seed search on the device (csrc/connect_seeds.hip): the _ex arguments after the context
-    "visfd_hip_label_connected_device_seeds": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_float, _vp, C.c_float,
-                                                         C.c_float, C.c_int, _vp, C.c_float, C.c_float, C.c_int, C.c_int, _i64,
-                                                         C.c_int, C.c_int, C.c_int, C.POINTER(_i64), _vp, _vp, _vp, _i64, _vp,
-                                                         _vp, _vp, _i64, _vp]),
-    "visfd_hip_label_connected_device_seeds_last": (C.c_int, [_vp, _ip, C.POINTER(_i64)]),
-    # LabelConnected as a graph problem (csrc/connect_graph.hip, connect_graph_host.cpp): the _ex arguments, after the context
-    # where there is one
-    "visfd_hip_label_connected_graph": (C.c_int, [_vp] + _LABEL_CONNECTED_EX),
-    "visfd_hip_label_connected_graph_dev": (C.c_int, [_vp] + _LABEL_CONNECTED_EX),
-    "visfd_hip_label_connected_graph_host": (C.c_int, list(_LABEL_CONNECTED_EX)),
-    "visfd_hip_label_connected_graph_last": (C.c_int, [_vp, _ip, C.POINTER(C.c_uint), C.POINTER(_i64), C.POINTER(_i64)]),
-    "visfd_hip_label_connected_graph_last_times": (C.c_int, [_vp, _fp]),
-    "visfd_hip_label_connected_graph_last_settled": (C.c_int, [_vp, C.POINTER(C.c_uint)]),
-    "visfd_hip_principal_directions_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
-    "visfd_hip_tensor_saliency_host": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
-    "visfd_hip_diagonalize_sym3_f32_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
-    "visfd_hip_diagonalize_flat_sym3_host": (C.c_int, [_vp, _vp, _i64, C.c_int]),
-    "visfd_hip_convert_flat_sym2_evects3_host": (C.c_int, [_vp, C.c_int, _vp, _vp]),
-    "visfd_hip_surface_points": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int, C.c_float,
-                                           _vp, _vp, _i64, C.POINTER(_i64)]),
-    # the same behind a context (csrc/surface_points.hip)
-    "visfd_hip_surface_points_ctx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int,
-                                               C.c_float, _vp, _vp, _i64, C.POINTER(_i64)]),
-    "visfd_hip_surface_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _fp, C.c_float, C.c_int,
-                                               C.c_float, _vp, _vp, _i64, C.POINTER(_i64)]),
-    "visfd_hip_surface_points_last": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_surface_points_last_times": (C.c_int, [_vp, _fp]),
-    "visfd_hip_sphere_overlap": (C.c_float, [C.c_float, C.c_float, C.c_float]),
-    "visfd_hip_sort_blobs": (C.c_int, [_fp, _fp, _fp, _i64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
-    "visfd_hip_discard_masked_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), _vp, _i64, _i64, _i64]),
-    "visfd_hip_discard_overlapping_blobs": (C.c_int, [_fp, _fp, _fp, C.POINTER(_i64), C.c_float, C.c_float,
-                                                     C.c_float, C.c_int, C.c_int]),
-    # DiscardOverlappingBlobs on the device (csrc/discard_overlap.hip)
-    "visfd_hip_discard_overlapping_blobs_ctx": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), C.c_float, C.c_float,
-                                                         C.c_float, C.c_int, C.c_int]),
-    "visfd_hip_discard_overlapping_blobs_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), C.c_float, C.c_float,
-                                                         C.c_float, C.c_int, C.c_int]),
-    "visfd_hip_discard_overlapping_blobs_last": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_discard_overlapping_blobs_last_times": (C.c_int, [_vp, _fp]),
-    # VoxelizeMesh (csrc/voxelize.hip)
-    "visfd_hip_voxelize_mesh": (C.c_int, _VOXELIZE),
-    "visfd_hip_voxelize_mesh_dev": (C.c_int, _VOXELIZE),
-    "visfd_hip_voxelize_last": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_voxelize_last_times": (C.c_int, [_vp, _fp]),
-    "visfd_hip_voxelize_quantize_host": (C.c_int, [_vp, _i64, C.c_double, C.POINTER(C.c_double), _vp]),
-    "visfd_hip_mesh_edges_host": (C.c_int, [_vp, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
-    # close_surface (csrc/close_surface.hip)
-    "visfd_hip_close_surface": (C.c_int, _CLOSE),
-    "visfd_hip_close_surface_dev": (C.c_int, _CLOSE),
-    "visfd_hip_close_surface_splat": (C.c_int, _CLOSE_SPLAT),
-    "visfd_hip_close_surface_splat_dev": (C.c_int, _CLOSE_SPLAT),
-    "visfd_hip_close_surface_splat_host": (C.c_int, _CLOSE_SPLAT[1:]),
-    "visfd_hip_close_surface_last": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
-    "visfd_hip_close_surface_last_times": (C.c_int, [_vp, _fp]),
-    # the isosurface mesh (csrc/isosurface.hip)
-    "visfd_hip_isosurface": (C.c_int, [_vp] + _ISOSURFACE),
-    "visfd_hip_isosurface_dev": (C.c_int, [_vp] + _ISOSURFACE),
-    "visfd_hip_isosurface_host": (C.c_int, _ISOSURFACE),
-    "visfd_hip_isosurface_last": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_isosurface_last_times": (C.c_int, [_vp, _fp]),
-    # FindSpheres and the supervised score thresholds (csrc/find_spheres.hip, csrc/blob_post.cpp)
-    "visfd_hip_find_spheres_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
-    "visfd_hip_find_spheres": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "visfd_hip_find_spheres_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "visfd_hip_find_spheres_last_path": (C.c_int, [_vp, _ip]),
-    "visfd_hip_choose_threshold_1d": (C.c_int, [_vp, _vp, _i64, C.c_int, _fp]),
-    "visfd_hip_find_blob_scores": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
-    "visfd_hip_choose_blob_score_thresholds": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_int, _fp, _fp,
-                                                        _vp]),
-    "visfd_hip_choose_blob_score_thresholds_multi": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
-                                                              _fp, _fp, _vp]),
-    "visfd_hip_discard_blobs_by_score_supervised": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _i64, _vp, _i64,
-                                                             C.c_int, _fp, _fp, _vp]),
-    # Z-slab runs (csrc/slab.hip)
-    "visfd_hip_slab_unique_id": (C.c_int, [_vp]),
-    "visfd_hip_slab_create_rccl": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, C.c_int, C.POINTER(_vp)]),
-    "visfd_hip_slab_create_custom": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i64, C.c_int, C.POINTER(_vp)]),
-    "visfd_hip_slab_destroy": (C.c_int, [_vp]),
-    "visfd_hip_slab_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
-    "visfd_hip_slab_set_reserve": (C.c_int, [_vp, C.c_int]),
-    "visfd_hip_slab_rccl_available": (C.c_int, []),
-    "visfd_hip_apply_gauss_slab": (C.c_int, [_vp, _vp, _i64, _i64, _fp, _ip, C.c_int, _vp, _fp]),
-    "visfd_hip_blob_dog_slab": (C.c_int, [_vp, _vp, _i64, _i64, _fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64)]),
-    "visfd_hip_blob_halo_depth": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, _ip]),
-    "visfd_hip_slab_selftest": (C.c_int, [_vp, _i64]),
-    "visfd_hip_slab_exchange_dev": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _i64, _i64, C.c_int]),
-    "visfd_hip_membrane_detect_slab_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int,
-                                                     C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, _fp]),
-    "visfd_hip_membrane_detect_slab": (C.c_int, [_vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
-                                                 C.c_int, C.c_float, _vp, _vp, _fp]),
-    "visfd_hip_blob_dog_slab_dev": (C.c_int, [_vp, _vp, _i64, _i64, _fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                              C.c_int, _vp, _i64, C.POINTER(_i64), _vp, _i64, C.POINTER(_i64)]),
-}
+
+_SIGS = _header_signatures()
 
 _SENDRECV = C.CFUNCTYPE(C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp)
 _ALLREDUCE = C.CFUNCTYPE(C.c_int, _vp, _vp, C.c_size_t, _vp)
@@ -465,6 +250,22 @@ def _dev(t):
         return None
     assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float32", "need contiguous cuda float32"
     return t.data_ptr()
+
+
+# A face of the C ABI as Context._rc takes it: (symbol suffix, converter of float32 arrays to addresses).  _HOST_CTX: the few
+# host-array entries named visfd_hip_<op>_ctx, where the plain name is the entry without a context.
+_HOST, _HOST_CTX, _DEVICE = ("", _np), ("_ctx", _np), ("_dev", _dev)
+_DEVICE_PLAIN = ("", _dev)   # device tensors behind a name without the suffix (visfd_hip_select_histogram_todev)
+
+
+def _face_of(a):
+    """The face of the methods that take numpy arrays or torch device tensors alike"""
+    return _HOST if isinstance(a, np.ndarray) else _DEVICE
+
+
+def _address(a):
+    """Where an array of any element type starts: numpy on the host, torch on the device (checked by the caller)"""
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
 
 
 def _points(points):
@@ -766,7 +567,7 @@ def label_connected_graph(saliency, threshold_saliency, mask=None, direction=Non
     if ctx is None:
         _chk_host(L, L.visfd_hip_label_connected_graph_host(*args))
     else:
-        _chk_host(L, L.visfd_hip_label_connected_graph(ctx._h, *args))
+        ctx._call("label_connected_graph", _HOST, *args)
     k = n.value
     return labels, k, cm[:k], cs[:k], csal[:k]
 
@@ -1231,17 +1032,17 @@ class Context:
             pass
 
     def synchronize(self):
-        self._chk(self._L.visfd_hip_synchronize(self._h))
+        self._call("synchronize", _HOST)
 
     def trim(self):
-        self._chk(self._L.visfd_hip_trim(self._h))
+        self._call("trim", _HOST)
 
     def workspace_bytes(self):
         return int(self._L.visfd_hip_workspace_bytes(self._h))
 
     def debug_poison_workspace(self):
         """Test aid (visfd_hip_debug_poison_workspace): 0xFF bytes in every workspace slot, in-slot caches forgotten."""
-        self._chk(self._L.visfd_hip_debug_poison_workspace(self._h))
+        self._call("debug_poison_workspace", _HOST)
 
     def blob_jobs_pending(self):
         return int(self._L.visfd_hip_blob_jobs_pending(self._h))
@@ -1251,11 +1052,11 @@ class Context:
 
     def set_option(self, name, value):
         """Tuning / test switch of this context (include/visfd_hip.h: visfd_hip_set_option)."""
-        self._chk(self._L.visfd_hip_set_option(self._h, name.encode(), int(value)))
+        self._call("set_option", _HOST, name.encode(), int(value))
 
     def get_option(self, name):
         v = C.c_int64()
-        self._chk(self._L.visfd_hip_get_option(self._h, name.encode(), C.byref(v)))
+        self._call("get_option", _HOST, name.encode(), C.byref(v))
         return int(v.value)
 
     def options(self, **kw):
@@ -1276,75 +1077,171 @@ class Context:
                 return False
         return _Scope()
 
-    # ---------------------------------------------------------------- host face (numpy)
-    def separable3d(self, src, taps_xyz, mask=None, normalize=True):
+    # ---------------------------------------------------------------- the call both faces go through
+    # Every operation below marshals its scalars once, in a private method that takes a face; its public methods are the
+    # host face (numpy: allocates or copies the output, shapes the return value) and the device face (`_dev`: the caller's
+    # torch tensors, asynchronous on the context's stream).
+    def _rc(self, name, face, *args):
+        """visfd_hip_<name><suffix>(ctx, *args) -> its return code.  face = (symbol suffix, pointer converter): _HOST,
+        _HOST_CTX or _DEVICE.  numpy arrays and torch tensors among the arguments go through the converter (float32,
+        contiguous, on the face's side); integers, floats, ctypes objects and None are passed as they are."""
+        suffix, ptr = face
+        fn = getattr(self._L, "visfd_hip_" + name + suffix)
+        return fn(self._h, *[ptr(a) if isinstance(a, np.ndarray) or hasattr(a, "data_ptr") else a for a in args])
+
+    def _call(self, name, face, *args):
+        self._chk(self._rc(name, face, *args))
+
+    def _vol(self, name, face, src, dst, mask, *args):
+        """_call for the entries that begin (ctx, src, dst, mask, nx, ny, nz, ...)"""
         nz, ny, nx = src.shape
+        self._call(name, face, src, dst, mask, nx, ny, nz, *args)
+
+    def _last_path(self, name):
+        """visfd_hip_<name>_last_path: which kernel the last call of that family ran (-1 before the first)"""
+        p = C.c_int(-1)
+        self._call(name + "_last_path", _HOST, C.byref(p))
+        return int(p.value)
+
+    def _last_times(self, name, n):
+        """visfd_hip_<name>_last_times: the n phase times of the last call, in milliseconds"""
+        ms = (C.c_float * n)()
+        self._call(name + "_last_times", _HOST, ms)
+        return tuple(ms)
+
+    # ---------------------------------------------------------------- filters
+    def separable3d(self, src, taps_xyz, mask=None, normalize=True):
         dst = np.empty_like(src)
         A = C.c_float()
         t = [np.ascontiguousarray(x, np.float32) for x in taps_xyz]
         h = [(len(x) - 1) // 2 for x in t]
-        self._chk(self._L.visfd_hip_separable3d(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
-                                                t[0].ctypes.data_as(_fp), h[0], t[1].ctypes.data_as(_fp), h[1],
-                                                t[2].ctypes.data_as(_fp), h[2], int(normalize), C.byref(A)))
+        self._vol("separable3d", _HOST, src, dst, mask, t[0].ctypes.data_as(_fp), h[0], t[1].ctypes.data_as(_fp), h[1],
+                  t[2].ctypes.data_as(_fp), h[2], int(normalize), C.byref(A))
         return dst, A.value
 
-    def gauss_hw(self, src, sigma, hw, mask=None, normalize=True):
-        nz, ny, nx = src.shape
-        dst = np.empty_like(src)
+    def _gauss(self, face, src, dst, mask, sigma, hw, normalize):
         A = C.c_float()
-        self._chk(self._L.visfd_hip_apply_gauss(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(sigma),
-                                                _i3(hw), int(normalize), C.byref(A)))
-        return dst, A.value
+        self._vol("apply_gauss", face, src, dst, mask, _f3(sigma), _i3(hw), int(normalize), C.byref(A))
+        return A.value
+
+    def gauss_hw(self, src, sigma, hw, mask=None, normalize=True):
+        dst = np.empty_like(src)
+        return dst, self._gauss(_HOST, src, dst, mask, sigma, hw, normalize)
+
+    def gauss_dev(self, src, dst, sigma, hw, mask=None, normalize=True):
+        return self._gauss(_DEVICE, src, dst, mask, sigma, hw, normalize)
 
     def gauss_ratio(self, src, sigma, ratio, mask=None, normalize=True):
         return self.gauss_hw(src, sigma, gauss_halfwidths(sigma, ratio), mask, normalize)
 
+    def gauss_slab_dev(self, src, dst, z_lo, nz_global, sigma, hw, normalize=True):
+        nz, ny, nx = src.shape
+        A = C.c_float()
+        self._call("apply_gauss_slab", _DEVICE, src, dst, nx, ny, nz, int(z_lo), int(nz_global), _f3(sigma), _i3(hw),
+                   int(normalize), C.byref(A))
+        return A.value
+
+    def _local_fluctuations(self, name, face, src, dst, mask, sigma, ratio, normalize, exponent):
+        self._vol(name, face, src, dst, mask, _f3(sigma), float(exponent), float(ratio), int(normalize))
+
     def local_fluctuations(self, src, sigma, ratio, mask=None, normalize=True, exponent=2.0):
         """LocalFluctuations (filter3d.hpp:1698-1853), Gaussian weights."""
-        nz, ny, nx = src.shape
         dst = np.empty_like(src)
-        self._chk(self._L.visfd_hip_local_fluctuations(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(sigma),
-                                                       float(exponent), float(ratio), int(normalize)))
+        self._local_fluctuations("local_fluctuations", _HOST, src, dst, mask, sigma, ratio, normalize, exponent)
         return dst
+
+    def local_fluctuations_dev(self, src, dst, sigma, ratio, mask=None, normalize=True, exponent=2.0):
+        self._local_fluctuations("local_fluctuations", _DEVICE, src, dst, mask, sigma, ratio, normalize, exponent)
 
     def local_fluctuations_gen(self, src, sigma, ratio, mask=None, normalize=True, exponent=2.0):
         """LocalFluctuations (filter3d.hpp:1698-1853) for any exponent: the dense generalised-Gaussian window unless the
         exponent is 2, which takes the separable path of local_fluctuations."""
-        nz, ny, nx = src.shape
         dst = np.empty_like(src)
-        self._chk(self._L.visfd_hip_local_fluctuations_gen(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
-                                                           _f3(sigma), float(exponent), float(ratio), int(normalize)))
+        self._local_fluctuations("local_fluctuations_gen", _HOST, src, dst, mask, sigma, ratio, normalize, exponent)
         return dst
+
+    def local_fluctuations_gen_dev(self, src, dst, sigma, ratio, mask=None, normalize=True, exponent=2.0):
+        self._local_fluctuations("local_fluctuations_gen", _DEVICE, src, dst, mask, sigma, ratio, normalize, exponent)
+
+    def _filter3d(self, face, src, dst, mask, table, normalize, den):
+        t, hw = _filter_table(table)
+        self._vol("filter3d", face, src, dst, mask, t.ctypes.data_as(_fp), hw, int(normalize), den)
 
     def filter3d(self, src, table, mask=None, normalize=False, want_den=False):
         """Filter3D::Apply (filter3d.hpp:81-198) with a table (2hz+1, 2hy+1, 2hx+1) indexed [jz][jy][jx]: -> dst, or
         (dst, den) with want_den (the second Apply overload's denominator).  Voxels with mask == 0 get 0 in both."""
-        nz, ny, nx = src.shape
-        t, hw = _filter_table(table)
         dst = np.empty_like(src)
         den = np.empty_like(src) if want_den else None
-        self._chk(self._L.visfd_hip_filter3d(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, t.ctypes.data_as(_fp), hw,
-                                             int(normalize), _np(den)))
+        self._filter3d(_HOST, src, dst, mask, table, normalize, den)
         return (dst, den) if want_den else dst
+
+    def filter3d_dev(self, src, dst, table, mask=None, normalize=False, den=None):
+        """filter3d on device tensors (the table is a host array); den: optional tensor for the denominator."""
+        self._filter3d(_DEVICE, src, dst, mask, table, normalize, den)
+
+    def filter3d_last_path(self):
+        """The kernel the last general-filter call ran: FILTER3D_PATH_GENERAL or FILTER3D_PATH_TILED (-1 before the first)."""
+        return self._last_path("filter3d")
+
+    def _apply_ggauss(self, face, src, dst, mask, width, m_exp, halfwidth, normalize):
+        A = C.c_float()
+        self._vol("apply_ggauss", face, src, dst, mask, _f3(width), float(m_exp), _i3(halfwidth), int(normalize), C.byref(A))
+        return A.value
 
     def apply_ggauss(self, src, width, m_exp, halfwidth, mask=None, normalize=True):
         """HandleGGauss (handlers.cpp:167-187): GenFilterGenGauss3D(width, m_exp, halfwidth) applied -> (dst, A)."""
-        nz, ny, nx = src.shape
         dst = np.empty_like(src)
-        A = C.c_float()
-        self._chk(self._L.visfd_hip_apply_ggauss(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(width),
-                                                 float(m_exp), _i3(halfwidth), int(normalize), C.byref(A)))
-        return dst, A.value
+        return dst, self._apply_ggauss(_HOST, src, dst, mask, width, m_exp, halfwidth, normalize)
+
+    def apply_ggauss_dev(self, src, dst, width, m_exp, halfwidth, mask=None, normalize=True):
+        return self._apply_ggauss(_DEVICE, src, dst, mask, width, m_exp, halfwidth, normalize)
+
+    def _apply_dogg(self, face, src, dst, mask, width_a, width_b, m_exp, n_exp, truncate_ratio, truncate_threshold):
+        A, B = C.c_float(), C.c_float()
+        self._vol("apply_dogg", face, src, dst, mask, _f3(width_a), _f3(width_b), float(m_exp), float(n_exp),
+                  float(truncate_ratio), float(truncate_threshold), C.byref(A), C.byref(B))
+        return A.value, B.value
 
     def apply_dogg(self, src, width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03, mask=None):
         """HandleDogg (handlers.cpp:265-293): GenFilterDogg3D applied, never normalised -> (dst, A, B)."""
-        nz, ny, nx = src.shape
+        dst = np.empty_like(src)
+        return (dst,) + self._apply_dogg(_HOST, src, dst, mask, width_a, width_b, m_exp, n_exp, truncate_ratio,
+                                         truncate_threshold)
+
+    def apply_dogg_dev(self, src, dst, width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03,
+                       mask=None):
+        return self._apply_dogg(_DEVICE, src, dst, mask, width_a, width_b, m_exp, n_exp, truncate_ratio, truncate_threshold)
+
+    def dog(self, src, sigma_a, sigma_b, hw, mask=None):
         dst = np.empty_like(src)
         A, B = C.c_float(), C.c_float()
-        self._chk(self._L.visfd_hip_apply_dogg(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(width_a),
-                                               _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio),
-                                               float(truncate_threshold), C.byref(A), C.byref(B)))
+        self._vol("apply_dog", _HOST, src, dst, mask, _f3(sigma_a), _f3(sigma_b), _i3(hw), C.byref(A), C.byref(B))
         return dst, A.value, B.value
+
+    def _log(self, face, src, dst, mask, sigma, delta, ratio, A, B):
+        self._vol("apply_log", face, src, dst, mask, _f3(sigma), float(delta), float(ratio), A, B)
+
+    def log(self, src, sigma, delta, ratio, mask=None):
+        dst = np.empty_like(src)
+        A, B = C.c_float(), C.c_float()
+        self._log(_HOST, src, dst, mask, sigma, delta, ratio, C.byref(A), C.byref(B))
+        return dst, A.value, B.value
+
+    def log_dev(self, src, dst, sigma, delta, ratio, mask=None):
+        """ApplyLog on device tensors; dst may be src.  Unmasked scales with one half-width 6..10 run both Gaussians in two
+        shared launches (csrc/gauss_pair.hip); options log_pair (0 never, 1 by its table, 2 wherever it applies) and
+        log_pair_chunk (march length, for tests).  The bits are the same on every route."""
+        self._log(_DEVICE, src, dst, mask, sigma, delta, ratio, None, None)
+
+    # ---------------------------------------------------------------- drawing, meshes, point clouds
+    def _draw_spheres(self, face, dst, mask, background, centers, diameters, shell_thicknesses, foreground, background_offset,
+                      background_rescale, background_normalize, foreground_normalize):
+        nz, ny, nx = background.shape
+        n, p, keep = _sphere_lists(centers, diameters, shell_thicknesses, foreground)
+        outside = C.c_int()
+        self._call("draw_spheres", face, dst, mask, background, nx, ny, nz, p[0], p[1], p[2], p[3], n, float(background_offset),
+                   float(background_rescale), int(background_normalize), int(foreground_normalize), C.byref(outside))
+        return bool(outside.value)
 
     def draw_spheres(self, background, centers, diameters=None, shell_thicknesses=None, foreground=None, mask=None,
                      background_offset=0.0, background_rescale=1.0, background_normalize=False,
@@ -1352,54 +1249,116 @@ class Context:
         """DrawSpheres (draw.hpp:238-457): spheres or shells at centers (n, 3) in voxels (x, y, z) over the rescaled
         background; later spheres overwrite earlier ones.  None lists take the reference's defaults (diameter 0, solid,
         foreground 1).  -> dst, or (dst, any_center_outside) with want_outside."""
-        nz, ny, nx = background.shape
         dst = np.empty_like(background)
-        n, p, keep = _sphere_lists(centers, diameters, shell_thicknesses, foreground)
-        outside = C.c_int()
-        self._chk(self._L.visfd_hip_draw_spheres(self._h, _np(dst), _np(mask), _np(background), nx, ny, nz, p[0], p[1], p[2],
-                                                 p[3], n, float(background_offset), float(background_rescale),
-                                                 int(background_normalize), int(foreground_normalize), C.byref(outside)))
-        return (dst, bool(outside.value)) if want_outside else dst
+        outside = self._draw_spheres(_HOST, dst, mask, background, centers, diameters, shell_thicknesses, foreground,
+                                     background_offset, background_rescale, background_normalize, foreground_normalize)
+        return (dst, outside) if want_outside else dst
+
+    def draw_spheres_dev(self, dst, background, centers, diameters=None, shell_thicknesses=None, foreground=None, mask=None,
+                         background_offset=0.0, background_rescale=1.0, background_normalize=False,
+                         foreground_normalize=False):
+        """draw_spheres on device tensors (the lists are host arrays); dst may be background.  -> any_center_outside"""
+        return self._draw_spheres(_DEVICE, dst, mask, background, centers, diameters, shell_thicknesses, foreground,
+                                  background_offset, background_rescale, background_normalize, foreground_normalize)
+
+    def _draw_regions(self, face, dst, mask, regions, negative_means_subtract):
+        nz, ny, nx = dst.shape
+        arr, n = _regions(regions)
+        self._call("draw_regions", face, dst, mask, nx, ny, nz, arr, n, int(negative_means_subtract))
+
+    def draw_regions(self, image, regions, mask=None, negative_means_subtract=False):
+        """DrawRegions (draw.hpp:90-224) on a copy of `image`: regions is a list of (REGION_RECT, (xmin, xmax, ymin, ymax,
+        zmin, zmax), value) and (REGION_SPHERE, (x0, y0, z0, r), value), acting in list order -> the new image."""
+        dst = np.array(image, np.float32, copy=True, order="C")
+        self._draw_regions(_HOST, dst, mask, regions, negative_means_subtract)
+        return dst
+
+    def draw_regions_dev(self, dst, regions, mask=None, negative_means_subtract=False):
+        """draw_regions on a device tensor, in place (the region list is a host array)."""
+        self._draw_regions(_DEVICE, dst, mask, regions, negative_means_subtract)
+
+    def draw_last_times(self):
+        """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""
+        return self._last_times("draw", 3)
+
+    def _voxelize_mesh(self, face, dst, vertices, triangles, voxel_width, origin, check_closed):
+        nz, ny, nx = dst.shape
+        v, t = _mesh(vertices, triangles)
+        self._call("voxelize_mesh", face, v.ctypes.data, len(v), t.ctypes.data, len(t), float(voxel_width), _d3(origin),
+                   nx, ny, nz, int(bool(check_closed)), dst)
 
     def voxelize_mesh(self, vertices, triangles, shape, voxel_width=1.0, origin=(0, 0, 0), check_closed=True):
         """Which samples of an image of `shape` (nz, ny, nx) lie inside the closed triangle mesh (the job of the reference's
         voxelize_mesh.py, by the exact rule of include/visfd_hip.h): vertices (n, 3) float32 (x, y, z) in physical units,
         triangles (m, 3) int32, origin = the position of voxel 0 in voxels.  -> float32 [nz, ny, nx] of 0 and 1."""
-        nz, ny, nx = [int(s) for s in shape]
-        v, t = _mesh(vertices, triangles)
-        dst = np.empty((nz, ny, nx), np.float32)
-        self._chk(self._L.visfd_hip_voxelize_mesh(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t), float(voxel_width),
-                                                  _d3(origin), nx, ny, nz, int(bool(check_closed)), _np(dst)))
+        dst = np.empty(tuple(int(s) for s in shape), np.float32)
+        self._voxelize_mesh(_HOST, dst, vertices, triangles, voxel_width, origin, check_closed)
         return dst
+
+    def voxelize_mesh_dev(self, dst, vertices, triangles, voxel_width=1.0, origin=(0, 0, 0), check_closed=True):
+        """voxelize_mesh into a device tensor [nz, ny, nx] (the mesh lists are host arrays); returns with the stream idle."""
+        self._voxelize_mesh(_DEVICE, dst, vertices, triangles, voxel_width, origin, check_closed)
+
+    def voxelize_last(self):
+        """(crossings, skipped triangles, odd rows, inside voxels) of the last voxelize_mesh[_dev]."""
+        s = (_i64 * 4)()
+        self._call("voxelize_last", _HOST, s)
+        return tuple(int(x) for x in s)
+
+    def voxelize_last_times(self):
+        """(zero fill, scatter, fill) milliseconds of the last voxelize_mesh[_dev] under the option voxelize_time."""
+        return self._last_times("voxelize", 3)
+
+    def _close_surface(self, face, points, normals, n, shape, pad, orientation, mask, chi):
+        nz, ny, nx = shape
+        self._call("close_surface", face, points if n else None, normals if n else None, n, nx, ny, nz, int(pad),
+                   _orientation(orientation), mask, chi)
 
     def close_surface(self, points, normals, shape, pad=0, orientation="outward", want_chi=False):
         """An oriented point cloud closed into a mask (include/visfd_hip.h): points and normals (n, 3) float32
         (x, y, z) in voxel coordinates, shape (nz, ny, nx), orientation "outward", "inward" or "auto".
         -> float32 [nz, ny, nx] of 0 and 1, or (mask, chi) with want_chi."""
-        nz, ny, nx = [int(s) for s in shape]
+        shape = tuple(int(s) for s in shape)
         p, m = _cloud(points, normals)
-        mask = np.empty((nz, ny, nx), np.float32)
-        chi = np.empty((nz, ny, nx), np.float32) if want_chi else None
-        self._chk(self._L.visfd_hip_close_surface(self._h, p.ctypes.data if len(p) else None, m.ctypes.data if len(p) else None,
-                                                  len(p), nx, ny, nz, int(pad), _orientation(orientation), _np(mask), _np(chi)))
+        mask = np.empty(shape, np.float32)
+        chi = np.empty(shape, np.float32) if want_chi else None
+        self._close_surface(_HOST, p, m, len(p), shape, pad, orientation, mask, chi)
         return (mask, chi) if want_chi else mask
+
+    def close_surface_dev(self, mask, points, normals, pad=0, orientation="outward", chi=None):
+        """close_surface on device tensors: mask (and chi, optional) [nz, ny, nx], points and normals (n, 3) float32; returns
+        with the stream idle."""
+        n = int(points.shape[0])
+        assert tuple(points.shape) == (n, 3) and tuple(normals.shape) == (n, 3), "points and normals are (n, 3)"
+        self._close_surface(_DEVICE, points, normals, n, mask.shape, pad, orientation, mask, chi)
+
+    def _close_surface_splat(self, face, points, normals, n, shape, pad, acc):
+        nz, ny, nx = shape
+        counts = (_i64 * 2)()
+        self._call("close_surface_splat", face, points if n else None, normals if n else None, n, nx, ny, nz, int(pad), acc,
+                   counts)
+        return int(counts[0]), int(counts[1])
 
     def close_surface_splat(self, points, normals, shape, pad=0):
         """Step 1 of close_surface on the device -> (acc int64 [3, Nz, Ny, Nx], used points, skipped points)."""
         nz, ny, nx = [int(s) for s in shape]
         p, m = _cloud(points, normals)
         acc = np.empty((3, max(nz + 2 * pad, 0), max(ny + 2 * pad, 0), max(nx + 2 * pad, 0)), np.int64)
-        counts = (_i64 * 2)()
-        self._chk(self._L.visfd_hip_close_surface_splat(self._h, p.ctypes.data if len(p) else None,
-                                                        m.ctypes.data if len(p) else None, len(p), nx, ny, nz, int(pad),
-                                                        acc.ctypes.data, counts))
-        return acc, int(counts[0]), int(counts[1])
+        return (acc,) + self._close_surface_splat(_HOST, p, m, len(p), (nz, ny, nx), pad, acc.ctypes.data)
+
+    def close_surface_splat_dev(self, acc, points, normals, shape, pad=0):
+        """close_surface_splat on device tensors: acc int64 [3, Nz, Ny, Nx] -> (used points, skipped points)."""
+        nz, ny, nx = [int(s) for s in shape]
+        n = int(points.shape[0])
+        assert acc.is_cuda and acc.is_contiguous() and str(acc.dtype) == "torch.int64", "need contiguous cuda int64"
+        assert tuple(acc.shape) == (3, nz + 2 * pad, ny + 2 * pad, nx + 2 * pad), "acc is [3, Nz, Ny, Nx]"
+        return self._close_surface_splat(_DEVICE, points, normals, n, (nz, ny, nx), pad, acc.data_ptr())
 
     def close_surface_last(self):
         """The last close_surface[_dev]: dict with n_used, n_skipped, cycles, stop (CLOSE_STOP_*), orientation
         ("outward" or "inward"), touches_face, ratio (the final residual ratio) and iso."""
         s, v = (_i64 * 6)(), (C.c_double * 2)()
-        self._chk(self._L.visfd_hip_close_surface_last(self._h, s, v))
+        self._call("close_surface_last", _HOST, s, v)
         return {"n_used": int(s[0]), "n_skipped": int(s[1]), "cycles": int(s[2]), "stop": int(s[3]),
                 "orientation": "inward" if s[4] == CLOSE_INWARD else "outward", "touches_face": int(s[5]),
                 "ratio": float(v[0]), "iso": float(v[1])}
@@ -1407,66 +1366,67 @@ class Context:
     def close_surface_last_times(self):
         """(splat and right-hand side, solve, level and cut) milliseconds of the last close_surface[_dev] under the option
         close_surface_time."""
-        ms = (C.c_float * 3)()
-        self._chk(self._L.visfd_hip_close_surface_last_times(self._h, ms))
-        return tuple(ms)
+        return self._last_times("close_surface", 3)
+
+    def _isosurface(self, face, vol, shape, *rest):
+        nz, ny, nx = shape
+        return _isosurface(lambda *tail: self._rc("isosurface", face, vol, nx, ny, nz, *tail), self._L, *rest)
 
     def isosurface(self, vol, iso, side="below", vertices=None, triangles=None, count_only=False):
         """isosurface_host's mesh, bit for bit, by the kernels of csrc/isosurface.hip: vol float32 [nz, ny, nx] on the host
         -> (vertices float32 (n, 3), triangles int32 (m, 3)); with arrays to write into -> (n_vertices, n_triangles), as
         isosurface_host."""
         vol = np.ascontiguousarray(vol, np.float32)
-        nz, ny, nx = vol.shape if vol.ndim == 3 else (0, 0, 0)
-        return _isosurface(lambda *tail: self._L.visfd_hip_isosurface(self._h, vol.ctypes.data, nx, ny, nz, *tail), self._L,
-                           iso, side, _iso_host_alloc,
-                           None if vertices is None else _iso_host_array(vertices, np.float32, "vertices"),
-                           None if triangles is None else _iso_host_array(triangles, np.int32, "triangles"), count_only)
+        return self._isosurface(_HOST, vol, vol.shape if vol.ndim == 3 else (0, 0, 0), iso, side, _iso_host_alloc,
+                                None if vertices is None else _iso_host_array(vertices, np.float32, "vertices"),
+                                None if triangles is None else _iso_host_array(triangles, np.int32, "triangles"), count_only)
+
+    def isosurface_dev(self, vol, iso, side="below", vertices=None, triangles=None, count_only=False):
+        """isosurface on device tensors: vol float32 [nz, ny, nx] -> (vertices float32 (n, 3), triangles int32 (m, 3)) as new
+        tensors on vol's device; with tensors to write into -> (n_vertices, n_triangles), as isosurface_host.  Returns with
+        the stream idle."""
+        import torch
+
+        def given(t, dtype, what):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3, \
+                what + " must be a contiguous cuda (n, 3) tensor of " + str(dtype)
+            return t, t.data_ptr(), int(t.shape[0])
+
+        def alloc(rows, kind):
+            t = torch.empty((rows, 3), dtype=torch.float32 if kind == "vertices" else torch.int32, device=vol.device)
+            return t, t.data_ptr()
+
+        return self._isosurface(_DEVICE, vol, vol.shape, iso, side, alloc,
+                                None if vertices is None else given(vertices, torch.float32, "vertices"),
+                                None if triangles is None else given(triangles, torch.int32, "triangles"), count_only)
 
     def isosurface_last(self):
         """The last isosurface[_dev]: dict with n_vertices, n_triangles, n_inside (inside nodes) and capped (1 when the
         image border cut the solid and the border layer closed it there)."""
         s = (_i64 * 4)()
-        self._chk(self._L.visfd_hip_isosurface_last(self._h, s))
+        self._call("isosurface_last", _HOST, s)
         return {"n_vertices": int(s[0]), "n_triangles": int(s[1]), "n_inside": int(s[2]), "capped": int(s[3])}
 
     def isosurface_last_times(self):
         """(classify, scan and the host's read of the totals, vertices, triangles) milliseconds of the last isosurface[_dev]
         under the option isosurface_time; -1 for a phase that did not run."""
-        ms = (C.c_float * 4)()
-        self._chk(self._L.visfd_hip_isosurface_last_times(self._h, ms))
-        return tuple(ms)
+        return self._last_times("isosurface", 4)
 
-    def voxelize_last(self):
-        """(crossings, skipped triangles, odd rows, inside voxels) of the last voxelize_mesh[_dev]."""
-        s = (_i64 * 4)()
-        self._chk(self._L.visfd_hip_voxelize_last(self._h, s))
-        return tuple(int(x) for x in s)
-
-    def voxelize_last_times(self):
-        """(zero fill, scatter, fill) milliseconds of the last voxelize_mesh[_dev] under the option voxelize_time."""
-        ms = (C.c_float * 3)()
-        self._chk(self._L.visfd_hip_voxelize_last_times(self._h, ms))
-        return tuple(ms)
-
-    def draw_regions(self, image, regions, mask=None, negative_means_subtract=False):
-        """DrawRegions (draw.hpp:90-224) on a copy of `image`: regions is a list of (REGION_RECT, (xmin, xmax, ymin, ymax,
-        zmin, zmax), value) and (REGION_SPHERE, (x0, y0, z0, r), value), acting in list order -> the new image."""
-        nz, ny, nx = image.shape
-        dst = np.array(image, np.float32, copy=True, order="C")
-        arr, n = _regions(regions)
-        self._chk(self._L.visfd_hip_draw_regions(self._h, _np(dst), _np(mask), nx, ny, nz, arr, n,
-                                                 int(negative_means_subtract)))
-        return dst
+    # ---------------------------------------------------------------- morphology and medians
+    def _morph_sphere(self, face, op, src, dst, mask, radius, radius_max, bmax):
+        self._vol("morph_sphere", face, src, dst, mask, int(op), float(radius), float(radius_max), float(bmax))
 
     def morph_sphere(self, op, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
         """DilateSphere / ErodeSphere / OpenSphere / CloseSphere / WhiteTopHatSphere / BlackTopHatSphere (op = MORPH_*,
         morphology.hpp:241-597).  dst (default: a copy of src, as filter_mrc starts its output) keeps its values where
         mask == 0 and is what the top-hats subtract from / are subtracted from; a new array is returned."""
-        nz, ny, nx = src.shape
         dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
-        self._chk(self._L.visfd_hip_morph_sphere(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, int(op),
-                                                 float(radius), float(radius_max), float(bmax)))
+        self._morph_sphere(_HOST, op, src, dst, mask, radius, radius_max, bmax)
         return dst
+
+    def morph_sphere_dev(self, op, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        """morph_sphere on device tensors; dst is read (top-hats, masked voxels) and written in place."""
+        self._morph_sphere(_DEVICE, op, src, dst, mask, radius, radius_max, bmax)
 
     def dilate_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
         return self.morph_sphere(MORPH_DILATE, src, radius, radius_max, bmax, mask, dst)
@@ -1486,35 +1446,90 @@ class Context:
     def black_top_hat_sphere(self, src, radius, radius_max=0.0, bmax=0.0, mask=None, dst=None):
         return self.morph_sphere(MORPH_TOP_HAT_BLACK, src, radius, radius_max, bmax, mask, dst)
 
+    def dilate_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_DILATE, src, dst, radius, radius_max, bmax, mask)
+
+    def erode_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_ERODE, src, dst, radius, radius_max, bmax, mask)
+
+    def open_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_OPEN, src, dst, radius, radius_max, bmax, mask)
+
+    def close_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_CLOSE, src, dst, radius, radius_max, bmax, mask)
+
+    def white_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_TOP_HAT_WHITE, src, dst, radius, radius_max, bmax, mask)
+
+    def black_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
+        self.morph_sphere_dev(MORPH_TOP_HAT_BLACK, src, dst, radius, radius_max, bmax, mask)
+
+    def _morph_table_op(self, face, op, src, dst, mask, dxyz, b):
+        d, bb = _morph_table(dxyz, b)
+        self._vol("morph_table", face, src, dst, mask, int(op), d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb))
+
     def morph_table(self, op, src, dxyz, b, mask=None, dst=None):
         """Dilate / Erode (op MORPH_DILATE or MORPH_ERODE, morphology.hpp:134-229) with an arbitrary element: dxyz (n, 3)
         offsets and b (n,), walked in the given order."""
-        nz, ny, nx = src.shape
-        d, bb = _morph_table(dxyz, b)
         dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
-        self._chk(self._L.visfd_hip_morph_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, int(op),
-                                                d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
+        self._morph_table_op(_HOST, op, src, dst, mask, dxyz, b)
         return dst
+
+    def morph_table_dev(self, op, src, dst, dxyz, b, mask=None):
+        self._morph_table_op(_DEVICE, op, src, dst, mask, dxyz, b)
+
+    def dilate(self, src, dxyz, b, mask=None, dst=None):
+        return self.morph_table(MORPH_DILATE, src, dxyz, b, mask, dst)
+
+    def erode(self, src, dxyz, b, mask=None, dst=None):
+        return self.morph_table(MORPH_ERODE, src, dxyz, b, mask, dst)
+
+    def dilate_dev(self, src, dst, dxyz, b, mask=None):
+        self.morph_table_dev(MORPH_DILATE, src, dst, dxyz, b, mask)
+
+    def erode_dev(self, src, dst, dxyz, b, mask=None):
+        self.morph_table_dev(MORPH_ERODE, src, dst, dxyz, b, mask)
+
+    def morph_last_path(self):
+        """What the last morphology call ran: MORPH_PATH_GENERAL, MORPH_PATH_XRUNS or MORPH_PATH_LEVELS (the distance-map path
+        of two-level images, option morph_levels); -1 before the first."""
+        return self._last_path("morph")
+
+    def _median_sphere(self, face, src, dst, mask, radius):
+        self._vol("median_sphere", face, src, dst, mask, float(radius))
 
     def median_sphere(self, src, radius, mask=None, dst=None):
         """MedianSphere (filter3d.hpp:1639-1674, semantics in include/visfd_hip.h): the value of rank n // 2 among the n
         neighbours within `radius` voxels that lie in the image and have mask != 0.  dst (default: a copy of src, as
         filter_mrc starts its output) keeps its values where mask == 0; a new array is returned."""
-        nz, ny, nx = src.shape
         dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
-        self._chk(self._L.visfd_hip_median_sphere(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, float(radius)))
+        self._median_sphere(_HOST, src, dst, mask, radius)
         return dst
+
+    def median_sphere_dev(self, src, dst, radius, mask=None):
+        """median_sphere on device tensors; dst keeps its values where mask == 0 and is written in place."""
+        self._median_sphere(_DEVICE, src, dst, mask, radius)
+
+    def _median_table(self, face, src, dst, mask, dxyz):
+        d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
+        self._vol("median_table", face, src, dst, mask, d.ctypes.data_as(_ip), len(d))
 
     def median_table(self, src, dxyz, mask=None, dst=None):
         """Median (filter3d.hpp:1577-1630) with an arbitrary footprint: dxyz (n, 3) offsets; duplicates count as often as
         they appear and the centre need not be among them."""
-        nz, ny, nx = src.shape
-        d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
         dst = np.array(src if dst is None else dst, np.float32, copy=True, order="C")
-        self._chk(self._L.visfd_hip_median_table(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz,
-                                                 d.ctypes.data_as(_ip), len(d)))
+        self._median_table(_HOST, src, dst, mask, dxyz)
         return dst
 
+    def median_table_dev(self, src, dst, dxyz, mask=None):
+        self._median_table(_DEVICE, src, dst, mask, dxyz)
+
+    def median_last_path(self):
+        """The kernel the last median call ran: MEDIAN_PATH_GENERAL or MEDIAN_PATH_TILED (-1 before the first)."""
+        return self._last_path("median")
+
+    # ---------------------------------------------------------------- distances, statistics, intensity maps
+    # (one method for both faces: numpy arrays in, numpy out; torch device tensors in, tensors out)
     def distance_sq(self, shape=None, points=None, src=None, mask=None, lo=-np.inf, hi=np.inf):
         """The exact squared distance map (include/visfd_hip.h): int32 min((nx + ny + nz)^2, |v - s|^2 over the seeds s).
         Seeds: the voxels of `src` with mask != 0 and lo <= src <= hi (src None: none) and the integer `points` ((n, 3)
@@ -1523,14 +1538,11 @@ class Context:
         nz, ny, nx = src.shape if src is not None else shape
         pts = _points(points)
         if src is None or isinstance(src, np.ndarray):
-            dsq = np.empty((nz, ny, nx), np.int32)
-            self._chk(self._L.visfd_hip_distance_sq(self._h, _np(src), _np(mask), nx, ny, nz, float(lo), float(hi),
-                                                    pts.ctypes.data, len(pts), dsq.ctypes.data))
-            return dsq
-        import torch
-        dsq = torch.empty((nz, ny, nx), dtype=torch.int32, device=src.device)
-        self._chk(self._L.visfd_hip_distance_sq_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(lo), float(hi),
-                                                    pts.ctypes.data, len(pts), dsq.data_ptr()))
+            face, dsq = _HOST, np.empty((nz, ny, nx), np.int32)
+        else:
+            import torch
+            face, dsq = _DEVICE, torch.empty((nz, ny, nx), dtype=torch.int32, device=src.device)
+        self._call("distance_sq", face, src, mask, nx, ny, nz, float(lo), float(hi), pts.ctypes.data, len(pts), _address(dsq))
         return dsq
 
     def distance_to_points(self, dst, points, voxel_width=1.0, mask=None):
@@ -1541,11 +1553,7 @@ class Context:
         pts = _points(points)
         if isinstance(dst, np.ndarray):
             dst = np.array(dst, np.float32, copy=True, order="C")
-            self._chk(self._L.visfd_hip_distance_to_points(self._h, _np(dst), _np(mask), nx, ny, nz, pts.ctypes.data, len(pts),
-                                                           float(voxel_width)))
-        else:
-            self._chk(self._L.visfd_hip_distance_to_points_dev(self._h, _dev(dst), _dev(mask), nx, ny, nz, pts.ctypes.data,
-                                                               len(pts), float(voxel_width)))
+        self._call("distance_to_points", _face_of(dst), dst, mask, nx, ny, nz, pts.ctypes.data, len(pts), float(voxel_width))
         return dst
 
     def distance_from_points(self, src, points, lo, hi, voxel_width=1.0, mask=None):
@@ -1554,19 +1562,36 @@ class Context:
         nz, ny, nx = src.shape
         pts = _points(points)
         out = np.empty(len(pts), np.float32)
-        if isinstance(src, np.ndarray):
-            fn, a, m = self._L.visfd_hip_distance_from_points, _np(src), _np(mask)
-        else:
-            fn, a, m = self._L.visfd_hip_distance_from_points_dev, _dev(src), _dev(mask)
-        self._chk(fn(self._h, a, m, nx, ny, nz, float(lo), float(hi), pts.ctypes.data, len(pts), float(voxel_width),
-                     out.ctypes.data))
+        self._call("distance_from_points", _face_of(src), src, mask, nx, ny, nz, float(lo), float(hi), pts.ctypes.data,
+                   len(pts), float(voxel_width), out.ctypes.data)
         return out
 
     def distance_last_path(self):
         """What the last distance call ran: DISTANCE_PATH_GENERAL or DISTANCE_PATH_TRANSFORM (-1 before the first)."""
-        p = C.c_int(-1)
-        self._chk(self._L.visfd_hip_distance_last_path(self._h, C.byref(p)))
-        return int(p.value)
+        return self._last_path("distance")
+
+    def image_stats(self, src, mask=None):
+        """Statistics of the voxels with mask != 0 (all without a mask): dict of count, n_nonfinite, min, max, the exact
+        sum rounded once to double (math.fsum's) and order_free (include/visfd_hip.h).  numpy arrays or torch device
+        tensors of any shape; returns with the stream idle."""
+        st = Stats()
+        self._call("image_stats", _face_of(src), src, mask, src.size if isinstance(src, np.ndarray) else src.numel(),
+                   C.byref(st))
+        return st.as_dict()
+
+    def intensity_map(self, p, out, src=None, mask=None, want_stats=False):
+        """One pass of the stages of `p` (api.intensity(...)) over `out`, IN PLACE: invert, one map (the threshold family
+        reads `src`, which may be `out` itself), mask fill, Rescale01.  3-D numpy arrays or torch device tensors.
+        want_stats: -> the statistics of what was written (the call then waits for the stream), else None."""
+        nz, ny, nx = out.shape
+        st = Stats()
+        self._call("intensity_map", _face_of(out), src, out, mask, nx, ny, nz, C.byref(p), C.byref(st) if want_stats else None)
+        return st.as_dict() if want_stats else None
+
+    # ---------------------------------------------------------------- blob lists
+    def _find_spheres(self, face, crds, sphere_crds, sphere_diameters, ids):
+        self._call("find_spheres", face, crds, int(crds.shape[0]), sphere_crds, sphere_diameters,
+                   int(sphere_diameters.shape[0]), _address(ids))
 
     def find_spheres(self, crds, sphere_crds, sphere_diameters, ids=None):
         """FindSpheres (visfd_utils.hpp:271-359) on the device, numpy in and out: for every point 1 + the index of the LAST
@@ -1577,8 +1602,7 @@ class Context:
         if ids is None:
             ids = np.empty(len(q), np.int64)
         assert isinstance(ids, np.ndarray) and ids.dtype == np.int64 and ids.flags["C_CONTIGUOUS"] and ids.size == len(q)
-        self._chk(self._L.visfd_hip_find_spheres(self._h, q.ctypes.data, len(q), c.ctypes.data, d.ctypes.data, len(d),
-                                                 ids.ctypes.data))
+        self._find_spheres(_HOST, q, c, d, ids)
         return ids
 
     def find_spheres_dev(self, crds, sphere_crds, sphere_diameters, ids=None):
@@ -1591,26 +1615,28 @@ class Context:
         if ids is None:
             ids = torch.empty(n, dtype=torch.int64, device=crds.device)
         assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64 and ids.numel() == n, "ids: n int64 on the device"
-        self._chk(self._L.visfd_hip_find_spheres_dev(self._h, _dev(crds), n, _dev(sphere_crds), _dev(sphere_diameters), m,
-                                                     ids.data_ptr()))
+        self._find_spheres(_DEVICE, crds, sphere_crds, sphere_diameters, ids)
         return ids
 
     def find_spheres_last_path(self):
         """What the last FindSpheres call ran: FIND_SPHERES_PATH_DEVICE or FIND_SPHERES_PATH_HOST (-1 before the first)."""
-        p = C.c_int(-1)
-        self._chk(self._L.visfd_hip_find_spheres_last_path(self._h, C.byref(p)))
-        return int(p.value)
+        return self._last_path("find_spheres")
+
+    def _discard_overlapping_blobs(self, face, crds, diameters, scores, n, min_radial_separation_ratio, max_volume_overlap_large,
+                                   max_volume_overlap_small, criteria, scale):
+        k = _i64(n)
+        self._call("discard_overlapping_blobs", face, crds, diameters, scores, C.byref(k), min_radial_separation_ratio,
+                   max_volume_overlap_large, max_volume_overlap_small, int(criteria), int(scale))
+        return int(k.value)
 
     def discard_overlapping_blobs(self, crds, diameters, scores, min_radial_separation_ratio, max_volume_overlap_large=np.inf,
                                   max_volume_overlap_small=np.inf, criteria=SORT_DECREASING_MAGNITUDE, scale=6):
         """DiscardOverlappingBlobs (feature.hpp:720-913) on the device, numpy in and out -> (crds, diameters, scores) of
         the kept blobs, best first: the bits of the module-level function.  discard_overlapping_blobs_last() says what ran."""
         c, d, s = _blob_arrays(crds, diameters, scores)
-        n = _i64(len(d))
-        self._chk(self._L.visfd_hip_discard_overlapping_blobs_ctx(
-            self._h, c.ctypes.data, d.ctypes.data, s.ctypes.data, C.byref(n), min_radial_separation_ratio,
-            max_volume_overlap_large, max_volume_overlap_small, int(criteria), int(scale)))
-        return c[:n.value], d[:n.value], s[:n.value]
+        k = self._discard_overlapping_blobs(_HOST_CTX, c, d, s, len(d), min_radial_separation_ratio, max_volume_overlap_large,
+                                            max_volume_overlap_small, criteria, scale)
+        return c[:k], d[:k], s[:k]
 
     def discard_overlapping_blobs_dev(self, crds, diameters, scores, min_radial_separation_ratio,
                                       max_volume_overlap_large=np.inf, max_volume_overlap_small=np.inf,
@@ -1621,52 +1647,100 @@ class Context:
         n = int(diameters.shape[0])
         for t, m in ((crds, 3 * n), (diameters, n), (scores, n)):
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == m, "float32 device lists of one length"
-        k = _i64(n)
-        self._chk(self._L.visfd_hip_discard_overlapping_blobs_dev(
-            self._h, _dev(crds), _dev(diameters), _dev(scores), C.byref(k), min_radial_separation_ratio,
-            max_volume_overlap_large, max_volume_overlap_small, int(criteria), int(scale)))
-        return int(k.value)
+        return self._discard_overlapping_blobs(_DEVICE, crds, diameters, scores, n, min_radial_separation_ratio,
+                                               max_volume_overlap_large, max_volume_overlap_small, criteria, scale)
 
     def discard_overlapping_blobs_last(self):
         """The last discard_overlapping_blobs[_dev] of this context: dict of path (DISCARD_OVERLAP_PATH_*), reason
         (DISCARD_OVERLAP_REASON_*), rounds, blobs_in, blobs_kept, pairs_crit, pairs_share, table_cells."""
         info = (_i64 * 8)()
-        self._chk(self._L.visfd_hip_discard_overlapping_blobs_last(self._h, info))
+        self._call("discard_overlapping_blobs_last", _HOST, info)
         return dict(zip(DISCARD_OVERLAP_LAST_FIELDS, (int(x) for x in info)))
 
     def discard_overlapping_blobs_last_times(self):
         """Option discard_overlap_time: the last call's phases in milliseconds (reduction, ranking and records, buckets,
         rounds, compaction), -1 where a phase did not run."""
-        ms = (C.c_float * 5)()
-        self._chk(self._L.visfd_hip_discard_overlapping_blobs_last_times(self._h, ms))
-        return dict(zip(("reduce", "rank", "buckets", "rounds", "compact"), (float(x) for x in ms)))
+        return dict(zip(("reduce", "rank", "buckets", "rounds", "compact"),
+                        (float(x) for x in self._last_times("discard_overlapping_blobs", 5))))
 
-    def image_stats(self, src, mask=None):
-        """Statistics of the voxels with mask != 0 (all without a mask): dict of count, n_nonfinite, min, max, the exact
-        sum rounded once to double (math.fsum's) and order_free (include/visfd_hip.h).  numpy arrays or torch device
-        tensors of any shape; returns with the stream idle."""
-        st = Stats()
-        if isinstance(src, np.ndarray):
-            self._chk(self._L.visfd_hip_image_stats(self._h, _np(src), _np(mask), src.size, C.byref(st)))
-        else:
-            self._chk(self._L.visfd_hip_image_stats_dev(self._h, _dev(src), _dev(mask), src.numel(), C.byref(st)))
-        return st.as_dict()
+    def _blob_call(self, face, src, mask, shape, sigmas, aspect, delta, ratio, minima_threshold, maxima_threshold,
+                   use_ratios, cap):
+        nz, ny, nx = shape
+        sig = np.ascontiguousarray(sigmas, np.float32)
+        asp = _f3(aspect) if aspect is not None else None
+        for attempt in (0, 1):
+            # the record arrays are kept by the context between calls (a pipeline asks for millions of records of capacity:
+            # mapping and unmapping 2 x 100 MB per call cost 1-25 ms of host time, depending on the state of the machine)
+            bufs = getattr(self, "_blob_bufs", None)
+            if bufs is None or len(bufs[0]) < cap:
+                bufs = self._blob_bufs = (np.empty(cap, _BLOB_DTYPE), np.empty(cap, _BLOB_DTYPE))   # visfd_hip_blob records
+            amin, amax = bufs   # (at least `cap` records; the call is still told `cap`)
+            nmin, nmax = _i64(), _i64()
+            rc = self._rc("blob_dog", face, src, mask, nx, ny, nz, sig.ctypes.data_as(_fp), len(sig), asp, float(delta),
+                          float(ratio), float(minima_threshold), float(maxima_threshold), int(use_ratios),
+                          amin.ctypes.data, cap, C.byref(nmin), amax.ctypes.data, cap, C.byref(nmax))
+            if rc == 4 and attempt == 0:   # VISFD_HIP_ECAPACITY: the exact counts came back; once more with room for them
+                cap = max(nmin.value, nmax.value, 1)
+                continue
+            self._chk(rc)
+            break
+        return _blobs_to_rows(amin, nmin.value)[0], _blobs_to_rows(amax, nmax.value)[0]
 
-    def intensity_map(self, p, out, src=None, mask=None, want_stats=False):
-        """One pass of the stages of `p` (api.intensity(...)) over `out`, IN PLACE: invert, one map (the threshold family
-        reads `src`, which may be `out` itself), mask fill, Rescale01.  3-D numpy arrays or torch device tensors.
-        want_stats: -> the statistics of what was written (the call then waits for the stream), else None."""
-        nz, ny, nx = out.shape
-        st = Stats()
-        sp = C.byref(st) if want_stats else None
-        if isinstance(out, np.ndarray):
-            self._chk(self._L.visfd_hip_intensity_map(self._h, _np(src), _np(out), _np(mask), nx, ny, nz, C.byref(p), sp))
-        else:
-            self._chk(self._L.visfd_hip_intensity_map_dev(self._h, _dev(src), _dev(out), _dev(mask), nx, ny, nz,
-                                                          C.byref(p), sp))
-        return st.as_dict() if want_stats else None
+    def blob_dog(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
+                 maxima_threshold=-np.inf, use_ratios=False, cap=1 << 16):
+        return self._blob_call(_HOST, src, mask, src.shape, sigmas, aspect, delta, ratio, minima_threshold,
+                               maxima_threshold, use_ratios, cap)
 
-    def _find_extrema(self, fn, src, mask, shape, find_minima, find_maxima, minima_threshold, maxima_threshold,
+    def blob_dog_dev(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
+                     maxima_threshold=-np.inf, use_ratios=False, cap=1 << 16):
+        return self._blob_call(_DEVICE, src, mask, tuple(src.shape), sigmas, aspect, delta, ratio, minima_threshold,
+                               maxima_threshold, use_ratios, cap)
+
+    def blob_dog_begin_dev(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
+                           maxima_threshold=-np.inf, use_ratios=False):
+        """First half of blob_dog_dev (visfd_hip_blob_dog_begin_dev): everything queued, most lists fetched; returns a job for
+        blob_dog_end().  Other calls of this context may be queued in between; src and mask must stay as they are until then."""
+        nz, ny, nx = src.shape
+        sig = np.ascontiguousarray(sigmas, np.float32)
+        asp = _f3(aspect) if aspect is not None else None
+        job = _vp()
+        self._call("blob_dog_begin", _DEVICE, src, mask, nx, ny, nz, sig.ctypes.data_as(_fp), len(sig), asp, float(delta),
+                   float(ratio), float(minima_threshold), float(maxima_threshold), int(use_ratios), C.byref(job))
+        job = [job, src, mask, sig]   # (the tensors and the sigma array live as long as the job)
+        self._jobs = getattr(self, "_jobs", []) + [job]   # close() ends what the caller has not
+        return job
+
+    def blob_dog_end(self, job, cap=1 << 16):
+        """Second half: -> (minima, maxima) rows x,y,z,sigma,score, as blob_dog_dev returns them."""
+        h = job[0]
+        if h is None:
+            raise ValueError("blob job already finished")
+        for attempt in (0, 1):
+            bufs = getattr(self, "_blob_bufs", None)
+            if bufs is None or len(bufs[0]) < cap:
+                bufs = self._blob_bufs = (np.empty(cap, _BLOB_DTYPE), np.empty(cap, _BLOB_DTYPE))
+            amin, amax = bufs
+            nmin, nmax = _i64(), _i64()
+            rc = self._L.visfd_hip_blob_dog_end(h, amin.ctypes.data, cap, C.byref(nmin), amax.ctypes.data, cap, C.byref(nmax))
+            if rc == 4 and attempt == 0:   # VISFD_HIP_ECAPACITY: the job is still alive, the counts came back
+                cap = max(nmin.value, nmax.value, 1)
+                continue
+            job[0] = None                   # every other outcome has freed the job
+            self._forget_job(job)
+            if rc == 4:
+                self._L.visfd_hip_blob_dog_abort(h)
+            self._chk(rc)
+            break
+        return _blobs_to_rows(amin, nmin.value)[0], _blobs_to_rows(amax, nmax.value)[0]
+
+    def blob_dog_abort(self, job):
+        if job[0] is not None:
+            self._L.visfd_hip_blob_dog_abort(job[0])
+            job[0] = None
+            self._forget_job(job)
+
+    # ---------------------------------------------------------------- extrema, watershed, clusters, surface points
+    def _find_extrema(self, face, src, mask, shape, find_minima, find_maxima, minima_threshold, maxima_threshold,
                       connectivity, allow_borders, labels):
         """The capacity protocol of visfd_hip_find_extrema[_dev]: a first call with room for max(65536, voxels / 32)
         entries per list, a second -- which repeats the device work -- with the returned counts if that was too little."""
@@ -1678,9 +1752,9 @@ class Context:
             tail = []
             for (i, sc, nv), c, cnt in zip(lists, cap, n):
                 tail += [i.ctypes.data, sc.ctypes.data, nv.ctypes.data, c, C.byref(cnt)]
-            rc = fn(self._h, src, mask, nx, ny, nz, int(bool(find_minima)), int(bool(find_maxima)),
-                    float(minima_threshold), float(maxima_threshold), int(connectivity), int(bool(allow_borders)),
-                    *(tail + [labels]))
+            rc = self._rc("find_extrema", face, src, mask, nx, ny, nz, int(bool(find_minima)), int(bool(find_maxima)),
+                          float(minima_threshold), float(maxima_threshold), int(connectivity), int(bool(allow_borders)),
+                          *(tail + [labels]))
             if rc == 4 and (n[0].value > cap[0] or n[1].value > cap[1]):   # VISFD_HIP_ECAPACITY
                 cap = [max(int(n[0].value), 1), max(int(n[1].value), 1)]
                 continue
@@ -1698,10 +1772,21 @@ class Context:
         if want_labels or labels is not None:
             out = np.zeros(src.shape, np.int32) if labels is None else np.array(labels, np.int32, copy=True, order="C")
             assert out.shape == src.shape
-        mins, maxs = self._find_extrema(self._L.visfd_hip_find_extrema, _np(src), _np(mask), src.shape, find_minima,
-                                        find_maxima, minima_threshold, maxima_threshold, connectivity, allow_borders,
+        mins, maxs = self._find_extrema(_HOST, src, mask, src.shape, find_minima, find_maxima, minima_threshold,
+                                        maxima_threshold, connectivity, allow_borders,
                                         None if out is None else out.ctypes.data)
         return (mins, maxs) if out is None else (mins, maxs, out)
+
+    def find_extrema_dev(self, src, mask=None, find_minima=True, find_maxima=True, minima_threshold=float("inf"),
+                         maxima_threshold=-float("inf"), connectivity=3, allow_borders=True, labels=None):
+        """find_extrema on device tensors: -> (minima, maxima) as numpy lists; labels (an int32 cuda tensor, optional) is
+        written in place where mask != 0.  Returns with the stream idle."""
+        if labels is not None:
+            assert labels.is_cuda and labels.is_contiguous() and str(labels.dtype) == "torch.int32" and \
+                tuple(labels.shape) == tuple(src.shape), "labels: contiguous cuda int32 of src's shape"
+        return tuple(self._find_extrema(_DEVICE, src, mask, tuple(src.shape), find_minima, find_maxima, minima_threshold,
+                                        maxima_threshold, connectivity, allow_borders,
+                                        None if labels is None else labels.data_ptr()))
 
     def find_minima_only(self, src, mask=None, threshold=float("inf"), connectivity=3, allow_borders=True, **kw):
         """visfd::FindMinima: -> (minima[, labels])."""
@@ -1715,6 +1800,11 @@ class Context:
         r = self.find_extrema(src, mask, False, True, float("inf"), threshold, connectivity, allow_borders, **kw)
         return r[1] if len(r) == 2 else (r[1], r[2])
 
+    def _watershed(self, face, src, mask, markers, labels, *params):
+        """_watershed (the capacity protocol) on this context; markers and labels as addresses (int32 images)"""
+        return _watershed(lambda *t: self._rc("watershed", face, *t), src, mask, None if markers is None else _address(markers),
+                          tuple(src.shape), _address(labels), *params)
+
     def watershed(self, src, mask=None, markers=None, halt_threshold=None, start_from_minima=True, connectivity=1,
                   show_boundaries=True, label_boundary=0, label_undefined=-1):
         """visfd::Watershed (segmentation.hpp:65-559) of a numpy volume (nz, ny, nx): -> (labels int32, basin index int64,
@@ -1724,10 +1814,8 @@ class Context:
         watershed_host, by the sequential flood on the host."""
         markers = _markers_np(markers, src.shape)
         labels = np.empty(src.shape, np.int32)
-        index, score = _watershed(lambda *t: self._L.visfd_hip_watershed(self._h, *t), _np(src), _np(mask),
-                                  None if markers is None else markers.ctypes.data, src.shape, labels.ctypes.data,
-                                  halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary,
-                                  label_undefined)
+        index, score = self._watershed(_HOST, src, mask, markers, labels, halt_threshold, start_from_minima, connectivity,
+                                       show_boundaries, label_boundary, label_undefined)
         return labels, index, score
 
     def watershed_dev(self, src, labels, mask=None, markers=None, halt_threshold=None, start_from_minima=True, connectivity=1,
@@ -1737,9 +1825,14 @@ class Context:
         for t in (labels, markers):
             assert t is None or (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.int32" and
                                  tuple(t.shape) == tuple(src.shape)), "labels / markers: contiguous cuda int32 of src's shape"
-        return _watershed(lambda *t: self._L.visfd_hip_watershed_dev(self._h, *t), _dev(src), _dev(mask),
-                          None if markers is None else markers.data_ptr(), tuple(src.shape), labels.data_ptr(),
-                          halt_threshold, start_from_minima, connectivity, show_boundaries, label_boundary, label_undefined)
+        return self._watershed(_DEVICE, src, mask, markers, labels, halt_threshold, start_from_minima, connectivity,
+                               show_boundaries, label_boundary, label_undefined)
+
+    def watershed_last_stats(self):
+        """(path, label rounds, boundary rounds, basins) of the last watershed call; path WATERSHED_PATH_HOST or _DEVICE."""
+        out = (_i64 * 4)()
+        self._call("watershed_last_stats", _HOST, out)
+        return tuple(int(v) for v in out)
 
     def label_connected_device_seeds(self, saliency, threshold_saliency, **kw):
         """api.label_connected with the seed search on this context's device (numpy arrays; the flood on the host)."""
@@ -1750,7 +1843,7 @@ class Context:
         device's seed list, or CONNECT_SEEDS_HOST and -1 (the image or the connectivity is beyond the device search);
         (-1, -1) before the first call."""
         p, n = C.c_int(), _i64()
-        self._chk(self._L.visfd_hip_label_connected_device_seeds_last(self._h, C.byref(p), C.byref(n)))
+        self._call("label_connected_device_seeds_last", _HOST, C.byref(p), C.byref(n))
         return p.value, n.value
 
     def label_connected_graph(self, saliency, threshold_saliency, **kw):
@@ -1775,13 +1868,13 @@ class Context:
         ptr = lambda a: None if a is None else a.ctypes.data
         assert labels.is_cuda and labels.is_contiguous() and str(labels.dtype) == "torch.int64" and \
             tuple(labels.shape) == tuple(saliency.shape), "labels: contiguous cuda int64 of the image's shape"
-        self._chk(self._L.visfd_hip_label_connected_graph_dev(
-            self._h, _dev(saliency), labels.data_ptr(), _dev(mask), nx, ny, nz, threshold_saliency, _dev(direction),
-            threshold_vector_saliency, threshold_vector_neighbor, int(bool(consider_dot_product_sign)), _dev(tensor),
+        self._call(
+            "label_connected_graph", _DEVICE, saliency, labels.data_ptr(), mask, nx, ny, nz, threshold_saliency, direction,
+            threshold_vector_saliency, threshold_vector_neighbor, int(bool(consider_dot_product_sign)), tensor,
             threshold_tensor_saliency, threshold_tensor_neighbor, int(bool(tensor_is_positive_definite_near_target)),
             int(connectivity), int(label_undefined), int(bool(sort_by_size)), int(bool(standardize_directions)),
             int(bool(start_from_saliency_maxima)), C.byref(n), cm.ctypes.data, cs.ctypes.data, csal.ctypes.data, cap,
-            _dev(voxel_weights), ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d)))
+            voxel_weights, ptr(ml_c), ptr(ml_n), ngroups, ptr(ml_d))
         k = n.value
         return k, cm[:k], cs[:k], csal[:k]
 
@@ -1793,24 +1886,26 @@ class Context:
         """Under the option connect_settle: the CONNECT_REASON_* bits among MUST_LINK, WEIGHTS and OUTWARD that the last
         device-path graph call settled itself; 0 after a call that took the flood or ran with the option off."""
         bits = C.c_uint(0)
-        self._chk(self._L.visfd_hip_label_connected_graph_last_settled(self._h, C.byref(bits)))
+        self._call("label_connected_graph_last_settled", _HOST, C.byref(bits))
         return bits.value
 
     def label_connected_graph_last_times(self):
         """Under the option connect_time: milliseconds of the last device-path graph call by stage (seed search, classify,
         host vector test, edges, clusters, directions, copies in, copies out)."""
-        ms = (C.c_float * 8)()
-        self._chk(self._L.visfd_hip_label_connected_graph_last_times(self._h, ms))
-        return tuple(ms)
+        return self._last_times("label_connected_graph", 8)
+
+    def _surface_points_call(self, face, saliency, direction, voxel2cluster, mask):
+        """call(*tail) -> return code of visfd_hip_surface_points_ctx / _dev with everything up to the sizes filled in"""
+        nz, ny, nx = saliency.shape
+        return lambda *tail: self._rc("surface_points", face, saliency, voxel2cluster, direction, mask, nx, ny, nz, *tail)
 
     def surface_points(self, saliency, direction, voxel2cluster=None, mask=None, select_cluster=1, voxel_width=(1, 1, 1),
                        curve_ds=0.2, find_ridge=True, max_distance_to_feature=1.3, capacity=None):
         """api.surface_points_host on this context's device (visfd_hip_surface_points_ctx; numpy arrays, direction
         [nz, ny, nx, 3]): the same points, bit for bit."""
-        nz, ny, nx = saliency.shape
-        return _surface_points(lambda *t: self._L.visfd_hip_surface_points_ctx(
-            self._h, _np(saliency), _np(voxel2cluster), _np(direction), _np(mask), nx, ny, nz, *t),
-            self._L, saliency.shape, select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity)
+        return _surface_points(self._surface_points_call(_HOST_CTX, saliency, direction, voxel2cluster, mask), self._L,
+                               saliency.shape, select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature,
+                               capacity)
 
     def surface_points_dev(self, saliency, direction, voxel2cluster=None, mask=None, select_cluster=1, voxel_width=(1, 1, 1),
                            curve_ds=0.2, find_ridge=True, max_distance_to_feature=1.3, capacity=None, crds=None, norms=None):
@@ -1820,15 +1915,14 @@ class Context:
         stream idle."""
         nz, ny, nx = saliency.shape
         assert tuple(direction.shape) == (3, nz, ny, nx), "direction: channel-planar [3, nz, ny, nx]"
-        args = (self._h, _dev(saliency), _dev(voxel2cluster), _dev(direction), _dev(mask), nx, ny, nz)
+        call = self._surface_points_call(_DEVICE, saliency, direction, voxel2cluster, mask)
         if crds is None:
-            return _surface_points(lambda *t: self._L.visfd_hip_surface_points_dev(*(args + t)), self._L, saliency.shape,
-                                   select_cluster, voxel_width, curve_ds, find_ridge, max_distance_to_feature, capacity)
+            return _surface_points(call, self._L, saliency.shape, select_cluster, voxel_width, curve_ds, find_ridge,
+                                   max_distance_to_feature, capacity)
         assert tuple(crds.shape) == tuple(norms.shape) and crds.shape[1] == 3, "crds, norms: [capacity, 3]"
         n = _i64(0)
-        rc = self._L.visfd_hip_surface_points_dev(*(args + (int(select_cluster), _f3(voxel_width), float(curve_ds),
-                                                            int(bool(find_ridge)), float(max_distance_to_feature), _dev(crds),
-                                                            _dev(norms), int(crds.shape[0]), C.byref(n))))
+        rc = call(int(select_cluster), _f3(voxel_width), float(curve_ds), int(bool(find_ridge)), float(max_distance_to_feature),
+                  crds, norms, int(crds.shape[0]), C.byref(n))
         if rc:
             err = VisfdHipError(rc, self._L.visfd_hip_last_error().decode())
             err.needed = int(n.value)
@@ -1840,489 +1934,118 @@ class Context:
         surface_points[_dev]: path
         SURFACE_POINTS_PATH_DEVICE or _HANDED_OVER (the host entry finished the call) with the SURFACE_POINTS_REASON_* bits."""
         out = (_i64 * 6)()
-        self._chk(self._L.visfd_hip_surface_points_last(self._h, out))
+        self._call("surface_points_last", _HOST, out)
         return tuple(int(v) for v in out)
 
     def surface_points_last_times(self):
         """Under the option surface_points_time: (select and compact, walk, ridge gather, host finish and copies out)
         milliseconds of the last device-path surface_points[_dev]."""
-        ms = (C.c_float * 4)()
-        self._chk(self._L.visfd_hip_surface_points_last_times(self._h, ms))
-        return tuple(ms)
+        return self._last_times("surface_points", 4)
 
-    def watershed_last_stats(self):
-        """(path, label rounds, boundary rounds, basins) of the last watershed call; path WATERSHED_PATH_HOST or _DEVICE."""
-        out = (_i64 * 4)()
-        self._chk(self._L.visfd_hip_watershed_last_stats(self._h, out))
-        return tuple(int(v) for v in out)
-
-    def filter3d_last_path(self):
-        """The kernel the last general-filter call ran: FILTER3D_PATH_GENERAL or FILTER3D_PATH_TILED (-1 before the first)."""
-        p = C.c_int()
-        self._chk(self._L.visfd_hip_filter3d_last_path(self._h, C.byref(p)))
-        return p.value
-
-    def morph_last_path(self):
-        """What the last morphology call ran: MORPH_PATH_GENERAL, MORPH_PATH_XRUNS or MORPH_PATH_LEVELS (the distance-map path
-        of two-level images, option morph_levels); -1 before the first."""
-        p = C.c_int()
-        self._chk(self._L.visfd_hip_morph_last_path(self._h, C.byref(p)))
-        return p.value
-
-    def median_last_path(self):
-        """The kernel the last median call ran: MEDIAN_PATH_GENERAL or MEDIAN_PATH_TILED (-1 before the first)."""
-        p = C.c_int()
-        self._chk(self._L.visfd_hip_median_last_path(self._h, C.byref(p)))
-        return p.value
-
-    def dilate(self, src, dxyz, b, mask=None, dst=None):
-        return self.morph_table(MORPH_DILATE, src, dxyz, b, mask, dst)
-
-    def erode(self, src, dxyz, b, mask=None, dst=None):
-        return self.morph_table(MORPH_ERODE, src, dxyz, b, mask, dst)
-
-    def dog(self, src, sigma_a, sigma_b, hw, mask=None):
+    # ---------------------------------------------------------------- ridges, tensor voting, the membrane stage
+    def _calc_hessian(self, face, src, grad, hess, mask, sigma, ratio):
         nz, ny, nx = src.shape
-        dst = np.empty_like(src)
-        A, B = C.c_float(), C.c_float()
-        self._chk(self._L.visfd_hip_apply_dog(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(sigma_a),
-                                              _f3(sigma_b), _i3(hw), C.byref(A), C.byref(B)))
-        return dst, A.value, B.value
-
-    def log(self, src, sigma, delta, ratio, mask=None):
-        nz, ny, nx = src.shape
-        dst = np.empty_like(src)
-        A, B = C.c_float(), C.c_float()
-        self._chk(self._L.visfd_hip_apply_log(self._h, _np(src), _np(dst), _np(mask), nx, ny, nz, _f3(sigma),
-                                              float(delta), float(ratio), C.byref(A), C.byref(B)))
-        return dst, A.value, B.value
-
-    def _blob_call(self, fn, psrc, pmask, shape, sigmas, aspect, delta, ratio, minima_threshold, maxima_threshold,
-                   use_ratios, cap):
-        nz, ny, nx = shape
-        sig = np.ascontiguousarray(sigmas, np.float32)
-        asp = _f3(aspect) if aspect is not None else None
-        for attempt in (0, 1):
-            # the record arrays are kept by the context between calls (a pipeline asks for millions of records of capacity:
-            # mapping and unmapping 2 x 100 MB per call cost 1-25 ms of host time, depending on the state of the machine)
-            bufs = getattr(self, "_blob_bufs", None)
-            if bufs is None or len(bufs[0]) < cap:
-                bufs = self._blob_bufs = (np.empty(cap, _BLOB_DTYPE), np.empty(cap, _BLOB_DTYPE))   # visfd_hip_blob records
-            amin, amax = bufs   # (at least `cap` records; the call is still told `cap`)
-            nmin, nmax = _i64(), _i64()
-            rc = fn(self._h, psrc, pmask, nx, ny, nz, sig.ctypes.data_as(_fp), len(sig), asp, float(delta),
-                    float(ratio), float(minima_threshold), float(maxima_threshold), int(use_ratios),
-                    amin.ctypes.data_as(C.POINTER(Blob)), cap, C.byref(nmin),
-                    amax.ctypes.data_as(C.POINTER(Blob)), cap, C.byref(nmax))
-            if rc == 4 and attempt == 0:   # VISFD_HIP_ECAPACITY: the exact counts came back; once more with room for them
-                cap = max(nmin.value, nmax.value, 1)
-                continue
-            self._chk(rc)
-            break
-        return _blobs_to_rows(amin, nmin.value)[0], _blobs_to_rows(amax, nmax.value)[0]
-
-    def blob_dog_begin_dev(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
-                           maxima_threshold=-np.inf, use_ratios=False):
-        """First half of blob_dog_dev (visfd_hip_blob_dog_begin_dev): everything queued, most lists fetched; returns a job for
-        blob_dog_end().  Other calls of this context may be queued in between; src and mask must stay as they are until then."""
-        nz, ny, nx = src.shape
-        sig = np.ascontiguousarray(sigmas, np.float32)
-        asp = _f3(aspect) if aspect is not None else None
-        job = _vp()
-        self._chk(self._L.visfd_hip_blob_dog_begin_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, sig.ctypes.data_as(_fp), len(sig),
-                                                       asp, float(delta), float(ratio), float(minima_threshold),
-                                                       float(maxima_threshold), int(use_ratios), C.byref(job)))
-        job = [job, src, mask, sig]   # (the tensors and the sigma array live as long as the job)
-        self._jobs = getattr(self, "_jobs", []) + [job]   # close() ends what the caller has not
-        return job
-
-    def blob_dog_end(self, job, cap=1 << 16):
-        """Second half: -> (minima, maxima) rows x,y,z,sigma,score, as blob_dog_dev returns them."""
-        h = job[0]
-        if h is None:
-            raise ValueError("blob job already finished")
-        for attempt in (0, 1):
-            bufs = getattr(self, "_blob_bufs", None)
-            if bufs is None or len(bufs[0]) < cap:
-                bufs = self._blob_bufs = (np.empty(cap, _BLOB_DTYPE), np.empty(cap, _BLOB_DTYPE))
-            amin, amax = bufs
-            nmin, nmax = _i64(), _i64()
-            rc = self._L.visfd_hip_blob_dog_end(h, amin.ctypes.data_as(C.POINTER(Blob)), cap, C.byref(nmin),
-                                                amax.ctypes.data_as(C.POINTER(Blob)), cap, C.byref(nmax))
-            if rc == 4 and attempt == 0:   # VISFD_HIP_ECAPACITY: the job is still alive, the counts came back
-                cap = max(nmin.value, nmax.value, 1)
-                continue
-            job[0] = None                   # every other outcome has freed the job
-            self._forget_job(job)
-            if rc == 4:
-                self._L.visfd_hip_blob_dog_abort(h)
-            self._chk(rc)
-            break
-        return _blobs_to_rows(amin, nmin.value)[0], _blobs_to_rows(amax, nmax.value)[0]
-
-    def blob_dog_abort(self, job):
-        if job[0] is not None:
-            self._L.visfd_hip_blob_dog_abort(job[0])
-            job[0] = None
-            self._forget_job(job)
-
-    def blob_dog(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
-                 maxima_threshold=-np.inf, use_ratios=False, cap=1 << 16):
-        return self._blob_call(self._L.visfd_hip_blob_dog, _np(src), _np(mask), src.shape, sigmas, aspect, delta,
-                               ratio, minima_threshold, maxima_threshold, use_ratios, cap)
+        self._call("calc_hessian", face, src, grad, hess, mask, nx, ny, nz, float(sigma), float(ratio))
 
     def calc_hessian(self, src, sigma, ratio, mask=None, want_grad=True):
         nz, ny, nx = src.shape
         hess = np.zeros((nz, ny, nx, 6), np.float32)
         grad = np.zeros((nz, ny, nx, 3), np.float32) if want_grad else None
-        self._chk(self._L.visfd_hip_calc_hessian(self._h, _np(src), _np(grad), _np(hess), _np(mask), nx, ny, nz,
-                                                 float(sigma), float(ratio)))
+        self._calc_hessian(_HOST, src, grad, hess, mask, sigma, ratio)
         return grad, hess
+
+    def calc_hessian_dev(self, src, grad, hess, sigma, ratio, mask=None):
+        self._calc_hessian(_DEVICE, src, grad, hess, mask, sigma, ratio)
 
     def diagonalize(self, m6, order):
         m6 = np.ascontiguousarray(m6, np.float32)
         out = np.empty_like(m6)
-        self._chk(self._L.visfd_hip_diagonalize_flat_sym3(self._h, _np(m6), _np(out), m6.size // 6, int(order)))
+        self._call("diagonalize_flat_sym3", _HOST, m6, out, m6.size // 6, int(order))
         return out
+
+    def _hessian_saliency(self, face, hess, mask, n, order, sal, dirs):
+        self._call("hessian_saliency", face, hess, mask, n, int(order), sal, dirs)
 
     def hessian_saliency(self, hess, order, mask=None):
         shp = hess.shape[:-1]
         sal = np.empty(shp, np.float32)
         dirs = np.zeros(shp + (3,), np.float32)
-        self._chk(self._L.visfd_hip_hessian_saliency(self._h, _np(hess), _np(mask), sal.size, int(order), _np(sal),
-                                                     _np(dirs)))
+        self._hessian_saliency(_HOST, hess, mask, sal.size, order, sal, dirs)
         return sal, dirs
 
-    def threshold_fraction(self, sal, fraction, mask=None):
-        thr = C.c_float()
-        self._chk(self._L.visfd_hip_threshold_fraction(self._h, _np(sal), _np(mask), sal.size, float(fraction),
-                                                       C.byref(thr)))
-        return thr.value
-
-    def tv_dense_stick(self, sal, dirs, sigma_tv, exponent=4, cutoff=2.0 ** 0.5, mask_src=None, mask_dst=None,
-                       curves=False):
-        nz, ny, nx = sal.shape
-        tensor = np.zeros((nz, ny, nx, 6), np.float32)
-        self._chk(self._L.visfd_hip_tv_dense_stick(self._h, _np(sal), _np(dirs), _np(tensor), _np(mask_src),
-                                                   _np(mask_dst), nx, ny, nz, float(sigma_tv), int(exponent),
-                                                   float(cutoff), int(curves)))
-        return tensor
-
-    def tv_weight_sum(self, sal, sigma_tv, cutoff=2.0 ** 0.5, mask_src=None, mask_dst=None):
-        """The normalisation denominators of TVDenseStick(normalize=true) (feature.hpp:1761-1822); zeros where mask_dst == 0."""
-        nz, ny, nx = sal.shape
-        den = np.zeros_like(sal)
-        self._chk(self._L.visfd_hip_tv_weight_sum(self._h, _np(sal), _np(den), _np(mask_src), _np(mask_dst), nx, ny, nz,
-                                                  float(sigma_tv), float(cutoff)))
-        return den
-
-    def tensor_saliency(self, tensor, order, sal_inout, mask=None):
-        self._chk(self._L.visfd_hip_tensor_saliency(self._h, _np(tensor), _np(mask), sal_inout.size, int(order),
-                                                    _np(sal_inout)))
-        return sal_inout
-
-    # ---- binning (resample.hpp:53-166); numpy shapes are [nz, ny, nx] -------------------------
-    @staticmethod
-    def _sizes(shape):
-        return (_i64 * 3)(int(shape[2]), int(shape[1]), int(shape[0]))
-
-    def bin_array3d(self, src, dst_shape, offset=None):
-        dst = np.empty(tuple(dst_shape), np.float32)
-        self._chk(self._L.visfd_hip_bin_array3d(self._h, _np(src), self._sizes(src.shape), _np(dst),
-                                                self._sizes(dst_shape), _i3(offset) if offset is not None else None))
-        return dst
-
-    def unbin_array3d(self, src, dst_shape, offset=None):
-        dst = np.empty(tuple(dst_shape), np.float32)
-        self._chk(self._L.visfd_hip_unbin_array3d(self._h, _np(src), self._sizes(src.shape), _np(dst),
-                                                  self._sizes(dst_shape), _i3(offset) if offset is not None else None))
-        return dst
-
-    def bin_array3d_dev(self, src, dst, offset=None):
-        self._chk(self._L.visfd_hip_bin_array3d_dev(self._h, _dev(src), self._sizes(src.shape), _dev(dst),
-                                                    self._sizes(dst.shape), _i3(offset) if offset is not None else None))
-
-    def unbin_array3d_dev(self, src, dst, offset=None):
-        self._chk(self._L.visfd_hip_unbin_array3d_dev(self._h, _dev(src), self._sizes(src.shape), _dev(dst),
-                                                      self._sizes(dst.shape), _i3(offset) if offset is not None else None))
-
-    def membrane_detect(self, src, sigma, ratio, order, best_fraction=0.05, threshold_abs=0.0, sigma_tv=0.0,
-                        tv_exponent=4, tv_cutoff=2.0 ** 0.5, mask=None, want_tensor=True, want_dir=False,
-                        sigma_background=0.0, normalize_background=True):
-        """HandleTV's compute section on host arrays -> (saliency, tensor or None, dirs or None, threshold).
-        sigma_background > 0: `-membrane-background`, both scores times (image - background)."""
-        nz, ny, nx = src.shape
-        sal = np.empty_like(src)
-        ten = np.zeros((nz, ny, nx, 6), np.float32) if want_tensor else None
-        dirs = np.zeros((nz, ny, nx, 3), np.float32) if want_dir else None
-        thr = C.c_float()
-        self._chk(self._L.visfd_hip_membrane_detect_bg(self._h, _np(src), _np(mask), nx, ny, nz, float(sigma),
-                                                       float(ratio), int(order), float(best_fraction),
-                                                       float(threshold_abs), float(sigma_tv), int(tv_exponent),
-                                                       float(tv_cutoff), float(sigma_background), int(bool(normalize_background)),
-                                                       _np(sal), _np(ten), _np(dirs), C.byref(thr)))
-        return sal, ten, dirs, thr.value
-
-    # ---------------------------------------------------------------- device face (torch)
-    def membrane_detect_dev(self, src, sal, sigma, ratio, order, best_fraction=0.05, threshold_abs=0.0, sigma_tv=0.0,
-                            tv_exponent=4, tv_cutoff=2.0 ** 0.5, mask=None, dirs=None, tensor=None, sigma_background=0.0,
-                            normalize_background=True):
-        """visfd_hip_membrane_detect_bg_dev: HandleTV's compute section on device tensors; sal receives the scores, and
-        -> the threshold.  dirs (3,nz,ny,nx) and tensor (6,nz,ny,nx) are optional outputs: None keeps them in the workspace."""
-        nz, ny, nx = src.shape
-        thr = C.c_float()
-        self._chk(self._L.visfd_hip_membrane_detect_bg_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma),
-                                                           float(ratio), int(order), float(best_fraction),
-                                                           float(threshold_abs), float(sigma_tv), int(tv_exponent),
-                                                           float(tv_cutoff), float(sigma_background),
-                                                           int(bool(normalize_background)), _dev(sal), _dev(tensor), _dev(dirs),
-                                                           C.byref(thr)))
-        return thr.value
-
-    def gauss_dev(self, src, dst, sigma, hw, mask=None, normalize=True):
-        nz, ny, nx = src.shape
-        A = C.c_float()
-        self._chk(self._L.visfd_hip_apply_gauss_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                    _f3(sigma), _i3(hw), int(normalize), C.byref(A)))
-        return A.value
-
-    def local_fluctuations_dev(self, src, dst, sigma, ratio, mask=None, normalize=True, exponent=2.0):
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_local_fluctuations_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                           _f3(sigma), float(exponent), float(ratio), int(normalize)))
-
-    def local_fluctuations_gen_dev(self, src, dst, sigma, ratio, mask=None, normalize=True, exponent=2.0):
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_local_fluctuations_gen_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                               _f3(sigma), float(exponent), float(ratio), int(normalize)))
-
-    def filter3d_dev(self, src, dst, table, mask=None, normalize=False, den=None):
-        """filter3d on device tensors (the table is a host array); den: optional tensor for the denominator."""
-        nz, ny, nx = src.shape
-        t, hw = _filter_table(table)
-        self._chk(self._L.visfd_hip_filter3d_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                 t.ctypes.data_as(_fp), hw, int(normalize), _dev(den)))
-
-    def apply_ggauss_dev(self, src, dst, width, m_exp, halfwidth, mask=None, normalize=True):
-        nz, ny, nx = src.shape
-        A = C.c_float()
-        self._chk(self._L.visfd_hip_apply_ggauss_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, _f3(width),
-                                                     float(m_exp), _i3(halfwidth), int(normalize), C.byref(A)))
-        return A.value
-
-    def apply_dogg_dev(self, src, dst, width_a, width_b, m_exp, n_exp, truncate_ratio=-1.0, truncate_threshold=0.03,
-                       mask=None):
-        nz, ny, nx = src.shape
-        A, B = C.c_float(), C.c_float()
-        self._chk(self._L.visfd_hip_apply_dogg_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, _f3(width_a),
-                                                   _f3(width_b), float(m_exp), float(n_exp), float(truncate_ratio),
-                                                   float(truncate_threshold), C.byref(A), C.byref(B)))
-        return A.value, B.value
-
-    def draw_spheres_dev(self, dst, background, centers, diameters=None, shell_thicknesses=None, foreground=None, mask=None,
-                         background_offset=0.0, background_rescale=1.0, background_normalize=False,
-                         foreground_normalize=False):
-        """draw_spheres on device tensors (the lists are host arrays); dst may be background.  -> any_center_outside"""
-        nz, ny, nx = background.shape
-        n, p, keep = _sphere_lists(centers, diameters, shell_thicknesses, foreground)
-        outside = C.c_int()
-        self._chk(self._L.visfd_hip_draw_spheres_dev(self._h, _dev(dst), _dev(mask), _dev(background), nx, ny, nz, p[0], p[1],
-                                                     p[2], p[3], n, float(background_offset), float(background_rescale),
-                                                     int(background_normalize), int(foreground_normalize),
-                                                     C.byref(outside)))
-        return bool(outside.value)
-
-    def voxelize_mesh_dev(self, dst, vertices, triangles, voxel_width=1.0, origin=(0, 0, 0), check_closed=True):
-        """voxelize_mesh into a device tensor [nz, ny, nx] (the mesh lists are host arrays); returns with the stream idle."""
-        nz, ny, nx = dst.shape
-        v, t = _mesh(vertices, triangles)
-        self._chk(self._L.visfd_hip_voxelize_mesh_dev(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t),
-                                                      float(voxel_width), _d3(origin), nx, ny, nz, int(bool(check_closed)),
-                                                      _dev(dst)))
-
-    def close_surface_dev(self, mask, points, normals, pad=0, orientation="outward", chi=None):
-        """close_surface on device tensors: mask (and chi, optional) [nz, ny, nx], points and normals (n, 3) float32; returns
-        with the stream idle."""
-        nz, ny, nx = mask.shape
-        n = int(points.shape[0])
-        assert tuple(points.shape) == (n, 3) and tuple(normals.shape) == (n, 3), "points and normals are (n, 3)"
-        self._chk(self._L.visfd_hip_close_surface_dev(self._h, _dev(points) if n else None, _dev(normals) if n else None, n,
-                                                      nx, ny, nz, int(pad), _orientation(orientation), _dev(mask), _dev(chi)))
-
-    def close_surface_splat_dev(self, acc, points, normals, shape, pad=0):
-        """close_surface_splat on device tensors: acc int64 [3, Nz, Ny, Nx] -> (used points, skipped points)."""
-        nz, ny, nx = [int(s) for s in shape]
-        n = int(points.shape[0])
-        assert acc.is_cuda and acc.is_contiguous() and str(acc.dtype) == "torch.int64", "need contiguous cuda int64"
-        assert tuple(acc.shape) == (3, nz + 2 * pad, ny + 2 * pad, nx + 2 * pad), "acc is [3, Nz, Ny, Nx]"
-        counts = (_i64 * 2)()
-        self._chk(self._L.visfd_hip_close_surface_splat_dev(self._h, _dev(points) if n else None, _dev(normals) if n else None,
-                                                            n, nx, ny, nz, int(pad), acc.data_ptr(), counts))
-        return int(counts[0]), int(counts[1])
-
-    def isosurface_dev(self, vol, iso, side="below", vertices=None, triangles=None, count_only=False):
-        """isosurface on device tensors: vol float32 [nz, ny, nx] -> (vertices float32 (n, 3), triangles int32 (m, 3)) as new
-        tensors on vol's device; with tensors to write into -> (n_vertices, n_triangles), as isosurface_host.  Returns with
-        the stream idle."""
-        import torch
-        nz, ny, nx = vol.shape
-
-        def given(t, dtype, what):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3, \
-                what + " must be a contiguous cuda (n, 3) tensor of " + str(dtype)
-            return t, t.data_ptr(), int(t.shape[0])
-
-        def alloc(rows, kind):
-            t = torch.empty((rows, 3), dtype=torch.float32 if kind == "vertices" else torch.int32, device=vol.device)
-            return t, t.data_ptr()
-
-        return _isosurface(lambda *tail: self._L.visfd_hip_isosurface_dev(self._h, _dev(vol), nx, ny, nz, *tail), self._L,
-                           iso, side, alloc, None if vertices is None else given(vertices, torch.float32, "vertices"),
-                           None if triangles is None else given(triangles, torch.int32, "triangles"), count_only)
-
-    def draw_last_times(self):
-        """(zero fill, scatter, resolve) milliseconds of the last draw_spheres under the option draw_time."""
-        ms = (C.c_float * 3)()
-        self._chk(self._L.visfd_hip_draw_last_times(self._h, ms))
-        return tuple(ms)
-
-    def draw_regions_dev(self, dst, regions, mask=None, negative_means_subtract=False):
-        """draw_regions on a device tensor, in place (the region list is a host array)."""
-        nz, ny, nx = dst.shape
-        arr, n = _regions(regions)
-        self._chk(self._L.visfd_hip_draw_regions_dev(self._h, _dev(dst), _dev(mask), nx, ny, nz, arr, n,
-                                                     int(negative_means_subtract)))
-
-    def morph_sphere_dev(self, op, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        """morph_sphere on device tensors; dst is read (top-hats, masked voxels) and written in place."""
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_morph_sphere_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, int(op),
-                                                     float(radius), float(radius_max), float(bmax)))
-
-    def dilate_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_DILATE, src, dst, radius, radius_max, bmax, mask)
-
-    def erode_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_ERODE, src, dst, radius, radius_max, bmax, mask)
-
-    def open_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_OPEN, src, dst, radius, radius_max, bmax, mask)
-
-    def close_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_CLOSE, src, dst, radius, radius_max, bmax, mask)
-
-    def white_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_TOP_HAT_WHITE, src, dst, radius, radius_max, bmax, mask)
-
-    def black_top_hat_sphere_dev(self, src, dst, radius, radius_max=0.0, bmax=0.0, mask=None):
-        self.morph_sphere_dev(MORPH_TOP_HAT_BLACK, src, dst, radius, radius_max, bmax, mask)
-
-    def find_extrema_dev(self, src, mask=None, find_minima=True, find_maxima=True, minima_threshold=float("inf"),
-                         maxima_threshold=-float("inf"), connectivity=3, allow_borders=True, labels=None):
-        """find_extrema on device tensors: -> (minima, maxima) as numpy lists; labels (an int32 cuda tensor, optional) is
-        written in place where mask != 0.  Returns with the stream idle."""
-        if labels is not None:
-            assert labels.is_cuda and labels.is_contiguous() and str(labels.dtype) == "torch.int32" and \
-                tuple(labels.shape) == tuple(src.shape), "labels: contiguous cuda int32 of src's shape"
-        return tuple(self._find_extrema(self._L.visfd_hip_find_extrema_dev, _dev(src), _dev(mask), tuple(src.shape),
-                                        find_minima, find_maxima, minima_threshold, maxima_threshold, connectivity,
-                                        allow_borders, None if labels is None else labels.data_ptr()))
-
-    def morph_table_dev(self, op, src, dst, dxyz, b, mask=None):
-        nz, ny, nx = src.shape
-        d, bb = _morph_table(dxyz, b)
-        self._chk(self._L.visfd_hip_morph_table_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, int(op),
-                                                    d.ctypes.data_as(_ip), bb.ctypes.data_as(_fp), len(bb)))
-
-    def median_sphere_dev(self, src, dst, radius, mask=None):
-        """median_sphere on device tensors; dst keeps its values where mask == 0 and is written in place."""
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_median_sphere_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz, float(radius)))
-
-    def median_table_dev(self, src, dst, dxyz, mask=None):
-        nz, ny, nx = src.shape
-        d = np.ascontiguousarray(dxyz, np.int32).reshape(-1, 3)
-        self._chk(self._L.visfd_hip_median_table_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                     d.ctypes.data_as(_ip), len(d)))
-
-    def dilate_dev(self, src, dst, dxyz, b, mask=None):
-        self.morph_table_dev(MORPH_DILATE, src, dst, dxyz, b, mask)
-
-    def erode_dev(self, src, dst, dxyz, b, mask=None):
-        self.morph_table_dev(MORPH_ERODE, src, dst, dxyz, b, mask)
-
-    def gauss_slab_dev(self, src, dst, z_lo, nz_global, sigma, hw, normalize=True):
-        nz, ny, nx = src.shape
-        A = C.c_float()
-        self._chk(self._L.visfd_hip_apply_gauss_slab_dev(self._h, _dev(src), _dev(dst), nx, ny, nz, int(z_lo),
-                                                         int(nz_global), _f3(sigma), _i3(hw), int(normalize),
-                                                         C.byref(A)))
-        return A.value
-
-    def log_dev(self, src, dst, sigma, delta, ratio, mask=None):
-        """ApplyLog on device tensors; dst may be src.  Unmasked scales with one half-width 6..10 run both Gaussians in two
-        shared launches (csrc/gauss_pair.hip); options log_pair (0 never, 1 by its table, 2 wherever it applies) and
-        log_pair_chunk (march length, for tests).  The bits are the same on every route."""
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_apply_log_dev(self._h, _dev(src), _dev(dst), _dev(mask), nx, ny, nz,
-                                                  _f3(sigma), float(delta), float(ratio), None, None))
-
-    def blob_dog_dev(self, src, sigmas, mask=None, aspect=None, delta=0.02, ratio=2.5, minima_threshold=np.inf,
-                     maxima_threshold=-np.inf, use_ratios=False, cap=1 << 16):
-        return self._blob_call(self._L.visfd_hip_blob_dog_dev, _dev(src), _dev(mask), tuple(src.shape), sigmas,
-                               aspect, delta, ratio, minima_threshold, maxima_threshold, use_ratios, cap)
-
-    def calc_hessian_dev(self, src, grad, hess, sigma, ratio, mask=None):
-        nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_calc_hessian_dev(self._h, _dev(src), _dev(grad), _dev(hess), _dev(mask), nx,
-                                                     ny, nz, float(sigma), float(ratio)))
-
     def hessian_saliency_dev(self, hess, sal, dirs, order, mask=None):
-        self._chk(self._L.visfd_hip_hessian_saliency_dev(self._h, _dev(hess), _dev(mask), sal.numel(), int(order),
-                                                         _dev(sal), _dev(dirs)))
+        self._hessian_saliency(_DEVICE, hess, mask, sal.numel(), order, sal, dirs)
 
     def ridge_saliency_dev(self, src, sal, dirs, sigma, ratio, order, mask=None):
         nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_ridge_saliency_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma),
-                                                       float(ratio), int(order), _dev(sal), _dev(dirs)))
+        self._call("ridge_saliency", _DEVICE, src, mask, nx, ny, nz, float(sigma), float(ratio), int(order), sal, dirs)
 
     def ridge_scores_dev(self, src, sal, smoothed, sigma, ratio, order, mask=None, background=None):
         """Smoothing + Hessian + eigenvalues + score for every voxel; `smoothed` receives the smoothed volume.
         background (a volume from peak_background_dev): every score times (src - background)."""
         nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_ridge_scores_bg_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma),
-                                                        float(ratio), int(order), _dev(background), _dev(sal), _dev(smoothed)))
+        self._call("ridge_scores_bg", _DEVICE, src, mask, nx, ny, nz, float(sigma), float(ratio), int(order), background, sal,
+                   smoothed)
 
     def peak_background_dev(self, src, background, sigma_background, ratio, mask=None, normalize=True):
         """The background of the peak-height factor: ApplyGauss(src, sigma_b, floor(sigma_b * ratio)) (handlers.cpp:1577-1592)."""
         nz, ny, nx = src.shape
-        self._chk(self._L.visfd_hip_peak_background_dev(self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma_background),
-                                                        float(ratio), int(bool(normalize)), _dev(background)))
+        self._call("peak_background", _DEVICE, src, mask, nx, ny, nz, float(sigma_background), float(ratio),
+                   int(bool(normalize)), background)
 
     def ridge_directions_dev(self, smoothed, sal, dirs, sigma, order):
         """Principal directions of the voxels with sal != 0 (the others keep what dirs held)."""
         nz, ny, nx = smoothed.shape
-        self._chk(self._L.visfd_hip_ridge_directions_dev(self._h, _dev(smoothed), nx, ny, nz, float(sigma), int(order),
-                                                         _dev(sal), _dev(dirs)))
-
-    def membrane_stage_dev(self, src, sal, dirs, tensor, scratch, sigma, ratio, order, best_fraction, sigma_tv, exponent=4,
-                           cutoff=2.0 ** 0.5, mask=None, sigma_background=0.0, background=None, normalize_background=True):
-        """visfd_hip_membrane_stage_dev: scores, fraction cut, directions of the survivors, vote and post-vote score on the
-        caller's tensors, queued in one go under the option membrane_queue (one wait, no threshold pass).  `scratch`
-        receives the smoothed image, `background` the background when sigma_background > 0.  Returns the threshold."""
-        nz, ny, nx = src.shape
-        thr = C.c_float()
-        self._chk(self._L.visfd_hip_membrane_stage_dev(
-            self._h, _dev(src), _dev(mask), nx, ny, nz, float(sigma), float(ratio), int(order), float(best_fraction),
-            float(sigma_tv), int(exponent), float(cutoff), float(sigma_background), int(bool(normalize_background)),
-            _dev(background), _dev(scratch), _dev(sal), _dev(dirs), _dev(tensor), C.byref(thr)))
-        return thr.value
+        self._call("ridge_directions", _DEVICE, smoothed, nx, ny, nz, float(sigma), int(order), sal, dirs)
 
     def debug_ridge_directions_thr_dev(self, smoothed, sal, dirs, sigma, order, thr_dev=None):
         """Test aid: ridge_directions_dev on a volume that has not been cut; thr_dev: a one-element device tensor."""
         nz, ny, nx = smoothed.shape
-        self._chk(self._L.visfd_hip_debug_ridge_directions_thr_dev(self._h, _dev(smoothed), nx, ny, nz, float(sigma), int(order),
-                                                                   _dev(sal), _dev(thr_dev), _dev(dirs)))
+        self._call("debug_ridge_directions_thr", _DEVICE, smoothed, nx, ny, nz, float(sigma), int(order), sal, thr_dev, dirs)
+
+    def _threshold_fraction(self, face, sal, mask, n, fraction):
+        thr = C.c_float()
+        self._call("threshold_fraction", face, sal, mask, n, float(fraction), C.byref(thr))
+        return thr.value
+
+    def threshold_fraction(self, sal, fraction, mask=None):
+        return self._threshold_fraction(_HOST, sal, mask, sal.size, fraction)
+
+    def threshold_fraction_dev(self, sal, fraction, mask=None):
+        return self._threshold_fraction(_DEVICE, sal, mask, sal.numel(), fraction)
+
+    def select_histogram_dev(self, sal, pass_, prefix, mask=None):
+        hist = np.zeros(2048, np.uint64)
+        n = C.c_uint64()
+        self._call("select_histogram", _DEVICE, sal, mask, sal.numel(), int(pass_), int(prefix), hist.ctypes.data, C.byref(n))
+        return hist, int(n.value)
+
+    def select_histogram_todev(self, sal, pass_, prefix, hist, mask=None):
+        """The round's histogram into `hist` (int64 tensor of 2048 on the device), asynchronous."""
+        assert hist.is_cuda and hist.numel() == 2048 and hist.element_size() == 8 and hist.is_contiguous()
+        self._call("select_histogram_todev", _DEVICE_PLAIN, sal, mask, sal.numel(), int(pass_), int(prefix), hist.data_ptr())
+
+    def stream_handle(self):
+        """The hipStream_t (as an integer) this context's device face runs on."""
+        return int(self._L.visfd_hip_get_stream(self._h) or 0)
+
+    def apply_threshold_dev(self, sal, thr):
+        self._call("apply_threshold", _DEVICE, sal, sal.numel(), float(thr))
+
+    def tv_dense_stick(self, sal, dirs, sigma_tv, exponent=4, cutoff=2.0 ** 0.5, mask_src=None, mask_dst=None,
+                       curves=False):
+        nz, ny, nx = sal.shape
+        tensor = np.zeros((nz, ny, nx, 6), np.float32)
+        self._call("tv_dense_stick", _HOST, sal, dirs, tensor, mask_src, mask_dst, nx, ny, nz, float(sigma_tv), int(exponent),
+                   float(cutoff), int(curves))
+        return tensor
+
+    def tv_dense_stick_dev(self, sal, dirs, tensor, sigma_tv, exponent=4, cutoff=2.0 ** 0.5, mask_src=None,
+                           mask_dst=None, curves=False, z_out=None):
+        nz, ny, nx = sal.shape
+        z0, z1 = (0, nz) if z_out is None else z_out
+        self._call("tv_dense_stick_slab", _DEVICE, sal, dirs, tensor, mask_src, mask_dst, nx, ny, nz, int(z0), int(z1),
+                   float(sigma_tv), int(exponent), float(cutoff), int(curves))
 
     def debug_tv_lists_dev(self, sal, dirs, h, mode=0, fold=False, thr_dev=None):
         """Test aid: the sender lists of tensor voting for the whole volume -> (rows uint32 [nz, ny + 1, ntx], entries float32
@@ -2334,55 +2057,95 @@ class Context:
         rows = np.empty((nz, ny + 1, ntx), np.uint32)
         ent, pos = np.empty((0, 4), np.float32), np.empty(0, np.uint32)
         for _ in range(2):   # the second call has arrays for the total the first one reported
-            self._chk(self._L.visfd_hip_debug_tv_lists_dev(
-                self._h, _dev(sal), _dev(dirs), _dev(thr_dev), nx, ny, nz, int(h), int(mode), int(bool(fold)),
-                rows.ctypes.data, rows.size, ent.ctypes.data, pos.ctypes.data, pos.size, C.byref(nrows), C.byref(total),
-                C.byref(flags)))
+            self._call("debug_tv_lists", _DEVICE, sal, dirs, thr_dev, nx, ny, nz, int(h), int(mode), int(bool(fold)),
+                       rows.ctypes.data, rows.size, ent.ctypes.data, pos.ctypes.data, pos.size, C.byref(nrows), C.byref(total),
+                       C.byref(flags))
             assert nrows.value == rows.size
             if total.value <= pos.size:
                 break
             ent, pos = np.empty((total.value, 4), np.float32), np.empty(total.value, np.uint32)
         return rows, ent[:total.value], pos[:total.value], int(flags.value)
 
-    def threshold_fraction_dev(self, sal, fraction, mask=None):
-        thr = C.c_float()
-        self._chk(self._L.visfd_hip_threshold_fraction_dev(self._h, _dev(sal), _dev(mask), sal.numel(),
-                                                           float(fraction), C.byref(thr)))
-        return thr.value
-
-    def select_histogram_dev(self, sal, pass_, prefix, mask=None):
-        hist = np.zeros(2048, np.uint64)
-        n = C.c_uint64()
-        self._chk(self._L.visfd_hip_select_histogram_dev(self._h, _dev(sal), _dev(mask), sal.numel(), int(pass_),
-                                                         int(prefix), hist.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                         C.byref(n)))
-        return hist, int(n.value)
-
-    def select_histogram_todev(self, sal, pass_, prefix, hist, mask=None):
-        """The round's histogram into `hist` (int64 tensor of 2048 on the device), asynchronous."""
-        assert hist.is_cuda and hist.numel() == 2048 and hist.element_size() == 8 and hist.is_contiguous()
-        self._chk(self._L.visfd_hip_select_histogram_todev(self._h, _dev(sal), _dev(mask), sal.numel(), int(pass_),
-                                                           int(prefix), hist.data_ptr()))
-
-    def stream_handle(self):
-        """The hipStream_t (as an integer) this context's device face runs on."""
-        return int(self._L.visfd_hip_get_stream(self._h) or 0)
-
-    def apply_threshold_dev(self, sal, thr):
-        self._chk(self._L.visfd_hip_apply_threshold_dev(self._h, _dev(sal), sal.numel(), float(thr)))
-
-    def tv_dense_stick_dev(self, sal, dirs, tensor, sigma_tv, exponent=4, cutoff=2.0 ** 0.5, mask_src=None,
-                           mask_dst=None, curves=False, z_out=None):
+    def tv_weight_sum(self, sal, sigma_tv, cutoff=2.0 ** 0.5, mask_src=None, mask_dst=None):
+        """The normalisation denominators of TVDenseStick(normalize=true) (feature.hpp:1761-1822); zeros where mask_dst == 0."""
         nz, ny, nx = sal.shape
-        z0, z1 = (0, nz) if z_out is None else z_out
-        self._chk(self._L.visfd_hip_tv_dense_stick_slab_dev(self._h, _dev(sal), _dev(dirs), _dev(tensor),
-                                                            _dev(mask_src), _dev(mask_dst), nx, ny, nz, int(z0),
-                                                            int(z1), float(sigma_tv), int(exponent), float(cutoff),
-                                                            int(curves)))
+        den = np.zeros_like(sal)
+        self._call("tv_weight_sum", _HOST, sal, den, mask_src, mask_dst, nx, ny, nz, float(sigma_tv), float(cutoff))
+        return den
+
+    def tensor_saliency(self, tensor, order, sal_inout, mask=None):
+        self._call("tensor_saliency", _HOST, tensor, mask, sal_inout.size, int(order), sal_inout)
+        return sal_inout
 
     def tensor_saliency_dev(self, tensor, sal, order, mask=None, image=None, background=None):
-        self._chk(self._L.visfd_hip_tensor_saliency_bg_dev(self._h, _dev(tensor), _dev(mask), sal.numel(), int(order),
-                                                           _dev(image), _dev(background), _dev(sal)))
+        self._call("tensor_saliency_bg", _DEVICE, tensor, mask, sal.numel(), int(order), image, background, sal)
+
+    # ---- binning (resample.hpp:53-166); numpy shapes are [nz, ny, nx] -------------------------
+    @staticmethod
+    def _sizes(shape):
+        return (_i64 * 3)(int(shape[2]), int(shape[1]), int(shape[0]))
+
+    def _rebin(self, name, face, src, dst, offset):
+        self._call(name, face, src, self._sizes(src.shape), dst, self._sizes(dst.shape),
+                   _i3(offset) if offset is not None else None)
+
+    def bin_array3d(self, src, dst_shape, offset=None):
+        dst = np.empty(tuple(dst_shape), np.float32)
+        self._rebin("bin_array3d", _HOST, src, dst, offset)
+        return dst
+
+    def unbin_array3d(self, src, dst_shape, offset=None):
+        dst = np.empty(tuple(dst_shape), np.float32)
+        self._rebin("unbin_array3d", _HOST, src, dst, offset)
+        return dst
+
+    def bin_array3d_dev(self, src, dst, offset=None):
+        self._rebin("bin_array3d", _DEVICE, src, dst, offset)
+
+    def unbin_array3d_dev(self, src, dst, offset=None):
+        self._rebin("unbin_array3d", _DEVICE, src, dst, offset)
+
+    def _membrane_detect(self, face, src, mask, sigma, ratio, order, best_fraction, threshold_abs, sigma_tv, tv_exponent,
+                         tv_cutoff, sigma_background, normalize_background, sal, tensor, dirs):
+        nz, ny, nx = src.shape
+        thr = C.c_float()
+        self._call("membrane_detect_bg", face, src, mask, nx, ny, nz, float(sigma), float(ratio), int(order),
+                   float(best_fraction), float(threshold_abs), float(sigma_tv), int(tv_exponent), float(tv_cutoff),
+                   float(sigma_background), int(bool(normalize_background)), sal, tensor, dirs, C.byref(thr))
+        return thr.value
+
+    def membrane_detect(self, src, sigma, ratio, order, best_fraction=0.05, threshold_abs=0.0, sigma_tv=0.0,
+                        tv_exponent=4, tv_cutoff=2.0 ** 0.5, mask=None, want_tensor=True, want_dir=False,
+                        sigma_background=0.0, normalize_background=True):
+        """HandleTV's compute section on host arrays -> (saliency, tensor or None, dirs or None, threshold).
+        sigma_background > 0: `-membrane-background`, both scores times (image - background)."""
+        nz, ny, nx = src.shape
+        sal = np.empty_like(src)
+        ten = np.zeros((nz, ny, nx, 6), np.float32) if want_tensor else None
+        dirs = np.zeros((nz, ny, nx, 3), np.float32) if want_dir else None
+        thr = self._membrane_detect(_HOST, src, mask, sigma, ratio, order, best_fraction, threshold_abs, sigma_tv, tv_exponent,
+                                    tv_cutoff, sigma_background, normalize_background, sal, ten, dirs)
+        return sal, ten, dirs, thr
+
+    def membrane_detect_dev(self, src, sal, sigma, ratio, order, best_fraction=0.05, threshold_abs=0.0, sigma_tv=0.0,
+                            tv_exponent=4, tv_cutoff=2.0 ** 0.5, mask=None, dirs=None, tensor=None, sigma_background=0.0,
+                            normalize_background=True):
+        """visfd_hip_membrane_detect_bg_dev: HandleTV's compute section on device tensors; sal receives the scores, and
+        -> the threshold.  dirs (3,nz,ny,nx) and tensor (6,nz,ny,nx) are optional outputs: None keeps them in the workspace."""
+        return self._membrane_detect(_DEVICE, src, mask, sigma, ratio, order, best_fraction, threshold_abs, sigma_tv,
+                                     tv_exponent, tv_cutoff, sigma_background, normalize_background, sal, tensor, dirs)
+
+    def membrane_stage_dev(self, src, sal, dirs, tensor, scratch, sigma, ratio, order, best_fraction, sigma_tv, exponent=4,
+                           cutoff=2.0 ** 0.5, mask=None, sigma_background=0.0, background=None, normalize_background=True):
+        """visfd_hip_membrane_stage_dev: scores, fraction cut, directions of the survivors, vote and post-vote score on the
+        caller's tensors, queued in one go under the option membrane_queue (one wait, no threshold pass).  `scratch`
+        receives the smoothed image, `background` the background when sigma_background > 0.  Returns the threshold."""
+        nz, ny, nx = src.shape
+        thr = C.c_float()
+        self._call("membrane_stage", _DEVICE, src, mask, nx, ny, nz, float(sigma), float(ratio), int(order),
+                   float(best_fraction), float(sigma_tv), int(exponent), float(cutoff), float(sigma_background),
+                   int(bool(normalize_background)), background, scratch, sal, dirs, tensor, C.byref(thr))
+        return thr.value
 
 
 class Slab:
